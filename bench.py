@@ -17,6 +17,8 @@ inside the timed region.  `--gather-trajectories` adds the gather of X / U (shar
 What is timed: `steps` solves between two fences (device synchronize + barrier + synchronize), per-launch profiling OFF, inputs
 resident in HBM.  Kernel durations for the roofline come from a SECOND pass with HIP events on the library's stream, after the
 timed region.  The oracle is used only for the `cpu_baseline` sample and the parity report (N = 1), never inside the timed region.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) before that second pass: the inputs are seeded, so two
+builds of the library run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -32,6 +34,8 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 METRIC = "iLQR iterations/sec (7-DoF, T=200, batch 4096) + final-cost rel-err vs Eigen ref"
+DUMP_BUDGET = 64 * 10**6  # bytes of .npy files --dump-outputs may write
+DUMP_SEED = 0  # the instance sample of --dump-outputs when the whole batch does not fit the budget
 
 
 # ----------------------------------------------------------------------------- multi-rank plumbing (covered by tests/test_sharding_gloo.py)
@@ -74,6 +78,39 @@ def gather_step(local_cost, total, local_X=None, local_U=None):
         out["X"] = sharding.gather_trajectories(local_X, total, dst=0)
         out["U"] = sharding.gather_trajectories(local_U, total, dst=0)
     return out
+
+
+# ----------------------------------------------------------------------------- outputs of the timed path (--dump-outputs)
+
+def dump_outputs(p, cfg, nb_iter, cost, out_dir, budget=DUMP_BUDGET):
+    """What the last timed step left for its caller, as out_dir/<name>.npy in float64: the per-instance cost the step copies out, the
+    solver's return values (ILQRRecursive: X, fX, U, K, d; AL-ILQR: X, fX, U; Batch-CP: U, and the X, fX it implies) and the per-iteration
+    message stream (cost_trace, alpha_trace).  Every array is indexed by instance first; when the whole batch exceeds `budget` bytes, all
+    arrays hold the same fixed, seeded sample of instances, whose indices are instance_index.  Returns what was written."""
+    import numpy as np
+
+    B, T, nb = p.B, p.T, nb_iter
+    nx, nu, nf = p.dims.n_x, p.dims.n_u, p.dims.n_f
+    per_instance = {"instance_index": 1, "cost": 1, "X": T * nx, "fX": T * nf, "U": (T - 1) * nu, "cost_trace": nb, "alpha_trace": nb}
+    if cfg["solver"] == "recursive":
+        per_instance.update(K=(T - 1) * nu * nx, d=(T - 1) * nu)
+    header = 128 * len(per_instance)  # one .npy header per file
+    n = min(B, (budget - header) // (8 * sum(per_instance.values())))
+    if n < 1:
+        raise SystemExit(f"bench.py: one instance's outputs exceed the --dump-outputs budget of {budget} bytes")
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    ct, at = p.trace(nb)
+    arrays = {"instance_index": idx, "cost": cost, "X": p.X(), "fX": p.fX(), "U": p.U(), "cost_trace": ct, "alpha_trace": at}
+    if cfg["solver"] == "recursive":
+        arrays.update(K=p.K(), d=p.d())
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        f = os.path.join(out_dir, name + ".npy")
+        np.save(f, np.ascontiguousarray(a if name == "instance_index" else a[idx], dtype=np.float64))
+        total += os.path.getsize(f)
+    assert total <= budget, (total, budget)
+    return {"dir": out_dir, "instances": int(n), "of": int(B), "arrays": sorted(arrays), "bytes": total}
 
 
 # ----------------------------------------------------------------------------- roofline bookkeeping
@@ -339,7 +376,11 @@ def main():
     ap.add_argument("--gather-trajectories", action="store_true", help="N>1: also gather X / U to rank 0 every step")
     ap.add_argument("--no-split", action="store_true", help="one kernel at a time on one stream (ilqr_ctx_set_split(0)): for rocprofv3 runs whose "
                     "per-kernel durations are to be compared with the roofline block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB; rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -398,6 +439,7 @@ def main():
         step()
     ctx.profile(False)
     elapsed = max_over_ranks(timed_region(step, args.steps, torch.cuda.synchronize, dist), dist, "cuda")
+    dumped = dump_outputs(p, cfg, nb_iter, cost_dev.cpu().numpy(), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # second pass, per-launch HIP events on: kernel durations for the roofline (not part of the headline)
     ctx.profile_reset()
@@ -479,6 +521,8 @@ def main():
             "nonfinite_frac": float(np.mean((status & 1) != 0)),
             "roofline": roof,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:  # the CPU baseline and the parity report belong to the N = 1 line only
             cb, ores = cpu_baseline(cfg, inp, nb_iter, psi)
             out["cpu_baseline"] = cb
