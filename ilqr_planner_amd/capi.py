@@ -108,7 +108,7 @@ def load():
     L.ilqr_ctx_set_stream.argtypes = [vp, vp]
     L.ilqr_ctx_synchronize.argtypes = [vp]
     L.ilqr_ctx_set_split.argtypes = [vp, C.c_int]
-    L.ilqr_ctx_set_crosscheck.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.ilqr_ctx_set_crosscheck.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.ilqr_problem_create.argtypes = [vp, C.POINTER(ProblemDesc), C.c_int, C.POINTER(vp)]
     L.ilqr_problem_destroy.argtypes = [vp]
     L.ilqr_problem_destroy.restype = None
@@ -260,20 +260,29 @@ class Context:
     def synchronize(self):
         self.check(self.L.ilqr_ctx_synchronize(self.h))
 
-    def set_crosscheck(self, generic_kernels=False, cp_lane_solve=False, cp_general=False, mfma_sweep=0):
-        """Cross-check kernel variants (ilqr_ctx_set_crosscheck); context state, in force until changed."""
-        self.check(self.L.ilqr_ctx_set_crosscheck(self.h, int(bool(generic_kernels)), int(bool(cp_lane_solve)), int(bool(cp_general)), int(mfma_sweep)))
+    _PINS = {"sweep": {None: 0, "mfma": 1, "rows": 2}, "forward": {None: 0, "wg": 1, "dpp": 2}, "reroll": {None: 0, "rows": 1, "dpp": 2}}  # ILQR_XC_*
+
+    def set_crosscheck(self, generic_kernels=False, cp_lane_solve=False, cp_general=False, sweep=None, forward=None, reroll=None):
+        """Cross-check kernel variants (ilqr_ctx_set_crosscheck); context state, in force until changed.  sweep "mfma"|"rows", forward "wg"|"dpp",
+        reroll "rows"|"dpp"; None = by batch size."""
+        pins = []
+        for name, v in (("sweep", sweep), ("forward", forward), ("reroll", reroll)):
+            if v not in self._PINS[name]:
+                raise ValueError(f"set_crosscheck: {name} must be one of {[k for k in self._PINS[name] if k]} or None (got {v!r})")
+            pins.append(self._PINS[name][v])
+        self.check(self.L.ilqr_ctx_set_crosscheck(self.h, int(bool(generic_kernels)), int(bool(cp_lane_solve)), int(bool(cp_general)), *pins))
 
     def crosscheck_from_env(self):
         """TEST PLUMBING of this Python wrapper (the library itself reads no environment variable): the parity tests select the cross-check
         variants per test case through ILQR_HIP_PATH=v1, ILQR_CP_SOLVE=lane, ILQR_CP=general, ILQR_SWEEP=mfma|rows, ILQR_FWD=wg|dpp, ILQR_APPLY=rows|dpp; every solve of BatchProblem passes them on."""
-        self.set_crosscheck(os.environ.get("ILQR_HIP_PATH") == "v1", os.environ.get("ILQR_CP_SOLVE") == "lane", os.environ.get("ILQR_CP") == "general",
-                            {"mfma": 1, "rows": 2}.get(os.environ.get("ILQR_SWEEP"), 0) + 4 * {"wg": 1, "dpp": 2}.get(os.environ.get("ILQR_FWD"), 0)
-                            + 16 * {"rows": 1, "dpp": 2}.get(os.environ.get("ILQR_APPLY"), 0))
+        env = os.environ
+        self.set_crosscheck(env.get("ILQR_HIP_PATH") == "v1", env.get("ILQR_CP_SOLVE") == "lane", env.get("ILQR_CP") == "general",
+                            sweep=env.get("ILQR_SWEEP") or None, forward=env.get("ILQR_FWD") or None, reroll=env.get("ILQR_APPLY") or None)
 
-    def set_split(self, on: bool):
-        """Two-stream solve of large batches on / off (ilqr_ctx_set_split); off = one kernel at a time, for profiler runs."""
-        self.check(self.L.ilqr_ctx_set_split(self.h, int(on)))
+    def set_split(self, mode: int):
+        """Two-stream solve of large batches (ilqr_ctx_set_split): 0 off (one kernel at a time, for profiler runs), 1 where it was measured to pay
+        (default), 2 every cooperative path (experiments); any other value raises."""
+        self.check(self.L.ilqr_ctx_set_split(self.h, int(mode)))
 
     def profile(self, on: bool):
         self.check(self.L.ilqr_profile_enable(self.h, int(on)))

@@ -18,6 +18,7 @@
 
 #include "ilqr_batchcp.hpp"
 #include "ilqr_kernels.hpp"
+#include "ilqr_plan.hpp"
 
 using namespace ilqr;
 
@@ -37,9 +38,9 @@ struct ilqr_ctx {
     // split solves (solve_riccati): the two halves of a batch run on their own streams, joined to `stream` by events
     int n_simd = 1024;  // SIMDs of the device (4 per CU)
     bool xc_generic = false, xc_cp_lane = false, xc_cp_general = false;  // cross-check kernel variants (ilqr_ctx_set_crosscheck)
-    int xc_sweep = 0;  // sweep of the 2nd-order / time systems: 0 = by batch size, 1 = matrix-core sweep, 2 = row sweep
-    int xc_apply = 0;  // re-roll of the winner on the time systems: 0 = by batch size, 1 = k_apply_rows_tm, 2 = k_apply_dpp_tm
-    int xc_fwd = 0;    // forward pass of the single-integrator systems: 0 = by batch size, 1 = k_forward_wg (bandwidth), 2 = k_forward_dpp (latency)
+    SweepPin xc_sweep = SweepPin::Auto;      // variant pins (ILQR_XC_*): sweep of the 2nd-order / time systems,
+    FwdPin xc_forward = FwdPin::Auto;        // forward pass of the single-integrator systems,
+    RerollPin xc_reroll = RerollPin::Auto;   // re-roll of the line-search winner on the time systems
     hipStream_t half_stream[2] = {nullptr, nullptr};
     hipEvent_t ev_begin = nullptr, ev_half_done[2] = {nullptr, nullptr}, ev_stagger = nullptr;
 };
@@ -67,11 +68,6 @@ struct ilqr_problem {
     BatchCPState cp;
     BatchWideState cpw;
 };
-
-// Batches of at least this many instances may be solved as two halves on two streams (solve_riccati): every kernel of an iteration is a
-// chain of T dependent steps that leaves much of the machine idle at these batch sizes, so one half's sweep can run under the other
-// half's forward pass and decision.
-constexpr int SPLIT_MIN_BATCH = 2048;
 
 static int fail(ilqr_ctx* c, const std::string& m) {
     if (c) c->err = m;
@@ -160,15 +156,23 @@ extern "C" int ilqr_ctx_set_stream(ilqr_ctx* c, void* s) {
 
 extern "C" int ilqr_ctx_set_split(ilqr_ctx* c, int on) {
     if (!c) return 1;
+    if (on < 0 || on > 2) return fail(c, "ilqr_ctx_set_split: mode must be 0, 1 or 2 (got " + std::to_string(on) + ")");
     c->split = on;
     return 0;
 }
 
-extern "C" int ilqr_ctx_set_crosscheck(ilqr_ctx* c, int generic_kernels, int cp_lane_solve, int cp_general, int mfma_sweep) {
+static_assert((int)SweepPin::Mfma == ILQR_XC_SWEEP_MFMA && (int)SweepPin::Rows == ILQR_XC_SWEEP_ROWS && (int)FwdPin::Wg == ILQR_XC_FWD_WG &&
+              (int)FwdPin::Dpp == ILQR_XC_FWD_DPP && (int)RerollPin::Rows == ILQR_XC_REROLL_ROWS && (int)RerollPin::Dpp == ILQR_XC_REROLL_DPP,
+              "variant pins of ilqr_plan.hpp and include/ilqr_hip.h");
+
+extern "C" int ilqr_ctx_set_crosscheck(ilqr_ctx* c, int generic_kernels, int cp_lane_solve, int cp_general, int sweep, int forward, int reroll) {
     if (!c) return 1;
-    c->xc_sweep = ((mfma_sweep & 3) == 1 || (mfma_sweep & 3) == 2) ? (mfma_sweep & 3) : 0;
-    c->xc_fwd = (((mfma_sweep >> 2) & 3) == 1 || ((mfma_sweep >> 2) & 3) == 2) ? ((mfma_sweep >> 2) & 3) : 0;
-    c->xc_apply = (mfma_sweep >> 4) & 3;
+    if (sweep < 0 || sweep > 2) return fail(c, "ilqr_ctx_set_crosscheck: sweep must be ILQR_XC_AUTO, ILQR_XC_SWEEP_MFMA or ILQR_XC_SWEEP_ROWS");
+    if (forward < 0 || forward > 2) return fail(c, "ilqr_ctx_set_crosscheck: forward must be ILQR_XC_AUTO, ILQR_XC_FWD_WG or ILQR_XC_FWD_DPP");
+    if (reroll < 0 || reroll > 2) return fail(c, "ilqr_ctx_set_crosscheck: reroll must be ILQR_XC_AUTO, ILQR_XC_REROLL_ROWS or ILQR_XC_REROLL_DPP");
+    c->xc_sweep = (SweepPin)sweep;
+    c->xc_forward = (FwdPin)forward;
+    c->xc_reroll = (RerollPin)reroll;
     c->xc_generic = generic_kernels != 0;
     c->xc_cp_lane = cp_lane_solve != 0;
     c->xc_cp_general = cp_general != 0;
@@ -397,9 +401,9 @@ extern "C" int ilqr_problem_create(ilqr_ctx* c, const ilqr_problem_desc* d, int 
     if (rc) { ilqr_problem_destroy(p); return 1; }
     b.U0 = U0; b.q0 = q0; b.dq0 = dq0; b.kp_tg = tg; b.desc = p->ddesc;
     bool up_ok = hipMemcpyAsync(p->ddesc, &p->hdesc, sizeof(DevDesc), hipMemcpyHostToDevice, c->stream) == hipSuccess;
-    if (p->B >= SPLIT_MIN_BATCH) {  // halves for the two-stream solve: cut at a multiple of 64 instances (whole waves, whole 128-byte lines)
+    if (p->B >= SPLIT_MIN_BATCH) {  // halves for the two-stream solve
         p->half_b0[0] = 0;
-        p->half_B[0] = ((p->B / 2) + 63) / 64 * 64;
+        p->half_B[0] = split_first_half(p->B);
         p->half_b0[1] = p->half_B[0];
         p->half_B[1] = p->B - p->half_B[0];
         for (int i = 0; i < 2 && up_ok; i++) {
@@ -556,12 +560,6 @@ static int ensure_trace(ilqr_problem* p, int nb_iter) {
     return 0;
 }
 
-// Which kernels run an iteration.  Default ("v2"): cooperative kernels -- closed-form single-integrator sweep or the f64-MFMA sweep, all
-// step sizes of the line search in one pass.  ilqr_ctx_set_crosscheck(ctx, 1, ..) forces the generic lane-per-instance kernels, the cross-check
-// set of the parity tests (also the product path where the cooperative kernels do not apply: joint-space AL rows on the controls, more
-// than 16 AL rows, a second limit set).  The library reads NO environment variable: the switch is context state.
-static int path_choice(const ilqr_ctx* c) { return c->xc_generic ? 1 : 2; }
-
 // The buffer table of one half of a split problem: every per-instance array is [..][Bp] with the instance innermost, so a half is the
 // same table with the base pointers moved by its first instance (gain records: by whole records) and its own descriptor (B = its size).
 static Bufs half_bufs(const ilqr_problem* p, int half) {
@@ -573,9 +571,30 @@ static Bufs half_bufs(const ilqr_problem* p, int half) {
     v.KD += o * (size_t)kd_rs(p->bufs.kd_sym, p->dims.n_u, kd_rowp(p->dims.n_x));
     v.cost += o; v.alpha += o; v.cur += o; v.active += o; v.iters += o; v.status += o; v.kpd += o; v.pend += o; v.pred += o;
     v.lsc += o; v.dun += o; v.kpdev += o; v.kpx += o; v.dunA += o;
+    if (v.ws) v.ws += o;
     if (v.cost_trace) { v.cost_trace += o; v.alpha_trace += o; }
     if (v.lambda) { v.lambda += o; v.Is += o; }
     return v;
+}
+
+// Which kernels run is decided by plan_riccati (ilqr_plan.hpp) from the problem's shape, the batch size and the context's pins: by default the
+// cooperative kernels, all step sizes of the line search in one pass; ilqr_ctx_set_crosscheck(ctx, 1, ..) forces the generic lane-per-instance
+// kernels, the cross-check set of the parity tests.  The library reads NO environment variable: the pins are context state.
+static PlanIn plan_input(const ilqr_problem* p, bool al, int nb_iter, int line_search) {
+    const ilqr_ctx* c = p->ctx;
+    const int T = p->T;
+    PlanIn in;
+    in.kind = p->desc.kind; in.nd = p->desc.nb_deriv; in.al = al; in.m = p->bufs.m; in.per_step = p->bufs.per_step; in.con_state_only = p->con_state_only;
+    in.limits2_set = p->desc.limits2_set != 0;
+    in.uniform_R = true;
+    for (int i = 1; i < p->dims.n_u; i++) in.uniform_R = in.uniform_R && (p->desc.R_diag[i] == p->desc.R_diag[0]);
+    // the register-resident sweep addresses x, u and the multipliers with 32-bit byte offsets (ilqr_kernels_dpp.hip): batches whose arrays pass
+    // 4 GiB (T * Bp beyond ~38 M) take the other sweeps
+    in.off32 = (size_t)2 * T * p->dims.n_x * p->Bp * 8 < ((size_t)1 << 32) && (size_t)T * (p->bufs.m > 0 ? p->bufs.m : 1) * p->Bp * 8 < ((size_t)1 << 32);
+    in.line_search = line_search != 0; in.alpha_floor = p->desc.alpha_floor; in.nb_iter = nb_iter;
+    in.B = p->B; in.n_simd = c->n_simd; in.halves = p->ddesc_half[0] != nullptr; in.split = c->split; in.profile = c->profile;
+    in.generic = c->xc_generic; in.sweep = c->xc_sweep; in.forward = c->xc_forward; in.reroll = c->xc_reroll;
+    return in;
 }
 
 static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double penalty0, double scaling, int line_search, int early_stop) {
@@ -587,45 +606,19 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     HIPCHK(c, hipSetDevice(c->device));
     if (ensure_trace(p, nb_iter)) return 1;
     p->last_nb_iter = nb_iter;
-    const int kind = p->desc.kind, nd = p->desc.nb_deriv;
-    // number of step sizes the do/while of ILQRRecursive.cpp:101-155 can reach: 1, 1/2, ... until alpha <= alpha_floor
-    int n_alpha = 1;
-    if (line_search) { double al_ = 1.0; while (al_ > p->desc.alpha_floor && n_alpha < 64) { al_ *= 0.5; n_alpha++; } }
-    const int path = p->desc.limits2_set ? 1 : path_choice(c);  // a second limit set exists in the generic kernels only
-    const bool coop = (path != 1) && n_alpha <= 16;            // all step sizes at once (16 lanes / rows per instance)
-    const bool fwd_wave = coop && forward_wave_supported(kind, nd, n_alpha);  // PosOrn-1 / JointSpace-1: linear line search, 32 lanes per instance
-    const bool fwd_lin = coop && !fwd_wave && forward_lin_supported(kind, nd, n_alpha);  // PosOrn-2: linear line search, 8 lanes per instance
-    // the register-resident sweep addresses x, u and the multipliers with 32-bit byte offsets (ilqr_kernels_dpp.hip): batches whose arrays pass
-    // 4 GiB (T * Bp beyond ~38 M) take the other sweeps
-    const bool off32 = (size_t)2 * p->T * p->dims.n_x * p->Bp * 8 < ((size_t)1 << 32) && (size_t)p->T * (p->bufs.m > 0 ? p->bufs.m : 1) * p->Bp * 8 < ((size_t)1 << 32);
-    const bool bwd_si = (path != 1) && off32 && backward_si_supported(kind, nd, al, p->bufs.m, p->bufs.per_step, p->con_state_only);
-    const bool bwd_mfma = (path != 1) && !bwd_si && backward_mfma_supported(kind, nd, al, p->bufs.m);  // wave per instance, f64 matrix cores
-    // 16 lanes per instance, rows in registers (round 3): a lone wave's chain is longer than the matrix-core sweep's (553 against 316 us at the C4 shape), but four
-    // instances share a wave: it wins as soon as the wave-per-instance sweep needs a second round of waves (measured: B = 2048 600 against 548 us, B = 4096 597 against 1040)
-    const bool bwd_rows = bwd_mfma && c->xc_sweep != 1 && (c->xc_sweep == 2 || p->B > 2 * c->n_simd) && backward_rows_supported(kind, nd, al, p->bufs.m);
-    bool uniform_R = true;
-    for (int i = 1; i < p->dims.n_u; i++) uniform_R = uniform_R && (p->desc.R_diag[i] == p->desc.R_diag[0]);
-    const bool fused = bwd_si && fwd_wave;  // the sweep applies the previous line search's winner itself (ilqr_kernels_dpp.hip)
-    // uniform control weights: the sweep's closed form for N = M D - I with D a multiple of I, writing the packed symmetric gain record (ilqr_kernels.hpp:
-    // KD_SYM_RS) that the two forward passes of this path and the getters read; any other forward pass reads plain records, so then the general form runs
-    const bool unif_sym = bwd_si && uniform_R && fwd_wave;
-    p->bufs.kd_sym = unif_sym ? 1 : 0;
+    const int kind = p->desc.kind, nd = p->desc.nb_deriv, T = p->T;
+    const RiccatiPlan pl = plan_riccati(plan_input(p, al, nb_iter, line_search));
+    if (pl.kd_sym != KD_SYM_KEEP) p->bufs.kd_sym = pl.kd_sym;  // before half_bufs: it sizes the half's offset into KD
+    if (pl.needs_ws && !p->bufs.ws)
+        if (dalloc(p, &p->bufs.ws, (size_t)backward_ws_entries(kind, nd) * p->Bp, false)) return 1;
 
     // ---- one or two independent halves ("lanes" of the launch schedule).  Instances never interact, so the halves of a large batch are
     // two complete solves on two streams; the second one starts one sweep later, so that its latency-bound sweep runs under the other
-    // half's bandwidth-bound forward pass.  Results do not depend on the split (bit for bit: tests/test_gpu_fullsize.py).  With
-    // per-launch profiling on the problem runs unsplit on the context's stream: the event marks time one kernel at a time.
+    // half's bandwidth-bound forward pass.  Results do not depend on the split (bit for bit: tests/test_gpu_fullsize.py).
     struct Half { Bufs bufs; int B; hipStream_t st; };
     Half hv[2];
     int nh = 1;
-    // Measured (rocprofv3 kernel trace, B = 4096): it pays for the wave-per-instance MFMA sweep (C4: 60.3 -> 51.7 ms per solve; 4096 one-wave
-    // workgroups on 3072 wave slots otherwise leave a one-third-full second round), not for the single-integrator pipeline (C3: the forward
-    // pass slows from 0.125 to 0.24 ms and k_kp_derivs from 0.017 to 0.08-0.14 ms when they share the SIMDs with the other half's sweep:
-    // 0.53 ms per iteration against 0.49 unsplit).
-    const bool split = coop && ((bwd_mfma && !bwd_rows && c->split) || c->split == 2) && !c->profile && p->ddesc_half[0] && nb_iter > 0;
-    if (!bwd_si && !bwd_mfma && nb_iter > 0 && !p->bufs.ws)  // the generic sweep keeps the matrices of a step in an explicit workspace
-        if (dalloc(p, &p->bufs.ws, (size_t)backward_ws_entries(kind, nd) * p->Bp, false)) return 1;
-    if (split) {
+    if (pl.split) {
         for (int i = 0; i < 2; i++) {
             if (!c->half_stream[i]) HIPCHK(c, hipStreamCreateWithFlags(&c->half_stream[i], hipStreamNonBlocking));
             if (!c->ev_half_done[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_half_done[i], hipEventDisableTiming));
@@ -652,32 +645,21 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
                 if (hipEventRecord(c->ev_half_done[i], c->half_stream[i]) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_half_done[i], 0) != hipSuccess)
                     (void)hipStreamSynchronize(c->half_stream[i]);  // last resort: drain it here
         }
-    } split_join{c, split};
+    } split_join{c, pl.split};
     FwdArgs f;
     std::memset(&f, 0, sizeof(f));
-    f.line_search = line_search; f.early_stop = early_stop; f.nb_iter = nb_iter; f.penalty_roll = penalty0; f.n_alpha = n_alpha; f.al = al ? 1 : 0; f.n_kp = p->desc.n_kp;
-    f.fused = fused ? 1 : 0;
+    f.line_search = line_search; f.early_stop = early_stop; f.nb_iter = nb_iter; f.penalty_roll = penalty0; f.n_alpha = pl.n_alpha; f.al = al ? 1 : 0; f.n_kp = p->desc.n_kp;
+    f.fused = pl.fused ? 1 : 0;
     f.limits = p->desc.limits_set ? 1 : 0;
-    // time systems, re-roll of the winner: 16 lanes per instance on registers up to a quarter wave of 4 instances per SIMD (B = 256: 64 against 92 us), the
-    // 8-lanes-per-instance kernel beyond (its waves cover 64 contiguous bytes of every [row][b] line, the other's 32: B = 2048 117 against 126 us, 4096 190 / 240)
-    f.apply_dpp = (c->xc_apply == 2 || (c->xc_apply == 0 && (p->B + 3) / 4 <= c->n_simd / 4)) ? 1 : 0;
-    // small batches (up to three quarters of a wave of 4 instances per SIMD): the rollout is a chain, not a stream -- k_forward_dpp.  Measured crossover
-    // with k_forward_wg on C3 (forward + decision, us): B = 2048 92 / 122, 3072 114 / 124, 4096 139 / 126
-    f.small = (fwd_wave && c->xc_fwd != 1 && (c->xc_fwd == 2 || (p->B + 3) / 4 <= 3 * c->n_simd / 4)) ? 1 : 0;
     for (int k = 0; k < p->desc.n_kp; k++) f.kp_ext |= p->desc.kp_dist[k] | p->desc.kp_has_frame[k] | p->desc.kp_has_Ru[k] | p->desc.kp_joint[k];
     for (int h = 0; h < nh; h++) {
         const Bufs& bf = hv[h].bufs;
-        const int B = hv[h].B;
-        hipStream_t st = hv[h].st;
         ProfScope ps(c, ILQR_PROF_ROLLOUT);
-        if (path != 1 && init_lti_supported(kind, nd)) {
-            launch_init_lti(kind, nd, bf, B, st);
-            if (al && !fused) {  // active-set weights of the initial trajectory: I_k = penalty * (g<0 && lambda==0 ? 0 : 1)
-                f.it = -1; f.do_update = 0;
-                launch_solver_v2(kind, nd, KER_AL_UPDATE, al, bf, B, p->T, st, f);
-            }
-        } else {
-            launch_solver(kind, nd, KER_INIT, al, bf, B, st, f);
+        if (pl.init == Init::Lti) launch_init_lti(kind, nd, bf, hv[h].B, hv[h].st);
+        else launch_init(kind, nd, al, bf, hv[h].B, hv[h].st, penalty0);
+        if (pl.init_al_update) {  // active-set weights of the initial trajectory: I_k = penalty * (g<0 && lambda==0 ? 0 : 1)
+            f.it = -1; f.do_update = 0;
+            launch_al_update(kind, nd, bf, hv[h].B, T, hv[h].st, f);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -695,54 +677,49 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
             const Bufs& bf = hv[h].bufs;
             const int B = hv[h].B;
             hipStream_t st = hv[h].st;
-            if (split && it == 0 && h == 1) HIPCHK(c, hipStreamWaitEvent(st, c->ev_stagger, 0));  // one sweep behind the first half
-            {
-                {   // l_x, l_xx at the keypoint steps (FK, log map, J'QJ) for every sweep: none of them holds keypoint code
-                    ProfScope ps(c, ILQR_PROF_OTHER);
-                    launch_solver(kind, nd, KER_KP_DERIVS, al, bf, B, st, fi);
-                }
-                ProfScope ps(c, ILQR_PROF_BACKWARD);
-                // rows in registers, DPP broadcasts (ilqr_kernels_dpp.hip): 16 lanes per instance while that gives every SIMD at most one wave
-                // (the launch is then bound by one wave's instruction stream, which is shorter with 4 instances per wave), 8 lanes per
-                // instance beyond (half the instructions per instance).  Measured crossover between 4096 and 8192 instances on 1024 SIMDs.
-                if (bwd_si) launch_backward_si_dpp(al, fused, unif_sym, (B + 3) / 4 <= c->n_simd ? 16 : 8, bf, B, st, sw);
-                else if (bwd_rows) launch_backward_rows(kind, nd, al, bf, B, st);
-                else if (bwd_mfma) launch_backward_mfma(kind, nd, al, bf, B, st);
-                else launch_solver(kind, nd, KER_BACKWARD, al, bf, B, st, fi);
+            if (pl.split && it == 0 && h == 1) HIPCHK(c, hipStreamWaitEvent(st, c->ev_stagger, 0));  // one sweep behind the first half
+            {   // l_x, l_xx at the keypoint steps (FK, log map, J'QJ) for every sweep: none of them holds keypoint code
+                ProfScope ps(c, ILQR_PROF_OTHER);
+                launch_kp_derivs(kind, nd, bf, B, st, fi);
             }
-            if (split && it == 0 && h == 0) HIPCHK(c, hipEventRecord(c->ev_stagger, st));
-            if (coop) {
-                {
-                    ProfScope ps(c, ILQR_PROF_FORWARD);
-                    if (fwd_wave) launch_forward_wave(kind, bf, B, st, fi);
-                    else if (fwd_lin) launch_forward_lin(nd, KER_FWD_SPEC, bf, B, p->T, st, fi);
-                    else launch_solver_v2(kind, nd, KER_FWD_SPEC, al, bf, B, p->T, st, fi);
+            {
+                ProfScope ps(c, ILQR_PROF_BACKWARD);
+                switch (pl.sweep) {
+                    case Sweep::SiDpp: launch_backward_si_dpp(al, pl.fused, pl.kd_sym == 1, pl.si_lanes[h], bf, B, st, sw); break;
+                    case Sweep::Rows: launch_backward_rows(kind, nd, al, bf, B, st); break;
+                    case Sweep::Mfma: launch_backward_mfma(kind, nd, al, bf, B, st); break;
+                    case Sweep::Generic: launch_backward_generic(kind, nd, al, bf, B, st); break;
                 }
-                if (fwd_wave) {  // winner applied, AL bookkeeping and buffer flip in one pass over the trajectory -- or by the next sweep (fused)
-                    if (!fused || it == nb_iter - 1) {
-                        ProfScope ps(c, ILQR_PROF_APPLY);
-                        launch_apply_wave(kind, bf, B, p->T, st, fi);
-                    }
-                } else if (fwd_lin) {  // the cost pass writes no trajectory: the winner is always re-rolled
-                    ProfScope ps(c, ILQR_PROF_APPLY);
-                    launch_forward_lin(nd, KER_FWD_APPLY, bf, B, p->T, st, fi);
-                } else if (line_search) {  // time systems: re-roll of the winner where the speculated step size lost, 8 lanes per instance
-                    ProfScope ps(c, ILQR_PROF_APPLY);
-                    launch_apply_rows_tm(kind, nd, bf, B, st, fi);
-                }
-                if (al && !fwd_wave) {  // active-set weights of the accepted trajectory (+ multiplier update every `lag` iterations)
-                    ProfScope ps(c, ILQR_PROF_OTHER);
-                    launch_solver_v2(kind, nd, KER_AL_UPDATE, al, bf, B, p->T, st, fi);
-                }
-            } else {
+            }
+            if (pl.split && it == 0 && h == 0) HIPCHK(c, hipEventRecord(c->ev_stagger, st));
+            {
                 ProfScope ps(c, ILQR_PROF_FORWARD);
-                launch_solver(kind, nd, KER_FORWARD, al, bf, B, st, fi);
+                switch (pl.forward) {
+                    case Forward::WaveWg: launch_forward_wave(kind, false, bf, B, st, fi); break;
+                    case Forward::WaveDpp: launch_forward_wave(kind, true, bf, B, st, fi); break;
+                    case Forward::Lin: launch_forward_lin(bf, B, st, fi); break;
+                    case Forward::Mfma: launch_forward_tm(kind, nd, bf, B, st, fi); break;
+                    case Forward::Generic: launch_forward_generic(kind, nd, al, bf, B, st, fi); break;
+                }
+            }
+            if (pl.apply != Apply::None && (pl.apply != Apply::WaveLast || it == nb_iter - 1)) {
+                ProfScope ps(c, ILQR_PROF_APPLY);
+                switch (pl.apply) {
+                    case Apply::Wave: case Apply::WaveLast: launch_apply_wave(kind, bf, B, T, st, fi); break;
+                    case Apply::Lin: launch_apply_lin(bf, B, T, st); break;
+                    case Apply::RerollRows: case Apply::RerollDpp: launch_apply_tm(kind, nd, pl.apply == Apply::RerollDpp, bf, B, st, fi); break;
+                    case Apply::None: break;
+                }
+            }
+            if (pl.al_update) {  // active-set weights of the accepted trajectory (+ multiplier update every `lag` iterations)
+                ProfScope ps(c, ILQR_PROF_OTHER);
+                launch_al_update(kind, nd, bf, B, T, st, fi);
             }
         }
         sw.pen_in = fi.penalty_roll; sw.pen_update_prev = fi.penalty_update; sw.do_update_prev = fi.do_update;  // for the next sweep
         HIPCHK(c, hipGetLastError());
     }
-    // (the caller's stream continues when both halves are done: SplitJoin below, on every exit path)
+    // (the caller's stream continues when both halves are done: SplitJoin above, on every exit path)
     prof_mark(c, -1);
     return 0;
 }

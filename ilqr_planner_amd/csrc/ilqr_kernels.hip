@@ -579,40 +579,52 @@ __global__ __launch_bounds__(64) void k_fk_batch(const DevDesc* dd, int n, const
 
 // ------------------------------------------------------------------------------------------------ launchers
 
-template <class S>
-static void launch_solver_kernel(int which, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    const dim3 grid((B + 63) / 64), block(64);
-    switch (which) {
-        case KER_KP_DERIVS:
-            if (f.n_kp > 0 && f.kp_ext) hipLaunchKernelGGL((k_kp_derivs<S, true>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a, f.fused);
-            else if (f.n_kp > 0) hipLaunchKernelGGL((k_kp_derivs<S, false>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a, f.fused);
-            break;
-        case KER_INIT:
-            if (al) hipLaunchKernelGGL((k_init_rollout<S, true>), grid, block, 0, st, a, f.penalty_roll);
-            else hipLaunchKernelGGL((k_init_rollout<S, false>), grid, block, 0, st, a, f.penalty_roll);
-            break;
-        case KER_BACKWARD:
-            if (al) hipLaunchKernelGGL((k_backward<S, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_backward<S, false>), grid, block, 0, st, a);
-            break;
-        case KER_FORWARD:
-            if (al)
-                hipLaunchKernelGGL((k_forward<S, true>), grid, block, 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
-                                   f.penalty_update, f.do_update, f.nb_iter);
-            else
-                hipLaunchKernelGGL((k_forward<S, false>), grid, block, 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
-                                   f.penalty_update, f.do_update, f.nb_iter);
-            break;
-    }
+// the system ladder of the four launchers below: calls launch(S{}) with the Sys of (kind, nd)
+template <class L>
+static void with_sys(int kind, int nd, L&& launch) {
+    if (kind == 2) launch(Sys<2, 1>{});
+    else if (kind == 3) launch(Sys<3, 1>{});
+    else if (kind == 0 && nd == 1) launch(Sys<0, 1>{});
+    else if (kind == 0 && nd == 2) launch(Sys<0, 2>{});
+    else if (kind == 1 && nd == 1) launch(Sys<1, 1>{});
+    else launch(Sys<1, 2>{});
 }
 
-void launch_solver(int kind, int nd, int which, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    if (kind == 2) launch_solver_kernel<Sys<2, 1>>(which, al, a, B, st, f);
-    else if (kind == 3) launch_solver_kernel<Sys<3, 1>>(which, al, a, B, st, f);
-    else if (kind == 0 && nd == 1) launch_solver_kernel<Sys<0, 1>>(which, al, a, B, st, f);
-    else if (kind == 0 && nd == 2) launch_solver_kernel<Sys<0, 2>>(which, al, a, B, st, f);
-    else if (kind == 1 && nd == 1) launch_solver_kernel<Sys<1, 1>>(which, al, a, B, st, f);
-    else launch_solver_kernel<Sys<1, 2>>(which, al, a, B, st, f);
+void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
+    if (f.n_kp <= 0) return;
+    with_sys(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if (f.kp_ext) hipLaunchKernelGGL((k_kp_derivs<S, true>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a, f.fused);
+        else hipLaunchKernelGGL((k_kp_derivs<S, false>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a, f.fused);
+    });
+}
+
+void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty) {
+    with_sys(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if (al) hipLaunchKernelGGL((k_init_rollout<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty);
+        else hipLaunchKernelGGL((k_init_rollout<S, false>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty);
+    });
+}
+
+void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st) {
+    with_sys(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if (al) hipLaunchKernelGGL((k_backward<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((k_backward<S, false>), dim3((B + 63) / 64), dim3(64), 0, st, a);
+    });
+}
+
+void launch_forward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
+    with_sys(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if (al)
+            hipLaunchKernelGGL((k_forward<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
+                               f.penalty_update, f.do_update, f.nb_iter);
+        else
+            hipLaunchKernelGGL((k_forward<S, false>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
+                               f.penalty_update, f.do_update, f.nb_iter);
+    });
 }
 
 void launch_fx_all(int kind, int nd, const Bufs& a, int B, int T, double* out, hipStream_t st) {

@@ -59,14 +59,12 @@ __host__ __device__ inline int kd_rs(int sym, int nu, int rowp) { return sym ? K
 
 struct FwdArgs {
     int it, line_search, early_stop, do_update, nb_iter;
-    int n_kp;     // number of keypoints (grid of KER_KP_DERIVS)
+    int n_kp;     // number of keypoints (grid of k_kp_derivs)
     int al;       // 1 = AL_ILQR semantics (early stop without the cost test)
     int n_alpha;  // number of step sizes 1, 1/2, ... the line search may try (11 for alpha_floor = 1e-3)
     double penalty_roll, penalty_update;
     int kp_ext;   // some keypoint has a dead zone, an object frame or its own control penalty (selects the full keypoint code)
-    int apply_dpp;  // time systems: the re-roll of the winner by k_apply_dpp_tm (16 lanes per instance on registers) instead of k_apply_rows_tm
     int limits;   // the descriptor's limits_set (host copy: selects kernel instantiations)
-    int small;    // batch of at most one wave per SIMD: the latency-built forward pass (k_forward_dpp) instead of the bandwidth-built one
     int fused;    // the acceptance of the line search is applied by the next sweep (k_backward_si_dpp<.., true>): until then the accepted
                   // trajectory of an instance with pend > 0 is xbar + alpha (x(1) - xbar) over its two buffers
 };
@@ -78,31 +76,26 @@ struct SweepArgs {
     int do_update_prev;      // the previous iteration was an update iteration
 };
 
-// v1 (one lane per instance, generic): KER_INIT, KER_BACKWARD, KER_FORWARD
-// v2: KER_FWD_SPEC  = all n_alpha line-search trials of an instance at once (16 lanes per instance), K read once
-//     KER_FWD_APPLY = re-roll the winning step size for the instances whose winner was not alpha = 1
-//     KER_AL_UPDATE = multiplier update on the accepted trajectory
-//     KER_KP_DERIVS = l_x, l_xx at the keypoint steps (FK + Jacobian), one lane per (instance, keypoint), feeding every sweep (launch_solver)
-enum { KER_INIT = 0, KER_BACKWARD = 1, KER_FORWARD = 2, KER_FWD_SPEC = 3, KER_FWD_APPLY = 4, KER_AL_UPDATE = 5, KER_KP_DERIVS = 7 };
-
-void launch_solver(int kind, int nd, int which, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);
-bool backward_si_supported(int kind, int nd, bool al, int m, int per_step, bool con_state_only);
-void launch_solver_v2(int kind, int nd, int which, bool al, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f);
-void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw);  // rows in registers, DPP broadcasts (ilqr_kernels_dpp.hip)
-bool backward_mfma_supported(int kind, int nd, bool al, int m);
-bool backward_rows_supported(int kind, int nd, bool al, int m);  // row-per-lane register sweep of the general systems (ilqr_kernels_rowsweep.hip)
-void launch_backward_rows(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // needs KER_KP_DERIVS first
+// Launchers of one Riccati iteration; which of them run is decided by plan_riccati (ilqr_plan.hpp).
+// generic lane-per-instance kernels (ilqr_kernels.hip)
+void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty);  // k_init_rollout
+void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // l_x, l_xx at the keypoint steps (FK + Jacobian), feeding every sweep
+void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // k_backward, needs Bufs::ws
 int backward_ws_entries(int kind, int nd);  // doubles per instance of k_backward's workspace
-void launch_backward_mfma(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // needs KER_KP_DERIVS first
-bool forward_lin_supported(int kind, int nd, int n_alpha);
-void launch_forward_mfma(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: all step sizes of an instance as one matrix-core product per step (ilqr_kernels_fwdm.hip)
-void launch_apply_rows_tm(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: re-roll of the winner, 8 lanes per instance
-void launch_forward_lin(int nd, int which, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f);
-bool forward_wave_supported(int kind, int nd, int n_alpha);
-bool init_lti_supported(int kind, int nd);
-void launch_init_lti(int kind, int nd, const Bufs& a, int B, hipStream_t st);  // followed by KER_AL_UPDATE (it = -1) for AL solves
-void launch_forward_wave(int kind, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);
+void launch_forward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // k_forward
+// cooperative kernels
+void launch_init_lti(int kind, int nd, const Bufs& a, int B, hipStream_t st);  // followed by launch_al_update (it = -1) for AL solves
+void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw);  // rows in registers, DPP broadcasts (ilqr_kernels_dpp.hip)
+void launch_backward_rows(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // row-per-lane register sweep (ilqr_kernels_rowsweep.hip); needs launch_kp_derivs first
+void launch_backward_mfma(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // needs launch_kp_derivs first
+void launch_forward_wave(int kind, bool small, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // k_forward_dpp (small) or k_forward_wg, + k_select
 void launch_apply_wave(int kind, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f);  // blend + AL bookkeeping + flip
+void launch_forward_lin(const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // PosOrn-2: k_forward_lin (cost pass of every step size)
+void launch_apply_lin(const Bufs& a, int B, int T, hipStream_t st);  // PosOrn-2: the winner re-rolled (k_blend) + flip
+void launch_forward_mfma(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: all step sizes of an instance as one matrix-core product per step (ilqr_kernels_fwdm.hip)
+void launch_forward_tm(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: launch_forward_mfma + k_select_x
+void launch_apply_tm(int kind, int nd, bool dpp, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: re-roll of the winner, k_apply_dpp_tm (dpp) or k_apply_rows_tm
+void launch_al_update(int kind, int nd, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f);  // k_al_post: active-set weights (+ multiplier update)
 void launch_fx_all(int kind, int nd, const Bufs& a, int B, int T, double* out, hipStream_t st);
 void launch_to_soa(const double* src, double* dst, int B, int Bp, int rows, hipStream_t st);
 void launch_from_soa(const double* src, double* dst, int B, int Bp, int rows, hipStream_t st);

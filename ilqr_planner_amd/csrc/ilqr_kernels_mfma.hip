@@ -413,11 +413,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
-bool backward_mfma_supported(int kind, int nd, bool al, int m) {
-    (void)nd;
-    return kind != 2 && (!al || m <= 16);
-}
-
 template <class S>
 static void launch_mfma_sys(bool al, const Bufs& a, int B, hipStream_t st) {
     const dim3 grid(grid_x8(B)), block(64);

@@ -581,28 +581,21 @@ __global__ __launch_bounds__(64) void k_apply_dpp_tm(Bufs a, FwdArgs f) {
 #undef AD_LO
 #undef AD_HI
 
-template <class S>
-static void launch_lin_sys(const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f, int which) {
-    if (which == KER_FWD_SPEC) {
-        const dim3 grid(grid_x8((B + 7) / 8)), block(64);
-        if (f.n_alpha <= 1) hipLaunchKernelGGL((k_forward_lin<S, 1>), grid, block, 0, st, a, f);
-        else if (f.n_alpha <= 11) hipLaunchKernelGGL((k_forward_lin<S, 11>), grid, block, 0, st, a, f);
-        else hipLaunchKernelGGL((k_forward_lin<S, 16>), grid, block, 0, st, a, f);
-    } else {
-        hipLaunchKernelGGL((k_blend<S>), dim3((B + 255) / 256, T), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_flip, dim3((B + 255) / 256), dim3(256), 0, st, a);
-    }
+void launch_forward_lin(const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {  // PosOrn-2
+    using S = Sys<0, 2>;
+    const dim3 grid(grid_x8((B + 7) / 8)), block(64);
+    if (f.n_alpha <= 1) hipLaunchKernelGGL((k_forward_lin<S, 1>), grid, block, 0, st, a, f);
+    else if (f.n_alpha <= 11) hipLaunchKernelGGL((k_forward_lin<S, 11>), grid, block, 0, st, a, f);
+    else hipLaunchKernelGGL((k_forward_lin<S, 16>), grid, block, 0, st, a, f);
 }
 
-bool forward_lin_supported(int kind, int nd, int n_alpha) { return kind == 0 && nd == 2 && n_alpha <= 16; }  // (PosOrn-1: k_forward_wg)
-
-void launch_forward_lin(int nd, int which, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f) {
-    (void)nd;
-    launch_lin_sys<Sys<0, 2>>(a, B, T, st, f, which);
+void launch_apply_lin(const Bufs& a, int B, int T, hipStream_t st) {  // PosOrn-2
+    hipLaunchKernelGGL((k_blend<Sys<0, 2>>), dim3((B + 255) / 256, T), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_flip, dim3((B + 255) / 256), dim3(256), 0, st, a);
 }
 
-void launch_apply_rows_tm(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    if (f.apply_dpp) {  // 16 lanes per instance on registers
+void launch_apply_tm(int kind, int nd, bool dpp, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
+    if (dpp) {  // 16 lanes per instance on registers
         const dim3 g4(grid_x8((B + 3) / 4)), blk(64);
         if (kind == 3) hipLaunchKernelGGL((k_apply_dpp_tm<Sys<3, 1>>), g4, blk, 0, st, a, f);
         else if (nd == 1) hipLaunchKernelGGL((k_apply_dpp_tm<Sys<1, 1>>), g4, blk, 0, st, a, f);

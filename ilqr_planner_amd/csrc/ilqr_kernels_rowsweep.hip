@@ -384,12 +384,6 @@ __global__ __launch_bounds__(64) void k_backward_rows(Bufs a) {
 #undef CLANE
 }
 
-bool backward_rows_supported(int kind, int nd, bool al, int m) {
-    if (kind == 2) return false;                 // JointSpace order 1: the single-integrator sweep
-    if (kind == 0 && nd == 1) return false;      // PosOrn order 1 with control rows in its constraints: the matrix-core sweep (n_x = 7 < 8)
-    return !al || m <= 16;
-}
-
 template <class S>
 static void launch_rows_sys(bool al, const Bufs& a, int B, hipStream_t st) {
     const dim3 grid(grid_x8((B + 3) / 4)), block(64);

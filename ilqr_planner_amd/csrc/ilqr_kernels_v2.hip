@@ -7,7 +7,7 @@
 //                  penalty * I_k the next backward sweep needs (AL-ILQR.cpp:21-44,190 -- every trial overwrites them, so
 //                  only the accepted trial's values survive in the reference too) and, every lag_update_step
 //                  iterations, the multiplier update (AL-ILQR.cpp:202-208).  Keeps the rollout kernels free of AL.
-// + the launchers of this file's kernels and the rule that selects the closed-form sweep (backward_si_supported).
+// + the launchers of this file's kernels.
 #include <cstdlib>
 #include <cstring>
 
@@ -106,29 +106,20 @@ static void launch_al_post(const Bufs& a, int B, int T, hipStream_t st, const Fw
     hipLaunchKernelGGL((k_al_post<S>), dim3((B + 255) / 256, T - 1), dim3(256), 0, st, a, f);
 }
 
-// closed-form sweep (k_backward_si_dpp): usable for single-integrator dynamics when no constraint row touches the controls, the rows
-// are shared over k and there are at most 4 of them (they live in registers)
-bool backward_si_supported(int kind, int nd, bool al, int m, int per_step, bool con_state_only) {
-    if (!((kind == 0 || kind == 2) && nd == 1)) return false;  // PosOrn-1 and JointSpace-1
-    if (!al) return true;
-    return con_state_only && per_step == 0 && m <= 4;
+void launch_forward_tm(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
+    launch_forward_mfma(kind, nd, a, B, st, f);
+    if (kind == 3) launch_select<Sys<3, 1>>(a, B, st, f);
+    else if (kind == 1 && nd == 1) launch_select<Sys<1, 1>>(a, B, st, f);
+    else if (kind == 1) launch_select<Sys<1, 2>>(a, B, st, f);
 }
 
-void launch_solver_v2(int kind, int nd, int which, bool al, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f) {
-    (void)al;
-    if (which == KER_FWD_SPEC) {  // time systems only (PosOrn: k_forward_wg / k_forward_lin): all step sizes of the line search + the decision
-        launch_forward_mfma(kind, nd, a, B, st, f);
-        if (kind == 3) launch_select<Sys<3, 1>>(a, B, st, f);
-        else if (kind == 1 && nd == 1) launch_select<Sys<1, 1>>(a, B, st, f);
-        else if (kind == 1) launch_select<Sys<1, 2>>(a, B, st, f);
-    } else if (which == KER_AL_UPDATE) {
-        if (kind == 2) launch_al_post<Sys<2, 1>>(a, B, T, st, f);
-        else if (kind == 3) launch_al_post<Sys<3, 1>>(a, B, T, st, f);
-        else if (kind == 0 && nd == 1) launch_al_post<Sys<0, 1>>(a, B, T, st, f);
-        else if (kind == 0 && nd == 2) launch_al_post<Sys<0, 2>>(a, B, T, st, f);
-        else if (kind == 1 && nd == 1) launch_al_post<Sys<1, 1>>(a, B, T, st, f);
-        else launch_al_post<Sys<1, 2>>(a, B, T, st, f);
-    }
+void launch_al_update(int kind, int nd, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f) {
+    if (kind == 2) launch_al_post<Sys<2, 1>>(a, B, T, st, f);
+    else if (kind == 3) launch_al_post<Sys<3, 1>>(a, B, T, st, f);
+    else if (kind == 0 && nd == 1) launch_al_post<Sys<0, 1>>(a, B, T, st, f);
+    else if (kind == 0 && nd == 2) launch_al_post<Sys<0, 2>>(a, B, T, st, f);
+    else if (kind == 1 && nd == 1) launch_al_post<Sys<1, 1>>(a, B, T, st, f);
+    else launch_al_post<Sys<1, 2>>(a, B, T, st, f);
 }
 
 }  // namespace ilqr

@@ -275,7 +275,7 @@ __global__ __launch_bounds__(FW_IW * 32) void k_forward_wg(Bufs a, FwdArgs f) {
 //   `v_fmac_f64_dpp`; the halves meet by one `row_ror:8` move, so both hold du_r and both advance dx_r += dt du_r.
 //   Memory: a wave may have 64 vector-memory instructions in flight, so what bounds the chain is instructions per step x latency / 64 (measured with
 //   8 per step: 0.23 us per step at any ring depth).  Hence 4 per step: the gain row as two 16-byte loads per lane (the halves take the two halves of
-//   the row), xbar_r | ubar_r as ONE load (half 0 / half 1), x(1)_r | u(1)_r as ONE store.  Ring of PF = 14 steps; a slot is refilled after its last
+//   the row), xbar_r | ubar_r as ONE load (half 0 / half 1), x(1)_r | u(1)_r as ONE store.  Ring of PF = 8 steps; a slot is refilled after its last
 //   use, so the loop-carried value and the load share a register (see ring_take in ilqr_kernels_dpp.hip for what happens otherwise).
 // Outputs as k_forward_wg: x(1), u(1) into the other buffer, (dx, du) at the keypoint steps, the limit cost of every step size, sum ||du||.
 // (Measured and dropped: this kernel, the decision and the next sweep's keypoint derivatives as ONE launch, a wave carrying its four instances through the
@@ -654,10 +654,6 @@ __global__ __launch_bounds__(64) void k_init_finish(Bufs a) {
     a.status[b] = isfinite(cost) ? 0 : 1;
 }
 
-bool init_lti_supported(int kind, int nd) {  // every system: the coordinates integrate independently given the step's dt
-    return ((kind == 0 || kind == 1) && (nd == 1 || nd == 2)) || ((kind == 2 || kind == 3) && nd == 1);
-}
-
 template <class S>
 static void launch_init_lti_sys(const Bufs& a, int B, hipStream_t st) {
     hipLaunchKernelGGL((k_init_roll_lti<S>), dim3((B + 255) / 256, DOF + S::TM), dim3(256), 0, st, a);
@@ -670,10 +666,6 @@ void launch_init_lti(int kind, int nd, const Bufs& a, int B, hipStream_t st) {
     else if (kind == 1) launch_init_lti_sys<Sys<1, 2>>(a, B, st);
     else if (nd == 1) launch_init_lti_sys<Sys<0, 1>>(a, B, st);
     else launch_init_lti_sys<Sys<0, 2>>(a, B, st);
-}
-
-bool forward_wave_supported(int kind, int nd, int n_alpha) {
-    return (kind == 0 || kind == 2) && nd == 1 && n_alpha <= 16;
 }
 
 template <class S>
@@ -710,26 +702,26 @@ static void launch_forward_dpp(const Bufs& a, dim3 grid, hipStream_t st, const F
 }
 // the rollout itself knows no keypoint function (single-integrator dynamics); the decision kernel is per system kind
 template <class S>
-static void launch_forward_wave_sys(const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
+static void launch_forward_wave_sys(bool small, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
     const dim3 grid(grid_x8((B + FW_IW - 1) / FW_IW)), block(FW_IW * 32);
     const dim3 sgrid(grid_x8((B + 3) / 4));  // small batches: 16 lanes per instance, one wave per workgroup (k_forward_dpp)
     if (f.n_alpha <= 1) {
-        if (f.small) launch_forward_dpp<1>(a, sgrid, st, f);
+        if (small) launch_forward_dpp<1>(a, sgrid, st, f);
         else hipLaunchKernelGGL((k_forward_wg<1>), grid, block, 0, st, a, f);
         launch_select<S, 1>(a, B, st, f);
     } else if (f.n_alpha <= 11) {
-        if (f.small) launch_forward_dpp<11>(a, sgrid, st, f);
+        if (small) launch_forward_dpp<11>(a, sgrid, st, f);
         else hipLaunchKernelGGL((k_forward_wg<11>), grid, block, 0, st, a, f);
         launch_select<S, 11>(a, B, st, f);
     } else {
-        if (f.small) launch_forward_dpp<16>(a, sgrid, st, f);
+        if (small) launch_forward_dpp<16>(a, sgrid, st, f);
         else hipLaunchKernelGGL((k_forward_wg<16>), grid, block, 0, st, a, f);
         launch_select<S, 16>(a, B, st, f);
     }
 }
-void launch_forward_wave(int kind, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    if (kind == 2) launch_forward_wave_sys<Sys<2, 1>>(a, B, st, f);
-    else launch_forward_wave_sys<Sys<0, 1>>(a, B, st, f);
+void launch_forward_wave(int kind, bool small, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
+    if (kind == 2) launch_forward_wave_sys<Sys<2, 1>>(small, a, B, st, f);
+    else launch_forward_wave_sys<Sys<0, 1>>(small, a, B, st, f);
 }
 
 }  // namespace ilqr

@@ -1,0 +1,160 @@
+// ilqr_plan.hpp -- which kernels run a Riccati solve (ILQRRecursive / AL_ILQR): one pure decision from the problem's shape, the batch size and
+// the context's pins, consumed by solve_riccati (ilqr_capi.cpp).  No HIP here: tests/cpp/plan_table_main.cpp checks the table on the host.
+#pragma once
+
+namespace ilqr {
+
+// Batches of at least this many instances may be solved as two halves on two streams (solve_riccati): every kernel of an iteration is a
+// chain of T dependent steps that leaves much of the machine idle at these batch sizes, so one half's sweep can run under the other
+// half's forward pass and decision.  The first half is cut at a multiple of 64 instances (whole waves, whole 128-byte lines).
+constexpr int SPLIT_MIN_BATCH = 2048;
+constexpr int split_first_half(int B) { return (B / 2 + 63) / 64 * 64; }
+
+// ---- what each cooperative kernel supports (system kind: 0 PosOrn, 1 PosOrnTime, 2 JointSpace, 3 JointSpaceTime; nd = nb_deriv)
+
+// k_backward_si_dpp: single-integrator dynamics; the constraint rows are shared over k, touch no control and live in registers (at most 4)
+constexpr bool backward_si_supported(int kind, int nd, bool al, int m, int per_step, bool con_state_only) {
+    return (kind == 0 || kind == 2) && nd == 1 && (!al || (con_state_only && per_step == 0 && m <= 4));
+}
+// k_backward_mfma: every system but JointSpace-1 (which always has the closed form), at most 16 AL rows in LDS
+constexpr bool backward_mfma_supported(int kind, int /*nd*/, bool al, int m) { return kind != 2 && (!al || m <= 16); }
+// k_backward_rows: one lane per row of [P|p] needs n_x >= 8 (not PosOrn-1) and at most 16 AL rows; JointSpace-1 has the closed form
+constexpr bool backward_rows_supported(int kind, int nd, bool al, int m) {
+    return kind != 2 && !(kind == 0 && nd == 1) && (!al || m <= 16);
+}
+// k_forward_wg / k_forward_dpp: the linear line search of the single-integrator systems, one lane row per step size (at most 16)
+constexpr bool forward_wave_supported(int kind, int nd, int n_alpha) { return (kind == 0 || kind == 2) && nd == 1 && n_alpha <= 16; }
+// k_forward_lin: the linear line search of PosOrn-2, at most 16 step sizes
+constexpr bool forward_lin_supported(int kind, int nd, int n_alpha) { return kind == 0 && nd == 2 && n_alpha <= 16; }
+// k_init_roll_lti: every system -- the coordinates integrate independently given the step's dt
+constexpr bool init_lti_supported(int kind, int nd) {
+    return ((kind == 0 || kind == 1) && (nd == 1 || nd == 2)) || ((kind == 2 || kind == 3) && nd == 1);
+}
+
+// number of step sizes the do/while of ILQRRecursive.cpp:101-155 can reach: 1, 1/2, ... until alpha <= alpha_floor
+inline int n_alpha_of(bool line_search, double alpha_floor) {
+    int n = 1;
+    if (line_search) { double a = 1.0; while (a > alpha_floor && n < 64) { a *= 0.5; n++; } }
+    return n;
+}
+
+// Lanes per instance of k_backward_si_dpp, decided on the LAUNCHED (half-)batch: 16 while that gives every SIMD at most one wave (the launch is
+// then bound by one wave's instruction stream, which is shorter with 4 instances per wave), 8 beyond (half the instructions per instance).
+// Measured crossover between 4096 and 8192 instances on 1024 SIMDs.  Both groupings are bit-identical (test_sweep_lane_groupings_agree).
+constexpr int si_lanes(int launched_B, int n_simd) { return (launched_B + 3) / 4 <= n_simd ? 16 : 8; }
+
+// Variant pins of ilqr_ctx_set_crosscheck: AUTO (0) = by batch size; the values are the ILQR_XC_* constants of include/ilqr_hip.h
+enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2 };
+enum class FwdPin { Auto = 0, Wg = 1, Dpp = 2 };
+enum class RerollPin { Auto = 0, Rows = 1, Dpp = 2 };
+
+struct PlanIn {
+    int kind = 0, nd = 1;
+    bool al = false;
+    int m = 0, per_step = 0;       // AL constraint rows (shared over k unless per_step)
+    bool con_state_only = false;   // no constraint row touches the controls
+    bool limits2_set = false;      // a second limit set (generic kernels only)
+    bool uniform_R = false;        // all control weights equal
+    bool off32 = true;             // x, u and the multipliers are addressable with 32-bit byte offsets (k_backward_si_dpp)
+    bool line_search = true;
+    double alpha_floor = 1e-3;
+    int nb_iter = 0;
+    int B = 0, n_simd = 1024;      // the whole batch; SIMDs of the device
+    bool halves = false;           // the problem has split halves (B >= SPLIT_MIN_BATCH)
+    int split = 1;                 // ilqr_ctx_set_split: 0 off, 1 where measured to pay, 2 every cooperative path
+    bool profile = false;          // per-launch profiling: one stream, one kernel at a time
+    bool generic = false;          // pin: the generic lane-per-instance kernels
+    SweepPin sweep = SweepPin::Auto;
+    FwdPin forward = FwdPin::Auto;
+    RerollPin reroll = RerollPin::Auto;
+};
+
+enum class Init { Lti, Generic };                          // k_init_roll_lti + k_init_finish, or k_init_rollout
+enum class Sweep { SiDpp, Mfma, Rows, Generic };           // k_backward_si_dpp, k_backward_mfma, k_backward_rows, k_backward (+ workspace)
+enum class Forward { WaveWg, WaveDpp, Lin, Mfma, Generic };  // k_forward_wg / k_forward_dpp + k_select, k_forward_lin, k_forward_mfma + k_select_x, k_forward
+enum class Apply {
+    None,
+    Wave,        // k_apply + k_flip_ran every iteration
+    WaveLast,    // ... on the last iteration only: the next sweep applies the winner (fused)
+    Lin,         // k_blend + k_flip
+    RerollRows,  // k_apply_rows_tm: time systems, 8 lanes per instance through LDS
+    RerollDpp,   // k_apply_dpp_tm: time systems, 16 lanes per instance on registers
+};
+constexpr int KD_SYM_KEEP = -1;  // no sweep runs: the gain records keep the layout of the last sweep that wrote them
+
+struct RiccatiPlan {
+    int n_alpha = 1;
+    Init init = Init::Generic;
+    bool init_al_update = false;  // k_al_post at it = -1 after the LTI rollout (active-set weights of the initial trajectory)
+    Sweep sweep = Sweep::Generic;
+    int si_lanes[2] = {16, 16};   // Sweep::SiDpp: lanes per instance of the whole batch or of each half (split)
+    Forward forward = Forward::Generic;
+    Apply apply = Apply::None;
+    bool al_update = false;       // k_al_post after every line search (the wave path does it in k_apply or the fused sweep)
+    bool fused = false;           // the sweep applies the previous line search's winner itself (ilqr_kernels_dpp.hip)
+    int kd_sym = 0;               // layout the sweep writes: 1 packed symmetric (KD_SYM_RS), 0 plain, or KD_SYM_KEEP
+    bool split = false;           // two halves on two streams
+    bool needs_ws = false;        // the generic sweep keeps the matrices of a step in an explicit workspace
+};
+
+inline RiccatiPlan plan_riccati(const PlanIn& in) {
+    RiccatiPlan p;
+    const int kind = in.kind, nd = in.nd;
+    p.n_alpha = n_alpha_of(in.line_search, in.alpha_floor);
+    const bool cooperative = !in.generic && !in.limits2_set;  // a second limit set exists in the generic kernels only
+    const bool coop_fwd = cooperative && p.n_alpha <= 16;       // all step sizes at once (16 lanes / rows per instance)
+
+    // sweep.  The row-per-lane sweep (16 lanes per instance, rows in registers): a lone wave's chain is longer than the matrix-core sweep's (553
+    // against 316 us at the C4 shape), but four instances share a wave: it wins as soon as the wave-per-instance sweep needs a second round of
+    // waves (measured: B = 2048 600 against 548 us, B = 4096 597 against 1040)
+    if (cooperative && in.off32 && backward_si_supported(kind, nd, in.al, in.m, in.per_step, in.con_state_only)) p.sweep = Sweep::SiDpp;
+    else if (cooperative && backward_mfma_supported(kind, nd, in.al, in.m)) {
+        const bool rows = in.sweep == SweepPin::Rows || (in.sweep == SweepPin::Auto && in.B > 2 * in.n_simd);
+        p.sweep = rows && backward_rows_supported(kind, nd, in.al, in.m) ? Sweep::Rows : Sweep::Mfma;
+    }
+
+    // forward pass.  Single-integrator systems: small batches (up to three quarters of a wave of 4 instances per SIMD) roll out a chain, not a
+    // stream -- k_forward_dpp.  Measured crossover with k_forward_wg on C3 (forward + decision, us): B = 2048 92 / 122, 3072 114 / 124, 4096 139 / 126
+    if (coop_fwd && forward_wave_supported(kind, nd, p.n_alpha)) {
+        const bool dpp = in.forward == FwdPin::Dpp || (in.forward == FwdPin::Auto && (in.B + 3) / 4 <= 3 * in.n_simd / 4);
+        p.forward = dpp ? Forward::WaveDpp : Forward::WaveWg;
+    } else if (coop_fwd && forward_lin_supported(kind, nd, p.n_alpha)) {
+        p.forward = Forward::Lin;
+    } else if (coop_fwd) {
+        p.forward = Forward::Mfma;  // the time systems
+    }
+    const bool wave = p.forward == Forward::WaveWg || p.forward == Forward::WaveDpp;
+    p.fused = p.sweep == Sweep::SiDpp && wave;
+    // uniform control weights: the sweep's closed form for N = M D - I with D a multiple of I, writing the packed symmetric gain record
+    // (ilqr_kernels.hpp: KD_SYM_RS) that the two forward passes of this path and the getters read; any other forward pass reads plain records
+    p.kd_sym = in.nb_iter == 0 ? KD_SYM_KEEP : (p.fused && in.uniform_R) ? 1 : 0;
+
+    // winner of the line search applied: the wave path in one pass with the AL bookkeeping and the buffer flip (or by the next sweep when fused);
+    // k_forward_lin's cost pass writes no trajectory; the time systems re-roll the winner where the speculated step size lost -- 16 lanes per
+    // instance on registers up to a quarter wave of 4 instances per SIMD (B = 256: 64 against 92 us), the 8-lanes-per-instance kernel beyond
+    // (its waves cover 64 contiguous bytes of every [row][b] line, the other's 32: B = 2048 117 against 126 us, 4096 190 / 240)
+    if (wave) p.apply = p.fused ? Apply::WaveLast : Apply::Wave;
+    else if (p.forward == Forward::Lin) p.apply = Apply::Lin;
+    else if (p.forward == Forward::Mfma && in.line_search) {
+        const bool dpp = in.reroll == RerollPin::Dpp || (in.reroll == RerollPin::Auto && (in.B + 3) / 4 <= in.n_simd / 4);
+        p.apply = dpp ? Apply::RerollDpp : Apply::RerollRows;
+    }
+    p.al_update = in.al && coop_fwd && !wave;
+
+    p.init = cooperative && init_lti_supported(kind, nd) ? Init::Lti : Init::Generic;
+    p.init_al_update = p.init == Init::Lti && in.al && !p.fused;
+
+    // Two halves on two streams, the second one sweep behind (with per-launch profiling on, one stream: the event marks time one kernel at a time).
+    // Measured (rocprofv3 kernel trace, B = 4096): it pays for the wave-per-instance MFMA sweep (C4: 60.3 -> 51.7 ms per solve; 4096 one-wave
+    // workgroups on 3072 wave slots otherwise leave a one-third-full second round), not for the single-integrator pipeline (C3: the forward
+    // pass slows from 0.125 to 0.24 ms and k_kp_derivs from 0.017 to 0.08-0.14 ms when they share the SIMDs with the other half's sweep:
+    // 0.53 ms per iteration against 0.49 unsplit).
+    p.split = coop_fwd && ((p.sweep == Sweep::Mfma && in.split) || in.split == 2) && !in.profile && in.halves && in.nb_iter > 0;
+    p.needs_ws = p.sweep == Sweep::Generic && in.nb_iter > 0;
+    const int b0 = p.split ? split_first_half(in.B) : in.B;
+    p.si_lanes[0] = si_lanes(b0, in.n_simd);
+    p.si_lanes[1] = si_lanes(in.B - b0, in.n_simd);
+    return p;
+}
+
+}  // namespace ilqr

@@ -151,18 +151,25 @@ int ilqr_ctx_synchronize(ilqr_ctx* ctx);
 /* Large batches of the systems that use the wave-per-instance MFMA sweep are solved as two halves on two internal streams, joined to the
  * context's stream by events (instances are independent: results do not depend on it).  on = 0 keeps every launch on the context's
  * stream, one kernel at a time -- what a profiler run wants.  Default: on (1).  on = 2 splits every cooperative path (experiments only: measured
- * slower on the single-integrator systems).  (No reference counterpart: the reference has no batch.) */
+ * slower on the single-integrator systems).  Any other value fails with an error text.  (No reference counterpart: the reference has no batch.) */
 int ilqr_ctx_set_split(ilqr_ctx* ctx, int on);
+/* Variant pins of ilqr_ctx_set_crosscheck: AUTO = by batch size; each pair of variants agrees to rounding, not bit for bit */
+#define ILQR_XC_AUTO 0
+#define ILQR_XC_SWEEP_MFMA 1   /* sweep of the 2nd-order / time systems: one instance per wave on the f64 matrix cores (AUTO: up to 2 n_simd instances) */
+#define ILQR_XC_SWEEP_ROWS 2   /*   ... 16 lanes per instance with the rows in registers (AUTO: beyond) */
+#define ILQR_XC_FWD_WG 1       /* forward pass of the single-integrator systems: the bandwidth-built k_forward_wg (AUTO: beyond 3 n_simd instances) */
+#define ILQR_XC_FWD_DPP 2      /*   ... the latency-built k_forward_dpp (AUTO: up to 3 n_simd) */
+#define ILQR_XC_REROLL_ROWS 1  /* re-roll of the line-search winner on the time systems: k_apply_rows_tm (AUTO: beyond n_simd instances) */
+#define ILQR_XC_REROLL_DPP 2   /*   ... k_apply_dpp_tm (AUTO: up to n_simd) */
 /* Cross-check kernel variants for parity tests (no reference counterpart; the library reads no environment variable -- these are context state,
  * in force for every later solve on the context): generic_kernels = 1 runs ILQRRecursive / AL_ILQR on the generic one-lane-per-instance kernel
  * set instead of the cooperative one; cp_lane_solve = 1 solves the Batch-CP normal equations with one lane per instance instead of one wave;
- * cp_general = 1 sends Batch-CP on the constant-dt systems through the general path of the time systems; mfma_sweep selects the backward sweep of
- * the 2nd-order / time systems: 0 = by batch size (one instance per wave on the f64 matrix cores up to two waves per SIMD, 16 lanes per instance
- * with rows in registers beyond), 1 = always the former, 2 = always the latter (the two agree to rounding, not bit for bit); its bits 2-3 select
- * the forward pass of the single-integrator systems the same way (0 = by batch size, 4 = the bandwidth-built k_forward_wg, 8 = the
- * latency-built k_forward_dpp); bits 4-5 the re-roll of the line-search winner on the time systems (0 = by batch size, 16 = k_apply_rows_tm,
- * 32 = k_apply_dpp_tm).  All 0 = the product path. */
-int ilqr_ctx_set_crosscheck(ilqr_ctx* ctx, int generic_kernels, int cp_lane_solve, int cp_general, int mfma_sweep);
+ * cp_general = 1 sends Batch-CP on the constant-dt systems through the general path of the time systems; sweep, forward and reroll pin one
+ * variant each (ILQR_XC_*); a value out of range fails with an error text.  All 0 = the product path.
+ * With all three pins at ILQR_XC_AUTO the product path picks between numerically different (rounding-level) kernels by batch size and the
+ * device's SIMD count: the same instance can give different bits in batches (or shards) of different sizes.  With all three pinned, the
+ * remaining size-dependent choices (the lane grouping of the single-integrator sweep, the two-stream split) are bit-identical. */
+int ilqr_ctx_set_crosscheck(ilqr_ctx* ctx, int generic_kernels, int cp_lane_solve, int cp_general, int sweep, int forward, int reroll);
 const char* ilqr_version(void);
 
 /* ---- a batch of B instances of one System ---------------------------------------------------------------- */

@@ -1,0 +1,216 @@
+// The decision table of plan_riccati (ilqr_planner_amd/csrc/ilqr_plan.hpp): which kernels a Riccati solve runs for a given shape, batch size
+// and pin set.  Host-only (g++); built and run by tests/test_plan_cpu.py.  n_simd = 1024 (MI355X: 256 CUs) throughout.
+#include <cstdio>
+#include <initializer_list>
+
+#include "ilqr_plan.hpp"
+
+using namespace ilqr;
+
+static int fails = 0;
+static const char* where = "";
+#define CHECK(cond)                                                                        \
+    do {                                                                                   \
+        if (!(cond)) { std::printf("FAIL [%s] line %d: %s\n", where, __LINE__, #cond); fails++; } \
+    } while (0)
+
+static PlanIn base(int kind, int nd, bool al, int B) {
+    PlanIn in;
+    in.kind = kind; in.nd = nd; in.al = al; in.B = B; in.n_simd = 1024; in.halves = B >= SPLIT_MIN_BATCH;
+    in.nb_iter = 10; in.uniform_R = true;
+    return in;
+}
+// C3: PosOrn-1 AL, two shared state-only rows, uniform control weights
+static PlanIn c3(int B) {
+    PlanIn in = base(0, 1, true, B);
+    in.m = 2; in.con_state_only = true;
+    return in;
+}
+static PlanIn c2(int B) { return base(0, 1, false, B); }  // PosOrn-1 recursive
+static PlanIn c4(int B) { return base(1, 2, false, B); }  // PosOrnTime-2 recursive
+static PlanIn with_control_row(PlanIn in, int m = 2) { in.m = m; in.con_state_only = false; return in; }
+
+int main() {
+    {
+        where = "C3 4096";
+        const RiccatiPlan p = plan_riccati(c3(4096));
+        CHECK(p.n_alpha == 11);
+        CHECK(p.init == Init::Lti); CHECK(!p.init_al_update);
+        CHECK(p.sweep == Sweep::SiDpp); CHECK(p.si_lanes[0] == 16);
+        CHECK(p.forward == Forward::WaveWg);
+        CHECK(p.apply == Apply::WaveLast); CHECK(p.fused); CHECK(!p.al_update);
+        CHECK(p.kd_sym == 1); CHECK(!p.split); CHECK(!p.needs_ws);
+    }
+    where = "C3 forward threshold";
+    CHECK(plan_riccati(c3(3072)).forward == Forward::WaveDpp);
+    CHECK(plan_riccati(c3(3073)).forward == Forward::WaveWg);
+    where = "C3 si lanes threshold";
+    CHECK(plan_riccati(c3(4096)).si_lanes[0] == 16);
+    CHECK(plan_riccati(c3(4097)).si_lanes[0] == 8);
+    CHECK(plan_riccati(c3(4100)).si_lanes[0] == 8);
+    CHECK(plan_riccati(c3(4100)).sweep == Sweep::SiDpp);
+    {
+        where = "C3, R not uniform";
+        PlanIn in = c3(4096);
+        in.uniform_R = false;
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(p.kd_sym == 0); CHECK(p.fused); CHECK(p.apply == Apply::WaveLast);
+    }
+    {
+        where = "C2 256";
+        const RiccatiPlan p = plan_riccati(c2(256));
+        CHECK(p.sweep == Sweep::SiDpp); CHECK(p.si_lanes[0] == 16);
+        CHECK(p.forward == Forward::WaveDpp); CHECK(p.fused); CHECK(p.apply == Apply::WaveLast);
+        CHECK(p.init == Init::Lti); CHECK(!p.init_al_update); CHECK(!p.al_update);
+    }
+    {
+        where = "C4 4096";
+        const RiccatiPlan p = plan_riccati(c4(4096));
+        CHECK(p.init == Init::Lti); CHECK(!p.init_al_update);
+        CHECK(p.sweep == Sweep::Rows); CHECK(p.forward == Forward::Mfma); CHECK(p.apply == Apply::RerollRows);
+        CHECK(!p.al_update); CHECK(!p.fused); CHECK(p.kd_sym == 0); CHECK(!p.split); CHECK(!p.needs_ws);
+    }
+    {
+        where = "C4 2048";
+        const RiccatiPlan p = plan_riccati(c4(2048));
+        CHECK(p.sweep == Sweep::Mfma); CHECK(p.split); CHECK(p.apply == Apply::RerollRows);
+        CHECK(split_first_half(2048) == 1024);
+    }
+    where = "C4 rows sweep threshold";
+    CHECK(plan_riccati(c4(2048)).sweep == Sweep::Mfma);
+    CHECK(plan_riccati(c4(2049)).sweep == Sweep::Rows);
+    CHECK(!plan_riccati(c4(2049)).split);
+    where = "C4 re-roll threshold";
+    CHECK(plan_riccati(c4(1024)).apply == Apply::RerollDpp);
+    CHECK(plan_riccati(c4(1025)).apply == Apply::RerollRows);
+    CHECK(!plan_riccati(c4(1024)).split);  // no halves below SPLIT_MIN_BATCH
+    {
+        where = "C4, line search off";
+        PlanIn in = c4(4096);
+        in.line_search = false;
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(p.n_alpha == 1); CHECK(p.forward == Forward::Mfma); CHECK(p.apply == Apply::None);
+    }
+    {
+        where = "C4 pins";
+        PlanIn in = c4(4096);
+        in.sweep = SweepPin::Mfma;
+        CHECK(plan_riccati(in).sweep == Sweep::Mfma); CHECK(plan_riccati(in).split);
+        in = c4(256);
+        in.sweep = SweepPin::Rows; in.reroll = RerollPin::Rows;
+        CHECK(plan_riccati(in).sweep == Sweep::Rows); CHECK(plan_riccati(in).apply == Apply::RerollRows);
+        in = c4(4096);
+        in.reroll = RerollPin::Dpp;
+        CHECK(plan_riccati(in).apply == Apply::RerollDpp);
+        in = c3(256);
+        in.forward = FwdPin::Wg;
+        CHECK(plan_riccati(in).forward == Forward::WaveWg);
+        in = c3(4096);
+        in.forward = FwdPin::Dpp;
+        CHECK(plan_riccati(in).forward == Forward::WaveDpp);
+    }
+    for (int B : {256, 4096}) {
+        where = "PosOrnTime AL, m 17";
+        PlanIn in = with_control_row(base(1, 1, true, B), 17);
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(p.sweep == Sweep::Generic); CHECK(p.needs_ws);
+        CHECK(p.forward == Forward::Mfma); CHECK(p.apply == (B == 256 ? Apply::RerollDpp : Apply::RerollRows));
+        CHECK(p.al_update); CHECK(p.init == Init::Lti); CHECK(p.init_al_update); CHECK(!p.split);
+    }
+    for (int B : {256, 4096}) {
+        where = "PosOrn-2 AL, m 16";
+        PlanIn in = with_control_row(base(0, 2, true, B), 16);
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(p.sweep == (B == 256 ? Sweep::Mfma : Sweep::Rows));
+        CHECK(p.forward == Forward::Lin); CHECK(p.apply == Apply::Lin); CHECK(p.al_update);
+        CHECK(p.init == Init::Lti); CHECK(p.init_al_update); CHECK(!p.fused); CHECK(p.kd_sym == 0);
+    }
+    {
+        where = "PosOrn-1 AL with a control row, 4096";
+        const RiccatiPlan p = plan_riccati(with_control_row(c3(4096)));
+        CHECK(p.sweep == Sweep::Mfma); CHECK(p.split);
+        CHECK(p.forward == Forward::WaveWg); CHECK(!p.fused); CHECK(p.apply == Apply::Wave); CHECK(!p.al_update);
+        CHECK(p.kd_sym == 0); CHECK(p.init_al_update); CHECK(!p.needs_ws);
+    }
+    {
+        where = "JointSpace-1 AL with a control row, 256";
+        PlanIn in = with_control_row(base(2, 1, true, 256));
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(p.sweep == Sweep::Generic); CHECK(p.needs_ws);
+        CHECK(p.forward == Forward::WaveDpp); CHECK(!p.fused); CHECK(p.apply == Apply::Wave);
+        CHECK(p.init == Init::Lti); CHECK(p.init_al_update); CHECK(p.kd_sym == 0);
+    }
+    for (int kind = 0; kind < 4; kind++) {
+        for (int generic = 0; generic < 2; generic++) {
+            where = generic ? "pin generic" : "limits2_set";
+            const int nd = kind == 1 ? 2 : 1;
+            PlanIn in = base(kind, nd, true, 4096);
+            in.m = 2; in.con_state_only = true;
+            if (generic) in.generic = true;
+            else in.limits2_set = true;
+            const RiccatiPlan p = plan_riccati(in);
+            CHECK(p.init == Init::Generic); CHECK(!p.init_al_update);
+            CHECK(p.sweep == Sweep::Generic); CHECK(p.needs_ws);
+            CHECK(p.forward == Forward::Generic); CHECK(p.apply == Apply::None); CHECK(!p.al_update);
+            CHECK(!p.fused); CHECK(p.kd_sym == 0); CHECK(!p.split);
+        }
+    }
+    {
+        where = "C3, alpha_floor 1e-6";
+        PlanIn in = c3(4096);
+        in.alpha_floor = 1e-6;
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(p.n_alpha == 21);
+        CHECK(p.init == Init::Lti); CHECK(p.init_al_update);
+        CHECK(p.sweep == Sweep::SiDpp); CHECK(p.forward == Forward::Generic); CHECK(p.apply == Apply::None);
+        CHECK(!p.fused); CHECK(p.kd_sym == 0); CHECK(!p.al_update); CHECK(!p.split);
+    }
+    for (int B : {2048, 4096}) {
+        where = "C3, off32 false";
+        PlanIn in = c3(B);
+        in.off32 = false;
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(p.sweep == Sweep::Mfma); CHECK(p.split); CHECK(!p.fused); CHECK(p.kd_sym == 0); CHECK(p.apply == Apply::Wave);
+    }
+    for (PlanIn in : {c3(4096), c4(2048), with_control_row(base(2, 1, true, 256))}) {
+        where = "nb_iter 0";
+        in.nb_iter = 0;
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(!p.split); CHECK(!p.needs_ws); CHECK(p.kd_sym == KD_SYM_KEEP);
+    }
+    {
+        where = "profiling on";
+        PlanIn in = c4(2048);
+        in.profile = true;
+        CHECK(!plan_riccati(in).split);
+    }
+    {
+        where = "split 0";
+        PlanIn in = c4(2048);
+        in.split = 0;
+        CHECK(!plan_riccati(in).split);
+    }
+    {
+        where = "split 2";
+        PlanIn in = c3(4096);
+        in.split = 2;
+        RiccatiPlan p = plan_riccati(in);
+        CHECK(p.split); CHECK(p.sweep == Sweep::SiDpp); CHECK(p.si_lanes[0] == 16); CHECK(p.si_lanes[1] == 16);
+        in = c3(10000);
+        in.split = 2;
+        p = plan_riccati(in);  // the lane count follows the launched half: 5056 and 4944 instances
+        CHECK(p.split); CHECK(p.si_lanes[0] == 8); CHECK(p.si_lanes[1] == 8);
+        in = c3(8192);
+        in.split = 2;
+        p = plan_riccati(in);  // two halves of 4096
+        CHECK(p.split); CHECK(p.si_lanes[0] == 16); CHECK(p.si_lanes[1] == 16);
+        CHECK(plan_riccati(c3(8192)).si_lanes[0] == 8);  // unsplit
+        in = with_control_row(base(2, 1, true, 4096));
+        in.split = 2;
+        p = plan_riccati(in);
+        CHECK(p.split); CHECK(p.sweep == Sweep::Generic); CHECK(p.needs_ws);
+    }
+    if (fails) { std::printf("%d check(s) failed\n", fails); return 1; }
+    std::printf("ok\n");
+    return 0;
+}

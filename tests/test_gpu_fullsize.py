@@ -230,3 +230,63 @@ def test_sweep_lane_groupings_agree(ctx, cfg_name, solver, monkeypatch):
                                        lambda i: oracle_solve_instance(cfg, inp_s, i, nb_iter, False, segs), always=(0, 1, 2, 3))
     small["p"].close()
     assert not failures, f"{len(failures)} instance(s) neither within 1e-4 nor proven: {failures[:3]}"
+
+
+@pytest.mark.parametrize("first,second", [("v2", "v1"), ("v1", "v2")])
+def test_zero_iteration_solve_keeps_the_gain_layout(ctx, first, second, monkeypatch):
+    """C2 (uniform control weights) writes packed symmetric gain records on the product path and plain ones on the generic kernels.  A solve of
+    0 iterations under the other kernel set runs no sweep: the gains must still be read in the layout of the sweep that wrote them."""
+    from ilqr_planner_amd import workloads
+
+    cfg = dict(workloads.config("C2"), T=40)
+    B = 256
+    desc, inp = workloads.make_batch(ctx, cfg, B=B)
+    p = workloads.load_batch(ctx, desc, inp, B)
+    monkeypatch.setenv("ILQR_HIP_PATH", first)
+    p.solve_recursive(4, True, False)
+    K = p.K()
+    monkeypatch.setenv("ILQR_HIP_PATH", second)
+    p.solve_recursive(0, True, False)
+    K0 = p.K()
+    p.close()
+    assert np.isfinite(K).all() and np.abs(K).max() > 0
+    np.testing.assert_array_equal(K0, K)
+
+
+def test_split_of_the_generic_sweep_does_not_change_results(ctx):
+    """JointSpace-1 AL with a constraint row on the controls takes the generic sweep (an explicit workspace per instance) under the cooperative
+    forward pass; set_split(2) splits it into two halves on two streams, each with its own part of the workspace: bit-identical to unsplit."""
+    from ilqr_planner_amd import workloads
+
+    cfg = dict(workloads.config("C1jal"), T=40)
+    B, nb_iter = 2304, 4
+    desc, inp = workloads.make_batch(ctx, cfg, B=B)
+    n = inp["A"].shape[1] // 2
+    A = np.zeros((2, 2 * n))
+    A[0] = inp["A"][0]
+    A[1, n] = 1.0  # u_0 <= 0.5
+    inp = dict(inp, A=A, b=np.array([inp["b"][0], 0.5]), lambda0=np.concatenate([inp["lambda0"], np.zeros_like(inp["lambda0"])], axis=2))
+    res = {}
+    try:
+        for mode in (0, 2):
+            ctx.set_split(mode)
+            res[mode] = _solve(ctx, cfg, desc, inp, B, nb_iter, "al")
+    finally:
+        ctx.set_split(1)
+    assert np.isfinite(res[0]["cost"]).mean() > 0.99
+    for k in ("cost", "U", "X", "iters", "alpha"):
+        np.testing.assert_array_equal(res[2][k], res[0][k])
+
+
+def test_split_modes_and_variant_pins_are_checked(ctx):
+    """ilqr_ctx_set_split takes 0, 1 or 2 and ilqr_ctx_set_crosscheck pins within ILQR_XC_*; anything else fails with an error text and
+    leaves the context as it was."""
+    with pytest.raises(RuntimeError, match="set_split"):
+        ctx.set_split(3)
+    for args in ((0, 0, 0, 3, 0, 0), (0, 0, 0, 0, -1, 0), (0, 0, 0, 0, 0, 3)):
+        with pytest.raises(RuntimeError, match="set_crosscheck"):
+            ctx.check(ctx.L.ilqr_ctx_set_crosscheck(ctx.h, *args))
+    with pytest.raises(ValueError):
+        ctx.set_crosscheck(sweep="wg")
+    ctx.set_crosscheck(sweep="rows", forward="dpp", reroll="dpp")
+    ctx.set_crosscheck()

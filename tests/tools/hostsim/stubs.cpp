@@ -13,21 +13,16 @@ namespace ilqr {
     std::fprintf(stderr, "hostsim: %s is a cooperative GPU kernel and cannot run on the sanitizer harness (use ILQR_HIP_PATH=v1)\n", what);
     std::abort();
 }
-bool backward_si_supported(int, int, bool, int, int, bool) { return false; }
-bool backward_mfma_supported(int, int, bool, int) { return false; }
-bool forward_lin_supported(int, int, int) { return false; }
-bool forward_wave_supported(int, int, int) { return false; }
-bool init_lti_supported(int, int) { return false; }
-void launch_solver_v2(int, int, int, bool, const Bufs&, int, int, hipStream_t, const FwdArgs&) { refuse("launch_solver_v2"); }
+void launch_al_update(int, int, const Bufs&, int, int, hipStream_t, const FwdArgs&) { refuse("k_al_post"); }
 void launch_backward_si_dpp(bool, bool, bool, int, const Bufs&, int, hipStream_t, const SweepArgs&) { refuse("k_backward_si_dpp"); }
 void launch_backward_mfma(int, int, bool, const Bufs&, int, hipStream_t) { refuse("k_backward_mfma"); }
-bool backward_rows_supported(int, int, bool, int) { return false; }
 void launch_backward_rows(int, int, bool, const Bufs&, int, hipStream_t) { refuse("k_backward_rows"); }
-void launch_apply_rows_tm(int, int, const Bufs&, int, hipStream_t, const FwdArgs&) { refuse("k_apply_rows_tm"); }
-void launch_forward_mfma(int, int, const Bufs&, int, hipStream_t, const FwdArgs&) { refuse("k_forward_mfma"); }
-void launch_forward_lin(int, int, const Bufs&, int, int, hipStream_t, const FwdArgs&) { refuse("k_forward_lin"); }
+void launch_apply_tm(int, int, bool, const Bufs&, int, hipStream_t, const FwdArgs&) { refuse("k_apply_rows_tm"); }
+void launch_forward_tm(int, int, const Bufs&, int, hipStream_t, const FwdArgs&) { refuse("k_forward_mfma"); }
+void launch_forward_lin(const Bufs&, int, hipStream_t, const FwdArgs&) { refuse("k_forward_lin"); }
+void launch_apply_lin(const Bufs&, int, int, hipStream_t) { refuse("k_blend"); }
 void launch_init_lti(int, int, const Bufs&, int, hipStream_t) { refuse("k_init_roll_lti"); }
-void launch_forward_wave(int, const Bufs&, int, hipStream_t, const FwdArgs&) { refuse("k_forward_wg"); }
+void launch_forward_wave(int, bool, const Bufs&, int, hipStream_t, const FwdArgs&) { refuse("k_forward_wg"); }
 void launch_apply_wave(int, const Bufs&, int, int, hipStream_t, const FwdArgs&) { refuse("k_apply"); }
 int batchwide_solve(BatchWideState&, const DevDesc&, Bufs&, int, int, const double*, int, int, int, bool, hipStream_t, std::string&, const ProfHook&) { refuse("batchwide_solve"); }
 void batchwide_free(BatchWideState&) {}
