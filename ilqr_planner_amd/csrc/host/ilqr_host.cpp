@@ -999,7 +999,7 @@ void SequentialSystem::lower(ilqr_problem_desc* d) const {
         const auto& a = subs[i];
         const bool mixed = a.kind != d->kind;
         if (mixed && !(hybrid && is_joint(a.kind) && is_time(a.kind) == is_time(d->kind) && d->nb_deriv == 1 && a.dof == d->dof))
-            throw std::runtime_error("[ilqr_hip] these sub-system kinds cannot be lowered together (joint-space next to PosOrn needs nbDeriv = 1 and 7 joints)");
+            throw std::runtime_error("[ilqr_hip] these sub-system kinds cannot be lowered together (joint-space next to PosOrn needs nbDeriv = 1 and the same joints)");
         if (a.dt != d->dt) throw std::runtime_error("[ilqr_hip] sub-systems of different kinds / dt cannot be lowered");
         if (!a.limits_set) continue;
         if (!first_set) {  // the first limited sub-system defines the first set (the base descriptor may be another sub-system's)
@@ -1156,30 +1156,6 @@ System::StepOut PosOrnPlannerSys::forwardPass(const Vec&, const Vec& uk, int) {
     return std::make_tuple(getState(), std::get<0>(fJ), A, B, std::get<1>(fJ));
 }
 
-// A joint-space descriptor of n < 7 joints widened to the 7 the device kernels are built for: the extra joints get zero precision,
-// zero limit weight and the first joint's control penalty; with u = 0 they stay at rest, so the n-joint problem is unchanged.
-static void pad_joint_desc(ilqr_problem_desc* d, int n, int tm) {
-    if (n >= 7) return;
-    const int D = 7, nu_old = n + tm, nx_old = n + tm, nn = D + tm;
-    double R[ILQR_MAX_NU];
-    for (int i = 0; i < D; i++) R[i] = d->R_diag[i < n ? i : 0];
-    if (tm) R[D] = d->R_diag[nu_old - 1];
-    for (int i = 0; i < nn; i++) d->R_diag[i] = R[i];
-    double smax[ILQR_MAX_NX + 1] = {0}, smin[ILQR_MAX_NX + 1] = {0};
-    int lw[ILQR_MAX_NX + 1] = {0};
-    for (int i = 0; i < n; i++) { smax[i] = d->state_max[i]; smin[i] = d->state_min[i]; lw[i] = d->limit_weight[i]; }
-    for (int i = 0; i < nn; i++) { d->state_max[i] = smax[i]; d->state_min[i] = smin[i]; d->limit_weight[i] = lw[i]; }
-    for (int k = 0; k < d->n_kp; k++) {
-        std::vector<double> Q((size_t)nn * nn, 0.0);
-        auto map = [&](int i) { return i < n ? i : D; };  // user index -> device index (the time entry moves to the end)
-        for (int a = 0; a < nx_old; a++)
-            for (int b = 0; b < nx_old; b++) Q[(size_t)map(a) * nn + map(b)] = d->kp_Q[k][a * nx_old + b];
-        for (int i = 0; i < nn * nn; i++) d->kp_Q[k][i] = Q[i];
-    }
-    d->dof = D;
-    d->n_seg = 0;
-}
-
 // ---- AngularKeypoint (AngularKeypoint.cpp:15-27), JointSpacePlannerSys (JointSpacePlannerSys.cpp:50-122)
 Vec AngularKeypoint::getState() const {
     Vec st = position_;
@@ -1236,8 +1212,7 @@ System::StepOut JointSpacePlannerSys::forwardPass(const Vec&, const Vec& uk, int
 void JointSpacePlannerSys::lower(ilqr_problem_desc* d) const {
     if (nb_deriv_ != 1) throw std::runtime_error("[ilqr_hip] JointSpacePlannerSys is lowered for nbDeriv = 1 only (the 2nd-order variant is inconsistent upstream)");
     if (r->getDOF() > 7) throw std::runtime_error("[ilqr_hip] joint-space systems are lowered for at most 7 joints");
-    System::lower(d);  // f(x) = x needs no chain, but a KDLRobot's chain is kept for ilqr_fk_batch users
-    pad_joint_desc(d, r->getDOF(), 0);
+    System::lower(d);  // f(x) = x needs no chain, but a KDLRobot's chain is kept for ilqr_fk_batch users; fewer than 7 joints: widened by the C ABI
 }
 
 // ---- AngularTimeKeypoint (AngularTimeKeypoint.cpp:15-30), JointSpaceTimePlannerSys (JointSpaceTimePlannerSys.cpp:50-160)
@@ -1301,8 +1276,7 @@ System::StepOut JointSpaceTimePlannerSys::forwardPass(const Vec&, const Vec& uk,
 void JointSpaceTimePlannerSys::lower(ilqr_problem_desc* d) const {
     if (nb_deriv_ != 1) throw std::runtime_error("[ilqr_hip] JointSpaceTimePlannerSys is lowered for nbDeriv = 1 only");
     if (r->getDOF() > 7) throw std::runtime_error("[ilqr_hip] joint-space systems are lowered for at most 7 joints");
-    System::lower(d);
-    pad_joint_desc(d, r->getDOF(), 1);
+    System::lower(d);  // fewer than 7 joints: widened by the C ABI
 }
 
 PosOrnTimePlannerSys::PosOrnTimePlannerSys(const std::shared_ptr<sim::SimulationInterface>& r, const std::vector<std::shared_ptr<Keypoint>>& kps, const Vec& Rt,
@@ -1405,68 +1379,6 @@ static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter,
     ilqr_ctx* ctx = device_context();
     const int B = in.B, T = d.horizon, dof = d.dof;
     if (B <= 0) throw std::runtime_error("[ilqr_hip] batch must be positive");
-    static thread_local bool widened = false;  // set while the widened problem of a padded joint-space system runs
-    const int padn = widened ? 0 : s.paddedFromDof();  // joint-space system of padn < 7 joints: inputs widened, outputs narrowed again
-    if (padn > 0) {
-        const int tm = (d.kind == ILQR_SYS_JOINT_TIME) ? 1 : 0, D = 7, wo = padn + tm, wn = D + tm;
-        auto widen = [&](const std::vector<double>& v, size_t rows) {  // [rows][wo] -> [rows][wn], the time entry moves to the end
-            std::vector<double> o(rows * wn, 0.0);
-            for (size_t r_ = 0; r_ < rows; r_++) {
-                for (int i = 0; i < padn; i++) o[r_ * wn + i] = v[r_ * wo + i];
-                if (tm) o[r_ * wn + D] = v[r_ * wo + padn];
-            }
-            return o;
-        };
-        auto narrow = [&](const std::vector<double>& v, size_t rows) {
-            std::vector<double> o(rows * wo, 0.0);
-            for (size_t r_ = 0; r_ < rows; r_++) {
-                for (int i = 0; i < padn; i++) o[r_ * wo + i] = v[r_ * wn + i];
-                if (tm) o[r_ * wo + padn] = v[r_ * wn + D];
-            }
-            return o;
-        };
-        BatchInputs in2 = in;
-        auto pad_q = [&](const std::vector<double>& v, const Vec& dflt) {
-            std::vector<double> src = v;
-            if (src.empty()) for (int b_ = 0; b_ < B; b_++) src.insert(src.end(), dflt.begin(), dflt.end());
-            std::vector<double> o((size_t)B * D, 0.0);
-            for (int b_ = 0; b_ < B; b_++) for (int i = 0; i < padn; i++) o[(size_t)b_ * D + i] = src[(size_t)b_ * padn + i];
-            return o;
-        };
-        in2.q0 = pad_q(in.q0, s.q0());
-        in2.dq0 = pad_q(in.dq0, s.dq0());
-        const auto& kps_ = s.getKeypoints();
-        in2.kp_targets.assign(kps_.size(), {});
-        for (size_t k = 0; k < kps_.size(); k++) {
-            std::vector<double> tg = (k < in.kp_targets.size() && !in.kp_targets[k].empty()) ? in.kp_targets[k] : std::vector<double>();
-            if (tg.empty()) for (int b_ = 0; b_ < B; b_++) { const Vec t_ = kps_[k]->targetFx(); tg.insert(tg.end(), t_.begin(), t_.end()); }
-            in2.kp_targets[k] = widen(tg, B);
-        }
-        const size_t nUo = (size_t)(T - 1) * wo;
-        std::vector<double> U0o = in.U0;
-        if (U0o.size() == nUo) { std::vector<double> t_; for (int b_ = 0; b_ < B; b_++) t_.insert(t_.end(), in.U0.begin(), in.U0.end()); U0o = t_; }
-        if (U0o.size() != nUo * B) throw std::runtime_error("[ilqr_hip] U0 must be (T-1) x nb_ctrl_var per instance");
-        in2.U0 = widen(U0o, (size_t)B * (T - 1));
-        // run on the widened problem (the descriptor is already widened by lower()), then narrow the outputs
-        widened = true;
-        BatchResult r;
-        try { r = run_batch(s, in2, nb_iter, gains, &d, pre_solve, solve, post_solve); } catch (...) { widened = false; throw; }
-        widened = false;
-        r.X = narrow(r.X, (size_t)B * T);
-        r.U = narrow(r.U, (size_t)B * (T - 1));
-        if (!r.fX.empty()) r.fX = narrow(r.fX, (size_t)B * T);
-        if (!r.d.empty()) r.d = narrow(r.d, (size_t)B * (T - 1));
-        if (!r.K.empty()) {  // [B][T-1][wn][wn] -> [B][T-1][wo][wo]
-            std::vector<double> Ko((size_t)B * (T - 1) * wo * wo, 0.0);
-            auto map = [&](int i) { return i < padn ? i : D; };
-            for (size_t m_ = 0; m_ < (size_t)B * (T - 1); m_++)
-                for (int a_ = 0; a_ < wo; a_++)
-                    for (int b_ = 0; b_ < wo; b_++) Ko[(m_ * wo + a_) * wo + b_] = r.K[(m_ * wn + map(a_)) * wn + map(b_)];
-            r.K = Ko;
-        }
-        r.n_x = r.n_u = r.n_f = wo;
-        return r;
-    }
     ProblemGuard g;
     check(ilqr_problem_create(ctx, &d, B, &g.p));
     auto tile = [&](const Vec& v, size_t per) {

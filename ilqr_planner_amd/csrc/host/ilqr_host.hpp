@@ -307,9 +307,6 @@ public:
     Vec q0() const { return q0_; }
     Vec dq0() const { return dq0_; }
     int getNbDeriv() const { return nb_deriv_; }
-    // joint-space systems of robots with fewer than 7 joints are padded to the device's 7 (zero precision, zero limit weight, u = 0):
-    // number of joints the user sees, 0 = no padding
-    virtual int paddedFromDof() const { return 0; }
     // true for the system classes of this header exactly as declared here (with built-in keypoints): the shapes the device descriptor
     // describes.  A user-defined subclass -- also one derived from a built-in class -- answers false and is solved over its virtuals by
     // ILQRRecursive::solve (ilqr_host_loop.cpp); the choice is made on the type, never on whether a device call succeeded.
@@ -353,8 +350,8 @@ protected:
     void localInit(double dt);
 };
 
-// Target space = joint space, J = I (JointSpacePlannerSys.h / .cpp:50-122).  Device path: nb_deriv = 1 and the 7 joints the
-// kernels are built for (the reference's 2nd-order variant is dimensionally inconsistent).
+// Target space = joint space, J = I (JointSpacePlannerSys.h / .cpp:50-122).  Device path: nb_deriv = 1 (the reference's 2nd-order variant is
+// dimensionally inconsistent) and 1 to 7 joints (the C ABI widens a shorter chain to the 7 the kernels are built for).
 class JointSpacePlannerSys : public System {
 public:
     bool builtinType() const override { return typeid(*this) == typeid(JointSpacePlannerSys); }
@@ -370,13 +367,13 @@ public:
     std::tuple<Vec, Mat> getFxJac() override;
     using System::getFxJac;
     void lower(ilqr_problem_desc* d) const override;
-    int paddedFromDof() const override { return r->getDOF() < 7 ? r->getDOF() : 0; }
 
 protected:
     void localInit(double dt);
 };
 
-// JointSpacePlannerSys with a time state and dt = u_last^2 (JointSpaceTimePlannerSys.h / .cpp:50-160); nb_deriv = 1, 7 joints on the device
+// JointSpacePlannerSys with a time state and dt = u_last^2 (JointSpaceTimePlannerSys.h / .cpp:50-160); nb_deriv = 1, 1 to 7 joints (widened
+// to 7 by the C ABI)
 class JointSpaceTimePlannerSys : public System {
 public:
     bool builtinType() const override { return typeid(*this) == typeid(JointSpaceTimePlannerSys); }
@@ -392,7 +389,6 @@ public:
     std::tuple<Vec, Mat> getFxJac() override;
     std::tuple<Vec, Mat> getFxJac(const Vec& xk) override;
     void lower(ilqr_problem_desc* d) const override;
-    int paddedFromDof() const override { return r->getDOF() < 7 ? r->getDOF() : 0; }
 
 protected:
     void localInit();

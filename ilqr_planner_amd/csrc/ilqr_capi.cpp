@@ -47,8 +47,12 @@ struct ilqr_ctx {
 
 struct ilqr_problem {
     ilqr_ctx* ctx = nullptr;
-    ilqr_problem_desc desc;
-    ilqr_dims dims;
+    ilqr_problem_desc desc;  // as given: the user's dof
+    ilqr_dims udims;         // the user's dimensions: every array crossing the ABI
+    ilqr_dims dims;          // the device's (7 joints): every device buffer
+    DofMap map;              // user index -> device index (ilqr_dofmap.hpp)
+    bool mapped = false;     // dof < 7: the layout conversions go through `map`; a 7-joint problem takes the plain ones
+    IndexMap qmap;           // q0 / dq0: [dof] -> [7]
     int B = 0, Bp = 0, T = 0;
     DevDesc hdesc;
     DevDesc* ddesc = nullptr;
@@ -258,9 +262,17 @@ static void mat3(const double* A, const double* B, double* C) {
         for (int j = 0; j < 3; j++) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
 }
 
-// Fold runs of fixed segments into the following joint's pre-transform; the rest becomes the tail.
+static_assert(DOF == DEV_DOF, "ilqr_dofmap.hpp and ilqr_device.hpp");
+
+static int check_dof(ilqr_ctx* c, int dof) {
+    if (dof < 1 || dof > DOF) return fail(c, "chains of 1 to 7 moving joints are supported (dof = " + std::to_string(dof) + ")");
+    return 0;
+}
+
+// Fold runs of fixed segments into the following joint's pre-transform; the rest becomes the tail.  A chain of dof < 7 joints gets 7 - dof
+// inert joints behind its last one (identity pre-transform, zero offset, zero axis; ilqr_dofmap.hpp): at q = 0 they are the identity exactly.
 static int lower_chain(ilqr_ctx* c, const ilqr_problem_desc& d, DevChain& ch) {
-    if (d.dof != DOF) return fail(c, "device path supports chains with exactly 7 moving joints (got " + std::to_string(d.dof) + ")");
+    if (check_dof(c, d.dof)) return 1;
     if (d.n_seg < 1 || d.n_seg > ILQR_MAX_SEG) return fail(c, "bad n_seg");
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
     int nj = 0;
@@ -271,7 +283,8 @@ static int lower_chain(ilqr_ctx* c, const ilqr_problem_desc& d, DevChain& ch) {
         std::memcpy(R, Rn, sizeof(R));
         const int j = d.seg_joint[s];
         if (j >= 0) {
-            if (j != nj || nj >= DOF) return fail(c, "moving joints must be numbered 0..dof-1 in chain order");
+            if (j != nj) return fail(c, "moving joints must be numbered 0..dof-1 in chain order");
+            if (nj >= DOF) return fail(c, "chain has more than 7 moving joints (chains of 1 to 7 moving joints are supported)");
             std::memcpy(ch.Rpre[nj], R, sizeof(R));
             std::memcpy(ch.ppre[nj], p, sizeof(p));
             std::memcpy(ch.axis[nj], d.seg_axis[s], 3 * sizeof(double));
@@ -281,20 +294,32 @@ static int lower_chain(ilqr_ctx* c, const ilqr_problem_desc& d, DevChain& ch) {
             p[0] = p[1] = p[2] = 0;
         }
     }
-    if (nj != DOF) return fail(c, "chain has " + std::to_string(nj) + " moving joints, descriptor says " + std::to_string(d.dof));
+    if (nj != d.dof)
+        return fail(c, "chain has " + std::to_string(nj) + " moving joints, descriptor says " + std::to_string(d.dof) + " (chains of 1 to 7 moving joints are supported)");
+    for (int j = nj; j < DOF; j++) {
+        const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        std::memcpy(ch.Rpre[j], I, sizeof(I));
+        for (int i = 0; i < 3; i++) ch.ppre[j][i] = ch.axis[j][i] = 0.0;
+    }
     std::memcpy(ch.Rtail, R, sizeof(R));
     std::memcpy(ch.ptail, p, sizeof(p));
     return 0;
 }
 
-static int lower_desc(ilqr_ctx* c, const ilqr_problem_desc& d, int B, int Bp, DevDesc& h) {
+// Every per-joint field goes through the map m (identity for 7 joints): padded control weights are the first joint's (a uniform R stays
+// uniform, so plan_riccati decides as for 7 joints), padded limits and precisions are 0.
+static int lower_desc(ilqr_ctx* c, const ilqr_problem_desc& d, const DofMap& m, int B, int Bp, DevDesc& h) {
     ilqr_dims dm;
     if (ilqr_dims_of(&d, &dm)) return fail(c, "unsupported system kind / nb_deriv");
+    const IndexMap &mx = m.x, &mu = m.u;
+    auto xs = [&](const double* v, int j) { return mx.usr[j] < 0 ? 0.0 : v[mx.usr[j]]; };
+    auto xi = [&](const int* v, int j) { return mx.usr[j] < 0 ? 0 : v[mx.usr[j]]; };
+    auto us = [&](const double* v, int j) { return v[mu.usr[j] < 0 ? 0 : mu.usr[j]]; };
     std::memset(&h, 0, sizeof(h));
     if (!((d.kind == ILQR_SYS_JOINT || d.kind == ILQR_SYS_JOINT_TIME) && d.n_seg == 0) && lower_chain(c, d, h.chain)) return 1;  // joint-space systems need no chain
     if (d.horizon < 2) return fail(c, "horizon must be >= 2");
     h.kind = d.kind; h.nd = d.nb_deriv; h.T = d.horizon; h.B = B; h.Bp = Bp; h.dt = d.dt;
-    for (int i = 0; i < dm.n_u; i++) h.R_diag[i] = d.R_diag[i];
+    for (int j = 0; j < mu.n_dev; j++) h.R_diag[j] = us(d.R_diag, j);
     {   // SequentialSystem: every sub-system adds the limit terms once -- q'Lq and L'q scale with the multiplicity, L'L too
         const double mult = d.limit_multiplicity > 1 ? (double)d.limit_multiplicity : 1.0;
         h.limits_set = d.limits_set;
@@ -306,10 +331,10 @@ static int lower_desc(ilqr_ctx* c, const ilqr_problem_desc& d, int B, int Bp, De
             const double mult2 = d.limit_multiplicity2 > 1 ? (double)d.limit_multiplicity2 : 1.0;
             h.penalty2 = d.penalty2 * mult2;
             h.pen_xx2 = d.penalty2 * d.penalty2 * mult2;
-            for (int i = 0; i < dm.n_x; i++) { h.smax2[i] = d.state_max2[i]; h.smin2[i] = d.state_min2[i]; h.lw2[i] = d.limit_weight2[i]; }
+            for (int j = 0; j < mx.n_dev; j++) { h.smax2[j] = xs(d.state_max2, j); h.smin2[j] = xs(d.state_min2, j); h.lw2[j] = xi(d.limit_weight2, j); }
         }
     }
-    for (int i = 0; i < dm.n_x; i++) { h.smax[i] = d.state_max[i]; h.smin[i] = d.state_min[i]; h.lw[i] = d.limit_weight[i]; }
+    for (int j = 0; j < mx.n_dev; j++) { h.smax[j] = xs(d.state_max, j); h.smin[j] = xs(d.state_min, j); h.lw[j] = xi(d.limit_weight, j); }
     if (d.n_kp < 0 || d.n_kp > ILQR_MAX_KP) return fail(c, "bad n_kp");
     h.n_kp = d.n_kp;
     for (int k = 0; k < d.n_kp; k++) {
@@ -320,14 +345,19 @@ static int lower_desc(ilqr_ctx* c, const ilqr_problem_desc& d, int B, int Bp, De
             return fail(c, "kp_joint is for PosOrn / PosOrnTime systems with nb_deriv = 1 (a joint-space system needs no flag)");
         if (d.kp_joint[k] && (d.kp_dist[k] || d.kp_has_frame[k])) return fail(c, "a joint-space keypoint has no dead zone and no object frame");
         h.kp_joint[k] = d.kp_joint[k];
-        const int nqk = d.kp_joint[k] ? dm.n_x : dm.n_Q;
-        for (int i = 0; i < nqk * nqk; i++) h.kp_Q[k][i] = d.kp_Q[k][i];
+        if (d.kp_joint[k] || d.kind == ILQR_SYS_JOINT || d.kind == ILQR_SYS_JOINT_TIME) {  // n_x x n_x precision: padded rows and columns 0
+            for (int a = 0; a < mx.n_dev; a++)
+                for (int b = 0; b < mx.n_dev; b++)
+                    h.kp_Q[k][a * mx.n_dev + b] = (mx.usr[a] < 0 || mx.usr[b] < 0) ? 0.0 : d.kp_Q[k][mx.usr[a] * mx.n_user + mx.usr[b]];
+        } else {  // PosOrn residual space: n_Q does not depend on dof
+            for (int i = 0; i < dm.n_Q * dm.n_Q; i++) h.kp_Q[k][i] = d.kp_Q[k][i];
+        }
         h.kp_dist[k] = d.kp_dist[k];
         h.kp_frame[k] = d.kp_has_frame[k];
         for (int i = 0; i < 9; i++) h.kp_fR[k][i] = d.kp_frame_R[k][i];
         for (int i = 0; i < 3; i++) h.kp_fp[k][i] = d.kp_frame_p[k][i];
         h.kp_has_Ru[k] = d.kp_has_Ru[k];
-        for (int i = 0; i < dm.n_u; i++) h.kp_Ru[k][i] = d.kp_Ru[k][i];
+        for (int j = 0; j < mu.n_dev; j++) h.kp_Ru[k][j] = us(d.kp_Ru[k], j);
         h.kp_pos_radius[k] = d.kp_pos_radius[k];
         for (int i = 0; i < 3; i++) h.kp_orn_thresh[k][i] = d.kp_orn_thresh[k][i];
     }
@@ -368,7 +398,18 @@ extern "C" int ilqr_problem_create(ilqr_ctx* c, const ilqr_problem_desc* d, int 
     // of a K block onto the same L2 sets / HBM channel; one extra 64-instance pad column breaks the alignment.
     if (p->Bp % 512 == 0) p->Bp += 64;
     p->T = d->horizon;
-    if (ilqr_dims_of(d, &p->dims) || lower_desc(c, *d, p->B, p->Bp, p->hdesc)) { delete p; return 1; }
+    if (ilqr_dims_of(d, &p->udims)) { delete p; return fail(c, "unsupported system kind / nb_deriv"); }
+    if (check_dof(c, d->dof) || !dof_map(d->kind, d->nb_deriv, d->dof, p->map)) { delete p; return 1; }
+    {   // the device's dimensions: those of the same problem with 7 joints
+        ilqr_problem_desc d7 = *d;
+        d7.dof = DOF;
+        (void)ilqr_dims_of(&d7, &p->dims);
+    }
+    p->mapped = !p->map.identity();
+    p->qmap.n_user = d->dof; p->qmap.n_dev = DOF;
+    for (int i = 0; i < MAP_MAX; i++) p->qmap.dev[i] = i < d->dof ? i : -1;
+    index_map_fill_usr(p->qmap);
+    if (lower_desc(c, *d, p->map, p->B, p->Bp, p->hdesc)) { delete p; return 1; }
     const int T = p->T, NX = p->dims.n_x, NU = p->dims.n_u, NF = p->dims.n_f, Bp = p->Bp;
     std::memset(&p->bufs, 0, sizeof(p->bufs));
     Bufs& b = p->bufs;
@@ -436,8 +477,9 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     delete p;
 }
 
-// natural [B][rows] host or device array -> SoA [rows][Bp] device buffer
-static int upload(ilqr_problem* p, const double* src, bool src_is_dev, double* dst, int rows) {
+// natural [B][rows] host or device array -> SoA [rows][Bp] device buffer; with a map m: natural [B][outer][m->n_user] -> [outer][m->n_dev][Bp]
+// (rows = outer * m->n_user), the padding written as 0
+static int upload(ilqr_problem* p, const double* src, bool src_is_dev, double* dst, int rows, const IndexMap* m = nullptr, int outer = 0) {
     ilqr_ctx* c = p->ctx;
     const size_t n = (size_t)p->B * rows;
     const double* dsrc = src;
@@ -446,7 +488,8 @@ static int upload(ilqr_problem* p, const double* src, bool src_is_dev, double* d
         HIPCHK(c, hipMemcpyAsync(p->staging, src, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         dsrc = p->staging;
     }
-    launch_to_soa(dsrc, dst, p->B, p->Bp, rows, c->stream);
+    if (m) launch_to_soa_map(dsrc, dst, p->B, p->Bp, outer, *m, c->stream);
+    else launch_to_soa(dsrc, dst, p->B, p->Bp, rows, c->stream);
     HIPCHK(c, hipGetLastError());
     if (!src_is_dev) HIPCHK(c, hipStreamSynchronize(c->stream));  // staging is reused; the host buffer may go away
     return 0;
@@ -455,9 +498,10 @@ static int upload(ilqr_problem* p, const double* src, bool src_is_dev, double* d
 static int set_init_state(ilqr_problem* p, const double* q0, const double* dq0, bool dev) {
     if (!p) return 1;
     if (!q0) return fail(p->ctx, "q0 is required");
-    if (upload(p, q0, dev, (double*)p->bufs.q0, DOF)) return 1;
+    const IndexMap* qm = p->mapped ? &p->qmap : nullptr;
+    if (upload(p, q0, dev, (double*)p->bufs.q0, p->desc.dof, qm, 1)) return 1;
     if (dq0) {
-        if (upload(p, dq0, dev, (double*)p->bufs.dq0, DOF)) return 1;
+        if (upload(p, dq0, dev, (double*)p->bufs.dq0, p->desc.dof, qm, 1)) return 1;
     } else {
         HIPCHK(p->ctx, hipMemsetAsync((void*)p->bufs.dq0, 0, sizeof(double) * DOF * p->Bp, p->ctx->stream));
     }
@@ -470,7 +514,14 @@ extern "C" int ilqr_problem_set_init_state_dev(ilqr_problem* p, const double* q0
 static int set_kp(ilqr_problem* p, int k, const double* tg, bool dev) {
     if (!p) return 1;
     if (k < 0 || k >= p->desc.n_kp || !tg) return fail(p->ctx, "bad keypoint index / null target");
-    return upload(p, tg, dev, (double*)p->bufs.kp_tg + (size_t)k * p->dims.n_f * p->Bp, p->dims.n_f);
+    double* dst = (double*)p->bufs.kp_tg + (size_t)k * p->dims.n_f * p->Bp;
+    if (p->mapped && (p->desc.kind == ILQR_SYS_JOINT || p->desc.kind == ILQR_SYS_JOINT_TIME))  // the target is a state
+        return upload(p, tg, dev, dst, p->udims.n_f, &p->map.x, 1);
+    if (p->mapped && p->desc.kp_joint[k]) {  // joint vector (+ time) in the first n_x of the n_f slots
+        const IndexMap tm = joint_target_map(p->map, p->dims.n_f);
+        return upload(p, tg, dev, dst, p->udims.n_f, &tm, 1);
+    }
+    return upload(p, tg, dev, dst, p->udims.n_f);
 }
 extern "C" int ilqr_problem_set_keypoint_targets(ilqr_problem* p, int k, const double* tg) { return set_kp(p, k, tg, false); }
 extern "C" int ilqr_problem_set_keypoint_targets_dev(ilqr_problem* p, int k, const double* tg) { return set_kp(p, k, tg, true); }
@@ -478,11 +529,11 @@ extern "C" int ilqr_problem_set_keypoint_targets_dev(ilqr_problem* p, int k, con
 static int set_controls(ilqr_problem* p, const double* U0, bool dev) {
     if (!p) return 1;
     if (!U0) return fail(p->ctx, "U0 is required");
-    if (upload(p, U0, dev, (double*)p->bufs.U0, (p->T - 1) * p->dims.n_u)) return 1;
+    if (upload(p, U0, dev, (double*)p->bufs.U0, (p->T - 1) * p->udims.n_u, p->mapped ? &p->map.u : nullptr, p->T - 1)) return 1;
     p->has_controls = true;
     p->u0_zero = false;
     if (!dev) {
-        const size_t n = (size_t)p->B * (p->T - 1) * p->dims.n_u;
+        const size_t n = (size_t)p->B * (p->T - 1) * p->udims.n_u;
         size_t i = 0;
         while (i < n && U0[i] == 0.0) i++;
         p->u0_zero = (i == n);
@@ -496,7 +547,7 @@ extern "C" int ilqr_problem_set_constraints(ilqr_problem* p, int m, int per_step
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
     if (m <= 0 || !A || !b) return fail(c, "bad constraint arguments");
-    const int ns = p->dims.n_x + p->dims.n_u, T = p->T;
+    const int ns = p->dims.n_x + p->dims.n_u, T = p->T, nsu = p->udims.n_x + p->udims.n_u;
     const size_t nk = per_step ? (size_t)(T - 1) : 1;
     if (p->bufs.m != m || p->bufs.per_step != per_step || !p->conA) {
         if (p->conA) {  // another shape: release the previous constraint buffers (nothing in flight may still read them)
@@ -518,14 +569,23 @@ extern "C" int ilqr_problem_set_constraints(ilqr_problem* p, int m, int per_step
         p->bufs.Is = Is;
         if (dalloc(p, &p->lambda0, (size_t)(T - 1) * m * p->Bp)) return 1;
     }
-    HIPCHK(c, hipMemcpyAsync(p->conA, A, nk * m * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    std::vector<double> Aw;  // columns of the [x; u] layout through the map: padded columns 0
+    if (p->mapped) {
+        const IndexMap &mx = p->map.x, &mu = p->map.u;
+        Aw.assign(nk * m * ns, 0.0);
+        for (size_t r = 0; r < nk * m; r++) {
+            for (int j = 0; j < mx.n_user; j++) Aw[r * ns + mx.dev[j]] = A[r * nsu + j];
+            for (int i = 0; i < mu.n_user; i++) Aw[r * ns + mx.n_dev + mu.dev[i]] = A[r * nsu + mx.n_user + i];
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(p->conA, p->mapped ? Aw.data() : A, nk * m * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(p->conb, b, nk * m * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     p->bufs.m = m; p->bufs.per_step = per_step; p->bufs.conA = p->conA; p->bufs.conb = p->conb;
     p->con_state_only = true;
     for (size_t k = 0; k < nk * m; k++)
-        for (int j = p->dims.n_x; j < ns; j++)
-            if (A[k * ns + j] != 0.0) p->con_state_only = false;
+        for (int j = p->udims.n_x; j < nsu; j++)
+            if (A[k * nsu + j] != 0.0) p->con_state_only = false;
     if (lambda0) {
         if (upload(p, lambda0, false, p->bufs.lambda, (T - 1) * m)) return 1;
     } else {
@@ -587,7 +647,7 @@ static PlanIn plan_input(const ilqr_problem* p, bool al, int nb_iter, int line_s
     in.kind = p->desc.kind; in.nd = p->desc.nb_deriv; in.al = al; in.m = p->bufs.m; in.per_step = p->bufs.per_step; in.con_state_only = p->con_state_only;
     in.limits2_set = p->desc.limits2_set != 0;
     in.uniform_R = true;
-    for (int i = 1; i < p->dims.n_u; i++) in.uniform_R = in.uniform_R && (p->desc.R_diag[i] == p->desc.R_diag[0]);
+    for (int i = 1; i < p->dims.n_u; i++) in.uniform_R = in.uniform_R && (p->hdesc.R_diag[i] == p->hdesc.R_diag[0]);
     // the register-resident sweep addresses x, u and the multipliers with 32-bit byte offsets (ilqr_kernels_dpp.hip): batches whose arrays pass
     // 4 GiB (T * Bp beyond ~38 M) take the other sweeps
     in.off32 = (size_t)2 * T * p->dims.n_x * p->Bp * 8 < ((size_t)1 << 32) && (size_t)T * (p->bufs.m > 0 ? p->bufs.m : 1) * p->Bp * 8 < ((size_t)1 << 32);
@@ -740,6 +800,15 @@ extern "C" int ilqr_solve_batch_cp(ilqr_problem* p, const double* psi, int Kw, i
     if (ensure_trace(p, nb_iter)) return 1;
     p->last_nb_iter = nb_iter;
     const bool cp_time = p->desc.kind == ILQR_SYS_POS_ORN_TIME || p->desc.kind == ILQR_SYS_JOINT_TIME;
+    std::vector<double> psiw;  // PSI on the device's controls: zero rows for the padded ones (they never move)
+    if (psi && Kw > 0 && p->mapped) {
+        const IndexMap& mu = p->map.u;
+        psiw.assign((size_t)(p->T - 1) * mu.n_dev * Kw, 0.0);
+        for (int k = 0; k < p->T - 1; k++)
+            for (int i = 0; i < mu.n_user; i++)
+                std::memcpy(&psiw[((size_t)k * mu.n_dev + mu.dev[i]) * Kw], psi + ((size_t)k * mu.n_user + i) * Kw, sizeof(double) * Kw);
+        psi = psiw.data();
+    }
     if (psi && Kw > 16 && !(cp_time && Kw <= 32)) {  // wide basis: low-rank form of the normal equations (ilqr_batchwide.hip)
         if (batchwide_solve(p->cpw, p->hdesc, p->bufs, p->dims.n_x, p->dims.n_u, psi, Kw, nb_iter, early_stop, p->u0_zero, c->stream, err, prof_hook(c))) return fail(c, err);
         prof_mark(c, -1);
@@ -768,7 +837,9 @@ extern "C" int ilqr_solve_batch(ilqr_problem* p, int nb_iter, int early_stop) {
 // ------------------------------------------------------------------------------------------------ results
 
 enum { GET_PLAIN, GET_CUR, GET_SCALED };
-static int download(ilqr_problem* p, int mode, const double* s0, const double* s1, double* dst, bool dst_is_dev, int rows) {
+// SoA [rows][Bp] -> natural [B][rows]; with a map m (GET_CUR only): [outer][m->n_dev][Bp] -> natural [B][outer][m->n_user], rows = outer * m->n_user
+static int download(ilqr_problem* p, int mode, const double* s0, const double* s1, double* dst, bool dst_is_dev, int rows, const IndexMap* m = nullptr,
+                    int outer = 0) {
     ilqr_ctx* c = p->ctx;
     if (!dst) return fail(c, "null output pointer");
     const size_t n = (size_t)p->B * rows;
@@ -777,7 +848,8 @@ static int download(ilqr_problem* p, int mode, const double* s0, const double* s
         if (ensure_staging(p, n)) return 1;
         ddst = p->staging;
     }
-    if (mode == GET_CUR) launch_from_soa_cur(s0, s1, p->bufs.cur, ddst, p->B, p->Bp, rows, c->stream);
+    if (m) launch_from_soa_cur_map(s0, s1, p->bufs.cur, ddst, p->B, p->Bp, outer, *m, c->stream);
+    else if (mode == GET_CUR) launch_from_soa_cur(s0, s1, p->bufs.cur, ddst, p->B, p->Bp, rows, c->stream);
     else if (mode == GET_SCALED) launch_from_soa_scaled(s0, p->bufs.alpha, p->bufs.iters, ddst, p->B, p->Bp, rows, c->stream);
     else launch_from_soa(s0, ddst, p->B, p->Bp, rows, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -788,19 +860,32 @@ static int download(ilqr_problem* p, int mode, const double* s0, const double* s
     return 0;
 }
 
-extern "C" int ilqr_problem_get_X(ilqr_problem* p, double* X) { return p ? download(p, GET_CUR, p->bufs.X[0], p->bufs.X[1], X, false, p->T * p->dims.n_x) : 1; }
-extern "C" int ilqr_problem_get_U(ilqr_problem* p, double* U) { return p ? download(p, GET_CUR, p->bufs.U[0], p->bufs.U[1], U, false, (p->T - 1) * p->dims.n_u) : 1; }
-extern "C" int ilqr_problem_get_X_dev(ilqr_problem* p, double* X) { return p ? download(p, GET_CUR, p->bufs.X[0], p->bufs.X[1], X, true, p->T * p->dims.n_x) : 1; }
-extern "C" int ilqr_problem_get_U_dev(ilqr_problem* p, double* U) { return p ? download(p, GET_CUR, p->bufs.U[0], p->bufs.U[1], U, true, (p->T - 1) * p->dims.n_u) : 1; }
+static int get_X(ilqr_problem* p, double* X, bool dev) {
+    if (!p) return 1;
+    return download(p, GET_CUR, p->bufs.X[0], p->bufs.X[1], X, dev, p->T * p->udims.n_x, p->mapped ? &p->map.x : nullptr, p->T);
+}
+static int get_U(ilqr_problem* p, double* U, bool dev) {
+    if (!p) return 1;
+    return download(p, GET_CUR, p->bufs.U[0], p->bufs.U[1], U, dev, (p->T - 1) * p->udims.n_u, p->mapped ? &p->map.u : nullptr, p->T - 1);
+}
+extern "C" int ilqr_problem_get_X(ilqr_problem* p, double* X) { return get_X(p, X, false); }
+extern "C" int ilqr_problem_get_U(ilqr_problem* p, double* U) { return get_U(p, U, false); }
+extern "C" int ilqr_problem_get_X_dev(ilqr_problem* p, double* X) { return get_X(p, X, true); }
+extern "C" int ilqr_problem_get_U_dev(ilqr_problem* p, double* U) { return get_U(p, U, true); }
 static int get_gains(ilqr_problem* p, double* K, double* d) {
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
     double* dst = K ? K : d;
     if (!dst) return fail(c, "null output pointer");
     const int T1 = p->T - 1, nu = p->dims.n_u, nx = p->dims.n_x;
-    const size_t n = (size_t)p->B * T1 * nu * (K ? nx : 1);
+    const size_t n = (size_t)p->B * T1 * p->udims.n_u * (K ? p->udims.n_x : 1);
     if (ensure_staging(p, n)) return 1;
-    launch_get_gains(p->bufs.KD, p->bufs.kd_sym, p->bufs.alpha, p->bufs.iters, K ? p->staging : nullptr, K ? nullptr : p->staging, p->B, p->Bp, T1, nu, nx, c->stream);
+    if (p->mapped)
+        launch_get_gains_map(p->bufs.KD, p->bufs.kd_sym, p->bufs.alpha, p->bufs.iters, K ? p->staging : nullptr, K ? nullptr : p->staging, p->B, p->Bp, T1, p->map,
+                             c->stream);
+    else
+        launch_get_gains(p->bufs.KD, p->bufs.kd_sym, p->bufs.alpha, p->bufs.iters, K ? p->staging : nullptr, K ? nullptr : p->staging, p->B, p->Bp, T1, nu, nx,
+                         c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(dst, p->staging, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -824,7 +909,7 @@ static int track(ilqr_problem* p, int k, const double* x_meas, int with_ff, doub
     if (!x_meas || !u_out) return fail(c, "null pointer");
     if (k < 0 || k >= p->T - 1) return fail(c, "timestep outside [0, T-2]");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t nxb = (size_t)p->B * p->dims.n_x, nub = (size_t)p->B * p->dims.n_u;
+    const size_t nxb = (size_t)p->B * p->udims.n_x, nub = (size_t)p->B * p->udims.n_u;
     const double* xs = x_meas;
     double* us = u_out;
     if (!dev) {
@@ -833,7 +918,8 @@ static int track(ilqr_problem* p, int k, const double* x_meas, int with_ff, doub
         xs = p->staging;
         us = p->staging + nxb;
     }
-    launch_track(p->bufs, xs, k, with_ff, us, p->B, p->dims.n_x, p->dims.n_u, c->stream);
+    if (p->mapped) launch_track_map(p->bufs, xs, k, with_ff, us, p->B, p->map, c->stream);
+    else launch_track(p->bufs, xs, k, with_ff, us, p->B, p->dims.n_x, p->dims.n_u, c->stream);
     HIPCHK(c, hipGetLastError());
     if (!dev) {
         HIPCHK(c, hipMemcpyAsync(u_out, us, nub * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -889,8 +975,15 @@ extern "C" int ilqr_problem_get_fX(ilqr_problem* p, double* fX) {
     }
     prof_mark(c, -1);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(fX, p->staging, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const bool narrow = p->udims.n_f != p->dims.n_f;  // f(x) = x of a joint-space system of fewer than 7 joints: the state map
+    std::vector<double> wide(narrow ? n : 0);
+    HIPCHK(c, hipMemcpyAsync(narrow ? wide.data() : fX, p->staging, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (narrow) {
+        const IndexMap& mx = p->map.x;
+        for (size_t r = 0; r < (size_t)p->B * p->T; r++)
+            for (int i = 0; i < mx.n_user; i++) fX[r * mx.n_user + i] = wide[r * mx.n_dev + mx.dev[i]];
+    }
     return 0;
 }
 
@@ -903,6 +996,16 @@ extern "C" int ilqr_fk_batch(ilqr_ctx* c, const ilqr_problem_desc* d, int n, con
     DevDesc h;
     std::memset(&h, 0, sizeof(h));
     if (lower_chain(c, *d, h.chain)) return 1;
+    const int dof = d->dof;  // a chain of fewer than 7 joints runs as 7 with the inert joints at q = 0 (ilqr_dofmap.hpp)
+    std::vector<double> qw, jw;
+    if (dof != DOF) {
+        qw.assign((size_t)n * DOF, 0.0);
+        for (int i = 0; i < n; i++) std::memcpy(&qw[(size_t)i * DOF], q + (size_t)i * dof, sizeof(double) * dof);
+        q = qw.data();
+        if (jac) jw.resize((size_t)n * 6 * DOF);
+    }
+    double* jac_out = jac;
+    if (jac && dof != DOF) jac = jw.data();
     DevDesc* dd = nullptr;
     double *dq = nullptr, *dp = nullptr, *dqt = nullptr, *dj = nullptr;
     int rc = 0;
@@ -923,5 +1026,7 @@ extern "C" int ilqr_fk_batch(ilqr_ctx* c, const ilqr_problem_desc* d, int n, con
     FKCHK(hipStreamSynchronize(c->stream));
 #undef FKCHK
     cleanup();
+    if (jac && dof != DOF)
+        for (size_t r = 0; r < (size_t)n * 6; r++) std::memcpy(jac_out + r * dof, &jw[r * DOF], sizeof(double) * dof);
     return rc;
 }

@@ -546,6 +546,63 @@ __global__ void k_track(Bufs a, const double* __restrict__ x_meas, int k, int wi
     }
 }
 
+// ---- chains of fewer than 7 joints (ilqr_dofmap.hpp): the conversions above with the per-step vectors widened / narrowed through their map.
+// The map is a kernel argument; row r of a block is one vector entry, so its map lookup is uniform over the block (a scalar load).
+
+// natural [B][outer][m.n_user] -> device [outer][m.n_dev][Bp]; padded entries are written as 0
+__global__ void k_to_soa_map(const double* __restrict__ src, double* __restrict__ dst, int B, int Bp, IndexMap m) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = blockIdx.y, o = r / m.n_dev, i = m.usr[r - o * m.n_dev];
+    const size_t rows_user = (size_t)(gridDim.y / m.n_dev) * m.n_user;
+    if (b < B) dst[(size_t)r * Bp + b] = i < 0 ? 0.0 : src[(size_t)b * rows_user + (size_t)o * m.n_user + i];
+}
+// device [outer][m.n_dev][Bp] (each instance's current buffer) -> natural [B][outer][m.n_user]
+__global__ void k_from_soa_cur_map(const double* __restrict__ s0, const double* __restrict__ s1, const int* __restrict__ cur,
+                                   double* __restrict__ dst, int B, int Bp, IndexMap m) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = blockIdx.y, o = r / m.n_user, j = m.dev[r - o * m.n_user];
+    const size_t rows_user = gridDim.y;
+    if (b < B) dst[(size_t)b * rows_user + r] = (cur && cur[b] ? s1 : s0)[((size_t)o * m.n_dev + j) * Bp + b];
+}
+// k_get_gains on the user's rows (controls) and columns (states)
+__global__ void k_get_gains_map(const double* __restrict__ kd, int sym, const double* __restrict__ alpha, const int* __restrict__ iters,
+                                double* __restrict__ K_out, double* __restrict__ d_out, int B, int Bp, int T1, IndexMap x, IndexMap u) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (b >= B) return;
+    const int nx = x.n_dev, rowp = kd_rowp(nx), rs = kd_rs(sym, u.n_dev, rowp);
+    const double* rec = KD_REC(kd, Bp, rs, k, b);
+    const double sc = (iters[b] > 0) ? alpha[b] : 1.0;
+    const int nu = u.n_user, nxu = x.n_user;
+    for (int i = 0; i < nu; i++) {
+        const int id = u.dev[i];
+        if (K_out)
+            for (int j = 0; j < nxu; j++) K_out[(((size_t)b * T1 + k) * nu + i) * nxu + j] = rec[kd_off(sym, rowp, id, x.dev[j])];
+        if (d_out) d_out[((size_t)b * T1 + k) * nu + i] = sc * rec[kd_off(sym, rowp, id, nx)];
+    }
+}
+// k_track on the user's layouts x_meas[B][x.n_user], u_out[B][u.n_user].  The padded state entries of the device trajectory are 0, as the
+// padding of a measured state would be: the terms left out add exactly 0.
+__global__ void k_track_map(Bufs a, const double* __restrict__ x_meas, int k, int with_ff, double* __restrict__ u_out, IndexMap x, IndexMap u) {
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= d.B) return;
+    const int Bp = d.Bp, nx = x.n_dev, nu = u.n_dev;
+    const int cur = a.cur[b];
+    const int sym = a.kd_sym, rowp = kd_rowp(nx), rs = kd_rs(sym, nu, rowp);
+    const double* rec = KD_REC(a.KD, Bp, rs, k, b);
+    const double sc = (a.iters[b] > 0) ? a.alpha[b] : 1.0;
+    for (int i = 0; i < u.n_user; i++) {
+        const int id = u.dev[i];
+        double s = AT(a.U[cur], k * nu + id, b);
+        for (int j = 0; j < x.n_user; j++) {
+            const int jd = x.dev[j];
+            s += rec[kd_off(sym, rowp, id, jd)] * (x_meas[(size_t)b * x.n_user + j] - AT(a.X[cur], k * nx + jd, b));
+        }
+        if (with_ff) s += sc * rec[kd_off(sym, rowp, id, nx)];
+        u_out[(size_t)b * u.n_user + i] = s;
+    }
+}
+
 // f(X) for every (instance, timestep): one lane per pair (tuple<1> of ILQRRecursive::solve)
 template <class S>
 __global__ __launch_bounds__(64) void k_fx_all(Bufs a, double* __restrict__ out /* natural [B][T][NF] */) {
@@ -661,6 +718,20 @@ void launch_track(const Bufs& a, const double* x_meas, int k, int with_ff, doubl
 }
 void launch_fk_batch(const DevDesc* dd, int n, const double* q, double* pos, double* quat, double* jac, hipStream_t st) {
     hipLaunchKernelGGL(k_fk_batch, dim3((n + 63) / 64), dim3(64), 0, st, dd, n, q, pos, quat, jac);
+}
+
+void launch_to_soa_map(const double* src, double* dst, int B, int Bp, int outer, const IndexMap& m, hipStream_t st) {
+    hipLaunchKernelGGL(k_to_soa_map, dim3((B + 255) / 256, outer * m.n_dev), dim3(256), 0, st, src, dst, B, Bp, m);
+}
+void launch_from_soa_cur_map(const double* s0, const double* s1, const int* cur, double* dst, int B, int Bp, int outer, const IndexMap& m, hipStream_t st) {
+    hipLaunchKernelGGL(k_from_soa_cur_map, dim3((B + 255) / 256, outer * m.n_user), dim3(256), 0, st, s0, s1, cur, dst, B, Bp, m);
+}
+void launch_get_gains_map(const double* kd, int kd_sym, const double* alpha, const int* iters, double* K_out, double* d_out, int B, int Bp, int T1,
+                          const DofMap& m, hipStream_t st) {
+    hipLaunchKernelGGL(k_get_gains_map, dim3((B + 63) / 64, T1), dim3(64), 0, st, kd, kd_sym, alpha, iters, K_out, d_out, B, Bp, T1, m.x, m.u);
+}
+void launch_track_map(const Bufs& a, const double* x_meas, int k, int with_ff, double* u_out, int B, const DofMap& m, hipStream_t st) {
+    hipLaunchKernelGGL(k_track_map, dim3((B + 63) / 64), dim3(64), 0, st, a, x_meas, k, with_ff, u_out, m.x, m.u);
 }
 
 }  // namespace ilqr

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ilqr_device.hpp"
+#include "ilqr_dofmap.hpp"
 
 namespace ilqr {
 
@@ -105,5 +106,13 @@ void launch_get_gains(const double* kd, int kd_sym, const double* alpha, const i
 void launch_warm_start(const Bufs& a, double* U0, double* q0, double* dq0, int shift, int B, int T, int nx, int nu, int nd, hipStream_t st);
 void launch_track(const Bufs& a, const double* x_meas, int k, int with_ff, double* u_out, int B, int nx, int nu, hipStream_t st);
 void launch_fk_batch(const DevDesc* dd, int n, const double* q, double* pos, double* quat, double* jac, hipStream_t st);
+// The layout conversions of a chain of fewer than 7 joints (ilqr_dofmap.hpp): the same passes with every per-step vector of `outer`
+// vectors widened (upload, padding written as 0) or narrowed (download) through its map.  Rows of the natural side: outer * m.n_user.
+void launch_to_soa_map(const double* src, double* dst, int B, int Bp, int outer, const IndexMap& m, hipStream_t st);
+void launch_from_soa_cur_map(const double* s0, const double* s1, const int* cur, double* dst, int B, int Bp, int outer, const IndexMap& m,
+                             hipStream_t st);  // cur == nullptr: s0
+void launch_get_gains_map(const double* kd, int kd_sym, const double* alpha, const int* iters, double* K_out, double* d_out, int B, int Bp, int T1,
+                          const DofMap& m, hipStream_t st);
+void launch_track_map(const Bufs& a, const double* x_meas, int k, int with_ff, double* u_out, int B, const DofMap& m, hipStream_t st);
 
 }  // namespace ilqr

@@ -117,7 +117,7 @@ def make_batch(ctx: capi.Context, cfg: dict, B: int | None = None, seed: int | N
                           kp_dist=cfg.get("kp_dist"), kp_joint=[1, 0] if hyb else None, kp_Ru=[[1e-3] * nu, [1e-5] * nu] if hyb else None,
                           limit_multiplicity=(1 if cfg.get("limits2") else 2) if hyb else 1,
                           limits2=dict(state_max=smax - 0.3 * (w != 0), state_min=smin + 0.3 * (w != 0), limit_weight=w, penalty=1.0) if cfg.get("limits2") else None)
-    q0 = np.clip(Q0_TUT[None, :] + rng.uniform(-0.3, 0.3, (B, dof)), lo, up)
+    q0 = np.clip(Q0_TUT[None, :dof] + rng.uniform(-0.3, 0.3, (B, dof)), lo, up)
     targets = []
     for i in range(2):
         qr = rng.uniform(lo, up, (B, dof))

@@ -68,7 +68,10 @@ typedef struct ilqr_problem ilqr_problem;
 typedef struct {
     int kind;      /* ILQR_SYS_* */
     int nb_deriv;  /* 1 or 2 */
-    int dof;       /* moving joints of the chain (device path: 7) */
+    int dof;       /* moving joints of the chain: 1..7.  The kernels are built for 7: a chain of fewer joints is solved as the 7-joint
+                      problem with inert joints (zero axis, identity transform) behind its last one; every array crossing this ABI keeps
+                      the user's layout (n_x, n_u, ... of ilqr_dims_of).  A 6-joint problem costs what a 7-joint one does.  dof < 1,
+                      dof > 7 or a chain of another joint count fails with an error text. */
     int horizon;   /* T */
     double dt;     /* PosOrn only; time systems take dt = u_last^2 */
     double R_diag[ILQR_MAX_NU];
