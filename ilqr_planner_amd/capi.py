@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libilqr_hip.so")
 MAX_SEG, MAX_KP, MAX_NX, MAX_NU, MAX_NF, MAX_NQ = 24, 8, 15, 8, 15, 13
 SYS_POS_ORN, SYS_POS_ORN_TIME, SYS_JOINT, SYS_JOINT_TIME = 0, 1, 2, 3
 STATUS_OK, STATUS_NONFINITE, STATUS_ALPHA_FLOOR = 0, 1, 2
+LQT_MAX_NX, LQT_MAX_NU = 16, 8
 PROF_ROLLOUT, PROF_BACKWARD, PROF_FORWARD, PROF_OTHER, PROF_APPLY = 0, 1, 2, 3, 4
 
 # every symbol include/ilqr_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -30,6 +31,9 @@ EXPORTS = [
     "ilqr_problem_get_X_dev", "ilqr_problem_get_U_dev", "ilqr_problem_get_cost_dev", "ilqr_fk_batch",
     "ilqr_profile_enable", "ilqr_profile_reset", "ilqr_profile_get", "ilqr_chain_from_urdf", "ilqr_urdf_last_error",
     "ilqr_problem_reset_multipliers", "ilqr_problem_warm_start", "ilqr_problem_track", "ilqr_problem_track_dev", "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck",
+    "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
+    "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
+    "ilqr_lqt_get_d",
 ]
 
 
@@ -450,6 +454,101 @@ class BatchProblem:
         if self.h:
             if self.ctx.h:  # a destroyed context has already destroyed its problems
                 self.L.ilqr_problem_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _lqt_prototypes(L):
+    """The ilqr_lqt_* prototypes, declared on first use (the sanitizer harness's host build of the library has no LQT translation unit)."""
+    if getattr(L, "_lqt_declared", False):
+        return
+    dp, vp = C.POINTER(C.c_double), C.c_void_p
+    L.ilqr_lqt_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, dp, C.c_int, C.POINTER(vp)]
+    L.ilqr_lqt_destroy.argtypes = [vp]
+    L.ilqr_lqt_destroy.restype = None
+    for n in ("set_targets", "set_targets_dev", "get_U", "get_U_dev", "get_X", "get_X_dev", "get_P", "get_d"):
+        getattr(L, "ilqr_lqt_" + n).argtypes = [vp, vp]
+    L.ilqr_lqt_solve_dp.argtypes = [vp]
+    L.ilqr_lqt_solve_lin_al.argtypes = [vp]
+    for n in ("ilqr_lqt_command", "ilqr_lqt_command_dev"):
+        getattr(L, n).argtypes = [vp, C.c_int, vp, vp]
+    L._lqt_declared = True
+
+
+class LQTBatch:
+    """B instances of solver::LQT (ilqr_lqt_*) sharing A, B and R = r I.  Qs: [N][n][n] shared, or [B][N][n][n] with qs_per_instance;
+    Qs[N-1] is the terminal weight.  mu: [B][N][n] targets.  r is the R diagonal value (PyLQR's LQT passes pow(float(rfactor), nb_deriv))."""
+
+    def __init__(self, ctx: Context, A, B, Qs, mu, r, qs_per_instance=False):
+        A, Bm, Qs, mu = _f64(A), _f64(B), _f64(Qs), _f64(mu)
+        if A.ndim != 2 or Bm.ndim != 2 or mu.ndim != 3 or Qs.ndim != (4 if qs_per_instance else 3):
+            raise ValueError("LQTBatch: A [n][n], B [n][m], Qs [N][n][n] (or [B][N][n][n] per instance), mu [B][N][n]")
+        self.ctx, self.L = ctx, ctx.L
+        _lqt_prototypes(self.L)
+        self.B, self.N, self.n = mu.shape
+        self.m = Bm.shape[1]
+        self.per_instance = bool(qs_per_instance)
+        self.h = C.c_void_p()
+        ctx.check(self.L.ilqr_lqt_create(ctx.h, A.shape[1], self.m, self.N, self.B, _dp(A), _dp(Bm), float(r), _dp(Qs), int(self.per_instance),
+                                         C.byref(self.h)))
+        ctx._problems.add(self)
+        self.set_targets(mu)
+
+    def set_targets(self, mu):
+        mu = _f64(mu, (self.B, self.N, self.n))
+        self.ctx.check(self.L.ilqr_lqt_set_targets(self.h, mu.ctypes.data))
+
+    def set_targets_dev(self, ptr):
+        self.ctx.check(self.L.ilqr_lqt_set_targets_dev(self.h, ptr))
+
+    def solve_dp(self):
+        self.ctx.check(self.L.ilqr_lqt_solve_dp(self.h))
+
+    def solve_lin_al(self):
+        self.ctx.check(self.L.ilqr_lqt_solve_lin_al(self.h))
+
+    def command(self, t: int, x):
+        """The reference's getCommand(t, x) for every instance: x [B][n] -> u [B][m]."""
+        x = _f64(x, (self.B, self.n))
+        u = np.empty((self.B, self.m))
+        self.ctx.check(self.L.ilqr_lqt_command(self.h, int(t), x.ctypes.data, u.ctypes.data))
+        return u
+
+    def command_dev(self, t: int, x_ptr, u_ptr):
+        self.ctx.check(self.L.ilqr_lqt_command_dev(self.h, int(t), x_ptr, u_ptr))
+
+    def _get(self, name, shape):
+        o = np.zeros(shape)
+        self.ctx.check(getattr(self.L, "ilqr_lqt_get_" + name)(self.h, o.ctypes.data))
+        return o
+
+    def U(self):
+        return self._get("U", (self.B, self.N - 1, self.m))
+
+    def X(self):
+        return self._get("X", (self.B, self.N, self.n))
+
+    def P(self):
+        return self._get("P", ((self.B,) if self.per_instance else ()) + (self.N, self.n, self.n))
+
+    def d(self):
+        return self._get("d", (self.B, self.N, self.n))
+
+    def U_dev(self, ptr):
+        self.ctx.check(self.L.ilqr_lqt_get_U_dev(self.h, ptr))
+
+    def X_dev(self, ptr):
+        self.ctx.check(self.L.ilqr_lqt_get_X_dev(self.h, ptr))
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:  # a destroyed context has already destroyed its handles
+                self.L.ilqr_lqt_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

@@ -1623,5 +1623,68 @@ Vec BatchILQRCP::solve(int nb_iter, const Vec& u0, bool early_stop, CallBackMess
     return r.U;
 }
 
+// ------------------------------------------------------------------------------------------------ LQT (src/solver/lqt.cpp)
+// Every solve is a B = 1 batch of the ilqr_lqt_* entry points.  State and indices are checked here, before any device call, with the
+// reference's error texts; an index out of range is std::out_of_range (IndexError in Python), where the reference's std::vector::at throws.
+
+LQT::LQT(const Mat& A_, const Mat& B_, const std::vector<Mat>& Qs_, const Vec& states, float rfactor, int nb_deriv)
+    : A(A_), B(B_), Qs(Qs_), mu(states), r(std::pow(rfactor, nb_deriv)), n(A_.cols), m(B_.cols), N(A_.cols > 0 ? (int)states.size() / A_.cols : 0) {}
+
+std::shared_ptr<ilqr_lqt> LQT::upload(const std::vector<Mat>& Q) const {
+    if (A.rows != n || B.rows != n) throw std::runtime_error("LQT: A must be n x n and B n x m");
+    std::vector<double> q;
+    for (const Mat& M : Q) {
+        if (M.rows != n || M.cols != n) throw std::runtime_error("LQT: every Qs[t] must be n x n");
+        q.insert(q.end(), M.d.begin(), M.d.end());
+    }
+    ilqr_ctx* c = device_context();
+    ilqr_lqt* h = nullptr;
+    check(ilqr_lqt_create(c, n, m, N, 1, A.d.data(), B.d.data(), r, q.data(), 0, &h));
+    std::shared_ptr<ilqr_lqt> p(h, ilqr_lqt_destroy);
+    check(ilqr_lqt_set_targets(h, mu.data()));
+    return p;
+}
+
+void LQT::solveDP() {  // lqt.cpp:29-53
+    if (Qs.empty() || (int)Qs.size() < N - 1) throw std::out_of_range("LQT::solveDP: Qs has " + std::to_string(Qs.size()) + " matrices, needs " + std::to_string(N - 1));
+    std::vector<Mat> q(Qs.begin(), Qs.begin() + std::max(N - 1, 0));
+    q.push_back(Qs.back());
+    auto h = upload(q);
+    check(ilqr_lqt_solve_dp(h.get()));
+    check(ilqr_ctx_synchronize(device_context()));
+    dp = h;
+}
+
+void LQT::solveLinAl() {  // lqt.cpp:55-89
+    if ((int)Qs.size() < N) throw std::out_of_range("LQT::solveLinAl: Qs has " + std::to_string(Qs.size()) + " matrices, needs " + std::to_string(N));
+    auto h = upload(std::vector<Mat>(Qs.begin(), Qs.begin() + N));
+    check(ilqr_lqt_solve_lin_al(h.get()));
+    Vec u((size_t)(N - 1) * m), x((size_t)N * n);
+    check(ilqr_lqt_get_U(h.get(), u.data()));
+    check(ilqr_lqt_get_X(h.get(), x.data()));
+    U = u;
+    X = x;
+}
+
+Vec LQT::getCommand(int timestep, const Vec& curr_state) {  // lqt.cpp:102-120
+    if (!dp) throw std::runtime_error("solveDP() first");
+    if (timestep < -1 || timestep > N - 2) throw std::out_of_range("LQT::getCommand: timestep " + std::to_string(timestep) + " outside -1.." + std::to_string(N - 2));
+    if ((int)curr_state.size() != n) throw std::runtime_error("LQT::getCommand: curr_state must have " + std::to_string(n) + " entries");
+    Vec u(m);
+    check(ilqr_lqt_command(dp.get(), timestep, curr_state.data(), u.data()));
+    return u;
+}
+
+Vec LQT::getCommand(int timestep) {  // lqt.cpp:95-100 (u.segment(t m, m))
+    if (U.empty()) throw std::runtime_error("solveLinal() or solveQP() first");
+    if (timestep < 0 || timestep > N - 2) throw std::out_of_range("LQT::getCommand: timestep " + std::to_string(timestep) + " outside 0.." + std::to_string(N - 2));
+    return Vec(U.begin() + (size_t)timestep * m, U.begin() + (size_t)(timestep + 1) * m);
+}
+
+Vec LQT::getPredictedStates() {  // lqt.cpp:122-127
+    if (U.empty()) throw std::runtime_error("solveLinal() or solveQP() first");
+    return X;
+}
+
 }  // namespace solver
 }  // namespace ilqr_planner

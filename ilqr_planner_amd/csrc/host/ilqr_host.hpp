@@ -4,13 +4,13 @@
 //   sim::SimulationInterface / sim::KDLRobot          include/ilqr_planner/sim/{SimulationInterface,KDLRobot}.h
 //   sys::Keypoint / PosOrnKeypoint / SpacetimeKeypoint include/ilqr_planner/system/*Keypoint.h
 //   sys::System / PosOrnPlannerSys / PosOrnTimePlannerSys  include/ilqr_planner/system/{System,PosOrn*PlannerSys}.h
-//   solver::ILQRRecursive / AL_ILQR / BatchILQRCP      include/ilqr_planner/solver/*.h
+//   solver::ILQRRecursive / AL_ILQR / BatchILQR / BatchILQRCP / LQT  include/ilqr_planner/solver/*.h
 //   primitives, Sd, CallBackMessage                   include/ilqr_planner/utils/*.h
 // No Eigen (absent from this image): Vec/Mat are plain row-major containers.  These classes hold state and LOWER it to
 // the POD descriptor of include/ilqr_hip.h; every solve and every kinematics evaluation runs on the GPU through that C
 // ABI -- there is no host solver for them (user-defined System / Keypoint subclasses, which have no descriptor, run
 // solver::ILQRRecursive over their own virtuals: ilqr_host_loop.cpp).  The single-point System API (forwardPass, cost*, getFxJac, fpBatch ...) is host glue over
-// the simulator for users who call it directly; the solvers never use it.  NOT mirrored: BatchILQR (no PSI), LQT -- see DESIGN.md.
+// the simulator for users who call it directly; the solvers never use it.
 #pragma once
 
 #include <memory>
@@ -531,6 +531,28 @@ private:
     Mat PSI;
     Mat Q;  // only the block-diagonal of the keypoints' precisions is supported on the device
     bool custom_Q = false;
+};
+
+class LQT {  // lqt.h:23-86: linear-quadratic tracking of the targets `states` (N = states.size() / n), R = pow(rfactor, nb_deriv) I
+public:
+    LQT(const Mat& A, const Mat& B, const std::vector<Mat>& Qs, const Vec& states, float rfactor = 0.1f, int nb_deriv = 2);
+    void solveDP();     // terminal weight Qs.back(), Qs.at(t) before it
+    void solveLinAl();  // Qs.at(0 .. N-1); x_0 = mu_0
+    Vec getCommand(int timestep, const Vec& curr_state);  // after solveDP; timestep in -1 .. N-2, else std::out_of_range
+    Vec getCommand(int timestep);                         // after solveLinAl; timestep in 0 .. N-2, else std::out_of_range (the reference
+                                                          // does not check it)
+    int getNbStates() const { return N; }
+    Vec getPredictedStates();  // after solveLinAl: [N * n], x_0 = mu_0 first
+
+private:
+    std::shared_ptr<ilqr_lqt> upload(const std::vector<Mat>& Q) const;
+    Mat A, B;
+    std::vector<Mat> Qs;
+    Vec mu;
+    double r;
+    int n, m, N;
+    std::shared_ptr<ilqr_lqt> dp;  // the device handle of solveDP (getCommand(t, x) runs on it)
+    Vec U, X;                      // solveLinAl's controls and predicted states
 };
 }  // namespace solver
 }  // namespace ilqr_planner

@@ -301,6 +301,15 @@ PYBIND11_MODULE(PyLQR, m) {
                  return self.solveBatch(batch_inputs(u0, q0, dq0, kp, true), nb_iter, es);
              },
              py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none());
+    // bindings.cpp:862-869: positional arguments only, no defaults
+    py::class_<solver::LQT>(m_sol, "LQT")
+        .def(py::init<const Mat&, const Mat&, const std::vector<Mat>&, const Vec&, float, int>())
+        .def("solve_DP", &solver::LQT::solveDP)
+        .def("solve_lin_al", &solver::LQT::solveLinAl)
+        .def("get_nb_states", &solver::LQT::getNbStates)
+        .def("get_predicted_states", &solver::LQT::getPredictedStates)
+        .def("get_command", static_cast<Vec (solver::LQT::*)(int)>(&solver::LQT::getCommand))
+        .def("get_command", static_cast<Vec (solver::LQT::*)(int, const Vec&)>(&solver::LQT::getCommand));
     py::class_<solver::BatchILQRCP>(m_sol, "BatchILQRCP")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&, const Mat&>(), py::arg("s"), py::arg("Q"), py::arg("psi"))
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("psi"))

@@ -17,33 +17,11 @@
 #include <vector>
 
 #include "ilqr_batchcp.hpp"
+#include "ilqr_ctx.hpp"
 #include "ilqr_kernels.hpp"
 #include "ilqr_plan.hpp"
 
 using namespace ilqr;
-
-struct ilqr_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    std::string err;
-    bool profile = false;
-    int split = 1;  // ilqr_ctx_set_split: 0 off, 1 where it was measured to pay, 2 every cooperative path (experiments)
-    double prof_ms[ILQR_PROF_COUNT] = {0, 0, 0, 0, 0};
-    int prof_n[ILQR_PROF_COUNT] = {0, 0, 0, 0, 0};
-    struct Pending { hipEvent_t a, b; int which; };
-    std::vector<Pending> pending;
-    std::vector<hipEvent_t> pool;
-    std::vector<ilqr_problem*> problems;  // live problems of this context (destroyed with it)
-    // split solves (solve_riccati): the two halves of a batch run on their own streams, joined to `stream` by events
-    int n_simd = 1024;  // SIMDs of the device (4 per CU)
-    bool xc_generic = false, xc_cp_lane = false, xc_cp_general = false;  // cross-check kernel variants (ilqr_ctx_set_crosscheck)
-    SweepPin xc_sweep = SweepPin::Auto;      // variant pins (ILQR_XC_*): sweep of the 2nd-order / time systems,
-    FwdPin xc_forward = FwdPin::Auto;        // forward pass of the single-integrator systems,
-    RerollPin xc_reroll = RerollPin::Auto;   // re-roll of the line-search winner on the time systems
-    hipStream_t half_stream[2] = {nullptr, nullptr};
-    hipEvent_t ev_begin = nullptr, ev_half_done[2] = {nullptr, nullptr}, ev_stagger = nullptr;
-};
 
 struct ilqr_problem {
     ilqr_ctx* ctx = nullptr;
@@ -72,16 +50,6 @@ struct ilqr_problem {
     BatchCPState cp;
     BatchWideState cpw;
 };
-
-static int fail(ilqr_ctx* c, const std::string& m) {
-    if (c) c->err = m;
-    return 1;
-}
-#define HIPCHK(ctx, call)                                                                                  \
-    do {                                                                                                   \
-        hipError_t e_ = (call);                                                                            \
-        if (e_ != hipSuccess) return fail((ctx), std::string(#call) + ": " + hipGetErrorString(e_));       \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------ misc
 
@@ -136,6 +104,7 @@ extern "C" void ilqr_ctx_destroy(ilqr_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     while (!c->problems.empty()) ilqr_problem_destroy(c->problems.back());  // handles held by the caller become invalid
+    while (!c->cleanups.empty()) { const auto cl = c->cleanups.back(); cl.destroy(cl.handle); }  // each destroy removes its own entry
     (void)hipStreamSynchronize(c->stream);
     for (auto& p : c->pending) (void)hipEventDestroy(p.a);
     for (auto e : c->pool) (void)hipEventDestroy(e);

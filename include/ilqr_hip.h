@@ -249,6 +249,42 @@ int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_meas, int wit
  * any output may be NULL.  Host pointers. */
 int ilqr_fk_batch(ilqr_ctx* ctx, const ilqr_problem_desc* desc, int n, const double* q, double* pos, double* quat, double* jac);
 
+/* ---- batched linear-quadratic tracking: solver::LQT (include/ilqr_planner/solver/lqt.h:23-86, src/solver/lqt.cpp) -------------------------
+ * B instances of LQT(A, B, Qs, states, rfactor, nb_deriv) that share A, B, R = r I and either share the precisions Qs (one Riccati chain for the
+ * batch, qs_per_instance = 0) or carry their own (one chain per instance).  n = n_x, m = n_u, N = number of targets.  Shapes (natural layout):
+ * A[n][n], Bm[n][m], Qs[N][n][n] shared or Qs[B][N][n][n] per instance, Qs[N-1] being the terminal weight P_{N-1} of the DP form (the reference's
+ * solveDP takes Qs.back() there, solveLinAl Qs[N-1]: a caller with more than N matrices passes the one it wants).  r is the R diagonal value
+ * (the reference's pow(float rfactor, nb_deriv) belongs to the caller).  Precisions are symmetric: Q enters as (Q + Q') / 2.
+ * Limits: 1 <= n <= ILQR_LQT_MAX_NX, 1 <= m <= ILQR_LQT_MAX_NU, N >= 1; beyond them creation fails with an error text naming the range.
+ * A handle belongs to its context: ilqr_ctx_destroy frees it (the caller's pointer becomes invalid).  No result depends on the batch size. */
+#define ILQR_LQT_MAX_NX 16
+#define ILQR_LQT_MAX_NU 8
+typedef struct ilqr_lqt ilqr_lqt;
+/* lqt.cpp:16-25 (the constructor) */
+int ilqr_lqt_create(ilqr_ctx* ctx, int n_x, int n_u, int N, int batch, const double* A, const double* Bm, double r, const double* Qs,
+                    int qs_per_instance, ilqr_lqt** out);
+void ilqr_lqt_destroy(ilqr_lqt* h);
+/* the constructor's `states`: mu[B][N][n_x] (target t of instance b at mu[b][t]); invalidates earlier solves */
+int ilqr_lqt_set_targets(ilqr_lqt* h, const double* mu);
+int ilqr_lqt_set_targets_dev(ilqr_lqt* h, const double* mu);
+/* solveDP (lqt.cpp:29-53): P_t, d_t for t = N-1 .. 0; asynchronous on the context's stream */
+int ilqr_lqt_solve_dp(ilqr_lqt* h);
+/* solveLinAl (lqt.cpp:55-89): the minimiser of the tracking cost from x_0 = mu_0, computed by the Riccati recursion and a forward rollout (the
+ * dense normal equations are never formed; the minimiser is unique, so the two agree to rounding times the problem's conditioning).  Runs
+ * ilqr_lqt_solve_dp first if it has not run on the current targets. */
+int ilqr_lqt_solve_lin_al(ilqr_lqt* h);
+/* getCommand(t, x) (lqt.cpp:102-120): x[B][n_x] -> u[B][n_u], the reference's law at tau = t + 1; t in -1 .. N-2.
+ * Fails with "solveDP() first" before ilqr_lqt_solve_dp. */
+int ilqr_lqt_command(ilqr_lqt* h, int t, const double* x, double* u);
+int ilqr_lqt_command_dev(ilqr_lqt* h, int t, const double* x, double* u);
+/* results; before the solve that makes them they fail with "solveLinal() or solveQP() first" (U, X) or "solveDP() first" (P, d) */
+int ilqr_lqt_get_U(ilqr_lqt* h, double* U);      /* [B][N-1][n_u]  u of solveLinAl, getCommand(t) = U[b][t] */
+int ilqr_lqt_get_U_dev(ilqr_lqt* h, double* U);
+int ilqr_lqt_get_X(ilqr_lqt* h, double* X);      /* [B][N][n_x]    getPredictedStates (lqt.cpp:122-127), x_0 = mu_0 first */
+int ilqr_lqt_get_X_dev(ilqr_lqt* h, double* X);
+int ilqr_lqt_get_P(ilqr_lqt* h, double* P);      /* [N][n_x][n_x] shared, [B][N][n_x][n_x] per instance: the reference's Ps */
+int ilqr_lqt_get_d(ilqr_lqt* h, double* d);      /* [B][N][n_x]    the reference's ds */
+
 /* ---- instrumentation ----------------------------------------------------------------------------------------- */
 /* When enabled, every kernel launch is bracketed by hipEvents on the launch stream; totals are read back with
  * ilqr_profile_get (index: ILQR_PROF_*).  Used by bench.py for the roofline figures. */
