@@ -925,6 +925,13 @@ int orc_solve_al(const orc_system* s, const orc_constraints* c, double* lambda, 
                          X, fX, U, NULL, NULL, cost, trace_cost, trace_alpha);
 }
 
+int orc_solve_al_gains(const orc_system* s, const orc_constraints* c, double* lambda, const double* U0, int nb_iter,
+                       int lag_update_step, double penalty, double scaling, int line_search, int early_stop,
+                       double* X, double* fX, double* U, double* K, double* d, double* cost, double* trace_cost, double* trace_alpha) {
+    return solve_riccati(s, c, lambda, U0, nb_iter, lag_update_step, penalty, scaling, line_search, early_stop,
+                         X, fX, U, K, d, cost, trace_cost, trace_alpha);
+}
+
 /* ------------------------------------------------------------------ BatchILQRCP (solver/BatchILQRCP.cpp) */
 
 typedef struct {

@@ -135,6 +135,10 @@ int orc_solve_al(const orc_system* s, const orc_constraints* c, double* lambda /
                  const double* U0, int nb_iter, int lag_update_step, double penalty, double scaling,
                  int line_search, int early_stop,
                  double* X, double* fX, double* U, double* cost, double* trace_cost, double* trace_alpha);
+/* ... and the gains of the last sweep, as orc_solve_recursive returns them (K [T-1][n_u][n_x], d [T-1][n_u] scaled by the accepted alpha) */
+int orc_solve_al_gains(const orc_system* s, const orc_constraints* c, double* lambda, const double* U0, int nb_iter,
+                       int lag_update_step, double penalty, double scaling, int line_search, int early_stop,
+                       double* X, double* fX, double* U, double* K, double* d, double* cost, double* trace_cost, double* trace_alpha);
 
 /* BatchILQRCP::solve; Qbig = block-diag keypoint precisions built from the system (getQMatrix(true)).
  * psi: ((T-1) n_u) x Kw row-major.  u: in = u0, out = solution ((T-1) n_u). */

@@ -136,6 +136,9 @@ def lib():
         L.orc_solve_al.argtypes = [C.POINTER(System), C.POINTER(Constraints), dp, dp, C.c_int, C.c_int, C.c_double,
                                    C.c_double, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp]
         L.orc_solve_al.restype = C.c_int
+        L.orc_solve_al_gains.argtypes = [C.POINTER(System), C.POINTER(Constraints), dp, dp, C.c_int, C.c_int, C.c_double,
+                                         C.c_double, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]
+        L.orc_solve_al_gains.restype = C.c_int
         L.orc_solve_batch_cp.argtypes = [C.POINTER(System), dp, C.c_int, dp, C.c_int, C.c_int, dp, dp]
         L.orc_solve_batch_cp.restype = C.c_int
         for n in ("rbf", "bernstein", "unitstep", "sawtooth", "linear"):
@@ -447,7 +450,8 @@ def solve_recursive(s: System, U0, nb_iter, line_search=True, early_stop=True, p
 
 def solve_al(s: System, A, b, lambda0, U0, nb_iter, lag_update_step, penalty, scaling, line_search=True, early_stop=True, probe=False, resume=None):
     """A: (m, n_x+n_u) or (T-1, m, n_x+n_u); b likewise; lambda0: (T-1, m) (copied; returned updated).
-    probe: also return the per-iteration decision margins; resume: dict(it0, init_penalty, lambda_mask) (test aids, ilqr_oracle.h)."""
+    probe: also return the per-iteration decision margins; resume: dict(it0, init_penalty, lambda_mask) (test aids, ilqr_oracle.h).
+    Returns the gains K, d of the last sweep as solve_recursive does."""
     T, nx, nu, nf = s.T, s.n_x, s.n_u, s.n_f
     A, b = _arr(A), _arr(b)
     per_step = 1 if A.ndim == 3 else 0
@@ -456,12 +460,14 @@ def solve_al(s: System, A, b, lambda0, U0, nb_iter, lag_update_step, penalty, sc
     lam = _arr(lambda0, (T - 1) * m).copy().reshape(T - 1, m)
     U0 = _arr(U0, (T - 1) * nu)
     X, fX, U = np.zeros((T, nx)), np.zeros((T, nf)), np.zeros((T - 1, nu))
+    K, d = np.zeros((T - 1, nu, nx)), np.zeros((T - 1, nu))
     cost_ = np.zeros(1)
     tc, ta = np.full(max(nb_iter, 1), np.nan), np.full(max(nb_iter, 1), np.nan)
     with _Aids(nb_iter, probe, resume) as aids:
-        n = lib().orc_solve_al(C.byref(s), C.byref(c), _dp(lam), _dp(U0), nb_iter, lag_update_step, penalty, scaling,
-                               int(line_search), int(early_stop), _dp(X), _dp(fX), _dp(U), _dp(cost_), _dp(tc), _dp(ta))
-    return dict(X=X, fX=fX, U=U, cost=float(cost_[0]), iters=n, trace_cost=tc[:n], trace_alpha=ta[:n], lam=lam, probe=aids.records(n), x_dev=aids.x_dev)
+        n = lib().orc_solve_al_gains(C.byref(s), C.byref(c), _dp(lam), _dp(U0), nb_iter, lag_update_step, penalty, scaling,
+                                     int(line_search), int(early_stop), _dp(X), _dp(fX), _dp(U), _dp(K), _dp(d), _dp(cost_), _dp(tc), _dp(ta))
+    return dict(X=X, fX=fX, U=U, K=K, d=d, cost=float(cost_[0]), iters=n, trace_cost=tc[:n], trace_alpha=ta[:n], lam=lam, probe=aids.records(n),
+                x_dev=aids.x_dev)
 
 
 def solve_batch_cp(s: System, psi, u0, nb_iter, early_stop=True, probe=False):

@@ -130,10 +130,11 @@ def test_wide_equals_narrow_path(ctx):
     p.close()
 
 
-@pytest.mark.parametrize("cfg_name,T,B", [("C2", 3, 67), ("C2", 9, 1), ("C4t1", 4, 5), ("C2nd", 5, 33)])
+@pytest.mark.parametrize("cfg_name,T,B", [("C2", 3, 67), ("C2", 9, 1), ("C4t1", 4, 5), ("C2nd", 5, 33), ("C2", 65, 13), ("C2nd", 66, 7)])
 def test_batch_ilqr_edge_shapes(ctx, cfg_name, T, B):
     """Shortest horizons (the first keypoint falls on step 0 or 1, where the reference's shifted sensitivity is empty), a single
-    instance, batches that are not a multiple of any lane grouping, early stop on: BatchILQR against the dense restatement."""
+    instance, batches that are not a multiple of any lane grouping, early stop on: BatchILQR against the dense restatement.  T = 65 and
+    66: T - 1 on and one step past a multiple of 64 steps."""
     from ilqr_planner_amd import workloads
 
     nb_iter = 4
