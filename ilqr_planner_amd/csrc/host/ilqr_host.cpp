@@ -806,23 +806,36 @@ void System::lower(ilqr_problem_desc* d) const {
         d->state_min[i] = state_min_[i];
         d->limit_weight[i] = joint_limits_weight_[i];
     }
-    if (keypoints.size() > ILQR_MAX_KP) throw std::runtime_error("[ilqr_hip] too many keypoints for the device descriptor");
-    d->n_kp = (int)keypoints.size();
-    for (size_t k = 0; k < keypoints.size(); k++) {
-        if (k > 0 && keypoints[k]->getTimestep() == keypoints[k - 1]->getTimestep())
-            throw std::runtime_error("[ilqr_hip] two keypoints share a timestep: not supported on the device");
-        d->kp_timestep[k] = keypoints[k]->getTimestep();
-        const Mat P = keypoints[k]->getPrecision();
+    const std::vector<int> dk = System::deviceKeypoints();  // the last keypoint given for a step; the others never reach the cost
+    if (dk.size() > ILQR_MAX_KP) throw std::runtime_error("[ilqr_hip] too many keypoints for the device descriptor");
+    d->n_kp = (int)dk.size();
+    for (size_t k = 0; k < dk.size(); k++) {
+        const std::shared_ptr<Keypoint>& kpk = keypoints[dk[k]];
+        d->kp_timestep[k] = kpk->getTimestep();
+        const Mat P = kpk->getPrecision();
         if (P.rows != nb_Q_var_ || P.cols != nb_Q_var_) throw std::runtime_error("[System] keypoint precision must be nb_Q_var x nb_Q_var");
         for (int a = 0; a < nb_Q_var_; a++)
             for (int b = 0; b < nb_Q_var_; b++) d->kp_Q[k][a * nb_Q_var_ + b] = P(a, b);
-        if (auto* df = dynamic_cast<const PosOrnKeypointDistFunct*>(keypoints[k].get())) {  // dead zones (PosOrnKeypointDistFunct.cpp:13-35)
+        if (auto* df = dynamic_cast<const PosOrnKeypointDistFunct*>(kpk.get())) {  // dead zones (PosOrnKeypointDistFunct.cpp:13-35)
             d->kp_dist[k] = 1;
             d->kp_pos_radius[k] = df->getPosRadius();
             for (int i = 0; i < 3; i++) d->kp_orn_thresh[k][i] = df->getOrnThresh()[i];
         }
         if (r->frame(d->kp_frame_R[k], d->kp_frame_p[k])) d->kp_has_frame[k] = 1;  // TransformedSimulationInterface
     }
+}
+
+std::vector<int> System::deviceKeypoints() const {  // keypoints are sorted stably by timestep (init): the last of a run of equal steps wins
+    std::vector<int> v;
+    for (size_t i = 0; i < keypoints.size(); i++)
+        if (i + 1 == keypoints.size() || keypoints[i + 1]->getTimestep() != keypoints[i]->getTimestep()) v.push_back((int)i);
+    return v;
+}
+
+bool System::hasSharedStep() const {
+    for (size_t i = 1; i < keypoints.size(); i++)
+        if (keypoints[i]->getTimestep() == keypoints[i - 1]->getTimestep()) return true;
+    return false;
 }
 
 // ---- SequentialSystem (SequentialSystem.cpp:20-76)
@@ -1026,7 +1039,8 @@ void SequentialSystem::lower(ilqr_problem_desc* d) const {
     d->limit_multiplicity = n_lim > 1 ? n_lim : 1;
     d->limit_multiplicity2 = n_lim2 > 1 ? n_lim2 : 1;
     d->is_sequence = 1;
-    // merge the keypoints by timestep
+    // merge the keypoints by timestep (each sub-system's already reduced to one per step by its own lowering); a step that several
+    // sub-systems share keeps them all, ordered by sub-system index: the device adds their terms in that order
     struct Src { int sys, k; };
     std::vector<Src> order;
     for (size_t i = 0; i < subs.size(); i++)
@@ -1037,8 +1051,6 @@ void SequentialSystem::lower(ilqr_problem_desc* d) const {
     for (size_t o = 0; o < order.size(); o++) {
         const auto& a = subs[order[o].sys];
         const int k = order[o].k;
-        if (o > 0 && a.kp_timestep[k] == d->kp_timestep[o - 1])
-            throw std::runtime_error("[ilqr_hip] two keypoints share a timestep: not supported on the device");
         d->kp_timestep[o] = a.kp_timestep[k];
         d->kp_joint[o] = (hybrid && is_joint(a.kind)) ? 1 : 0;  // its kp_Q is n_x x n_x with leading dimension n_x already
         std::memcpy(d->kp_Q[o], a.kp_Q[k], sizeof(a.kp_Q[k]));
@@ -1051,6 +1063,24 @@ void SequentialSystem::lower(ilqr_problem_desc* d) const {
         d->kp_has_Ru[o] = 1;
         for (int i = 0; i < nb_ctrl_var_; i++) d->kp_Ru[o][i] = a.R_diag[i];
     }
+}
+
+// The sequence's keypoint list is the sub-systems' lists concatenated and sorted stably by timestep (constructor + init): sub-system i's
+// keypoint r sits at the position of (t, i, r) in that order.  The descriptor keeps each sub-system's deviceKeypoints(), in the same order.
+std::vector<int> SequentialSystem::deviceKeypoints() const {
+    struct Pos { int t, sys, r; bool keep; };
+    std::vector<Pos> all;
+    for (size_t i = 0; i < systems_.size(); i++) {
+        const auto& kps = systems_[i]->getKeypoints();
+        const std::vector<int> keep = systems_[i]->deviceKeypoints();
+        for (size_t r = 0; r < kps.size(); r++)
+            all.push_back({kps[r]->getTimestep(), (int)i, (int)r, std::find(keep.begin(), keep.end(), (int)r) != keep.end()});
+    }
+    std::stable_sort(all.begin(), all.end(), [](const Pos& a, const Pos& b) { return a.t < b.t; });
+    std::vector<int> v;
+    for (size_t j = 0; j < all.size(); j++)
+        if (all[j].keep) v.push_back((int)j);
+    return v;
 }
 
 PosOrnPlannerSys::PosOrnPlannerSys(const std::shared_ptr<sim::SimulationInterface>& r, const std::vector<std::shared_ptr<Keypoint>>& kps, const Vec& Rt,
@@ -1390,8 +1420,10 @@ static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter,
     if (q0.size() != (size_t)B * dof || dq0.size() != (size_t)B * dof) throw std::runtime_error("[ilqr_hip] q0/dq0 must be B x dof");
     check(ilqr_problem_set_init_state(g.p, q0.data(), dq0.data()));
     const auto& kps = s.getKeypoints();
-    for (size_t k = 0; k < kps.size(); k++) {
-        std::vector<double> tg = (k < in.kp_targets.size() && !in.kp_targets[k].empty()) ? in.kp_targets[k] : tile(kps[k]->targetFx(), dm.n_f);
+    const std::vector<int> dk = s.deviceKeypoints();  // descriptor keypoint k is kps[dk[k]]; in.kp_targets follows getKeypoints()
+    for (size_t k = 0; k < dk.size(); k++) {
+        const size_t h = (size_t)dk[k];
+        std::vector<double> tg = (h < in.kp_targets.size() && !in.kp_targets[h].empty()) ? in.kp_targets[h] : tile(kps[h]->targetFx(), dm.n_f);
         if (tg.size() != (size_t)B * dm.n_f) throw std::runtime_error("[ilqr_hip] keypoint targets must be B x nb_target_var");
         check(ilqr_problem_set_keypoint_targets(g.p, (int)k, tg.data()));
     }
@@ -1569,6 +1601,10 @@ BatchILQRCP::BatchILQRCP(const std::shared_ptr<sys::System>& s_, const Mat& psi)
 static BatchResult batch_gauss_newton(sys::System& s, const Mat* psi, const Mat* Q, const BatchInputs& in, int nb_iter, bool early_stop) {
     const int T = s.getHorizon(), nu = s.getNbCtrlVar();
     if (psi && psi->rows != (T - 1) * nu) throw std::runtime_error("[BatchILQRCP] psi must have (horizon-1)*nb_ctrl_var rows");
+    // the sparse form of the reference stacks a target block per keypoint of the concatenated list, every sub-system's target into each of a
+    // shared step's blocks (SequentialSystem.cpp:186-260); a plain System evaluates its last keypoint in the blocks of all: not reproduced
+    if (s.hasSharedStep())
+        throw std::runtime_error("[ilqr_hip] keypoints that share a timestep are not supported by the batch solvers (BatchILQRCP, BatchILQR)");
     ilqr_problem_desc d;
     s.lower(&d);
     if (Q) {  // BatchILQRCP.cpp:21-26 / BatchILQR.cpp:22-26: a user Q replaces the keypoints' precisions; the device takes its diagonal blocks

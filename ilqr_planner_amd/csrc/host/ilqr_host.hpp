@@ -302,6 +302,12 @@ public:
     const std::vector<std::shared_ptr<Keypoint>>& getKeypoints() const { return keypoints; }
     // Lowering to the C ABI's POD descriptor.  Throws for systems the device cannot run.
     virtual void lower(ilqr_problem_desc* d) const;
+    // Indices into getKeypoints() of the descriptor's keypoints, in descriptor order: of the keypoints given for one timestep a plain System
+    // keeps the last (the map of System::init, System.cpp:78-80); a SequentialSystem keeps each sub-system's and orders a shared step's
+    // keypoints by sub-system index.
+    virtual std::vector<int> deviceKeypoints() const;
+    // some timestep holds more than one keypoint of getKeypoints() (the batch solvers refuse such systems)
+    bool hasSharedStep() const;
     virtual bool builtinType() const { return false; }  // overridden by the classes of this header: typeid(*this) == typeid(<that class>)
     // per-instance pieces for B = 1: q0, dq0 captured by localInit
     Vec q0() const { return q0_; }
@@ -434,6 +440,7 @@ public:
     Vec getMuVector(bool sparse) override;                            // :185-226
     Mat getQMatrix(bool sparse) override;                             // :228-274 (block diagonals of the sub-systems)
     void lower(ilqr_problem_desc* d) const override;
+    std::vector<int> deviceKeypoints() const override;
     const std::vector<std::shared_ptr<System>>& systems() const { return systems_; }
 
 protected:

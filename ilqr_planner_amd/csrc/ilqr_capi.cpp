@@ -232,6 +232,7 @@ static void mat3(const double* A, const double* B, double* C) {
 }
 
 static_assert(DOF == DEV_DOF, "ilqr_dofmap.hpp and ilqr_device.hpp");
+static_assert(STEP_MAX_KP == ILQR_MAX_KP && MAX_KP == ILQR_MAX_KP, "ilqr_steps.hpp, ilqr_device.hpp and include/ilqr_hip.h");
 
 static int check_dof(ilqr_ctx* c, int dof) {
     if (dof < 1 || dof > DOF) return fail(c, "chains of 1 to 7 moving joints are supported (dof = " + std::to_string(dof) + ")");
@@ -308,7 +309,10 @@ static int lower_desc(ilqr_ctx* c, const ilqr_problem_desc& d, const DofMap& m, 
     h.n_kp = d.n_kp;
     for (int k = 0; k < d.n_kp; k++) {
         if (d.kp_timestep[k] < 0 || d.kp_timestep[k] >= d.horizon) return fail(c, "keypoint timestep outside the horizon");
-        if (k > 0 && d.kp_timestep[k] <= d.kp_timestep[k - 1]) return fail(c, "keypoint timesteps must be unique and ascending");
+        if (k > 0 && d.kp_timestep[k] < d.kp_timestep[k - 1]) return fail(c, "keypoint timesteps must be non-decreasing");
+        // a plain System keeps one keypoint per step (System.cpp:78-80): only the sub-systems of a sequence put several on one step
+        if (k > 0 && d.kp_timestep[k] == d.kp_timestep[k - 1] && !d.is_sequence && d.limit_multiplicity <= 1)
+            return fail(c, "keypoint timesteps must be unique and ascending unless is_sequence = 1 (the keypoints of a SequentialSystem's sub-systems may share a step)");
         h.kp_t[k] = d.kp_timestep[k];
         if (d.kp_joint[k] && !((d.kind == ILQR_SYS_POS_ORN || d.kind == ILQR_SYS_POS_ORN_TIME) && d.nb_deriv == 1))
             return fail(c, "kp_joint is for PosOrn / PosOrnTime systems with nb_deriv = 1 (a joint-space system needs no flag)");
@@ -330,6 +334,7 @@ static int lower_desc(ilqr_ctx* c, const ilqr_problem_desc& d, const DofMap& m, 
         h.kp_pos_radius[k] = d.kp_pos_radius[k];
         for (int i = 0; i < 3; i++) h.kp_orn_thresh[k][i] = d.kp_orn_thresh[k][i];
     }
+    if (!build_step_table(h.kp_t, h.n_kp, h.steps)) return fail(c, "keypoint timesteps must be non-decreasing");
     h.reg = d.reg; h.alpha_floor = d.alpha_floor; h.stop_tol = d.stop_tol;
     return 0;
 }
@@ -407,7 +412,10 @@ extern "C" int ilqr_problem_create(ilqr_ctx* c, const ilqr_problem_desc* d, int 
     rc |= dalloc(p, &b.kpdev, (size_t)(d->n_kp > 0 ? d->n_kp : 1) * (NX + NU) * Bp);
     rc |= dalloc(p, &b.kpx, (size_t)(d->n_kp > 0 ? d->n_kp : 1) * 16 * (NX + NU) * Bp);
     rc |= dalloc(p, &b.dunA, (size_t)16 * Bp);
-    rc |= dalloc(p, &b.kpd, (size_t)(d->n_kp > 0 ? d->n_kp : 1) * (NX + NX * NX) * Bp);
+    {   // one slot per keypoint step; with shared steps the keypoints' own terms follow in a slot each (k_kp_terms, k_kp_sum)
+        const int slots = p->hdesc.steps.n + (has_shared_step(p->hdesc.steps) ? d->n_kp : 0);
+        rc |= dalloc(p, &b.kpd, (size_t)(slots > 0 ? slots : 1) * (NX + NX * NX) * Bp);
+    }
     if (rc) { ilqr_problem_destroy(p); return 1; }
     b.U0 = U0; b.q0 = q0; b.dq0 = dq0; b.kp_tg = tg; b.desc = p->ddesc;
     bool up_ok = hipMemcpyAsync(p->ddesc, &p->hdesc, sizeof(DevDesc), hipMemcpyHostToDevice, c->stream) == hipSuccess;
@@ -615,6 +623,7 @@ static PlanIn plan_input(const ilqr_problem* p, bool al, int nb_iter, int line_s
     PlanIn in;
     in.kind = p->desc.kind; in.nd = p->desc.nb_deriv; in.al = al; in.m = p->bufs.m; in.per_step = p->bufs.per_step; in.con_state_only = p->con_state_only;
     in.limits2_set = p->desc.limits2_set != 0;
+    in.shared_steps = has_shared_step(p->hdesc.steps);
     in.uniform_R = true;
     for (int i = 1; i < p->dims.n_u; i++) in.uniform_R = in.uniform_R && (p->hdesc.R_diag[i] == p->hdesc.R_diag[0]);
     // the register-resident sweep addresses x, u and the multipliers with 32-bit byte offsets (ilqr_kernels_dpp.hip): batches whose arrays pass
@@ -677,7 +686,9 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     } split_join{c, pl.split};
     FwdArgs f;
     std::memset(&f, 0, sizeof(f));
-    f.line_search = line_search; f.early_stop = early_stop; f.nb_iter = nb_iter; f.penalty_roll = penalty0; f.n_alpha = pl.n_alpha; f.al = al ? 1 : 0; f.n_kp = p->desc.n_kp;
+    f.line_search = line_search; f.early_stop = early_stop; f.nb_iter = nb_iter; f.penalty_roll = penalty0; f.n_alpha = pl.n_alpha; f.al = al ? 1 : 0; f.n_kp = p->hdesc.steps.n;
+    f.shared = has_shared_step(p->hdesc.steps) ? 1 : 0;
+    f.n_kp_all = p->desc.n_kp;
     f.fused = pl.fused ? 1 : 0;
     f.limits = p->desc.limits_set ? 1 : 0;
     for (int k = 0; k < p->desc.n_kp; k++) f.kp_ext |= p->desc.kp_dist[k] | p->desc.kp_has_frame[k] | p->desc.kp_has_Ru[k] | p->desc.kp_joint[k];
@@ -760,9 +771,15 @@ extern "C" int ilqr_solve_al(ilqr_problem* p, int nb_iter, int lag, double penal
     return solve_riccati(p, true, nb_iter, lag, penalty, scaling, line_search, early_stop);
 }
 
+// The batch solvers' sparse form stacks one target block per keypoint of the reference's concatenated list, and at a shared timestep the
+// reference's SequentialSystem stacks every sub-system's target into each of them (getMuVector(true) / getQMatrix(true)): not reproduced.
+static const char* const BATCH_SHARED_STEP_TEXT =
+    "keypoints that share a timestep are not supported by the batch solvers (ilqr_solve_batch_cp, ilqr_solve_batch)";
+
 extern "C" int ilqr_solve_batch_cp(ilqr_problem* p, const double* psi, int Kw, int nb_iter, int early_stop) {
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
+    if (has_shared_step(p->hdesc.steps)) return fail(c, BATCH_SHARED_STEP_TEXT);
     if (!p->has_state || !p->has_controls) return fail(c, "set_init_state and set_controls must be called before a solve");
     HIPCHK(c, hipSetDevice(c->device));
     std::string err;
@@ -793,6 +810,7 @@ extern "C" int ilqr_solve_batch_cp(ilqr_problem* p, const double* psi, int Kw, i
 extern "C" int ilqr_solve_batch(ilqr_problem* p, int nb_iter, int early_stop) {
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
+    if (has_shared_step(p->hdesc.steps)) return fail(c, BATCH_SHARED_STEP_TEXT);
     if (!p->has_state || !p->has_controls) return fail(c, "set_init_state and set_controls must be called before a solve");
     HIPCHK(c, hipSetDevice(c->device));
     std::string err;

@@ -13,6 +13,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ilqr_steps.hpp"
+
 namespace ilqr {
 
 constexpr int DOF = 7;
@@ -57,6 +59,8 @@ struct DevDesc {
     int batch_limits;                  // 0: the batch solvers see no limit terms (sequence of sub-systems: SequentialSystem does not override
                                        // fpBatch, and the sequence object itself has no limits); 1: plain system
     double pen_xx;                     // penalty^2 x limit multiplicity (l_xx of a violated limit); `penalty` holds penalty x multiplicity
+    StepTable steps;                   // distinct keypoint steps and the keypoints on each (ilqr_steps.hpp).  The cooperative kernels walk kp_t
+                                       // and run only where every step holds one keypoint (plan_riccati); the generic kernels walk this table
 };
 
 template <int KIND_, int ND_>

@@ -17,6 +17,8 @@ namespace ilqr {
 
 // ------------------------------------------------------------------------------------------------ kernels
 
+#define NOUNR _Pragma("unroll 1")
+
 // Initial rollout from U0 (ILQRRecursive.cpp:27-56): X, cost0; resets the per-instance solve state.
 template <class S, bool AL>
 __global__ __launch_bounds__(64) void k_init_rollout(Bufs a, double penalty) {
@@ -28,7 +30,7 @@ __global__ __launch_bounds__(64) void k_init_rollout(Bufs a, double penalty) {
     double x[NX], u[NU], xn[NX];
     init_state<S>(d, a, b, x);
     double cost = 0;
-    int kpi = 0;
+    int st = 0;  // next entry of the step table (ilqr_steps.hpp): all keypoints on one timestep add their terms
     double* X = a.X[0];
     double* U = a.U[0];
     for (int k = 0; k < T - 1; k++) {
@@ -41,18 +43,18 @@ __global__ __launch_bounds__(64) void k_init_rollout(Bufs a, double penalty) {
                 AT(a.Is, k * a.m + r, b) = penalty * ((g < 0 && lam == 0) ? 0.0 : 1.0);
             }
         }
-        const bool iskp = (kpi < d.n_kp && d.kp_t[kpi] == k);
-        cost += stage_cost<S>(d, a, b, iskp ? kpi : -1, x, u);
-        if (iskp) kpi++;
+        const bool iskp = (st < d.steps.n && d.steps.t[st] == k);
+        cost += stage_cost<S>(d, a, b, iskp ? st : -1, x, u);
+        if (iskp) st++;
         dyn_step<S>(d, x, u, xn);
         UNR for (int i = 0; i < NX; i++) x[i] = xn[i];
     }
     UNR for (int i = 0; i < NX; i++) AT(X, (T - 1) * NX + i, b) = x[i];
     {
-        const bool iskp = (kpi < d.n_kp && d.kp_t[kpi] == T - 1);
+        const bool iskp = (st < d.steps.n && d.steps.t[st] == T - 1);
         double zu[NU];
         UNR for (int i = 0; i < NU; i++) zu[i] = 0;
-        cost += stage_cost<S>(d, a, b, iskp ? kpi : -1, x, zu);
+        cost += stage_cost<S>(d, a, b, iskp ? st : -1, x, zu);
     }
     a.cost[b] = cost;
     a.alpha[b] = 1.0;
@@ -102,6 +104,66 @@ __global__ __launch_bounds__(64) void k_kp_derivs(Bufs a, int fused) {
     });
 }
 
+// k_kp_derivs for problems whose keypoints share a timestep (ilqr_steps.hpp), in two launches.  k_kp_terms: one block column per KEYPOINT
+// (as k_kp_derivs: the keypoint index is the uniform blockIdx.y), its l_x | l_xx without the limit terms into its own slot behind the steps'
+// slots (kpd slot n_steps + keypoint).  k_kp_sum: one block column per distinct step, whose kpd slot receives the sum of its keypoints' slots in
+// keypoint order (by sub-system index within a step: SequentialSystem.cpp:144-165 sums cost_x / cost_xx over the sub-systems), then the limit
+// terms once.  (One kernel looping over a step's keypoints kept the FK and Jacobian code live across the loop: 2 KB of scratch on the
+// 2nd-order systems.)  Only the generic kernels read these slots (plan_riccati routes shared steps there), so there is no fused acceptance.
+template <class S>
+__global__ __launch_bounds__(64) void k_kp_terms(Bufs a) {
+    constexpr int NX = S::NX;
+    constexpr int ROLLN = (!S::JOINT && S::ND == 1) ? 64 : 0;
+    __shared__ double sj[ROLLN ? 7 * DOF : 1][64];
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    const int kpi = blockIdx.y;
+    if (b >= d.B) return;
+    if (!a.active[b]) return;
+    const int Bp = d.Bp;
+    const int k = d.kp_t[kpi];
+    const double* X = a.X[a.cur[b]];
+    double x[NX];
+    UNR for (int i = 0; i < NX; i++) x[i] = AT(X, k * NX + i, b);
+    double* out = a.kpd + (size_t)(d.steps.n + kpi) * (NX + NX * NX) * Bp;
+    stage_derivs_rows<S, true, ROLLN, false>(d, a, b, x, kpi, &sj[0][threadIdx.x], [&](int i, const double* row, double lxi) {
+        AT(out, i, b) = lxi;
+        UNR for (int j = 0; j < NX; j++) AT(out, NX + i * NX + j, b) = row[j];
+    });
+}
+
+template <class S>
+__global__ __launch_bounds__(64) void k_kp_sum(Bufs a) {
+    constexpr int NX = S::NX, W = NX + NX * NX;
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    const int st = blockIdx.y;
+    if (b >= d.B) return;
+    if (!a.active[b]) return;
+    const int Bp = d.Bp;
+    const int k = d.steps.t[st], kp0 = d.steps.kp[st], kp1 = d.steps.kp[st + 1];
+    double* out = a.kpd + (size_t)st * W * Bp;
+    const double* src = a.kpd + (size_t)(d.steps.n + kp0) * W * Bp;
+    NOUNR for (int e = 0; e < W; e++) {
+        double v = AT(src, e, b);
+        NOUNR for (int j = 1; j < kp1 - kp0; j++) v += AT(src, (size_t)j * W + e, b);
+        AT(out, e, b) = v;
+    }
+    if (d.limits_set) {  // limit terms (System.cpp:121-142), once per step, as stage_derivs_rows adds them for a lone keypoint
+        const double* X = a.X[a.cur[b]];
+        NOUNR for (int i = 0; i < NX; i++) {
+            if (d.lw[i] != 0) {
+                const double xi = AT(X, k * NX + i, b);
+                double qv = 0, L = 0;
+                if (xi > d.smax[i]) { qv = d.smax[i] - xi; L = d.penalty; }
+                else if (xi < d.smin[i]) { qv = d.smin[i] - xi; L = d.penalty; }
+                AT(out, i, b) += -L * qv;
+                AT(out, NX + i * NX + i, b) += (L != 0.0) ? d.pen_xx : 0.0;
+            }
+        }
+    }
+}
+
 // Backward Riccati sweep (ILQRRecursive.cpp:68-97): writes K_k, d_k for k = T-2..0.  Needs k_kp_derivs first.
 //
 // One lane per instance, the reference's operation order (dense products, partial-pivot LU as Eigen's inverse()).  The matrices of a step
@@ -111,7 +173,6 @@ __global__ __launch_bounds__(64) void k_kp_derivs(Bufs a, int fused) {
 // lane, and in round 1 one of them -- then still with the keypoint code inlined -- ended in a memory aperture violation: DESIGN.md 5.5.)
 // The stage derivatives come from k_kp_derivs at the keypoint steps (FK, the quaternion log map, frames, dead zones and J'QJ stay out of
 // the sweep) and are the limit terms elsewhere; the second limit set on top of either.
-#define NOUNR _Pragma("unroll 1")
 template <class S>
 constexpr int backward_ws_doubles() {
     return 3 * S::NX * S::NX + 5 * S::NU * S::NX + 3 * S::NU * S::NU + 4 * S::NX + 2 * S::NU;
@@ -181,10 +242,10 @@ __global__ __launch_bounds__(64) void k_backward(Bufs a) {
     };
     auto is_v = [](int i) { return ND == 2 && i >= DOF && i < 2 * DOF; };
 
-    int kpi = d.n_kp - 1;
+    int kpi = d.steps.n - 1;  // step table walk: the kpd slot of a step holds the sum over its keypoints (k_kp_sum)
     NOUNR for (int i = 0; i < NX; i++) WV(ox, i) = AT(X, (T - 1) * NX + i, b);
     {
-        const bool iskp = (kpi >= 0 && d.kp_t[kpi] == T - 1);
+        const bool iskp = (kpi >= 0 && d.steps.t[kpi] == T - 1);
         stage_to_ws(iskp ? kpi : -1, oP, op);
         if (iskp) kpi--;
     }
@@ -209,7 +270,7 @@ __global__ __launch_bounds__(64) void k_backward(Bufs a) {
             WV(obc, NX - 1) = 2 * dts;
         }
         {   // l_xx, l_x of the stage go straight into the Qxx / Qx slots (Qxx = l_xx + A'PA below)
-            const bool iskp = (kpi >= 0 && d.kp_t[kpi] == k);
+            const bool iskp = (kpi >= 0 && d.steps.t[kpi] == k);
             stage_to_ws(iskp ? kpi : -1, oQxx, oQx);
             if (iskp) kpi--;
         }
@@ -401,7 +462,7 @@ __global__ __launch_bounds__(64) void k_forward(Bufs a, int it, int line_search,
         init_state<S>(d, a, b, x);
         dun = 0;
         newCost = 0;
-        int kpi = 0;
+        int st = 0;  // step table walk, as in k_init_rollout
         for (int k = 0; k < T - 1; k++) {
             double dx[NX];
             UNR for (int i = 0; i < NX; i++) dx[i] = x[i] - AT(X, k * NX + i, b);
@@ -423,18 +484,18 @@ __global__ __launch_bounds__(64) void k_forward(Bufs a, int it, int line_search,
                     AT(a.Is, k * a.m + r, b) = penalty_roll * ((g < 0 && lam == 0) ? 0.0 : 1.0);
                 }
             }
-            const bool iskp = (kpi < d.n_kp && d.kp_t[kpi] == k);
-            newCost += stage_cost<S>(d, a, b, iskp ? kpi : -1, x, u);
-            if (iskp) kpi++;
+            const bool iskp = (st < d.steps.n && d.steps.t[st] == k);
+            newCost += stage_cost<S>(d, a, b, iskp ? st : -1, x, u);
+            if (iskp) st++;
             dyn_step<S>(d, x, u, xn);
             UNR for (int i = 0; i < NX; i++) x[i] = xn[i];
         }
         UNR for (int i = 0; i < NX; i++) AT(Xn, (T - 1) * NX + i, b) = x[i];
         {
-            const bool iskp = (kpi < d.n_kp && d.kp_t[kpi] == T - 1);
+            const bool iskp = (st < d.steps.n && d.steps.t[st] == T - 1);
             double zu[NU];
             UNR for (int i = 0; i < NU; i++) zu[i] = 0;
-            newCost += stage_cost<S>(d, a, b, iskp ? kpi : -1, x, zu);
+            newCost += stage_cost<S>(d, a, b, iskp ? st : -1, x, zu);
         }
     } while (((newCost >= cost0) || isnan(newCost)) && alpha > d.alpha_floor && line_search);
 
@@ -651,7 +712,10 @@ void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, co
     if (f.n_kp <= 0) return;
     with_sys(kind, nd, [&](auto s) {
         using S = decltype(s);
-        if (f.kp_ext) hipLaunchKernelGGL((k_kp_derivs<S, true>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a, f.fused);
+        if (f.shared) {  // f.n_kp = distinct steps, f.n_kp_all = keypoints
+            hipLaunchKernelGGL((k_kp_terms<S>), dim3((B + 63) / 64, f.n_kp_all), dim3(64), 0, st, a);
+            hipLaunchKernelGGL((k_kp_sum<S>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a);
+        } else if (f.kp_ext) hipLaunchKernelGGL((k_kp_derivs<S, true>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a, f.fused);
         else hipLaunchKernelGGL((k_kp_derivs<S, false>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a, f.fused);
     });
 }

@@ -60,7 +60,9 @@ __host__ __device__ inline int kd_rs(int sym, int nu, int rowp) { return sym ? K
 
 struct FwdArgs {
     int it, line_search, early_stop, do_update, nb_iter;
-    int n_kp;     // number of keypoints (grid of k_kp_derivs)
+    int n_kp;     // number of distinct keypoint steps (grid of k_kp_derivs); with unique timesteps the number of keypoints
+    int shared;   // some timestep holds more than one keypoint: k_kp_terms + k_kp_sum sum them (generic kernels only, plan_riccati)
+    int n_kp_all; // number of keypoints (grid of k_kp_terms)
     int al;       // 1 = AL_ILQR semantics (early stop without the cost test)
     int n_alpha;  // number of step sizes 1, 1/2, ... the line search may try (11 for alpha_floor = 1e-3)
     double penalty_roll, penalty_update;

@@ -130,12 +130,13 @@ ILQR_DEV void stage_derivs(const DevDesc& d, const Bufs& a, int b, const double*
 
 // The same derivatives of a KEYPOINT stage handed out row by row -- sink(i, row_i of l_xx, l_x[i]) -- for k_kp_derivs: a lane that holds the
 // whole n_x x n_x matrix (225 doubles for n_x = 15) spills; a row at a time does not.  Expression for expression stage_derivs (same bits).
-template <class S, bool EXT, int ROLL, class Sink>
+// LIM = false: the keypoint's terms alone (a further keypoint on a shared step: the limit terms come with the first one)
+template <class S, bool EXT, int ROLL, bool LIM = true, class Sink>
 ILQR_DEV void stage_derivs_rows(const DevDesc& d, const Bufs& a, int b, const double* x, int kpi, double* lj, Sink&& sink) {
     constexpr int NX = S::NX, NQ = S::NQ, NF = S::NF;
     const int Bp = d.Bp;
     auto finish = [&](int i, double* row, double lxi) {  // limit terms of coordinate i (System.cpp:121-142), then out
-        if (d.limits_set && d.lw[i] != 0) {
+        if (LIM && d.limits_set && d.lw[i] != 0) {
             double qv = 0, L = 0;
             if (x[i] > d.smax[i]) { qv = d.smax[i] - x[i]; L = d.penalty; }
             else if (x[i] < d.smin[i]) { qv = d.smin[i] - x[i]; L = d.penalty; }
@@ -287,15 +288,18 @@ ILQR_DEV void lim2_derivs(const DevDesc& d, const double* x, double (*lxx)[S::NX
     }
 }
 
-// stage cost l(x,u,k) (System::cost): task part only at keypoint steps, limits always
+// stage cost l(x,u,k) (System::cost): task part only at keypoint steps, limits always.  st = index of the step in the step table
+// (d.steps) or -1: every keypoint on the step adds its own term (SequentialSystem.cpp:144-150 sums the sub-systems), in keypoint order
 template <class S>
-ILQR_DEV double stage_cost(const DevDesc& d, const Bufs& a, int b, int kpi, const double* x, const double* u) {
+ILQR_DEV double stage_cost(const DevDesc& d, const Bufs& a, int b, int st, const double* x, const double* u) {
     const int Bp = d.Bp;
     double c = 0;
-    if (kpi >= 0) {
-        double tg[S::NF];
-        UNR for (int i = 0; i < S::NF; i++) tg[i] = AT(a.kp_tg, kpi * S::NF + i, b);
-        c += kp_cost<S>(d, kpi, tg, x, u);
+    if (st >= 0) {
+        for (int kpi = d.steps.kp[st]; kpi < d.steps.kp[st + 1]; kpi++) {
+            double tg[S::NF];
+            UNR for (int i = 0; i < S::NF; i++) tg[i] = AT(a.kp_tg, kpi * S::NF + i, b);
+            c += kp_cost<S>(d, kpi, tg, x, u);
+        }
     }
     if (d.limits_set) c += limit_cost<S>(d, x);
     if (d.lim2) c += lim2_cost<S>(d, x);

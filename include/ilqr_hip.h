@@ -61,8 +61,7 @@ typedef struct ilqr_problem ilqr_problem;
  *   R_diag           <- System::R (src/system/System.cpp:41,73)
  *   limits_*         <- state_max_/state_min_/joint_limits_weight_/penalty_ (src/system/System.cpp:38-61)
  *   kp_*             <- Keypoint::getTimestep()/getPrecision() (include/ilqr_planner/system/Keypoint.h:23-35);
- *                       timesteps must be unique and ascending (System.cpp:77-86 sorts them; a std::map keeps the
- *                       last of duplicates).  Keypoint TARGETS are per instance: ilqr_problem_set_keypoint_targets.
+ *                       timesteps must be non-decreasing.  Keypoint TARGETS are per instance: ilqr_problem_set_keypoint_targets.
  *   reg,alpha_floor,stop_tol <- hard-coded constants of ILQRRecursive.cpp:89,155,174
  */
 typedef struct {
@@ -84,7 +83,12 @@ typedef struct {
     double seg_xyz[ILQR_MAX_SEG][3];
     double seg_R[ILQR_MAX_SEG][9]; /* row-major */
     double seg_axis[ILQR_MAX_SEG][3];
-    int n_kp;
+    int n_kp;      /* at most ILQR_MAX_KP in all */
+    /* Non-decreasing.  Keypoints on the same timestep ADD their terms, each with its own kp_Q, kp_dist, frame, kp_Ru and kp_joint, in index
+     * order (a SequentialSystem's sub-systems whose keypoints share a step: SequentialSystem.cpp:115-160 sums them); a shared step needs
+     * is_sequence = 1 (or limit_multiplicity > 1), otherwise the timesteps must be strictly ascending.  A plain System keeps only the last
+     * keypoint given for a step (System.cpp:78-80,96-101 fill a std::map): its lowering passes that one alone.  Shared steps run on the
+     * generic kernels; the batch solvers refuse them with an error text. */
     int kp_timestep[ILQR_MAX_KP];
     double kp_Q[ILQR_MAX_KP][ILQR_MAX_NQ * ILQR_MAX_NQ]; /* row-major n_Q x n_Q, leading dimension n_Q */
     /* PosOrnKeypointDistFunct (src/system/PosOrnKeypointDistFunct.cpp:13-35): dead zones on the residual of keypoint k --
@@ -99,7 +103,8 @@ typedef struct {
      * kp_has_frame[k] = 0: base frame.  sys::SequentialSystem (src/system/SequentialSystem.cpp:78-168) sums the costs of its
      * sub-systems: every keypoint carries the control penalty of its own sub-system (kp_has_Ru / kp_Ru; the sequential
      * system's own Rt stays in R_diag for l_u, l_uu) and the limit terms are added once per sub-system (limit_multiplicity;
-     * 0 = 1).  Sub-systems whose keypoints share a timestep are not lowered.  With limit_multiplicity > 1 the batch solvers
+     * 0 = 1).  Sub-systems whose keypoints share a timestep are lowered as keypoints on one step, ordered by sub-system index (each keeps its
+     * own residual, frame, dead zone and kp_Ru; the terms add, see kp_timestep).  With limit_multiplicity > 1 the batch solvers
      * (ilqr_solve_batch_cp, ilqr_solve_batch) apply NO limit terms: the reference's SequentialSystem does not override fpBatch, which
      * then runs on the sequence object itself, constructed without limits (SequentialSystem.cpp:12-18). */
     int kp_has_frame[ILQR_MAX_KP];
