@@ -15,10 +15,13 @@ collective); the only exchange is the all-gather of the converged costs over RCC
 inside the timed region.  `--gather-trajectories` adds the gather of X / U (sharding.gather_trajectories).
 
 What is timed: `steps` solves between two fences (device synchronize + barrier + synchronize), per-launch profiling OFF, inputs
-resident in HBM.  Kernel durations for the roofline come from a SECOND pass with HIP events on the library's stream, after the
-timed region.  The oracle is used only for the `cpu_baseline` sample and the parity report (N = 1), never inside the timed region.
-`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) before that second pass: the inputs are seeded, so two
-builds of the library run with the same arguments can be compared output for output.
+resident in HBM.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs): the inputs are seeded, so two builds of
+the library run with the same arguments can be compared output for output.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump if asked for, the result line.  `--full` adds
+what takes runs of its own, all after the timed region and the dump: the roofline block, whose kernel durations come from a SECOND pass
+with HIP events on the library's stream, and at N = 1 the `cpu_baseline` sample and the parity report (the only uses of the oracle;
+`--no-cpu-baseline` drops these two).
 """
 from __future__ import annotations
 
@@ -152,6 +155,56 @@ def algorithmic_bytes(cfg, nx, nu, m, B, fused):
         bwd += 8 * 2 * (nx + nu) * steps
     fwd = 8 * ((nu * nx + nu) + (nx + nu) + (nx + nu)) * steps
     return dict(backward=bwd, forward=fwd, apply=None, rollout=None)
+
+
+def roofline(cfg, config, prof, at, nx, nu, m, B):
+    """The roofline block of the --full line: the dominant rated kernel category of the profiled pass (prof: category -> (total ms,
+    launches) over its two solves) against the HBM peak, the other categories beside it.  at = the per-iteration step sizes of the
+    Riccati solvers (None for Batch-CP).  None when no launched category has algorithmic bytes."""
+    import numpy as np
+
+    riccati = cfg["solver"] != "batch_cp"
+    v1 = os.environ.get("ILQR_HIP_PATH") == "v1"
+    fused = (not v1) and cfg["kind"] in (0, 2) and cfg["nb_deriv"] == 1 and riccati
+    alg = algorithmic_bytes(cfg, nx, nu, m, B, fused)
+    trials = float(np.mean(1 + np.round(-np.log2(at)))) if at is not None else None
+    kern = {}
+    for name in ("rollout", "backward", "forward", "apply", "other"):
+        ms, n = prof[name]
+        if n:
+            avg = ms / n
+            byts = alg.get(name)
+            if byts is not None and name == "forward" and v1:
+                byts = byts * trials  # the generic kernels re-roll the horizon once per trial
+            kern[name] = dict(avg_ms=avg, launches=n, total_ms=ms, alg_bytes=byts, gbs=(byts / (avg * 1e-3) / 1e9) if byts else None)
+    rated = {k: v for k, v in kern.items() if v["alg_bytes"]}
+    dom = max(rated, key=lambda k: rated[k]["total_ms"]) if rated else None
+    if not dom:
+        return None
+    k = kern[dom]
+    traffic, traffic_src = pmc_traffic(config, dom) if not v1 else (None, None)
+    roof = dict(bound="hbm", kernel=dom, achieved=round(k["gbs"], 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(k["gbs"] / HBM_PEAK_GBS, 5),
+                traffic=traffic, traffic_source=traffic_src, avg_launch_ms=round(k["avg_ms"], 4), alg_bytes_per_launch=int(k["alg_bytes"]),
+                launches_per_step={n_: v["launches"] // 2 for n_, v in kern.items()},
+                other={n_: dict(avg_launch_ms=round(v["avg_ms"], 4), achieved=round(v["gbs"], 2) if v["gbs"] else None) for n_, v in kern.items() if n_ != dom},
+                timing="HIP events on the library's stream, separate pass after the timed region")
+    if trials is not None:
+        roof["mean_line_search_trials"] = round(trials, 3)
+    if fused:  # uniform control weights: K = N / dt is symmetric and the sweep writes its upper triangle (36 of the 56 doubles of a gain record)
+        roof["traffic_note"] = ("algorithmic bytes count the full gain record K | d of SURVEY 8(d) (56 doubles per instance-step); the kernels move its packed "
+                                "symmetric form (36 doubles), so the measured traffic lies BELOW the algorithmic bytes")
+    # what share of the solve the rated kernels are: a roofline fraction speaks for its own kernel only
+    tot_ms = sum(v["total_ms"] for v in kern.values())
+    roof["rated_share_of_solve"] = round(sum(v["total_ms"] for v in rated.values()) / tot_ms, 4) if tot_ms else None
+    roof["dominant_share_of_solve"] = round(k["total_ms"] / tot_ms, 4) if tot_ms else None
+    if not riccati:  # Batch-CP: the horizon is walked twice per solve (rated); the iterations work on keypoint-sized data
+        unr = {n_: round(v["total_ms"] / tot_ms, 4) for n_, v in kern.items() if n_ not in rated}
+        roof["unrated"] = {"share_of_solve": unr, "bound": "latency",
+                           "note": "backward = linearize + solve of the 14 x 14 normal equations, forward = the two line-search passes: per-iteration launches on "
+                                   "keypoint-sized data (7 x 14 W, 14 x 14 H), each the chain of ONE FK / cost evaluation or ONE solve at one to two waves per SIMD; "
+                                   "SQ_WAIT_ANY / SQ_WAVE_CYCLES = 52-77 % (profiles/r02_sq_counters.txt): no memory or matrix-core roofline applies, "
+                                   "the figure of the rated kernel is NOT the configuration's"}
+    return roof
 
 
 # ----------------------------------------------------------------------------- CPU baseline (the oracle, timed beside the GPU number)
@@ -372,7 +425,9 @@ def main():
     ap.add_argument("--config", default="C3", help="workload (ilqr_planner_amd.workloads.config); C3 = the metric's configuration")
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU (default: the configuration's per-GPU batch)")
     ap.add_argument("--iters", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU-baseline sample and the parity report (profiler runs)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also the roofline pass and (N = 1) the CPU-baseline sample and the "
+                    "parity report; a plain run prints the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline sample and the parity report (profiler runs)")
     ap.add_argument("--gather-trajectories", action="store_true", help="N>1: also gather X / U to rank 0 every step")
     ap.add_argument("--no-split", action="store_true", help="one kernel at a time on one stream (ilqr_ctx_set_split(0)): for rocprofv3 runs whose "
                     "per-kernel durations are to be compared with the roofline block")
@@ -441,62 +496,21 @@ def main():
     elapsed = max_over_ranks(timed_region(step, args.steps, torch.cuda.synchronize, dist), dist, "cuda")
     dumped = dump_outputs(p, cfg, nb_iter, cost_dev.cpu().numpy(), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
-    # second pass, per-launch HIP events on: kernel durations for the roofline (not part of the headline)
-    ctx.profile_reset()
-    ctx.profile(True)
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    ctx.profile(False)
-    prof = {n: ctx.profile_get(w) for n, w in (("rollout", capi.PROF_ROLLOUT), ("backward", capi.PROF_BACKWARD), ("forward", capi.PROF_FORWARD),
-                                               ("apply", capi.PROF_APPLY), ("other", capi.PROF_OTHER))}
-    cost = cost_dev.cpu().numpy()
-    status = p.status()
     riccati = cfg["solver"] != "batch_cp"
-    at = p.trace(nb_iter)[1] if riccati else None
+    prof = at = None
+    if args.full:  # second pass, per-launch HIP events on: kernel durations for the roofline (not part of the headline)
+        ctx.profile_reset()
+        ctx.profile(True)
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        ctx.profile(False)
+        prof = {n: ctx.profile_get(w) for n, w in (("rollout", capi.PROF_ROLLOUT), ("backward", capi.PROF_BACKWARD), ("forward", capi.PROF_FORWARD),
+                                                   ("apply", capi.PROF_APPLY), ("other", capi.PROF_OTHER))}
+        at = p.trace(nb_iter)[1] if riccati else None
+    status = p.status()
 
     if rank == 0:
-        m = p.m
-        v1 = os.environ.get("ILQR_HIP_PATH") == "v1"
-        fused = (not v1) and cfg["kind"] in (0, 2) and cfg["nb_deriv"] == 1 and riccati
-        alg = algorithmic_bytes(cfg, nx, nu, m, B, fused)
-        trials = float(np.mean(1 + np.round(-np.log2(at)))) if at is not None else None
-        kern = {}
-        for name in ("rollout", "backward", "forward", "apply", "other"):
-            ms, n = prof[name]
-            if n:
-                avg = ms / n
-                byts = alg.get(name)
-                if byts is not None and name == "forward" and v1:
-                    byts = byts * trials  # the generic kernels re-roll the horizon once per trial
-                kern[name] = dict(avg_ms=avg, launches=n, total_ms=ms, alg_bytes=byts, gbs=(byts / (avg * 1e-3) / 1e9) if byts else None)
-        rated = {k: v for k, v in kern.items() if v["alg_bytes"]}
-        dom = max(rated, key=lambda k: rated[k]["total_ms"]) if rated else None
-        roof = None
-        if dom:
-            k = kern[dom]
-            traffic, traffic_src = pmc_traffic(args.config, dom) if not v1 else (None, None)
-            roof = dict(bound="hbm", kernel=dom, achieved=round(k["gbs"], 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(k["gbs"] / HBM_PEAK_GBS, 5),
-                        traffic=traffic, traffic_source=traffic_src, avg_launch_ms=round(k["avg_ms"], 4), alg_bytes_per_launch=int(k["alg_bytes"]),
-                        launches_per_step={n_: v["launches"] // 2 for n_, v in kern.items()},
-                        other={n_: dict(avg_launch_ms=round(v["avg_ms"], 4), achieved=round(v["gbs"], 2) if v["gbs"] else None) for n_, v in kern.items() if n_ != dom},
-                        timing="HIP events on the library's stream, separate pass after the timed region")
-            if trials is not None:
-                roof["mean_line_search_trials"] = round(trials, 3)
-            if fused:  # uniform control weights: K = N / dt is symmetric and the sweep writes its upper triangle (36 of the 56 doubles of a gain record)
-                roof["traffic_note"] = ("algorithmic bytes count the full gain record K | d of SURVEY 8(d) (56 doubles per instance-step); the kernels move its packed "
-                                        "symmetric form (36 doubles), so the measured traffic lies BELOW the algorithmic bytes")
-            # what share of the solve the rated kernels are: a roofline fraction speaks for its own kernel only
-            tot_ms = sum(v["total_ms"] for v in kern.values())
-            roof["rated_share_of_solve"] = round(sum(v["total_ms"] for v in rated.values()) / tot_ms, 4) if tot_ms else None
-            roof["dominant_share_of_solve"] = round(k["total_ms"] / tot_ms, 4) if tot_ms else None
-            if not riccati:  # Batch-CP: the horizon is walked twice per solve (rated); the iterations work on keypoint-sized data
-                unr = {n_: round(v["total_ms"] / tot_ms, 4) for n_, v in kern.items() if n_ not in rated}
-                roof["unrated"] = {"share_of_solve": unr, "bound": "latency",
-                                   "note": "backward = linearize + solve of the 14 x 14 normal equations, forward = the two line-search passes: per-iteration launches on "
-                                           "keypoint-sized data (7 x 14 W, 14 x 14 H), each the chain of ONE FK / cost evaluation or ONE solve at one to two waves per SIMD; "
-                                           "SQ_WAIT_ANY / SQ_WAVE_CYCLES = 52-77 % (profiles/r02_sq_counters.txt): no memory or matrix-core roofline applies, "
-                                           "the figure of the rated kernel is NOT the configuration's"}
         kinds = ("PosOrn", "PosOrnTime", "JointSpace", "JointSpaceTime")
         out = {
             "metric": METRIC,
@@ -519,11 +533,12 @@ def main():
                        "exchange": "all-gather of costs" + (" + gather of X, U to rank 0" if X_dev is not None else "") if world > 1 else "none"},
             "batch_sweeps_per_s": nb_iter * args.steps / elapsed,
             "nonfinite_frac": float(np.mean((status & 1) != 0)),
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roofline(cfg, args.config, prof, at, nx, nu, p.m, B)
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline and the parity report belong to the N = 1 line only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline and the parity report belong to the N = 1 line only
             cb, ores = cpu_baseline(cfg, inp, nb_iter, psi)
             out["cpu_baseline"] = cb
             if riccati:

@@ -10,7 +10,7 @@ cut = args.index("--") if "--" in args else 0
 bench_args, libs = (args[:cut], args[cut + 1:]) if "--" in args else ([], args)
 bench_args = bench_args or ["--no-cpu-baseline", "--steps", "5", "--warmup", "1"]
 code = ("import sys, runpy; sys.path.insert(0, %r); import ilqr_planner_amd.capi as c; c.LIB_PATH = sys.argv[1]; "
-        "sys.argv = ['bench.py'] + sys.argv[2:]; runpy.run_path(%r, run_name='__main__')") % (ROOT, os.path.join(ROOT, "bench.py"))
+        "sys.argv = ['bench.py', '--full'] + sys.argv[2:]; runpy.run_path(%r, run_name='__main__')") % (ROOT, os.path.join(ROOT, "bench.py"))
 for lib in libs:
     out = subprocess.run([sys.executable, "-c", code, os.path.abspath(lib)] + bench_args, capture_output=True, text=True)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
