@@ -67,6 +67,8 @@ struct BatchWideState {
     // per instance
     double *xbk = nullptr, *av = nullptr, *v0 = nullptr, *p0 = nullptr, *scal = nullptr, *cv = nullptr, *beta = nullptr, *dvb = nullptr, *sc = nullptr,
            *Ckp = nullptr, *rkp = nullptr, *u0hat = nullptr, *g0 = nullptr, *y0 = nullptr, *psi = nullptr, *h0inv = nullptr;
+    // m = n_kp n_x > 32 (ilqr_batchwide_big.hip): keypoint states of the iterate, their change per unit step, the first cost's keypoint terms
+    double *xs = nullptr, *dxs = nullptr, *kc = nullptr;
 };
 int batchwide_solve(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nx, int nu, const double* psi_host, int Kw, int nb_iter, int early_stop,
                     bool u0_zero, hipStream_t stream, std::string& err, const ProfHook& ph = ProfHook());

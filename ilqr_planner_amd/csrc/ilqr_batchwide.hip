@@ -3,7 +3,7 @@
 //
 // The reference forms H = PSI'Su'(J'QJ + L)Su PSI + PSI'R PSI (Kw x Kw, 693 x 693 for the first tutorial) and inverts it every
 // iteration.  H is a positive matrix H0 = PSI'R PSI that does not depend on the instance or the iterate, plus a term of rank
-// m = n_kp n_x (14 .. 30): with V = Su PSI at the keypoint rows (m x Kw) and C = blkdiag(J'QJ + L) (m x m)
+// m = n_kp n_x (7 .. 120; m > 32: ilqr_batchwide_big.hip): with V = Su PSI at the keypoint rows (m x Kw) and C = blkdiag(J'QJ + L) (m x m)
 //     H^-1 = H0^-1 - H0^-1 V' (I + C G)^-1 C V H0^-1,      G = V H0^-1 V'            (push-through identity; C may be singular)
 // so the step only needs an m x m solve.  Nothing of size Kw x Kw is built per instance, and no GEMM: the work per iteration is
 // the rollout / keypoint evaluation, as for the recursive solver (HBM-bound streaming, not MFMA work).
@@ -31,29 +31,9 @@
 #include <cstring>
 
 #include "ilqr_batch_dev.hpp"
+#include "ilqr_batchwide.hpp"
 
 namespace ilqr {
-
-struct WArgs {
-    const double *G, *Et, *ZPZ, *PZ;  // shared tables (LTI)
-    double *xbk, *av, *v0, *p0, *scal, *cv, *beta, *Ckp, *rkp, *dvb, *sc;
-    const double* u0hat;
-    int m, it, early_stop;
-};
-
-// s <- A s + B u of the constant-dt systems
-template <class S>
-ILQR_DEV void lin_step(const DevDesc& d, double* s, const double* u) {
-    const double dt = d.dt, hdt2 = dt * dt / 2;
-    if (S::ND == 1) {
-        UNR for (int i = 0; i < DOF; i++) s[i] += dt * u[i];
-    } else {
-        UNR for (int i = 0; i < DOF; i++) {
-            s[i] += dt * s[DOF + i] + hdt2 * u[i];
-            s[DOF + i] += dt * u[i];
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ LTI systems
 
@@ -161,11 +141,6 @@ ILQR_DEV double wl_task_cost(const DevDesc& d, const Bufs& a, const WArgs& c, in
         }
     }
     return cost_e + cost_l;
-}
-
-// control cost of the family member (beta (1 - al), c + al d):  u'Ru = c00 + (bn^2 - 1) gamma + 2 bn v0.(c + al d) + (c + al d)'G(c + al d)
-ILQR_DEV double wl_uru(double c00, double gam, double bn, double al, double v0c, double v0d, double cGc, double cGd, double dGd) {
-    return c00 + (bn * bn - 1) * gam + 2 * bn * (v0c + al * v0d) + ((cGc + 2 * al * cGd) + al * al * dGd);
 }
 
 // Linearisation at the current iterate, one lane per (instance, keypoint): C_k = J'QJ + L, r_k = J'Q e + L ql (System::fpBatch +
@@ -384,11 +359,6 @@ __global__ void k_w_matvec(const double* __restrict__ M, const double* __restric
 
 // ------------------------------------------------------------------------------------------------ time systems, identity basis
 
-struct WTArgs {
-    double *Ckp, *rkp, *dun2;
-    int m, it, early_stop;
-};
-
 // System::fpBatch of the current controls (System.cpp:181-211): X out, C_k / r_k at the keypoint steps, cost0
 template <class S>
 __global__ __launch_bounds__(64) void k_wt_roll(Bufs a, WTArgs c) {
@@ -427,25 +397,6 @@ __global__ __launch_bounds__(64) void k_wt_roll(Bufs a, WTArgs c) {
     }
     UNR for (int i = 0; i < NX; i++) AT(a.X[0], (T - 1) * NX + i, b) = x[i];
     a.cost[b] = cost_e + cost_u + cost_l;  // cost0 of this iteration (BatchILQR.cpp:135)
-}
-
-// entry (r, cc) of B_j, the linearisation of the step x_{j-1}, u_{j-1} -> x_j (PosOrnTimePlannerSys.cpp:149-185; the 2nd-order
-// time column uses the velocity AFTER the step)
-template <class S>
-ILQR_DEV double wt_bj(int r, int cc, const double* up, const double* xj) {
-    constexpr int NX = S::NX, NU = S::NU;
-    const double dts = up[NU - 1], dt = dts * dts;
-    if (r == NX - 1) return cc == NU - 1 ? 2 * dts : 0.0;
-    if (S::ND == 1) {
-        if (cc == NU - 1) return 2 * dts * up[r];
-        return r == cc ? dt : 0.0;
-    }
-    if (r < DOF) {
-        if (cc == NU - 1) return 2 * dts * xj[DOF + r] + 2 * dts * dts * dts * up[r];
-        return r == cc ? dt * dt / 2 : 0.0;
-    }
-    if (cc == NU - 1) return 2 * dts * up[r - DOF];
-    return (r - DOF) == cc ? dt : 0.0;
 }
 
 // One wave per instance.  G = sum_j V_j R^-1 V_j' and V u over the column blocks of the reference's Su (block j: Phi_{k,j} B_j for
@@ -640,7 +591,7 @@ static bool spd_inverse(std::vector<double>& A, int n) {
     return true;
 }
 
-// LTI systems.  psi == nullptr: identity basis.
+// LTI systems.  psi == nullptr: identity basis.  MC = 0: the kernels of ilqr_batchwide_big.hip (m > 32).
 template <class S, int MC>
 static int run_wl(BatchWideState& st, const DevDesc& h, Bufs& bufs, const double* psi, int Kw, int nb_iter, int early_stop, bool u0_zero,
                   hipStream_t stream, std::string& err) {
@@ -665,6 +616,9 @@ static int run_wl(BatchWideState& st, const DevDesc& h, Bufs& bufs, const double
                   w_alloc(st, &st.scal, (size_t)3 * Bp, stream) && w_alloc(st, &st.cv, (size_t)m * Bp, stream) && w_alloc(st, &st.beta, (size_t)Bp, stream) &&
                   w_alloc(st, &st.Ckp, (size_t)nkp * NX * NX * Bp, stream) && w_alloc(st, &st.rkp, (size_t)m * Bp, stream) &&
                   w_alloc(st, &st.dvb, (size_t)m * Bp, stream) && w_alloc(st, &st.sc, (size_t)6 * Bp, stream);
+        if (ok && MC == 0)
+            ok = w_alloc(st, &st.xs, (size_t)nkp * 2 * NX * Bp, stream) && w_alloc(st, &st.dxs, (size_t)nkp * 2 * NX * Bp, stream) &&
+                 w_alloc(st, &st.kc, (size_t)nkp * 2 * Bp, stream);
         if (ok && !ident)
             ok = w_alloc(st, &st.u0hat, (size_t)N * Bp, stream) && w_alloc(st, &st.g0, (size_t)Kw * Bp, stream) && w_alloc(st, &st.y0, (size_t)Kw * Bp, stream) &&
                  w_alloc(st, &st.psi, (size_t)N * Kw, stream) && w_alloc(st, &st.h0inv, (size_t)Kw * Kw, stream);
@@ -788,14 +742,26 @@ static int run_wl(BatchWideState& st, const DevDesc& h, Bufs& bufs, const double
         hipLaunchKernelGGL(k_w_matvec, dim3((B + 63) / 64, Kw), block, 0, stream, st.h0inv, st.g0, bufs.desc, st.y0, Kw, Kw);
         hipLaunchKernelGGL(k_w_matvec, dim3((B + 63) / 64, N), block, 0, stream, st.psi, st.y0, bufs.desc, st.u0hat, N, Kw);
     }
-    hipLaunchKernelGGL((k_wl_init<S, MC>), dim3((B + 64 / MC - 1) / (64 / MC)), dim3(64), 0, stream, bufs, c);
-    for (int it = 0; it < nb_iter; it++) {
-        c.it = it;
-        hipLaunchKernelGGL((k_wl_linearize<S, MC>), dim3((B + 15) / 16, nkp), dim3(16), 0, stream, bufs, c);
-        hipLaunchKernelGGL((k_wl_solve<S, MC>), dim3(B), dim3(64), 0, stream, bufs, c);
-        hipLaunchKernelGGL((k_wl_linesearch<S, MC>), dim3((B + 3) / 4), dim3(64), 0, stream, bufs, c);
+    if constexpr (MC == 0) {
+        WBig g;
+        g.xs = st.xs; g.dxs = st.dxs; g.kc = st.kc;
+        bool ok = wb_lti_launch(WB_INIT, h.kind, ND, B, T, nkp, bufs, c, g, stream);
+        for (int it = 0; ok && it < nb_iter; it++) {
+            c.it = it;
+            ok = wb_lti_launch(WB_LINEARIZE, h.kind, ND, B, T, nkp, bufs, c, g, stream) && wb_lti_launch(WB_SOLVE, h.kind, ND, B, T, nkp, bufs, c, g, stream) &&
+                 wb_lti_launch(WB_LINESEARCH, h.kind, ND, B, T, nkp, bufs, c, g, stream);
+        }
+        if (!ok || !wb_lti_launch(WB_CONTROLS, h.kind, ND, B, T, nkp, bufs, c, g, stream)) { err = "wide-basis batch solve: no kernel for this system and m"; return 1; }
+    } else {
+        hipLaunchKernelGGL((k_wl_init<S, MC>), dim3((B + 64 / MC - 1) / (64 / MC)), dim3(64), 0, stream, bufs, c);
+        for (int it = 0; it < nb_iter; it++) {
+            c.it = it;
+            hipLaunchKernelGGL((k_wl_linearize<S, MC>), dim3((B + 15) / 16, nkp), dim3(16), 0, stream, bufs, c);
+            hipLaunchKernelGGL((k_wl_solve<S, MC>), dim3(B), dim3(64), 0, stream, bufs, c);
+            hipLaunchKernelGGL((k_wl_linesearch<S, MC>), dim3((B + 3) / 4), dim3(64), 0, stream, bufs, c);
+        }
+        hipLaunchKernelGGL((k_wl_controls<S, MC>), dim3((B + 63) / 64, T - 1), block, 0, stream, bufs, c);
     }
-    hipLaunchKernelGGL((k_wl_controls<S, MC>), dim3((B + 63) / 64, T - 1), block, 0, stream, bufs, c);
     hipLaunchKernelGGL((k_wide_final<S>), grid, block, 0, stream, bufs);
     if (hipGetLastError() != hipSuccess) { err = "wide-basis batch solve: kernel launch failed"; return 1; }
     return 0;
@@ -807,11 +773,12 @@ static int run_wl_m(BatchWideState& st, const DevDesc& h, Bufs& bufs, const doub
     const int m = h.n_kp * S::NX;
     if (m <= 16) return run_wl<S, 16>(st, h, bufs, psi, Kw, nb_iter, early_stop, u0_zero, stream, err);
     if (m <= 32) return run_wl<S, 32>(st, h, bufs, psi, Kw, nb_iter, early_stop, u0_zero, stream, err);
-    err = "wide-basis batch solve: n_keypoints * n_x must not exceed 32";
+    if (m <= ILQR_MAX_KP * S::NX) return run_wl<S, 0>(st, h, bufs, psi, Kw, nb_iter, early_stop, u0_zero, stream, err);
+    err = "wide-basis batch solve: n_keypoints * n_x must not exceed ILQR_MAX_KP * n_x";
     return 1;
 }
 
-// time systems, identity basis
+// time systems, identity basis.  MC = 0: the solve kernel of ilqr_batchwide_big.hip (m > 32).
 template <class S, int MC>
 static int run_wt(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nb_iter, int early_stop, hipStream_t stream, std::string& err) {
     constexpr int NX = S::NX, NU = S::NU;
@@ -835,7 +802,11 @@ static int run_wt(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nb_iter,
     for (int it = 0; it < nb_iter; it++) {
         c.it = it;
         hipLaunchKernelGGL((k_wt_roll<S>), grid, block, 0, stream, bufs, c);
-        hipLaunchKernelGGL((k_wt_solve<S, MC>), dim3(B), block, 0, stream, bufs, c);
+        if constexpr (MC == 0) {
+            if (!wb_time_solve_launch(h.kind, h.nd, B, bufs, c, stream)) { err = "wide-basis batch solve: no kernel for this system and m"; return 1; }
+        } else {
+            hipLaunchKernelGGL((k_wt_solve<S, MC>), dim3(B), block, 0, stream, bufs, c);
+        }
         BTArgs bt;
         bt.it = it; bt.early_stop = early_stop;
         hipLaunchKernelGGL((k_bt_linesearch<S>), dim3((B + 3) / 4), dim3(64), 0, stream, bufs, bt);
@@ -850,7 +821,8 @@ static int run_wt_m(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nb_ite
     const int m = h.n_kp * S::NX;
     if (m <= 16) return run_wt<S, 16>(st, h, bufs, nb_iter, early_stop, stream, err);
     if (m <= 32) return run_wt<S, 32>(st, h, bufs, nb_iter, early_stop, stream, err);
-    err = "wide-basis batch solve: n_keypoints * n_x must not exceed 32";
+    if (m <= ILQR_MAX_KP * S::NX) return run_wt<S, 0>(st, h, bufs, nb_iter, early_stop, stream, err);
+    err = "wide-basis batch solve: n_keypoints * n_x must not exceed ILQR_MAX_KP * n_x";
     return 1;
 }
 

@@ -87,12 +87,28 @@ def config(name: str):
     return dict(cfgs[name])
 
 
-def make_batch(ctx: capi.Context, cfg: dict, B: int | None = None, seed: int | None = None, limits: str = "inactive", chain=None):
-    """Returns (desc, inputs) where inputs = dict(q0, dq0, targets[list per keypoint], U0, [A, b, lambda0])."""
+def _keypoint_steps(cfg, kp_t):
+    """The default via point and goal, or the given steps; cfg's "Qdiag" (and "ctimes" on the time systems) hold one entry per keypoint."""
+    T = cfg["T"]
+    if kp_t is None:
+        return [T // 2 - 1, T - 1]
+    kp_t = [int(t) for t in kp_t]
+    if not kp_t or any(b <= a for a, b in zip(kp_t, kp_t[1:])) or kp_t[0] < 0 or kp_t[-1] > T - 1:
+        raise ValueError("kp_t must be increasing steps in 0 .. T-1")
+    if len(cfg["Qdiag"]) != len(kp_t) or (cfg.get("ctimes") is not None and len(cfg["ctimes"]) != len(kp_t)):
+        raise ValueError("cfg['Qdiag'] (and cfg['ctimes']) need one entry per keypoint of kp_t")
+    if cfg.get("hybrid"):
+        raise ValueError("kp_t is not supported for the hybrid configurations")
+    return kp_t
+
+
+def make_batch(ctx: capi.Context, cfg: dict, B: int | None = None, seed: int | None = None, limits: str = "inactive", chain=None, kp_t=None):
+    """Returns (desc, inputs) where inputs = dict(q0, dq0, targets[list per keypoint], U0, [A, b, lambda0]).
+    kp_t: keypoint steps (default: [T//2 - 1, T - 1]); the targets are drawn keypoint by keypoint, so kp_t=None draws what it always did."""
     B = int(B if B is not None else cfg["B"])
     seed = int(seed if seed is not None else cfg["seed"])
     if cfg["kind"] in (capi.SYS_JOINT, capi.SYS_JOINT_TIME):
-        return _make_joint_batch(cfg, B, seed, limits)
+        return _make_joint_batch(cfg, B, seed, limits, kp_t)
     chain = chain or panda_chain()
     dof = chain["dof"]
     lo, up = chain["lower"], chain["upper"]
@@ -100,7 +116,7 @@ def make_batch(ctx: capi.Context, cfg: dict, B: int | None = None, seed: int | N
     kind, nd, T = cfg["kind"], cfg["nb_deriv"], cfg["T"]
     tm = 1 if kind == capi.SYS_POS_ORN_TIME else 0
     nu = dof + tm
-    kp_t = [T // 2 - 1, T - 1]
+    kp_t = _keypoint_steps(cfg, kp_t)
     if limits == "inactive":
         qmax = np.full(dof, 10 * np.pi)
         qmin = -qmax
@@ -119,7 +135,7 @@ def make_batch(ctx: capi.Context, cfg: dict, B: int | None = None, seed: int | N
                           limits2=dict(state_max=smax - 0.3 * (w != 0), state_min=smin + 0.3 * (w != 0), limit_weight=w, penalty=1.0) if cfg.get("limits2") else None)
     q0 = np.clip(Q0_TUT[None, :dof] + rng.uniform(-0.3, 0.3, (B, dof)), lo, up)
     targets = []
-    for i in range(2):
+    for i in range(len(kp_t)):
         qr = rng.uniform(lo, up, (B, dof))
         pos, quat, _ = ctx.fk_batch(desc, qr)
         cols = [pos, quat]
@@ -142,13 +158,13 @@ def make_batch(ctx: capi.Context, cfg: dict, B: int | None = None, seed: int | N
     return desc, inp
 
 
-def _make_joint_batch(cfg, B, seed, limits):
+def _make_joint_batch(cfg, B, seed, limits, kp_t=None):
     """JointSpace(Time)PlannerSys batches (Angular(Time)Keypoint targets); `dof` < 7 joints are padded to the device's 7."""
     rng = np.random.default_rng(seed)
     T, dofu, D = cfg["T"], cfg.get("dof", 7), 7
     tm = 1 if cfg["kind"] == capi.SYS_JOINT_TIME else 0
     n = D + tm
-    kp_t = [T // 2 - 1, T - 1]
+    kp_t = _keypoint_steps(cfg, kp_t)
     lim = 10 * np.pi if limits == "inactive" else 2.0
     smax, smin, w = np.zeros(n), np.zeros(n), np.zeros(n, dtype=int)
     smax[:dofu], smin[:dofu], w[:dofu] = lim, -lim, 1
@@ -166,7 +182,7 @@ def _make_joint_batch(cfg, B, seed, limits):
     base = np.asarray(cfg.get("q0", [0.0] * dofu), float)
     q0[:, :dofu] = base[None, :] + (rng.uniform(-0.3, 0.3, (B, dofu)) if B > 1 else 0.0)
     targets = []
-    for i in range(2):
+    for i in range(len(kp_t)):
         t = np.zeros((B, n))
         t[:, :dofu] = rng.uniform(-2.5, 2.5, (B, dofu)) if not tm else rng.uniform(-1.0, 1.0, (B, dofu))
         if tm:

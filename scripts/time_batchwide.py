@@ -1,4 +1,5 @@
-"""Wall time of the wide-basis batch solvers (BatchILQR / BatchILQRCP with Kw > 16) at batch sizes of the BASELINE configs."""
+"""Wall time of the wide-basis batch solvers (BatchILQR / BatchILQRCP with Kw > 16) at batch sizes of the BASELINE configs.
+`--keypoints`: BatchILQR with 4 and 8 keypoints (m = n_kp n_x > 32) instead."""
 import sys
 import time
 
@@ -12,8 +13,15 @@ from PyLQR.utils import primitives  # the product's own basis builders (no oracl
 ctx = capi.Context(0)
 
 
-def run(label, cfg, B, nb_iter, psi=None):
-    desc, inp = workloads.make_batch(ctx, cfg, B=B)
+def run(label, cfg, B, nb_iter, psi=None, n_kp=None):
+    kp_t = None
+    if n_kp:  # keypoints spread over the horizon, the last on the last step; via points weighted like the config's via point
+        T = cfg["T"]
+        kp_t = [int(round((k + 1) * (T - 1) / n_kp)) for k in range(n_kp)]
+        cfg = dict(cfg, Qdiag=[cfg["Qdiag"][0]] * (n_kp - 1) + [cfg["Qdiag"][1]])
+        if cfg.get("ctimes"):
+            cfg["ctimes"] = [cfg["ctimes"][1] * (k + 1) / n_kp for k in range(n_kp)]
+    desc, inp = workloads.make_batch(ctx, cfg, B=B, kp_t=kp_t)
     p = workloads.load_batch(ctx, desc, inp, B)
     go = (lambda: p.solve_batch(nb_iter, False)) if psi is None else (lambda: p.solve_batch_cp(psi, nb_iter, False))
     go()
@@ -31,6 +39,15 @@ def run(label, cfg, B, nb_iter, psi=None):
     p.close()
 
 
+if "--keypoints" in sys.argv:  # many keypoints: m = n_kp n_x > 32 rows (ilqr_batchwide_big.hip), next to m = 28 of the 2-keypoint PosOrn-2 case
+    run("BatchILQR PosOrn-2 (T=100) 2 kp, m=28", dict(workloads.config("C2nd"), T=100), 4096, 10)
+    run("BatchILQR PosOrn-1 (T=100) 8 kp, m=56", dict(workloads.config("C2"), T=100), 4096, 10, n_kp=8)
+    run("BatchILQR PosOrn-2 (T=100) 4 kp, m=56", dict(workloads.config("C2nd"), T=100), 4096, 10, n_kp=4)
+    run("BatchILQR PosOrn-2 (T=100) 8 kp, m=112", dict(workloads.config("C2nd"), T=100), 4096, 10, n_kp=8)
+    run("BatchILQR PosOrnTime-2 (T=50) 2 kp, m=30", dict(workloads.config("C4"), T=50), 4096, 10)
+    run("BatchILQR PosOrnTime-2 (T=50) 4 kp, m=60", dict(workloads.config("C4"), T=50), 4096, 10, n_kp=4)
+    run("BatchILQR PosOrnTime-2 (T=50) 8 kp, m=120", dict(workloads.config("C4"), T=50), 4096, 10, n_kp=8)
+    sys.exit(0)
 run("BatchILQR PosOrn-1 (tutorial shape, 693 controls)", dict(workloads.config("C2"), T=100), 4096, 10)
 run("BatchILQR PosOrn-1 C5 shape (2793 controls)", workloads.config("C5"), 8192, 10)
 run("BatchILQR PosOrn-2 (T=100)", dict(workloads.config("C2nd"), T=100), 4096, 10)
