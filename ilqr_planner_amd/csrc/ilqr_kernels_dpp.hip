@@ -143,11 +143,22 @@ __device__ __forceinline__ double dpp64(double v) {
     hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double oct_sum(double v) {  // sum over lanes 8m .. 8m+7, result in all eight
-    v += dpp64<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp64<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp64<0x141>(v);  // row_half_mirror
+// Sum over lanes 8m .. 8m+7, result in all eight.  Every addition is rounded on its own: left to contraction, the first one became
+// fma(a_l, x_l, a_l' x_l') in each lane -- another value in lane l than in its partner l', so the lanes of an instance disagreed in the last
+// bits of g (and could disagree on the sign of a g at zero), and no other kernel could restate the sum.  As written it is the tree
+// ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)) in every lane: con_g_oct (ilqr_kernels_wave.hip) gives the same bits.
+__device__ __forceinline__ double oct_sum(double v) {
+#pragma clang fp contract(off)
+    v = v + dpp64<0xB1>(v);   // quad_perm [1,0,3,2]
+    v = v + dpp64<0x4E>(v);   // quad_perm [2,3,0,1]
+    v = v + dpp64<0x141>(v);  // row_half_mirror
     return v;
+}
+// g = a_r . x - b over the eight lanes of an instance: product, tree and subtraction each rounded once
+__device__ __forceinline__ double oct_row_g(double a_l, double x_l, double b) {
+#pragma clang fp contract(off)
+    const double p = a_l * x_l;
+    return oct_sum(p) - b;
 }
 
 __device__ __forceinline__ double ldg(const double* base, unsigned byte_off) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + byte_off); }
@@ -423,10 +434,10 @@ __global__ __launch_bounds__(64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
             UNR for (int rr = 0; rr < MRR; rr++) {
                 if (MR == 1 || rr < m) {
                     // g = A_r . x - b: every lane multiplies its own component, 8-lane butterfly (lane 7 adds 0); all lanes of the instance hold it
-                    const double gr = -bbr[rr] + oct_sum(Av[rr] * xv);
+                    const double gr = oct_row_g(Av[rr], xv, bbr[rr]);
                     if (FUSED) {  // AL-ILQR.cpp:190 (mask with the multipliers before the update), :202-208 (update)
                         Isk[rr] = sw.pen_in * ((gr < 0 && lam[rr] == 0) ? 0.0 : 1.0);
-                        const double nv = lam[rr] + sw.pen_update_prev * gr;
+                        const double nv = fma(sw.pen_update_prev, gr, lam[rr]);  // (k_apply's expression on this path)
                         const double nl = nv > 0 ? nv : 0;  // cwiseMax(0); a NaN becomes 0 as before
                         lam[rr] = upd ? nl : lam[rr];
                         if (upd && l == 0) stg(a.lambda, oLw + rofs[rr], lam[rr]);

@@ -511,6 +511,23 @@ __global__ __launch_bounds__(64 * KW) void k_select(Bufs a, FwdArgs f) {
 //   x(alpha) = xbar + alpha (x(1) - xbar) written over x(1) unless alpha = 1; on that accepted (x, u) the AL bookkeeping of
 //   AL-ILQR.cpp:190,202-208: I_k = penalty (g<0 && lambda==0 ? 0 : 1) with the multipliers BEFORE the update,
 //   lambda_k = max(0, lambda_k + penalty' g) on update iterations.  k_flip then swaps the buffers of the instances that ran.
+// g = A_r . x - b of a shared state-only row in the summation order of the register-resident sweep (k_backward_si_dpp: products and sums
+// rounded one by one, the 8-lane butterfly's tree; the eighth lane holds 0 . x_0).  On the fused path the sweep of the next iteration does
+// the AL bookkeeping of every iteration but the last, which is k_apply's: with this order a solve of n iterations leaves the multipliers a
+// longer solve holds after its first n, bit for bit, also where a row has several non-zero coefficients.
+template <class S>
+__device__ __forceinline__ double con_g_oct(const Bufs& a, int r, const double* x) {
+#pragma clang fp contract(off)
+    static_assert(S::NX == 7, "the register-resident sweep: single-integrator systems of seven joints");
+    const double* Ar = a.conA + (size_t)r * (S::NX + S::NU);
+    double p[8];
+    UNR for (int j = 0; j < 7; j++) p[j] = Ar[j] * x[j];
+    p[7] = 0.0 * x[0];
+    const double q0 = (p[0] + p[1]) + (p[2] + p[3]);
+    const double q1 = (p[4] + p[5]) + (p[6] + p[7]);
+    return (q0 + q1) - a.conb[r];
+}
+
 template <class S>
 __global__ __launch_bounds__(256) void k_apply(Bufs a, FwdArgs f) {
     constexpr int NX = S::NX, NU = S::NU;
@@ -549,11 +566,11 @@ __global__ __launch_bounds__(256) void k_apply(Bufs a, FwdArgs f) {
     }
     if (k < T - 1) {
         for (int r = 0; r < m; r++) {
-            const double g = con_g<S>(a, k, r, x, u);
+            const double g = f.fused ? con_g_oct<S>(a, r, x) : con_g<S>(a, k, r, x, u);  // fused: the sweep's bits
             const double lam = AT(a.lambda, k * m + r, b);
             AT(a.Is, k * m + r, b) = f.penalty_roll * ((g < 0 && lam == 0) ? 0.0 : 1.0);
             if (f.do_update) {
-                const double v = lam + f.penalty_update * g;
+                const double v = f.fused ? fma(f.penalty_update, g, lam) : lam + f.penalty_update * g;
                 AT(a.lambda, k * m + r, b) = v > 0 ? v : 0;
             }
         }

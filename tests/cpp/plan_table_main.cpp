@@ -140,6 +140,69 @@ int main() {
         CHECK(p.forward == Forward::WaveDpp); CHECK(!p.fused); CHECK(p.apply == Apply::Wave);
         CHECK(p.init == Init::Lti); CHECK(p.init_al_update); CHECK(p.kd_sym == 0);
     }
+    for (int B : {256, 4096}) {
+        // the register-resident sweep holds at most 4 shared state-only rows: one more row, one set per step or a control row leave it --
+        // PosOrn-1 for the matrix-core sweep (k_apply does the AL bookkeeping), JointSpace-1 for the generic sweep and its workspace
+        where = "PosOrn-1 AL, m 4 / 5";
+        PlanIn in = c3(B);
+        in.m = 4;
+        RiccatiPlan p = plan_riccati(in);
+        CHECK(p.sweep == Sweep::SiDpp); CHECK(p.fused); CHECK(p.apply == Apply::WaveLast); CHECK(p.kd_sym == 1);
+        CHECK(!p.al_update); CHECK(!p.init_al_update); CHECK(!p.needs_ws); CHECK(!p.split);
+        in.m = 5;
+        p = plan_riccati(in);
+        CHECK(p.sweep == Sweep::Mfma); CHECK(!p.fused); CHECK(p.apply == Apply::Wave); CHECK(p.kd_sym == 0);
+        CHECK(!p.al_update); CHECK(p.init_al_update); CHECK(!p.needs_ws); CHECK(p.split == (B == 4096));
+        for (int per_step = 0; per_step < 2; per_step++) {
+            for (int state_only = 0; state_only < 2; state_only++) {
+                where = "PosOrn-1 AL, m 4, per_step x con_state_only";
+                in = c3(B);
+                in.m = 4; in.per_step = per_step; in.con_state_only = state_only != 0;
+                p = plan_riccati(in);
+                const bool si = !per_step && state_only;
+                CHECK(p.sweep == (si ? Sweep::SiDpp : Sweep::Mfma)); CHECK(p.fused == si); CHECK(!p.needs_ws);
+                CHECK(p.apply == (si ? Apply::WaveLast : Apply::Wave)); CHECK(p.init_al_update == !si);
+                where = "JointSpace-1 AL, m 4, per_step x con_state_only";
+                in = base(2, 1, true, B);
+                in.m = 4; in.per_step = per_step; in.con_state_only = state_only != 0;
+                p = plan_riccati(in);
+                CHECK(p.sweep == (si ? Sweep::SiDpp : Sweep::Generic)); CHECK(p.fused == si); CHECK(p.needs_ws == !si);
+                CHECK(p.forward == (B == 256 ? Forward::WaveDpp : Forward::WaveWg)); CHECK(p.init == Init::Lti);
+            }
+        }
+        where = "JointSpace-1 AL, m 4 / 5";
+        in = base(2, 1, true, B);
+        in.m = 4; in.con_state_only = true;
+        CHECK(plan_riccati(in).sweep == Sweep::SiDpp); CHECK(!plan_riccati(in).needs_ws);
+        in.m = 5;
+        p = plan_riccati(in);
+        CHECK(p.sweep == Sweep::Generic); CHECK(p.needs_ws); CHECK(!p.fused); CHECK(p.apply == Apply::Wave); CHECK(p.init_al_update);
+        CHECK(!p.al_update); CHECK(!p.split);
+        // 16 rows fit the LDS of the matrix-core sweep and the lanes of an instance's group in the row-per-lane sweep; 17 do not
+        for (int nd = 1; nd <= 2; nd++) {
+            for (int kind : {0, 1, 3}) {
+                if (kind == 3 && nd == 2) continue;
+                where = "AL, m 16 / 17";
+                in = base(kind, nd, true, B);
+                in.m = 16; in.con_state_only = true;
+                p = plan_riccati(in);
+                const bool rows_ok = !(kind == 0 && nd == 1);
+                CHECK(p.sweep == (B == 4096 && rows_ok ? Sweep::Rows : Sweep::Mfma)); CHECK(!p.needs_ws);
+                in.sweep = SweepPin::Rows;
+                CHECK(plan_riccati(in).sweep == (rows_ok ? Sweep::Rows : Sweep::Mfma));
+                in.sweep = SweepPin::Mfma;
+                CHECK(plan_riccati(in).sweep == Sweep::Mfma);
+                for (SweepPin pin : {SweepPin::Auto, SweepPin::Mfma, SweepPin::Rows}) {
+                    in.m = 17; in.sweep = pin;
+                    p = plan_riccati(in);
+                    CHECK(p.sweep == Sweep::Generic); CHECK(p.needs_ws); CHECK(!p.fused); CHECK(p.kd_sym == 0);
+                    CHECK(p.forward != Forward::Generic); CHECK(p.init == Init::Lti); CHECK(p.init_al_update);
+                    CHECK(p.al_update == !(kind == 0 && nd == 1));  // (the wave path updates the multipliers in k_apply)
+                    CHECK(p.split == false);
+                }
+            }
+        }
+    }
     for (int kind = 0; kind < 4; kind++) {
         for (int generic = 0; generic < 2; generic++) {
             where = generic ? "pin generic" : "limits2_set";

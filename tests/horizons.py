@@ -76,13 +76,14 @@ def _check_gains(tag, K, d, iters, at, runs, rerun):
     return n, n_ill
 
 
-def check_case(ctx, cfg, desc, inp, tag, nb_iter=NIT, always=(0, 1)):
+def check_case(ctx, cfg, desc, inp, tag, nb_iter=NIT, always=(0, 1), out=None):
     """One case: a 1-iteration solve (its sweep starts from the same rollout on both sides) and a nb_iter-iteration solve with early stop, both
     against the oracle.  Gates: the parity proof of the longer one (tests/parity_proof.py, instances in `always` proven whatever their
     distance); the gains at every step -- of the 1-iteration solve against the oracle's, of the longer one against the oracle's sweep from
     the device's own state before its last iteration (the iteration that wrote them: a gain image left from an earlier iteration shows
     there, while the drift of an ill-conditioned instance over several iterations does not); the trajectories where the path is the
-    oracle's.  Returns a one-line summary."""
+    oracle's.  Returns a one-line summary; out: a dict that receives the longer solve's cost, iters, step sizes, multipliers (AL), its
+    distance to the oracle's runs and those runs."""
     Bn = len(inp["q0"])
     segs = panda_segs()
     p = workloads.load_batch(ctx, desc, inp, Bn)
@@ -97,16 +98,19 @@ def check_case(ctx, cfg, desc, inp, tag, nb_iter=NIT, always=(0, 1)):
         workloads.run_solver(p, cfg, nb_iter=nb_iter, early_stop=True)
         K, d, X, U, cost, iters = p.K(), p.d(), p.X(), p.U(), p.cost(), p.iters()
         at = p.trace(nb_iter)[1]
+        lam = p.lam() if cfg["solver"] == "al" else None
         runs = {}
 
         def oracle_solve(i):
             runs[i] = oracle_solve_instance(cfg, inp, i, nb_iter, True, segs)
             return runs[i]
 
-        summ, rel, failures = pp.check_batch(p, cfg, inp, nb_iter, True, workloads.run_solver, oracle_solve, always=always)
+        states = []
+        summ, rel, failures = pp.check_batch(p, cfg, inp, nb_iter, True, workloads.run_solver, oracle_solve, always=always, states_out=states)
         assert not failures, f"{tag}: {len(failures)} instance(s) neither within 1e-4 nor proven: {failures[:3]}"
         assert summ["frac_unexplained"] == 0.0 and summ["n_proven_always"] == len(always), (tag, summ)
-        states = pp.gpu_states(p, cfg, nb_iter, False, workloads.run_solver, upto=int(iters.max()))
+        if len(states) < int(iters.max()):  # (the proof needed fewer re-runs than the gains of the last iteration do)
+            states = pp.gpu_states(p, cfg, nb_iter, False, workloads.run_solver, upto=int(iters.max()))
     finally:
         p.close()
     last = {}  # the oracle's iteration from the device's state before each instance's last one, where it takes the device's step size
@@ -131,6 +135,12 @@ def check_case(ctx, cfg, desc, inp, tag, nb_iter=NIT, always=(0, 1)):
             np.testing.assert_allclose(X[i][:, :nxo], r["X"], rtol=0, atol=2e-4, err_msg=f"{tag}: X of instance {i}")
             np.testing.assert_allclose(U[i][:, :nuo], r["U"], rtol=0, atol=2e-3, err_msg=f"{tag}: U of instance {i}")
             nxu += 1
+    if out is not None:
+        out.update(cost=cost, iters=iters, alpha=at, lam=lam, rel=rel, runs=runs)
+    mult = ""
+    if "n_multiplier_checked" in summ:  # AL: every multiplier update recomputed (parity_proof.check_multipliers)
+        mult = (f", multipliers of {summ['n_multiplier_checked']} ({summ['n_multiplier_updates']} updates, {summ['n_multiplier_skipped']} skipped, "
+                f"{summ['n_clamp_ties']} clamp ties, worst {summ['worst_multiplier_ratio']:.2f} of the bound)")
     return (f"{tag}: gains of {n1} / {n4} instances (1 / {nb_iter} iterations; {ill1} / {ill4} ill-conditioned), trajectories of {nxu}, within 1e-4 "
             f"{summ['frac_within_1e4']:.2f}, proofs {summ['n_proofs']} ({summ['n_steps_checked']} steps, {summ['n_tie_decisions']} ties, "
-            f"{summ['n_steps_ill_conditioned']} ill-conditioned)")
+            f"{summ['n_steps_ill_conditioned']} ill-conditioned)" + mult)

@@ -26,9 +26,16 @@ final cost and the oracle's own end-to-end run is the reference map's own sensit
 Nothing is excused on a margin alone any more (round 2 accepted an active-set or limit test within 1e-12 of its threshold without
 checking the other branch): with the GPU's own trajectory handed over, those tests see identical numbers on both sides.  The one
 exception left is an AL row with more than one non-zero coefficient, whose value g = A [x; u] - b is a sum formed in another order on
-the GPU: there a mask test within MASK_ATOL of zero is a tie, and it is counted.  The GPU states come from deterministic re-runs with
+the GPU: there a mask test within MASK_ATOL of zero is a tie, and it is counted -- once per iteration: the oracle cannot take the other
+branch of its own mask, so neither the decision nor the cost of that iteration is held against the instance.  The GPU states come from deterministic re-runs with
 nb_iter = it (the kernels use no atomics: a solve with fewer iterations reproduces the prefix of a longer one bit for bit, which the
 proof also checks through (a)).
+
+The multipliers of an AL solve are the one part of that state the replay cannot vouch for: the oracle takes lambda_it from the device as
+the INPUT of iteration `it`, so a row whose multiplier is never updated, or is updated from another row's g, is replayed faithfully from
+that wrong state.  check_multipliers closes this: every update lambda <- max(0, lambda + penalty g) the device made (AL-ILQR.cpp:202-208)
+is recomputed in extended precision from the device's own accepted trajectory and previous multipliers, and between updates the
+multipliers must not move by a bit.
 """
 from __future__ import annotations
 
@@ -230,9 +237,10 @@ def prove_instance(cfg, inp, i, states, ct, at, iters, segs=None, nb_iter=None, 
                     n_ill += 1
                     worst_ratio = max(worst_ratio, rel / sens if np.isfinite(sens) and sens > 0 else 0.0)
             if not ill:
-                if multi and pr["mask_margin_in"] <= MASK_ATOL and "mask_tie" not in st:
-                    ties += 1
-                    st["mask_tie"] = pr["mask_margin_in"]
+                if multi and pr["mask_margin_in"] <= MASK_ATOL:  # the same tie that may already have excused the decision: counted once
+                    if "mask_tie" not in st:
+                        ties += 1
+                        st["mask_tie"] = pr["mask_margin_in"]
                 else:
                     fails.append("cost")
         st["how"] = "FAIL:" + ",".join(fails) if fails else ("tie" if ties else ("same" if rel <= STEP_RTOL else "same:ill-conditioned"))
@@ -258,11 +266,12 @@ def prove_instance(cfg, inp, i, states, ct, at, iters, segs=None, nb_iter=None, 
     return dict(verdict=verdict, steps=steps, n_ties=n_ties, n_ill=n_ill, worst_ill_ratio=worst_ratio)
 
 
-def check_batch(p, cfg, inp, nb_iter, early_stop, run_solver, oracle_solve, always=(0, 1, 2, 3), rtol=1e-4, indices=None):
+def check_batch(p, cfg, inp, nb_iter, early_stop, run_solver, oracle_solve, always=(0, 1, 2, 3), rtol=1e-4, indices=None, states_out=None):
     """The parity gate of a solved batch `p` (already solved with nb_iter / early_stop): every instance is within `rtol` of the oracle's
     own end-to-end run, or is PROVEN (see the module header).  The instances in `always` are proven whatever their distance.  Returns
     (summary, rel, failures) -- failures lists the unexplained instances with their failing steps; the caller asserts it is empty.
-    indices: check only these instances (a sample of a big batch); rel is then indexed like the batch, zero elsewhere."""
+    indices: check only these instances (a sample of a big batch); rel is then indexed like the batch, zero elsewhere.
+    states_out: a list that receives the states of the re-runs (gpu_states), for a caller that needs them too."""
     cost, iters = p.cost(), p.iters()
     ct, at = p.trace(nb_iter)
     B = len(cost)
@@ -278,17 +287,128 @@ def check_batch(p, cfg, inp, nb_iter, early_stop, run_solver, oracle_solve, alwa
             rel[i] = np.inf  # NaN on one side only: never excused, must be proven step by step
         if rel[i] > rtol or i in always:
             flagged.append(i)
-    states = gpu_states(p, cfg, nb_iter, False, run_solver, upto=int(max(iters[flagged])) if flagged else 0) if flagged else None
+    al = cfg["solver"] == "al"
+    if al:  # the multipliers of every instance are checked: the state after its last iteration is read before the re-runs overwrite it
+        final = dict(U=p.U(), X=p.X(), lam=p.lam())
+        upto = int(max(iters[todo])) if todo else 0
+    else:
+        upto = int(max(iters[flagged])) if flagged else 0
+    states = gpu_states(p, cfg, nb_iter, False, run_solver, upto=upto) if (flagged or al) else None
+    if states_out is not None and states:
+        states_out.extend(states)
     results, failures = [], []
     proofs = {i: prove_instance(cfg, inp, i, states, ct, at, iters, segs, nb_iter, early_stop) for i in flagged}
+    mult = check_multipliers(cfg, inp, states, final, iters, todo) if al else None
     for i in todo:
-        results.append((rel[i] <= rtol, proofs.get(i)))
         pf = proofs.get(i)
+        bad = mult["failures"].get(i) if mult else None
+        if bad:  # wrong multipliers fail the instance, whatever its cost does
+            pf = pf or dict(steps=[], n_ties=0, n_ill=0, worst_ill_ratio=0.0)
+            pf.update(verdict="unexplained", reason="multipliers")
+            pf["steps"] = pf["steps"] + bad
+        results.append((rel[i] <= rtol and not bad, pf))
         if pf and pf["verdict"] == "unexplained":
             failures.append(dict(i=i, rel=float(rel[i]), steps=[st for st in pf["steps"] if st["how"].startswith("FAIL") or st.get("stop") == "FAIL"]))
+            if bad:
+                failures[-1]["reason"] = "multipliers"
     summ = summarize(results)
-    summ["n_proven_always"] = sum(1 for i in always if i in proofs and proofs[i]["verdict"] != "unexplained")
+    summ["n_proven_always"] = sum(1 for i in always if i in proofs and proofs[i]["verdict"] != "unexplained" and not (mult and i in mult["failures"]))
+    if mult:
+        summ.update({k: v for k, v in mult.items() if k != "failures"})
     return summ, rel, failures
+
+
+def al_penalty(al, n_updates):
+    """The penalty after `n_updates` multiplier updates, formed as the solvers form it (penalty *= scaling, AL-ILQR.cpp:203)."""
+    pen = float(al["penalty"])
+    for _ in range(int(n_updates)):
+        pen *= float(al["scaling"])
+    return pen
+
+
+def multiplier_update(lam_prev, X, U, A, b, pen):
+    """lambda + pen (A [x_k; u_k] - b_k) for k = 0 .. T-2 BEFORE the clamp at zero, in numpy.longdouble, and the distance a double
+    evaluation of it may keep from that value.  lam_prev [T-1][m]; X [T][n_x]; U [T-1][n_u]; A [m][n_x+n_u] and b [m], or one set per step
+    ([T-1][m][n_x+n_u], [T-1][m]); pen: the penalty in force at the update (already scaled).
+    The bound, per entry: pen (n_nz + 2) 2^-52 (sum_j |a_rj z_j| + |b_r|) + 2^-52 |lambda| with n_nz the non-zeros of the row -- the rounding
+    of an n_nz-term dot product in any order, with or without contracted multiply-adds (n_nz 2^-53 sum |a z| to first order; 2^-52 leaves
+    the higher orders room), then of the subtraction of b, the product with pen and the sum with lambda (three more roundings of at most
+    2^-53 of operands that sum |a z| + |b|, times pen, and |lambda| bound)."""
+    ld = np.longdouble
+    T1 = U.shape[0]
+    Z = np.concatenate([np.asarray(X)[:T1], np.asarray(U)], axis=1).astype(ld)          # [T-1][n]
+    A3 = np.broadcast_to(np.asarray(A, float), (T1,) + np.asarray(A).shape[-2:]).astype(ld)  # [T-1][m][n]
+    b2 = np.broadcast_to(np.asarray(b, float), (T1, A3.shape[1])).astype(ld)
+    terms = A3 * Z[:, None, :]
+    g = terms.sum(axis=2) - b2
+    lam_prev = np.asarray(lam_prev, float).astype(ld)
+    v = lam_prev + ld(pen) * g
+    n_nz = np.count_nonzero(A3, axis=2)
+    eps = ld(2.0) ** -52
+    tol = ld(pen) * (n_nz + 2) * eps * (np.abs(terms).sum(axis=2) + np.abs(b2)) + eps * np.abs(lam_prev)
+    return v, tol
+
+
+def check_multipliers(cfg, inp, states, final, iters, indices=None):
+    """Every multiplier update of an AL solve against multiplier_update.  states[it]: the device's U, X, lam after `it` iterations (gpu_states);
+    final: the same after the solve under test; iters: iterations each instance made.  For instance i and each iteration `it` it made:
+    the update that closes `it` runs when (it + 1) % lag == 0 with the penalty already scaled (ilqr_oracle.c:874-881) on the trajectory
+    that iteration accepted; otherwise lambda_{it+1} is lambda_it bit for bit.  The state after an instance's last iteration is the solve's
+    own (`final`); where the re-runs went further (another instance made more iterations) their state after that many iterations must be
+    the same bits -- a stopped instance's multipliers do not move.  The clamp may go the other way than the reference's only where the
+    unclamped value is within the bound of zero: counted in n_clamp_ties.  Instances whose trajectory is not finite or leaves |x| < 1e3
+    are skipped (n_multiplier_skipped).  Returns dict(failures = {i: [step records]}, n_multiplier_checked, n_multiplier_updates,
+    n_multiplier_skipped, n_clamp_ties, worst_multiplier_ratio = max |lambda - reference| / bound)."""
+    al = cfg["al"]
+    lag = int(al["lag"])
+    A, b = np.asarray(inp["A"], float), np.asarray(inp["b"], float)
+    out = dict(failures={}, n_multiplier_checked=0, n_multiplier_updates=0, n_multiplier_skipped=0, n_clamp_ties=0, worst_multiplier_ratio=0.0)
+    todo = range(len(iters)) if indices is None else indices
+
+    def state(i, it, n):  # the device's state of instance i after `it` of its n iterations
+        src = final if it == n else states[it]
+        return _unpad(cfg, inp, src["U"][i]), _unpad(cfg, inp, src["X"][i]), np.asarray(src["lam"][i])
+
+    def bits(a):
+        return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+    for i in todo:
+        i, n = int(i), int(iters[i])
+        sts = [state(i, it, n) for it in range(n + 1)]
+        if not all(np.all(np.isfinite(U)) and np.all(np.isfinite(X)) and np.all(np.abs(X) < 1e3) and np.all(np.isfinite(lam)) for U, X, lam in sts):
+            out["n_multiplier_skipped"] += 1
+            continue
+        out["n_multiplier_checked"] += 1
+        fails = []
+        if n < len(states) and not np.array_equal(bits(states[n]["lam"][i]), bits(final["lam"][i])):
+            k, r = np.argwhere(bits(states[n]["lam"][i]) != bits(final["lam"][i]))[0]
+            fails.append(dict(it=n - 1, how="FAIL:multipliers", why="the solve's multipliers are not those of a solve of as many iterations",
+                              instance=i, step=int(k), row=int(r)))
+        for it in range(n):
+            lam0, (U1, X1, lam1) = sts[it][2], sts[it + 1]
+            if (it + 1) % lag:
+                if not np.array_equal(bits(lam0), bits(lam1)):
+                    k, r = np.argwhere(bits(lam0) != bits(lam1))[0]
+                    fails.append(dict(it=it, how="FAIL:multipliers", why="moved on an iteration that is not an update step", instance=i, step=int(k),
+                                      row=int(r), got=float(lam1[k, r]), want=float(lam0[k, r])))
+                continue
+            out["n_multiplier_updates"] += 1
+            v, tol = multiplier_update(lam0, X1, U1, A, b, al_penalty(al, (it + 1) // lag))
+            want = np.maximum(v, 0)
+            dev = np.abs(lam1.astype(np.longdouble) - want)
+            near0 = np.abs(v) <= tol
+            ok = np.where(lam1 == 0, v <= tol, (lam1 > 0) & (dev <= tol) & ((v > 0) | near0))
+            out["n_clamp_ties"] += int(np.sum(ok & ((lam1 == 0) != (v <= 0))))
+            good = ok & (tol > 0)
+            if np.any(good):
+                out["worst_multiplier_ratio"] = max(out["worst_multiplier_ratio"], float(np.max(dev[good] / tol[good])))
+            if not np.all(ok):
+                k, r = np.argwhere(~ok)[0]
+                fails.append(dict(it=it, how="FAIL:multipliers", why="not the update of the previous multipliers on the accepted trajectory", instance=i,
+                                  step=int(k), row=int(r), got=float(lam1[k, r]), want=float(want[k, r]), tol=float(tol[k, r]), n_wrong=int(np.sum(~ok))))
+        if fails:
+            out["failures"][i] = fails
+    return out
 
 
 def summarize(results):

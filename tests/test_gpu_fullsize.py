@@ -46,6 +46,8 @@ def _solve(ctx, cfg, desc, inp, B, nb_iter, solver, keep=False):
     else:
         workloads.run_solver(p, cfg, nb_iter=nb_iter, early_stop=False)
     out = dict(cost=p.cost(), U=p.U(), X=p.X(), iters=p.iters(), alpha=p.alpha(), trace=p.trace(nb_iter)[0])
+    if solver == "al":
+        out["lam"] = p.lam()
     if keep:
         out["p"] = p
     else:
@@ -75,6 +77,8 @@ def test_full_size_properties(ctx, cfg_name, B, nb_iter, solver, monkeypatch):
     np.testing.assert_array_equal(big["cost"][:h], big["cost"][h:])
     np.testing.assert_array_equal(big["U"][:h], big["U"][h:])
     np.testing.assert_array_equal(big["iters"][:h], big["iters"][h:])
+    if solver == "al":
+        np.testing.assert_array_equal(big["lam"][:h], big["lam"][h:])
     rng = np.random.default_rng(7)
     idx = np.sort(rng.choice(B, 61, replace=False))  # ragged: not a multiple of the wave size
     desc_s, _ = workloads.make_batch(ctx, cfg, B=len(idx))
@@ -83,6 +87,8 @@ def test_full_size_properties(ctx, cfg_name, B, nb_iter, solver, monkeypatch):
     np.testing.assert_array_equal(small["cost"], big["cost"][idx])
     np.testing.assert_array_equal(small["U"], big["U"][idx])
     np.testing.assert_array_equal(small["X"], big["X"][idx])
+    if solver == "al":
+        np.testing.assert_array_equal(small["lam"], big["lam"][idx])
     # the returned trajectory is the rollout of the returned controls; recursive solver: the returned cost is the cost of that trajectory
     segs = panda_segs()
     T = cfg["T"]
@@ -159,23 +165,42 @@ def test_forward_passes_agree(ctx, cfg_name, solver, B, monkeypatch):
     np.testing.assert_allclose(b["X"], a["X"], rtol=0, atol=1e-11)
 
 
+def _with_rows(ctx, name, T, m, layout, inp):
+    """inp with the binding m-row set of tests/al_shapes.py in place of the workload's one row: the bounds are the medians of a 13-instance
+    batch of the same workload, so the rows bind for part of any batch of it; multipliers from zero, an update every 2 iterations."""
+    from tests import al_shapes
+
+    cfg_s, _, inp_s = al_shapes.make_case(ctx, name, T, m, layout)
+    return cfg_s, dict(inp, A=inp_s["A"], b=inp_s["b"], lambda0=np.zeros((len(inp["q0"]), T - 1, m)))
+
+
 def test_two_stream_split_does_not_change_results(ctx, monkeypatch):
     """Large batches on the matrix-core sweep (one instance per wave) are solved as two halves on two internal streams, the second one sweep behind
     the first (ilqr_ctx_set_split).  Since round 3 the time systems take the row-per-lane sweep at these sizes, so the schedule is reached through the
-    cross-check switch (and by the shapes only the matrix-core sweep takes); instances are independent: bit-identical results with the split on and off."""
+    cross-check switch (and by the shapes only the matrix-core sweep takes); instances are independent: bit-identical results with the split on and off.
+    C4al with 16 binding rows: the second half's multipliers sit m rows per step behind the first's -- the multipliers are bit-identical too."""
     from ilqr_planner_amd import workloads
 
     monkeypatch.setenv("ILQR_SWEEP", "mfma")
-    cfg = dict(workloads.config("C4"), T=40)
-    B, nb_iter = 2304, 3
-    desc, inp = workloads.make_batch(ctx, cfg, B=B)
-    res = {}
-    for on in (1, 0):
-        ctx.set_split(on)
-        res[on] = _solve(ctx, cfg, desc, inp, B, nb_iter, "recursive")
-    ctx.set_split(1)
-    for k in ("cost", "U", "X", "iters", "alpha"):
-        np.testing.assert_array_equal(res[1][k], res[0][k])
+    for cfg_name, solver, m in (("C4", "recursive", 0), ("C4al", "al", 16)):
+        cfg = dict(workloads.config(cfg_name), T=40)
+        B, nb_iter = 2304, 3
+        desc, inp = workloads.make_batch(ctx, cfg, B=B)
+        if m:
+            nb_iter = 4  # two multiplier updates
+            cfg_s, inp = _with_rows(ctx, cfg_name, 40, m, "state", inp)
+            cfg = dict(cfg, al=cfg_s["al"])
+        res = {}
+        try:
+            for on in (1, 0):
+                ctx.set_split(on)
+                res[on] = _solve(ctx, cfg, desc, inp, B, nb_iter, solver)
+        finally:
+            ctx.set_split(1)
+        for k in ("cost", "U", "X", "iters", "alpha") + (("lam",) if m else ()):
+            np.testing.assert_array_equal(res[1][k], res[0][k], err_msg=f"{cfg_name}: {k}")
+        if m:  # the rows bind in this batch
+            assert np.any(res[1]["lam"] > 0)
 
 
 @pytest.mark.parametrize("cfg_name,B", [("C4", 256), ("C4t1", 100), ("C1t", 64)])
@@ -201,13 +226,14 @@ def test_rerolls_of_the_winner_agree(ctx, cfg_name, B, monkeypatch):
     np.testing.assert_allclose(b["X"][fin], a["X"][fin], rtol=0, atol=1e-8)
 
 
-@pytest.mark.parametrize("cfg_name,solver", [("C3", "al"), ("C2", "recursive")])
-def test_sweep_lane_groupings_agree(ctx, cfg_name, solver, monkeypatch):
+@pytest.mark.parametrize("cfg_name,solver,m", [("C3", "al", 0), ("C2", "recursive", 0), ("C3", "al", 4)], ids=["C3-al", "C2-recursive", "C3-al-m4"])
+def test_sweep_lane_groupings_agree(ctx, cfg_name, solver, m, monkeypatch):
     """The register-resident sweep of the single-integrator systems runs with 16 lanes per instance while that gives every SIMD at most one
     wave and with 8 lanes per instance (two instances per DPP row, every broadcast issued once per half with a bank mask) beyond: a batch
     just over 4 x 1024 instances takes the second form, a 61-instance cut-out of it the first.  Same operations on the same operands in the
     same order in both: bit-identical results, whichever half of a DPP row an instance sits in; the cut-out then goes through the
-    per-instance proof."""
+    per-instance proof.  C3 with m = 4: the binding 4-row set of tests/al_shapes.py, all four register rows in use; the multipliers are
+    bit-identical too."""
     from ilqr_planner_amd import workloads
     from tests import parity_proof as pp
 
@@ -215,6 +241,9 @@ def test_sweep_lane_groupings_agree(ctx, cfg_name, solver, monkeypatch):
     cfg = dict(workloads.config(cfg_name), T=40)
     B, nb_iter = 4200, 6
     desc, inp = workloads.make_batch(ctx, cfg, B=B)
+    if m:
+        cfg_s, inp = _with_rows(ctx, cfg_name, 40, m, "state", inp)
+        cfg = dict(cfg, al=cfg_s["al"])
     big = _solve(ctx, cfg, desc, inp, B, nb_iter, solver)
     rng = np.random.default_rng(11)
     idx = np.sort(rng.choice(B, 61, replace=False))
@@ -225,6 +254,10 @@ def test_sweep_lane_groupings_agree(ctx, cfg_name, solver, monkeypatch):
     np.testing.assert_array_equal(small["U"], big["U"][idx])
     np.testing.assert_array_equal(small["X"], big["X"][idx])
     np.testing.assert_array_equal(small["trace"], big["trace"][idx])
+    if solver == "al":
+        np.testing.assert_array_equal(small["lam"], big["lam"][idx])
+    if m:
+        assert np.any(big["lam"] > 0)
     segs = panda_segs()
     summ, _, failures = pp.check_batch(small["p"], cfg, inp_s, nb_iter, False, workloads.run_solver,
                                        lambda i: oracle_solve_instance(cfg, inp_s, i, nb_iter, False, segs), always=(0, 1, 2, 3))

@@ -171,3 +171,93 @@ def test_batch_solver_replay_and_gate(name, T, early_stop):
     assert pp.prove_instance_batch(cfg, inp, 0, psi, states, bad_n, at_ext, int(iters[0]), early_stop, nb_iter)["verdict"] == "unexplained"
     if early_stop and iters[0] < nb_iter:  # a solve that went on although the stop test had fired
         assert pp.prove_instance_batch(cfg, inp, 0, psi, states, ct_ext, at_ext, int(iters[0]) + 1, early_stop, nb_iter)["verdict"] == "unexplained"
+
+
+class TamperedProblem(OracleProblem):
+    """OracleProblem whose lam() passes through `tamper(p, nb_iter of the last solve, lam)`; hist[n] keeps the true multipliers after n iterations."""
+
+    def __init__(self, cfg, inp, B, tamper=None):
+        super().__init__(cfg, inp, B)
+        self.tamper, self.hist = tamper, {}
+
+    def lam(self):
+        lam = super().lam()
+        self.hist[self.nb] = lam.copy()
+        return self.tamper(self, self.nb, lam) if self.tamper else lam
+
+
+def _recomputed(p, nb, pen, clamp=True):
+    """The update that closes iteration nb - 1, recomputed from the double's own state with penalty `pen` (all instances)."""
+    out = []
+    for i, r in enumerate(p.res):
+        v = pp.multiplier_update(p.hist[nb - 1][i], r["X"], r["U"], p.inp["A"], p.inp["b"], pen)[0]
+        out.append(np.asarray(np.maximum(v, 0) if clamp else v, dtype=float))
+    return np.stack(out)
+
+
+def _keep_row(p, nb, lam):       # (a) row 1 keeps its old value across the update that closes iteration 3
+    if nb == 4:
+        lam[:, :, 1] = p.hist[3][:, :, 1]
+    return lam
+
+
+def _swap_rows(p, nb, lam):      # (b) rows 0 and 1 written to each other's place
+    if nb == 4:
+        lam[:, :, [0, 1]] = lam[:, :, [1, 0]]
+    return lam
+
+
+def _no_clamp(p, nb, lam):       # (c) negative values left unclamped
+    return _recomputed(p, nb, pp.al_penalty(p.cfg["al"], 1), clamp=False) if nb == 2 else lam
+
+
+def _moves_between(p, nb, lam):  # (d) a multiplier moves by one unit in the last place on an iteration that is no update step
+    if nb == 3:
+        lam[0, 0, 0] = np.nextafter(lam[0, 0, 0], np.inf)
+    return lam
+
+
+def _unscaled(p, nb, lam):       # (e) the update used the penalty before its scaling
+    return _recomputed(p, nb, p.cfg["al"]["penalty"]) if nb == 2 else lam
+
+
+def _al_four_rows():
+    from tests import al_shapes
+
+    return al_shapes.make_case(OracleFK(), "C3", 25, 4, "state")
+
+
+def _check_multipliers_of(tamper, always=()):
+    cfg, desc, inp = _al_four_rows()
+    B, nb_iter = len(inp["q0"]), 6
+    p = TamperedProblem(cfg, inp, B, tamper)
+    p.solve(nb_iter, False)
+    full = list(p.res)
+    return pp.check_batch(p, cfg, inp, nb_iter, False, _run_solver, lambda i: full[i], always=always)
+
+
+def test_multiplier_check_passes_on_the_oracle():
+    """The oracle's own multipliers are the extended-precision update of its own trajectory within the derived bound, three updates in six
+    iterations on a 4-row set that binds for part of the batch; no clamp decided inside the bound."""
+    summ, rel, failures = _check_multipliers_of(None, always=(0, 1))
+    assert not failures and summ["frac_unexplained"] == 0.0 and summ["n_proven_always"] == 2, (summ, failures)
+    assert summ["n_multiplier_checked"] == 13 and summ["n_multiplier_skipped"] == 0 and summ["n_multiplier_updates"] == 3 * 13
+    assert summ["n_clamp_ties"] == 0 and 0.0 < summ["worst_multiplier_ratio"] <= 1.0, summ
+
+
+@pytest.mark.parametrize("tamper,why", [(_keep_row, "not the update"), (_swap_rows, "not the update"), (_no_clamp, "not the update"),
+                                        (_moves_between, "not an update step"), (_unscaled, "not the update")],
+                         ids=["row-not-updated", "rows-swapped", "unclamped", "moves-between-updates", "unscaled-penalty"])
+def test_multiplier_check_detects_faults(tamper, why):
+    """The multiplier check is not vacuous: each planted fault is reported as unexplained with reason "multipliers", naming iteration,
+    step and row, although costs, step sizes and trajectories are the oracle's own."""
+    summ, rel, failures = _check_multipliers_of(tamper)
+    assert np.all(rel == 0.0)
+    assert failures and summ["frac_unexplained"] > 0.0, summ
+    assert all(f["reason"] == "multipliers" for f in failures)
+    st = failures[0]["steps"][0]
+    assert st["how"] == "FAIL:multipliers" and why in st["why"] and {"instance", "it", "step", "row"} <= set(st), st
+    if tamper is _moves_between:
+        assert [f["i"] for f in failures] == [0] and (st["it"], st["step"], st["row"]) == (2, 0, 0)
+    if tamper is _keep_row:
+        assert all(s_["row"] == 1 for f in failures for s_ in f["steps"] if s_["it"] == 3)
