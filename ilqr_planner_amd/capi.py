@@ -30,7 +30,8 @@ EXPORTS = [
     "ilqr_problem_get_iters", "ilqr_problem_get_status", "ilqr_problem_get_lambda", "ilqr_problem_get_trace",
     "ilqr_problem_get_X_dev", "ilqr_problem_get_U_dev", "ilqr_problem_get_cost_dev", "ilqr_fk_batch",
     "ilqr_profile_enable", "ilqr_profile_reset", "ilqr_profile_get", "ilqr_chain_from_urdf", "ilqr_urdf_last_error",
-    "ilqr_problem_reset_multipliers", "ilqr_problem_warm_start", "ilqr_problem_track", "ilqr_problem_track_dev", "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck",
+    "ilqr_problem_reset_multipliers", "ilqr_problem_warm_start", "ilqr_problem_track", "ilqr_problem_track_dev",
+    "ilqr_problem_closed_loop", "ilqr_problem_closed_loop_dev", "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
     "ilqr_lqt_get_d",
@@ -127,6 +128,8 @@ def load():
     L.ilqr_problem_warm_start.argtypes = [vp, C.c_int]
     L.ilqr_problem_track.argtypes = [vp, C.c_int, dp, C.c_int, dp]
     L.ilqr_problem_track_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    L.ilqr_problem_closed_loop.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp]
+    L.ilqr_problem_closed_loop_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
     L.ilqr_solve_recursive.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.ilqr_solve_al.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]
     L.ilqr_solve_batch_cp.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
@@ -449,6 +452,31 @@ class BatchProblem:
         u = np.empty((self.B, self.dims.n_u))
         self.ctx.check(self.L.ilqr_problem_track(self.h, int(k), _dp(x), int(bool(with_feedforward)), _dp(u)))
         return u
+
+    def closed_loop(self, x0=None, w=None, samples=None, with_feedforward: bool = False, want_X: bool = True, want_U: bool = True):
+        """Closed loop of the tracking law on the last Riccati solve's plan (ilqr_problem_closed_loop): x0 [B][S][n_x] or None (the plan's start),
+        w [B][S][T-1][n_x] or None (no disturbance); samples: S, needed only where neither array gives it.  Returns (cost [B][S],
+        X [B][S][T][n_x] or None, U [B][S][T-1][n_u] or None)."""
+        S = samples
+        for arr in (x0, w):
+            if S is None and arr is not None:
+                S = np.shape(arr)[1]
+        S = 1 if S is None else int(S)
+        n = max(S, 0)  # (the library refuses S < 1; the arrays below must merely exist)
+        x0 = _f64(x0, (self.B, n, self.dims.n_x)) if x0 is not None else None
+        w = _f64(w, (self.B, n, self.T - 1, self.dims.n_x)) if w is not None else None
+        cost = np.empty((self.B, n))
+        X = np.empty((self.B, n, self.T, self.dims.n_x)) if want_X else None
+        U = np.empty((self.B, n, self.T - 1, self.dims.n_u)) if want_U else None
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop(self.h, S, _dp(x0), _dp(w), int(bool(with_feedforward)), _dp(cost), _dp(X), _dp(U)))
+        return cost, X, U
+
+    def closed_loop_dev(self, samples: int, x0_ptr, w_ptr, with_feedforward: bool, cost_ptr, X_ptr=None, U_ptr=None):
+        """Device pointers (0 / None where ilqr_problem_closed_loop takes NULL), asynchronous on the context's stream."""
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_dev(self.h, int(samples), x0_ptr or None, w_ptr or None, int(bool(with_feedforward)),
+                                                           cost_ptr or None, X_ptr or None, U_ptr or None))
 
     def close(self):
         if self.h:

@@ -1495,6 +1495,26 @@ BatchResult ILQRRecursive::solveBatch(const BatchInputs& in, int nb_iter, bool l
     return run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) { check(ilqr_solve_recursive(p, nb_iter, line_search, early_stop)); }, nullptr);
 }
 
+// ilqr_problem_closed_loop on the problem a batched solve has just finished with
+static void closed_loop_of(ilqr_problem* p, sys::System& s, int B, const ClosedLoopInputs& cl, ClosedLoopResult& o) {
+    o.B = B; o.S = cl.S; o.T = s.getHorizon(); o.n_x = s.getNbStateVar(); o.n_u = s.getNbCtrlVar();
+    if (cl.S < 1) throw std::runtime_error("[closed_loop_batch] samples must be >= 1");
+    const size_t n = (size_t)B * cl.S;
+    if (!cl.x0.empty() && cl.x0.size() != n * o.n_x) throw std::runtime_error("[closed_loop_batch] x0 must be B x S x nb_state_var");
+    if (!cl.w.empty() && cl.w.size() != n * (o.T - 1) * o.n_x) throw std::runtime_error("[closed_loop_batch] w must be B x S x (horizon-1) x nb_state_var");
+    o.cost.resize(n); o.X.resize(n * o.T * o.n_x); o.U.resize(n * (o.T - 1) * o.n_u);
+    check(ilqr_problem_closed_loop(p, cl.S, cl.x0.empty() ? nullptr : cl.x0.data(), cl.w.empty() ? nullptr : cl.w.data(), cl.with_feedforward ? 1 : 0,
+                                   o.cost.data(), o.X.data(), o.U.data()));
+}
+
+std::pair<BatchResult, ClosedLoopResult> ILQRRecursive::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool line_search,
+                                                                        bool early_stop) {
+    ClosedLoopResult o;
+    BatchResult r = run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) { check(ilqr_solve_recursive(p, nb_iter, line_search, early_stop)); },
+                              [&](ilqr_problem* p) { closed_loop_of(p, *s, in.B, cl, o); });
+    return {std::move(r), std::move(o)};
+}
+
 std::tuple<std::vector<Vec>, std::vector<Vec>, std::vector<Vec>, std::vector<Mat>, std::vector<Vec>, double> ILQRRecursive::solve(
     const std::vector<Vec>& U0, int nb_iter, bool line_search, bool early_stop, CallBackMessage* cb) {  // ILQRRecursive.cpp:21-181
     if (!s->builtin()) return solve_over_virtuals(*s, U0, nb_iter, line_search, early_stop, cb);  // user-defined System / Keypoint
@@ -1522,6 +1542,19 @@ AL_ILQR::AL_ILQR(const std::shared_ptr<sys::System>& s_, const std::vector<Const
     : s(s_), inequality(ineq), multipliers(initLambda) {}
 
 BatchResult AL_ILQR::solveBatch(const BatchInputs& in, int nb_iter, int lag, double penalty, double scaling, bool line_search, bool early_stop) {
+    return solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, nullptr);
+}
+
+std::pair<BatchResult, ClosedLoopResult> AL_ILQR::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, int lag, double penalty,
+                                                                  double scaling, bool line_search, bool early_stop) {
+    ClosedLoopResult o;
+    BatchResult r = solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, [&](ilqr_problem* p) { closed_loop_of(p, *s, in.B, cl, o); });
+    return {std::move(r), std::move(o)};
+}
+
+// the batched solve; `then` (or null) runs on the solved problem before it is released
+BatchResult AL_ILQR::solveBatchThen(const BatchInputs& in, int nb_iter, int lag, double penalty, double scaling, bool line_search, bool early_stop,
+                                    const std::function<void(ilqr_problem*)>& then) {
     const int T = s->getHorizon(), ns = s->getNbStateVar() + s->getNbCtrlVar();
     if ((int)inequality.size() != T - 1 || (int)multipliers.size() != T - 1)
         throw std::runtime_error("[AL_ILQR] need one Constraint and one multiplier vector per timestep (horizon-1)");
@@ -1563,6 +1596,7 @@ BatchResult AL_ILQR::solveBatch(const BatchInputs& in, int nb_iter, int lag, dou
         [&](ilqr_problem* p) {
             lam_out.resize(lam.size());
             check(ilqr_problem_get_lambda(p, lam_out.data()));
+            if (then) then(p);
         });
     // persist instance 0's multipliers (the reference's `multipliers` member)
     double pen = penalty;

@@ -13,6 +13,7 @@
 // the simulator for users who call it directly; the solvers never use it.
 #pragma once
 
+#include <functional>
 #include <memory>
 #include <typeinfo>
 #include <string>
@@ -470,6 +471,18 @@ struct BatchInputs {
     bool want_fX = true, want_gains = true;
 };
 
+// Closed loop of the tracking law on the plan a batched Riccati solve leaves (ilqr_problem_closed_loop): S executions per instance.
+struct ClosedLoopInputs {
+    int S = 1;
+    std::vector<double> x0;   // [B][S][n_x] or empty: every execution starts on the plan
+    std::vector<double> w;    // [B][S][T-1][n_x] or empty: no disturbance
+    bool with_feedforward = false;
+};
+struct ClosedLoopResult {
+    int B = 0, S = 0, T = 0, n_x = 0, n_u = 0;
+    std::vector<double> cost, X, U;  // [B][S], [B][S][T][n_x], [B][S][T-1][n_u]
+};
+
 struct Constraint {  // AL-ILQR.h:20-23
     Mat A;
     Vec b;
@@ -493,6 +506,9 @@ public:
     std::tuple<std::vector<Vec>, std::vector<Vec>, std::vector<Vec>, std::vector<Mat>, std::vector<Vec>, double> solve(
         const std::vector<Vec>& U0, int nb_iter, bool line_search = true, bool early_stop = true, CallBackMessage* cb = nullptr);
     BatchResult solveBatch(const BatchInputs& in, int nb_iter, bool line_search = true, bool early_stop = true);
+    // solveBatch, then the closed loop on its plan, in one stateless call
+    std::pair<BatchResult, ClosedLoopResult> closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool line_search = true,
+                                                             bool early_stop = true);
 
 private:
     std::shared_ptr<sys::System> s;
@@ -506,8 +522,12 @@ public:
                                                                           CallBackMessage* cb = nullptr);
     BatchResult solveBatch(const BatchInputs& in, int nb_iter, int lag_update_step, double penalty, double scaling_factor, bool line_search = true,
                            bool early_stop = false);
+    std::pair<BatchResult, ClosedLoopResult> closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, int lag_update_step, double penalty,
+                                                             double scaling_factor, bool line_search = true, bool early_stop = false);
 
 private:
+    BatchResult solveBatchThen(const BatchInputs& in, int nb_iter, int lag_update_step, double penalty, double scaling_factor, bool line_search, bool early_stop,
+                               const std::function<void(ilqr_problem*)>& then);
     std::shared_ptr<sys::System> s;
     std::vector<Constraint> inequality;
     std::vector<Vec> multipliers;  // persists across solve() calls like the reference's member

@@ -94,6 +94,27 @@ static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& 
     return in;
 }
 
+// numpy -> ClosedLoopInputs: x0 [B][S][n_x] or None, w [B][S][T-1][n_x] or None; samples: S where neither array gives it
+static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const py::object& w, const py::object& samples, bool with_ff) {
+    solver::ClosedLoopInputs cl;
+    cl.with_feedforward = with_ff;
+    int S = samples.is_none() ? -1 : samples.cast<int>();
+    if (!x0.is_none()) {
+        arr_t a = arr_t::ensure(x0);
+        if (!a || a.ndim() != 3) throw std::runtime_error("[closed_loop_batch] x0 must be B x S x nb_state_var");
+        cl.x0.assign(a.data(), a.data() + a.size());
+        if (S < 0) S = (int)a.shape(1);
+    }
+    if (!w.is_none()) {
+        arr_t a = arr_t::ensure(w);
+        if (!a || a.ndim() != 4) throw std::runtime_error("[closed_loop_batch] w must be B x S x (horizon-1) x nb_state_var");
+        cl.w.assign(a.data(), a.data() + a.size());
+        if (S < 0) S = (int)a.shape(1);
+    }
+    cl.S = S < 0 ? 1 : S;
+    return cl;
+}
+
 PYBIND11_MODULE(PyLQR, m) {
     m.doc() = "PyLQR: the reference's Python surface over the MI355X-native batched iLQR hot path (libilqr_hip.so)";
 
@@ -271,6 +292,10 @@ PYBIND11_MODULE(PyLQR, m) {
         .def_property_readonly("cost_trace", [](const solver::BatchResult& r) { return shaped(r.cost_trace, {r.cost_trace.empty() ? 0 : r.B, r.nb_iter}); })
         .def_property_readonly("alpha_trace", [](const solver::BatchResult& r) { return shaped(r.alpha_trace, {r.alpha_trace.empty() ? 0 : r.B, r.nb_iter}); })
         .def_readonly("seconds", &solver::BatchResult::seconds);
+    py::class_<solver::ClosedLoopResult>(m_sol, "ClosedLoopResult")
+        .def_property_readonly("cost", [](const solver::ClosedLoopResult& r) { return shaped(r.cost, {r.B, r.S}); })
+        .def_property_readonly("X", [](const solver::ClosedLoopResult& r) { return shaped(r.X, {r.B, r.S, r.T, r.n_x}); })
+        .def_property_readonly("U", [](const solver::ClosedLoopResult& r) { return shaped(r.U, {r.B, r.S, r.T - 1, r.n_u}); });
     py::class_<solver::Constraint>(m_sol, "Constraint").def(py::init<>()).def_readwrite("A", &solver::Constraint::A).def_readwrite("b", &solver::Constraint::b);
     py::class_<solver::ILQRRecursive>(m_sol, "ILQRRecursive")
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
@@ -280,7 +305,15 @@ PYBIND11_MODULE(PyLQR, m) {
                  return self.solveBatch(batch_inputs(U0, q0, dq0, kp), nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
-             py::arg("kp_targets") = py::none());
+             py::arg("kp_targets") = py::none())
+        .def("closed_loop_batch",
+             [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
+                const py::object& x0, const py::object& w, bool ff, const py::object& samples) {
+                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff), nb_iter, ls, es);
+             },
+             py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
+             py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(), py::arg("w") = py::none(), py::arg("with_feedforward") = false,
+             py::arg("samples") = py::none());
     py::class_<solver::AL_ILQR>(m_sol, "AL_ILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const std::vector<solver::Constraint>&, const std::vector<Vec>&>(), py::arg("s"), py::arg("inequality"),
              py::arg("initLambda"))
@@ -290,7 +323,15 @@ PYBIND11_MODULE(PyLQR, m) {
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
                 const py::object& kp) { return self.solveBatch(batch_inputs(U0, q0, dq0, kp), nb_iter, lag, pen, sc, ls, es); },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
-             py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none());
+             py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none())
+        .def("closed_loop_batch",
+             [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
+                const py::object& kp, const py::object& x0, const py::object& w, bool ff, const py::object& samples) {
+                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff), nb_iter, lag, pen, sc, ls, es);
+             },
+             py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
+             py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(),
+             py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none());
     // bindings.cpp:778-782
     py::class_<solver::BatchILQR>(m_sol, "BatchILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("Q"))

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ilqr_batchcp.hpp"
+#include "ilqr_closed_loop.hpp"
 #include "ilqr_ctx.hpp"
 #include "ilqr_kernels.hpp"
 #include "ilqr_plan.hpp"
@@ -46,6 +47,9 @@ struct ilqr_problem {
     size_t staging_elems = 0;
     int last_nb_iter = 0;
     bool has_controls = false, has_state = false;
+    bool has_gains = false;  // a Riccati solve with nb_iter >= 1 has run since the inputs last changed: X, U, KD are one plan (closed_loop)
+    double* cl_kpx = nullptr;  // closed_loop: state | control of every sample at the step-table entries (k_closed_loop_coop -> k_closed_loop_kp)
+    size_t cl_kpx_elems = 0;
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
     BatchCPState cp;
     BatchWideState cpw;
@@ -449,6 +453,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     (void)hipStreamSynchronize(p->ctx->stream);
     for (void* q : p->allocs) (void)hipFree(q);
     if (p->staging) (void)hipFree(p->staging);
+    if (p->cl_kpx) (void)hipFree(p->cl_kpx);
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
     delete p;
@@ -475,6 +480,7 @@ static int upload(ilqr_problem* p, const double* src, bool src_is_dev, double* d
 static int set_init_state(ilqr_problem* p, const double* q0, const double* dq0, bool dev) {
     if (!p) return 1;
     if (!q0) return fail(p->ctx, "q0 is required");
+    p->has_gains = false;
     const IndexMap* qm = p->mapped ? &p->qmap : nullptr;
     if (upload(p, q0, dev, (double*)p->bufs.q0, p->desc.dof, qm, 1)) return 1;
     if (dq0) {
@@ -491,6 +497,7 @@ extern "C" int ilqr_problem_set_init_state_dev(ilqr_problem* p, const double* q0
 static int set_kp(ilqr_problem* p, int k, const double* tg, bool dev) {
     if (!p) return 1;
     if (k < 0 || k >= p->desc.n_kp || !tg) return fail(p->ctx, "bad keypoint index / null target");
+    p->has_gains = false;
     double* dst = (double*)p->bufs.kp_tg + (size_t)k * p->dims.n_f * p->Bp;
     if (p->mapped && (p->desc.kind == ILQR_SYS_JOINT || p->desc.kind == ILQR_SYS_JOINT_TIME))  // the target is a state
         return upload(p, tg, dev, dst, p->udims.n_f, &p->map.x, 1);
@@ -506,6 +513,7 @@ extern "C" int ilqr_problem_set_keypoint_targets_dev(ilqr_problem* p, int k, con
 static int set_controls(ilqr_problem* p, const double* U0, bool dev) {
     if (!p) return 1;
     if (!U0) return fail(p->ctx, "U0 is required");
+    p->has_gains = false;
     if (upload(p, U0, dev, (double*)p->bufs.U0, (p->T - 1) * p->udims.n_u, p->mapped ? &p->map.u : nullptr, p->T - 1)) return 1;
     p->has_controls = true;
     p->u0_zero = false;
@@ -524,6 +532,7 @@ extern "C" int ilqr_problem_set_constraints(ilqr_problem* p, int m, int per_step
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
     if (m <= 0 || !A || !b) return fail(c, "bad constraint arguments");
+    p->has_gains = false;
     const int ns = p->dims.n_x + p->dims.n_u, T = p->T, nsu = p->udims.n_x + p->udims.n_u;
     const size_t nk = per_step ? (size_t)(T - 1) : 1;
     if (p->bufs.m != m || p->bufs.per_step != per_step || !p->conA) {
@@ -575,6 +584,7 @@ extern "C" int ilqr_problem_set_constraints(ilqr_problem* p, int m, int per_step
 extern "C" int ilqr_problem_reset_multipliers(ilqr_problem* p) {
     if (!p) return 1;
     if (p->bufs.m <= 0) return fail(p->ctx, "no constraints set");
+    p->has_gains = false;
     HIPCHK(p->ctx, hipMemcpyAsync(p->bufs.lambda, p->lambda0, sizeof(double) * (size_t)(p->T - 1) * p->bufs.m * p->Bp,
                                   hipMemcpyDeviceToDevice, p->ctx->stream));
     return 0;
@@ -644,6 +654,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     HIPCHK(c, hipSetDevice(c->device));
     if (ensure_trace(p, nb_iter)) return 1;
     p->last_nb_iter = nb_iter;
+    p->has_gains = false;  // until this solve's launches are queued; a 0-iteration solve re-rolls X from U0 and leaves the gains of another plan
     const int kind = p->desc.kind, nd = p->desc.nb_deriv, T = p->T;
     const RiccatiPlan pl = plan_riccati(plan_input(p, al, nb_iter, line_search));
     if (pl.kd_sym != KD_SYM_KEEP) p->bufs.kd_sym = pl.kd_sym;  // before half_bufs: it sizes the half's offset into KD
@@ -761,6 +772,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     }
     // (the caller's stream continues when both halves are done: SplitJoin above, on every exit path)
     prof_mark(c, -1);
+    p->has_gains = nb_iter >= 1;
     return 0;
 }
 
@@ -781,6 +793,7 @@ extern "C" int ilqr_solve_batch_cp(ilqr_problem* p, const double* psi, int Kw, i
     ilqr_ctx* c = p->ctx;
     if (has_shared_step(p->hdesc.steps)) return fail(c, BATCH_SHARED_STEP_TEXT);
     if (!p->has_state || !p->has_controls) return fail(c, "set_init_state and set_controls must be called before a solve");
+    p->has_gains = false;  // the batch solvers leave no gains
     HIPCHK(c, hipSetDevice(c->device));
     std::string err;
     if (ensure_trace(p, nb_iter)) return 1;
@@ -812,6 +825,7 @@ extern "C" int ilqr_solve_batch(ilqr_problem* p, int nb_iter, int early_stop) {
     ilqr_ctx* c = p->ctx;
     if (has_shared_step(p->hdesc.steps)) return fail(c, BATCH_SHARED_STEP_TEXT);
     if (!p->has_state || !p->has_controls) return fail(c, "set_init_state and set_controls must be called before a solve");
+    p->has_gains = false;  // the batch solvers leave no gains
     HIPCHK(c, hipSetDevice(c->device));
     std::string err;
     if (ensure_trace(p, nb_iter)) return 1;
@@ -884,6 +898,7 @@ extern "C" int ilqr_problem_warm_start(ilqr_problem* p, int shift) {
     ilqr_ctx* c = p->ctx;
     if (!p->has_state || !p->has_controls) return fail(c, "warm start needs a previous solve (set_init_state, set_controls, solve)");
     if (shift < 0 || shift >= p->T) return fail(c, "shift must be in [0, T)");
+    p->has_gains = false;  // U0 and the start state change
     HIPCHK(c, hipSetDevice(c->device));
     launch_warm_start(p->bufs, const_cast<double*>(p->bufs.U0), const_cast<double*>(p->bufs.q0), const_cast<double*>(p->bufs.dq0), shift, p->B, p->T,
                       p->dims.n_x, p->dims.n_u, p->desc.nb_deriv, c->stream);
@@ -919,6 +934,67 @@ extern "C" int ilqr_problem_track(ilqr_problem* p, int k, const double* x_meas, 
 }
 extern "C" int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_meas, int with_feedforward, double* u_out) {
     return track(p, k, x_meas, with_feedforward, u_out, true);
+}
+
+
+// Closed loop of the tracking law on the last plan (ilqr_closed_loop.hpp): n_samples executions per instance.  Which kernel runs is decided by
+// plan_closed_loop; chains of fewer than 7 joints take the generic kernel's mapped variant.
+static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w, int with_ff, double* cost, double* X, double* U, bool dev) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    if (!p->has_gains)
+        return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) since the problem's inputs last changed");
+    if (S < 1) return fail(c, "n_samples must be >= 1");
+    if (!cost) return fail(c, "cost is a null pointer");
+    const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u;
+    const size_t n = (size_t)p->B * S;
+    const size_t n_x0 = x0 ? n * nxu : 0, n_w = w ? n * (T - 1) * nxu : 0, n_X = X ? n * T * nxu : 0, n_U = U ? n * (T - 1) * nuu : 0;
+    // the kernels address the caller's arrays with 32-bit element offsets
+    if (n * T * (size_t)(nxu > nuu ? nxu : nuu) >= ((size_t)1 << 31))
+        return fail(c, "closed loop: B * n_samples * T * n_x overflows the kernels' 32-bit offsets (split the samples over several calls)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const ClosedLoopPlan pl = plan_closed_loop(p->desc.kind, p->desc.nb_deriv, S, p->B, c->n_simd, c->xc_generic || p->mapped);
+    if (pl.coop) {
+        if (!launch_closed_loop_coop) return fail(c, "closed loop: the cooperative kernels are not part of this build (pin the generic kernels)");
+        const size_t need = (size_t)(p->hdesc.steps.n > 0 ? p->hdesc.steps.n : 1) * (p->dims.n_x + p->dims.n_u) * n;
+        if (p->cl_kpx_elems < need) {
+            if (p->cl_kpx) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p->cl_kpx)); p->cl_kpx = nullptr; p->cl_kpx_elems = 0; }
+            HIPCHK(c, hipMalloc((void**)&p->cl_kpx, need * sizeof(double)));
+            p->cl_kpx_elems = need;
+        }
+    }
+    ClArgs a;
+    a.S = S; a.with_ff = with_ff ? 1 : 0; a.x0 = x0; a.w = w; a.cost = cost; a.X = X; a.U = U;
+    if (!dev) {  // staging: x0 | w | cost | X | U
+        if (ensure_staging(p, n_x0 + n_w + n + n_X + n_U)) return 1;
+        double* s = p->staging;
+        if (x0) { HIPCHK(c, hipMemcpyAsync(s, x0, n_x0 * sizeof(double), hipMemcpyHostToDevice, c->stream)); a.x0 = s; }
+        s += n_x0;
+        if (w) { HIPCHK(c, hipMemcpyAsync(s, w, n_w * sizeof(double), hipMemcpyHostToDevice, c->stream)); a.w = s; }
+        s += n_w;
+        a.cost = s; s += n;
+        if (X) a.X = s;
+        s += n_X;
+        if (U) a.U = s;
+    }
+    if (pl.coop) launch_closed_loop_coop(p->desc.kind, p->desc.nb_deriv, p->bufs, a, p->B, pl, p->cl_kpx, c->stream);
+    else launch_closed_loop(p->desc.kind, p->desc.nb_deriv, p->bufs, a, p->B, p->mapped ? &p->map : nullptr, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if (!dev) {
+        HIPCHK(c, hipMemcpyAsync(cost, a.cost, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, n_X * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (U) HIPCHK(c, hipMemcpyAsync(U, a.U, n_U * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+extern "C" int ilqr_problem_closed_loop(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost, double* X,
+                                        double* U) {
+    return closed_loop(p, n_samples, x0, w, with_feedforward, cost, X, U, false);
+}
+extern "C" int ilqr_problem_closed_loop_dev(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost,
+                                            double* X, double* U) {
+    return closed_loop(p, n_samples, x0, w, with_feedforward, cost, X, U, true);
 }
 
 extern "C" int ilqr_problem_get_K(ilqr_problem* p, double* K) { return get_gains(p, K, nullptr); }

@@ -1,0 +1,67 @@
+// ilqr_closed_loop.hpp -- one lane's pieces of the batched closed-loop rollout (ilqr_problem_closed_loop), shared by the generic kernel
+// (k_closed_loop, ilqr_kernels.hip) and the cooperative one (k_closed_loop_coop + k_closed_loop_kp, ilqr_closed_loop.hip): both evaluate the same
+// expressions in the same order, so their results are expected to agree bit for bit.
+//
+//   u_k     = ubar_k + K_k (x_k - xbar_k) [+ alpha d_k]          the tracking law of k_track
+//   x_{k+1} = f(x_k, u_k) + w_k                                  dyn_step
+//   J       = sum_k limit terms(x_k)  +  sum over the step table of the keypoint terms(x_t, u_t)   (System::cost without AL terms)
+#pragma once
+#include "ilqr_closed_loop_plan.hpp"
+#include "ilqr_step.hpp"
+
+namespace ilqr {
+
+// Arguments of a closed-loop launch.  Natural layouts on the user's dimensions; g = b * S + s numbers the (instance, sample) pairs.
+struct ClArgs {
+    int S;              // samples per instance
+    int with_ff;        // add alpha d_k
+    const double* x0;   // [B][S][n_x] or null: xbar_0
+    const double* w;    // [B][S][T-1][n_x] or null: no disturbance
+    double* cost;       // [B][S]
+    double* X;          // [B][S][T][n_x] or null
+    double* U;          // [B][S][T-1][n_u] or null
+};
+
+// The control of one lane at one step.  rec: the step's gain record (entry (i, j) at kd_off, the feed-forward at column n_x); xb, ub: the plan's
+// state and control, entry i at xb[i * xs] (xs = Bp in the trajectory buffers, 1 in a staged record); sc: the alpha scaling rule of k_track.
+template <class S>
+ILQR_DEV void cl_control(const double* rec, int sym, int with_ff, const double* xb, const double* ub, size_t xs, double sc, const double* x, double* u) {
+    constexpr int NX = S::NX, NU = S::NU, ROWP = kd_rowp(NX);
+    double dx[NX];
+    UNR for (int j = 0; j < NX; j++) dx[j] = x[j] - xb[j * xs];
+    UNR for (int i = 0; i < NU; i++) {
+        double s = ub[i * xs];
+        UNR for (int j = 0; j < NX; j++) s += rec[kd_off(sym, ROWP, i, j)] * dx[j];
+        if (with_ff) s += sc * rec[kd_off(sym, ROWP, i, NX)];
+        u[i] = s;
+    }
+}
+
+// limit terms of a stage, summed as stage_cost sums them (first set, then the second one)
+template <class S>
+ILQR_DEV double cl_limits(const DevDesc& d, const double* x) {
+    double c = 0;
+    if (d.limits_set) c += limit_cost<S>(d, x);
+    if (d.lim2) c += lim2_cost<S>(d, x);
+    return c;
+}
+
+// acc + the task terms of step-table entry st: every keypoint on the step adds its own, in keypoint order (stage_cost)
+template <class S>
+ILQR_DEV double cl_kp_terms(const DevDesc& d, const Bufs& a, int b, int st, const double* x, const double* u, double acc) {
+    const int Bp = d.Bp;
+    for (int kpi = d.steps.kp[st]; kpi < d.steps.kp[st + 1]; kpi++) {
+        double tg[S::NF];
+        UNR for (int i = 0; i < S::NF; i++) tg[i] = AT(a.kp_tg, kpi * S::NF + i, b);
+        acc += kp_cost<S>(d, kpi, tg, x, u);
+    }
+    return acc;
+}
+
+// generic kernel (ilqr_kernels.hip); m: the maps of a chain of fewer than 7 joints, or null
+void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const DofMap* m, hipStream_t st);
+// cooperative kernels (ilqr_closed_loop.hip), 7-joint layouts only; kpx: [steps.n][n_x + n_u][B * S] workspace.  A weak declaration: the host
+// builds of the generic kernel set link without that file, and a launch that needs it there is an error (closed_loop, ilqr_capi.cpp).
+__attribute__((weak)) void launch_closed_loop_coop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const ClosedLoopPlan& pl, double* kpx, hipStream_t st);
+
+}  // namespace ilqr

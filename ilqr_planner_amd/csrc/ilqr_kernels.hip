@@ -10,6 +10,7 @@
 //   backward Riccati sweep     src/solver/ILQRRecursive.cpp:68-97   (AL terms: src/solver/AL-ILQR.cpp:110-134)
 //   forward pass + line search src/solver/ILQRRecursive.cpp:101-176 (AL: src/solver/AL-ILQR.cpp:149-227)
 // A_k, B_k are never stored: they are rebuilt from (x_k, u_k) exactly as forwardPass builds them.
+#include "ilqr_closed_loop.hpp"
 #include "ilqr_kernels.hpp"
 #include "ilqr_step.hpp"
 
@@ -664,6 +665,59 @@ __global__ void k_track_map(Bufs a, const double* __restrict__ x_meas, int k, in
     }
 }
 
+// Closed loop of the tracking law (ilqr_closed_loop.hpp): S executions per instance from the caller's start states under the caller's
+// disturbances, one lane per (instance, sample), k_init_rollout's loop with the control of k_track in place of U0.  Natural layouts on the
+// user's dimensions (ClArgs), addressed with 32-bit element offsets (checked by the host).  MAP: a chain of fewer than 7 joints -- device
+// entry i is the user's mx.usr[i]; padded entries start on the plan (0), get no disturbance and keep the plan's control.
+template <class S, bool MAP>
+__global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap mx, IndexMap mu) {
+    constexpr int NX = S::NX, NU = S::NU;
+    const DevDesc& d = *a.desc;
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= d.B * c.S) return;
+    const int b = g / c.S;
+    const int Bp = d.Bp, T = d.T, cur = a.cur[b];
+    const int nxu = MAP ? mx.n_user : NX, nuu = MAP ? mu.n_user : NU;
+    const int sym = a.kd_sym, rs = kd_rs(sym, NU, kd_rowp(NX));
+    const double sc = (a.iters[b] > 0) ? a.alpha[b] : 1.0;
+    const double* Xb = a.X[cur] + b;  // entry `row` of the plan: Xb[row * Bp]
+    const double* Ub = a.U[cur] + b;
+    double x[NX], u[NU], xn[NX];
+    UNR for (int i = 0; i < NX; i++) {
+        const int iu = MAP ? mx.usr[i] : i;
+        x[i] = (c.x0 && iu >= 0) ? c.x0[g * nxu + iu] : Xb[(size_t)i * Bp];
+    }
+    double lim = 0, kpc = 0;
+    int st = 0;  // step table walk, as in k_init_rollout
+    for (int k = 0; k < T - 1; k++) {
+        if (c.X) {
+            UNR for (int i = 0; i < NX; i++) { const int iu = MAP ? mx.usr[i] : i; if (iu >= 0) c.X[(g * T + k) * nxu + iu] = x[i]; }
+        }
+        cl_control<S>(KD_REC(a.KD, Bp, rs, k, b), sym, c.with_ff, Xb + (size_t)k * NX * Bp, Ub + (size_t)k * NU * Bp, Bp, sc, x, u);
+        if (MAP) { UNR for (int i = 0; i < NU; i++) if (mu.usr[i] < 0) u[i] = Ub[((size_t)k * NU + i) * Bp]; }
+        if (c.U) {
+            UNR for (int i = 0; i < NU; i++) { const int iu = MAP ? mu.usr[i] : i; if (iu >= 0) c.U[(g * (T - 1) + k) * nuu + iu] = u[i]; }
+        }
+        lim += cl_limits<S>(d, x);
+        if (st < d.steps.n && d.steps.t[st] == k) { kpc = cl_kp_terms<S>(d, a, b, st, x, u, kpc); st++; }
+        dyn_step<S>(d, x, u, xn);
+        if (c.w) {
+            UNR for (int i = 0; i < NX; i++) { const int iu = MAP ? mx.usr[i] : i; if (iu >= 0) xn[i] += c.w[(g * (T - 1) + k) * nxu + iu]; }
+        }
+        UNR for (int i = 0; i < NX; i++) x[i] = xn[i];
+    }
+    if (c.X) {
+        UNR for (int i = 0; i < NX; i++) { const int iu = MAP ? mx.usr[i] : i; if (iu >= 0) c.X[(g * T + T - 1) * nxu + iu] = x[i]; }
+    }
+    lim += cl_limits<S>(d, x);
+    if (st < d.steps.n && d.steps.t[st] == T - 1) {
+        double zu[NU];
+        UNR for (int i = 0; i < NU; i++) zu[i] = 0;
+        kpc = cl_kp_terms<S>(d, a, b, st, x, zu, kpc);
+    }
+    c.cost[g] = lim + kpc;
+}
+
 // f(X) for every (instance, timestep): one lane per pair (tuple<1> of ILQRRecursive::solve)
 template <class S>
 __global__ __launch_bounds__(64) void k_fx_all(Bufs a, double* __restrict__ out /* natural [B][T][NF] */) {
@@ -779,6 +833,14 @@ void launch_warm_start(const Bufs& a, double* U0, double* q0, double* dq0, int s
 }
 void launch_track(const Bufs& a, const double* x_meas, int k, int with_ff, double* u_out, int B, int nx, int nu, hipStream_t st) {
     hipLaunchKernelGGL(k_track, dim3((B + 63) / 64), dim3(64), 0, st, a, x_meas, k, with_ff, u_out, nx, nu);
+}
+void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const DofMap* m, hipStream_t st) {
+    const dim3 grid(((unsigned)B * c.S + 63) / 64), block(64);
+    with_sys(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if (m) hipLaunchKernelGGL((k_closed_loop<S, true>), grid, block, 0, st, a, c, m->x, m->u);
+        else hipLaunchKernelGGL((k_closed_loop<S, false>), grid, block, 0, st, a, c, IndexMap{}, IndexMap{});
+    });
 }
 void launch_fk_batch(const DevDesc* dd, int n, const double* q, double* pos, double* quat, double* jac, hipStream_t st) {
     hipLaunchKernelGGL(k_fk_batch, dim3((n + 63) / 64), dim3(64), 0, st, dd, n, q, pos, quat, jac);

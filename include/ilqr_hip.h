@@ -250,6 +250,18 @@ int ilqr_problem_warm_start(ilqr_problem* p, int shift);
  * x_meas[B][n_x] -> u_out[B][n_u]; K_k, d_k = the gains ilqr_problem_get_K / get_d return. */
 int ilqr_problem_track(ilqr_problem* p, int k, const double* x_meas, int with_feedforward, double* u_out);
 int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_meas, int with_feedforward, double* u_out);
+/* Closed loop of that law on the plan of the last Riccati solve: n_samples executions of every instance,
+ *   x_0 = x0[b][s] (NULL: xbar_0);  u_k = ilqr_problem_track(k, x_k, with_feedforward);  x_{k+1} = f(x_k, u_k) + w[b][s][k] (NULL: none);
+ *   cost[b][s] = sum_{k<T-1} cost(x_k, u_k, k) + cost(x_{T-1}, 0, T-1)     (the system's stage cost, no AL terms: what ilqr_solve_recursive reports),
+ * with f the system's own step (dt = u_last^2 on the time systems).  Start states and disturbances are the caller's: no device random numbers.
+ * x0[B][S][n_x] or NULL, w[B][S][T-1][n_x] or NULL; cost[B][S]; X[B][S][T][n_x] or NULL; U[B][S][T-1][n_u] or NULL.
+ * Fails unless ilqr_solve_recursive / ilqr_solve_al with nb_iter >= 1 has run since the problem's inputs last changed (the batch solvers leave no
+ * gains), for n_samples < 1, for a null cost, and when B * n_samples * T * n_x reaches 2^31 (the kernels' 32-bit offsets).
+ * _dev: device pointers, asynchronous on the context's stream. */
+int ilqr_problem_closed_loop(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost, double* X,
+                             double* U);
+int ilqr_problem_closed_loop_dev(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost, double* X,
+                                 double* U);
 
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];

@@ -1,0 +1,22 @@
+"""Batched closed-loop rollouts of the tracking law on the host: the generic kernel k_closed_loop and the C-ABI entry points built with g++ (the
+sources and include paths of tests/tools/hostsim/build.sh, without sanitizers), driven by tests/tools/hostsim/closed_loop_checks.py in a child
+process of its own.  Every system shape of tests/horizons.py, a 3-joint chain, a shared-step case and binding limits at T = 2, 3, 9, 25,
+B = 13, S = 1, 3, 5 against the NumPy replay of the law with the oracle's step and cost (tests/closed_loop.py).  The device kernels:
+tests/test_gpu_closed_loop.py."""
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOSTSIM = os.path.join(ROOT, "tests", "tools", "hostsim")
+SRC = os.path.join(ROOT, "ilqr_planner_amd", "csrc")
+
+
+def test_closed_loop_on_host_build(tmp_path):
+    lib = str(tmp_path / "libilqr_hostsim.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-I" + HOSTSIM, "-I" + SRC, "-Wno-unused-result", "-x", "c++",
+                           os.path.join(SRC, "ilqr_kernels.hip"), os.path.join(SRC, "ilqr_capi.cpp"), os.path.join(SRC, "urdf_chain.cpp"),
+                           os.path.join(HOSTSIM, "stubs.cpp"), "-o", lib])
+    r = subprocess.run([sys.executable, os.path.join(HOSTSIM, "closed_loop_checks.py"), lib], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+    assert r.stdout.strip().splitlines()[-1] == "closed loop: ok"
