@@ -5,6 +5,7 @@ if the library is missing or no HIP device is visible, construction raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -17,6 +18,7 @@ MAX_SEG, MAX_KP, MAX_NX, MAX_NU, MAX_NF, MAX_NQ = 24, 8, 15, 8, 15, 13
 SYS_POS_ORN, SYS_POS_ORN_TIME, SYS_JOINT, SYS_JOINT_TIME = 0, 1, 2, 3
 STATUS_OK, STATUS_NONFINITE, STATUS_ALPHA_FLOOR = 0, 1, 2
 LQT_MAX_NX, LQT_MAX_NU = 16, 8
+CL_STATS = 5  # mean, variance, min, max, n_bad (ILQR_CL_STATS)
 PROF_ROLLOUT, PROF_BACKWARD, PROF_FORWARD, PROF_OTHER, PROF_APPLY = 0, 1, 2, 3, 4
 
 # every symbol include/ilqr_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -31,7 +33,8 @@ EXPORTS = [
     "ilqr_problem_get_X_dev", "ilqr_problem_get_U_dev", "ilqr_problem_get_cost_dev", "ilqr_fk_batch",
     "ilqr_profile_enable", "ilqr_profile_reset", "ilqr_profile_get", "ilqr_chain_from_urdf", "ilqr_urdf_last_error",
     "ilqr_problem_reset_multipliers", "ilqr_problem_warm_start", "ilqr_problem_track", "ilqr_problem_track_dev",
-    "ilqr_problem_closed_loop", "ilqr_problem_closed_loop_dev", "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck",
+    "ilqr_problem_closed_loop", "ilqr_problem_closed_loop_dev", "ilqr_problem_closed_loop_noise", "ilqr_problem_closed_loop_noise_dev",
+    "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
     "ilqr_lqt_get_d",
@@ -88,6 +91,15 @@ class Dims(C.Structure):
     _fields_ = [("n_x", C.c_int), ("n_u", C.c_int), ("n_f", C.c_int), ("n_Q", C.c_int)]
 
 
+class Noise(C.Structure):
+    """Mirror of ilqr_noise."""
+
+    _fields_ = [("seed", C.c_ulonglong), ("instance_offset", C.c_uint), ("sample_offset", C.c_uint), ("sigma_w", C.c_double * MAX_NX),
+                ("sigma_x0", C.c_double * MAX_NX)]
+
+
+ClosedLoopNoise = collections.namedtuple("ClosedLoopNoise", "cost stats X U w")
+
 _lib = None
 
 
@@ -130,6 +142,8 @@ def load():
     L.ilqr_problem_track_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.ilqr_problem_closed_loop.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp]
     L.ilqr_problem_closed_loop_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    L.ilqr_problem_closed_loop_noise.argtypes = [vp, C.c_int, C.POINTER(Noise), dp, C.c_int, dp, dp, dp, dp, dp]
+    L.ilqr_problem_closed_loop_noise_dev.argtypes = [vp, C.c_int, C.POINTER(Noise), vp, C.c_int, vp, vp, vp, vp, vp]
     L.ilqr_solve_recursive.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.ilqr_solve_al.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]
     L.ilqr_solve_batch_cp.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
@@ -477,6 +491,45 @@ class BatchProblem:
         self.ctx.crosscheck_from_env()
         self.ctx.check(self.L.ilqr_problem_closed_loop_dev(self.h, int(samples), x0_ptr or None, w_ptr or None, int(bool(with_feedforward)),
                                                            cost_ptr or None, X_ptr or None, U_ptr or None))
+
+    def noise(self, seed, sigma_w=None, sigma_x0=None, instance_offset=0, sample_offset=0):
+        """The ilqr_noise of a call: sigma_w / sigma_x0 a scalar (every entry) or n_x values in the user's state layout, None = 0."""
+        nz = Noise()
+        nz.seed, nz.instance_offset, nz.sample_offset = int(seed), int(instance_offset), int(sample_offset)
+        for field, sig in ((nz.sigma_w, sigma_w), (nz.sigma_x0, sigma_x0)):
+            v = np.broadcast_to(np.asarray(0.0 if sig is None else sig, dtype=np.float64), (self.dims.n_x,))
+            for i in range(self.dims.n_x):
+                field[i] = v[i]
+        return nz
+
+    def closed_loop_noise(self, samples, seed, sigma_w=None, sigma_x0=None, x0=None, with_feedforward: bool = False, instance_offset=0,
+                          sample_offset=0, want_cost: bool = True, want_stats: bool = True, want_X: bool = False, want_U: bool = False,
+                          want_w: bool = False):
+        """The closed loop with its disturbances sigma_w z and start perturbations sigma_x0 z drawn on the device (ilqr_problem_closed_loop_noise):
+        the draw of (seed, instance_offset + b, sample_offset + s, step, entry) is the definition in include/ilqr_hip.h.  x0 [B][S][n_x] or None
+        is the centre of the start perturbation.  Returns a ClosedLoopNoise of cost [B][S], stats [B][5] (mean, variance, min, max of the
+        finite costs, n_bad), X, U, w [B][S][T-1][n_x]; what was not asked for is None."""
+        S = int(samples)
+        n = max(S, 0)
+        x0 = _f64(x0, (self.B, n, self.dims.n_x)) if x0 is not None else None
+        cost = np.empty((self.B, n)) if want_cost else None
+        stats = np.empty((self.B, CL_STATS)) if want_stats else None
+        X = np.empty((self.B, n, self.T, self.dims.n_x)) if want_X else None
+        U = np.empty((self.B, n, self.T - 1, self.dims.n_u)) if want_U else None
+        w = np.empty((self.B, n, self.T - 1, self.dims.n_x)) if want_w else None
+        nz = self.noise(seed, sigma_w, sigma_x0, instance_offset, sample_offset)
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_noise(self.h, S, C.byref(nz), _dp(x0), int(bool(with_feedforward)), _dp(cost), _dp(stats),
+                                                             _dp(X), _dp(U), _dp(w)))
+        return ClosedLoopNoise(cost, stats, X, U, w)
+
+    def closed_loop_noise_dev(self, samples: int, noise, x0_ptr, with_feedforward: bool, cost_ptr=None, stats_ptr=None, X_ptr=None, U_ptr=None,
+                              w_ptr=None):
+        """Device pointers (0 / None where ilqr_problem_closed_loop_noise takes NULL), asynchronous on the context's stream; noise: self.noise(..)."""
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_noise_dev(self.h, int(samples), C.byref(noise) if noise is not None else None, x0_ptr or None,
+                                                                 int(bool(with_feedforward)), cost_ptr or None, stats_ptr or None, X_ptr or None,
+                                                                 U_ptr or None, w_ptr or None))
 
     def close(self):
         if self.h:

@@ -477,10 +477,16 @@ struct ClosedLoopInputs {
     std::vector<double> x0;   // [B][S][n_x] or empty: every execution starts on the plan
     std::vector<double> w;    // [B][S][T-1][n_x] or empty: no disturbance
     bool with_feedforward = false;
+    // seed given: the disturbances sigma_w z and the start perturbations sigma_x0 z are drawn on the device (ilqr_problem_closed_loop_noise);
+    // x0 is then the centre of the start perturbation and w must be empty
+    bool has_seed = false;
+    unsigned long long seed = 0;
+    std::vector<double> sigma_w, sigma_x0;   // one value (every entry) or n_x values; empty: 0
 };
 struct ClosedLoopResult {
     int B = 0, S = 0, T = 0, n_x = 0, n_u = 0;
     std::vector<double> cost, X, U;  // [B][S], [B][S][T][n_x], [B][S][T-1][n_u]
+    std::vector<double> stats;       // [B][5]: mean, unbiased variance, min, max of the finite costs in sample order, and the number that are not finite
 };
 
 struct Constraint {  // AL-ILQR.h:20-23

@@ -95,9 +95,23 @@ static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& 
 }
 
 // numpy -> ClosedLoopInputs: x0 [B][S][n_x] or None, w [B][S][T-1][n_x] or None; samples: S where neither array gives it
-static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const py::object& w, const py::object& samples, bool with_ff) {
+static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const py::object& w, const py::object& samples, bool with_ff,
+                                                   const py::object& seed = py::none(), const py::object& sigma_w = py::none(),
+                                                   const py::object& sigma_x0 = py::none()) {
     solver::ClosedLoopInputs cl;
     cl.with_feedforward = with_ff;
+    if (!seed.is_none()) {
+        if (!w.is_none()) throw std::runtime_error("[closed_loop_batch] give either w or seed (with seed the disturbances are drawn on the device), not both");
+        cl.has_seed = true;
+        cl.seed = seed.cast<unsigned long long>();
+        for (int which = 0; which < 2; which++) {
+            const py::object& sg = which ? sigma_x0 : sigma_w;
+            if (sg.is_none()) continue;
+            arr_t a = arr_t::ensure(sg);
+            if (!a || a.ndim() > 1) throw std::runtime_error("[closed_loop_batch] sigma_w and sigma_x0 must be a scalar or have nb_state_var entries");
+            (which ? cl.sigma_x0 : cl.sigma_w).assign(a.data(), a.data() + a.size());
+        }
+    } else if (!sigma_w.is_none() || !sigma_x0.is_none()) throw std::runtime_error("[closed_loop_batch] sigma_w and sigma_x0 need a seed");
     int S = samples.is_none() ? -1 : samples.cast<int>();
     if (!x0.is_none()) {
         arr_t a = arr_t::ensure(x0);
@@ -295,7 +309,8 @@ PYBIND11_MODULE(PyLQR, m) {
     py::class_<solver::ClosedLoopResult>(m_sol, "ClosedLoopResult")
         .def_property_readonly("cost", [](const solver::ClosedLoopResult& r) { return shaped(r.cost, {r.B, r.S}); })
         .def_property_readonly("X", [](const solver::ClosedLoopResult& r) { return shaped(r.X, {r.B, r.S, r.T, r.n_x}); })
-        .def_property_readonly("U", [](const solver::ClosedLoopResult& r) { return shaped(r.U, {r.B, r.S, r.T - 1, r.n_u}); });
+        .def_property_readonly("U", [](const solver::ClosedLoopResult& r) { return shaped(r.U, {r.B, r.S, r.T - 1, r.n_u}); })
+        .def_property_readonly("stats", [](const solver::ClosedLoopResult& r) { return shaped(r.stats, {r.B, ILQR_CL_STATS}); });
     py::class_<solver::Constraint>(m_sol, "Constraint").def(py::init<>()).def_readwrite("A", &solver::Constraint::A).def_readwrite("b", &solver::Constraint::b);
     py::class_<solver::ILQRRecursive>(m_sol, "ILQRRecursive")
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
@@ -308,12 +323,13 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("kp_targets") = py::none())
         .def("closed_loop_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
-                const py::object& x0, const py::object& w, bool ff, const py::object& samples) {
-                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff), nb_iter, ls, es);
+                const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
+                const py::object& sigma_x0) {
+                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0), nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
              py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(), py::arg("w") = py::none(), py::arg("with_feedforward") = false,
-             py::arg("samples") = py::none());
+             py::arg("samples") = py::none(), py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none());
     py::class_<solver::AL_ILQR>(m_sol, "AL_ILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const std::vector<solver::Constraint>&, const std::vector<Vec>&>(), py::arg("s"), py::arg("inequality"),
              py::arg("initLambda"))
@@ -326,12 +342,15 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none())
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
-                const py::object& kp, const py::object& x0, const py::object& w, bool ff, const py::object& samples) {
-                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff), nb_iter, lag, pen, sc, ls, es);
+                const py::object& kp, const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed,
+                const py::object& sigma_w, const py::object& sigma_x0) {
+                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0), nb_iter, lag, pen, sc, ls,
+                                             es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(),
-             py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none());
+             py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none(), py::arg("seed") = py::none(),
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none());
     // bindings.cpp:778-782
     py::class_<solver::BatchILQR>(m_sol, "BatchILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("Q"))

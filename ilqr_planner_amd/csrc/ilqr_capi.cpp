@@ -48,6 +48,8 @@ struct ilqr_problem {
     int last_nb_iter = 0;
     bool has_controls = false, has_state = false;
     bool has_gains = false;  // a Riccati solve with nb_iter >= 1 has run since the inputs last changed: X, U, KD are one plan (closed_loop)
+    double* cl_cost = nullptr; // closed_loop_noise without a cost array: the per-sample costs k_closed_loop_stats reduces
+    size_t cl_cost_elems = 0;
     double* cl_kpx = nullptr;  // closed_loop: state | control of every sample at the step-table entries (k_closed_loop_coop -> k_closed_loop_kp)
     size_t cl_kpx_elems = 0;
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
@@ -454,6 +456,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     for (void* q : p->allocs) (void)hipFree(q);
     if (p->staging) (void)hipFree(p->staging);
     if (p->cl_kpx) (void)hipFree(p->cl_kpx);
+    if (p->cl_cost) (void)hipFree(p->cl_cost);
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
     delete p;
@@ -939,18 +942,33 @@ extern "C" int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_me
 
 // Closed loop of the tracking law on the last plan (ilqr_closed_loop.hpp): n_samples executions per instance.  Which kernel runs is decided by
 // plan_closed_loop; chains of fewer than 7 joints take the generic kernel's mapped variant.
-static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w, int with_ff, double* cost, double* X, double* U, bool dev) {
+// nz: ilqr_problem_closed_loop_noise (noisy) -- the draws of ilqr_noise.hpp in place of w, and stats / w_out.
+static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w, int with_ff, double* cost, double* X, double* U, bool dev,
+                       bool noisy = false, const ilqr_noise* nz = nullptr, double* stats = nullptr, double* w_out = nullptr) {
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
     if (!p->has_gains)
         return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) since the problem's inputs last changed");
     if (S < 1) return fail(c, "n_samples must be >= 1");
-    if (!cost) return fail(c, "cost is a null pointer");
     const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u;
+    if (noisy) {
+        if (!nz) return fail(c, "noise is a null pointer");
+        for (int i = 0; i < nxu; i++)
+            if (!(nz->sigma_w[i] >= 0) || !std::isfinite(nz->sigma_w[i]) || !(nz->sigma_x0[i] >= 0) || !std::isfinite(nz->sigma_x0[i]))
+                return fail(c, "closed loop: every sigma_w and sigma_x0 must be finite and >= 0");
+        if (!cost && !stats) return fail(c, "cost and stats are both null pointers");
+        if ((unsigned long long)nz->instance_offset + (unsigned long long)p->B > (1ull << 32) ||
+            (unsigned long long)nz->sample_offset + (unsigned long long)S > (1ull << 32))
+            return fail(c, "closed loop: instance_offset + B or sample_offset + n_samples exceeds 2^32 (the generator's counter)");
+    } else if (!cost) return fail(c, "cost is a null pointer");
     const size_t n = (size_t)p->B * S;
     const size_t n_x0 = x0 ? n * nxu : 0, n_w = w ? n * (T - 1) * nxu : 0, n_X = X ? n * T * nxu : 0, n_U = U ? n * (T - 1) * nuu : 0;
+    const size_t n_wo = w_out ? n * (T - 1) * nxu : 0, n_st = stats ? (size_t)p->B * ILQR_CL_STATS : 0;
     // the kernels address the caller's arrays with 32-bit element offsets
-    if (n * T * (size_t)(nxu > nuu ? nxu : nuu) >= ((size_t)1 << 31))
+    if (noisy && !X && !U && !w_out) {  // no per-step array: x0 and cost are the longest
+        if (n * (size_t)nxu >= ((size_t)1 << 31))
+            return fail(c, "closed loop: B * n_samples * n_x overflows the kernels' 32-bit offsets (split the samples over several calls)");
+    } else if (n * T * (size_t)(nxu > nuu ? nxu : nuu) >= ((size_t)1 << 31))
         return fail(c, "closed loop: B * n_samples * T * n_x overflows the kernels' 32-bit offsets (split the samples over several calls)");
     HIPCHK(c, hipSetDevice(c->device));
     const ClosedLoopPlan pl = plan_closed_loop(p->desc.kind, p->desc.nb_deriv, S, p->B, c->n_simd, c->xc_generic || p->mapped);
@@ -965,8 +983,21 @@ static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w
     }
     ClArgs a;
     a.S = S; a.with_ff = with_ff ? 1 : 0; a.x0 = x0; a.w = w; a.cost = cost; a.X = X; a.U = U;
-    if (!dev) {  // staging: x0 | w | cost | X | U
-        if (ensure_staging(p, n_x0 + n_w + n + n_X + n_U)) return 1;
+    if (noisy) {
+        a.noise = 1; a.seed = nz->seed; a.b_off = nz->instance_offset; a.s_off = nz->sample_offset; a.w_out = w_out;
+        for (int i = 0; i < nxu; i++) { a.sigma_w[i] = nz->sigma_w[i]; a.sigma_x0[i] = nz->sigma_x0[i]; }
+    }
+    double* dstats = stats;
+    if (dev && !cost) {  // the per-sample costs live in a workspace of the problem
+        if (p->cl_cost_elems < n) {
+            if (p->cl_cost) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p->cl_cost)); p->cl_cost = nullptr; p->cl_cost_elems = 0; }
+            HIPCHK(c, hipMalloc((void**)&p->cl_cost, n * sizeof(double)));
+            p->cl_cost_elems = n;
+        }
+        a.cost = p->cl_cost;
+    }
+    if (!dev) {  // staging: x0 | w | cost | X | U | w_out | stats
+        if (ensure_staging(p, n_x0 + n_w + n + n_X + n_U + n_wo + n_st)) return 1;
         double* s = p->staging;
         if (x0) { HIPCHK(c, hipMemcpyAsync(s, x0, n_x0 * sizeof(double), hipMemcpyHostToDevice, c->stream)); a.x0 = s; }
         s += n_x0;
@@ -976,12 +1007,19 @@ static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w
         if (X) a.X = s;
         s += n_X;
         if (U) a.U = s;
+        s += n_U;
+        if (w_out) a.w_out = s;
+        s += n_wo;
+        if (stats) dstats = s;
     }
     if (pl.coop) launch_closed_loop_coop(p->desc.kind, p->desc.nb_deriv, p->bufs, a, p->B, pl, p->cl_kpx, c->stream);
     else launch_closed_loop(p->desc.kind, p->desc.nb_deriv, p->bufs, a, p->B, p->mapped ? &p->map : nullptr, c->stream);
+    if (stats) launch_closed_loop_stats(a.cost, p->B, S, dstats, c->stream);
     HIPCHK(c, hipGetLastError());
     if (!dev) {
-        HIPCHK(c, hipMemcpyAsync(cost, a.cost, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (cost) HIPCHK(c, hipMemcpyAsync(cost, a.cost, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (stats) HIPCHK(c, hipMemcpyAsync(stats, dstats, n_st * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (w_out) HIPCHK(c, hipMemcpyAsync(w_out, a.w_out, n_wo * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, n_X * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (U) HIPCHK(c, hipMemcpyAsync(U, a.U, n_U * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -995,6 +1033,15 @@ extern "C" int ilqr_problem_closed_loop(ilqr_problem* p, int n_samples, const do
 extern "C" int ilqr_problem_closed_loop_dev(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost,
                                             double* X, double* U) {
     return closed_loop(p, n_samples, x0, w, with_feedforward, cost, X, U, true);
+}
+
+extern "C" int ilqr_problem_closed_loop_noise(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, int with_feedforward,
+                                              double* cost, double* stats, double* X, double* U, double* w_out) {
+    return closed_loop(p, n_samples, x0, nullptr, with_feedforward, cost, X, U, false, true, noise, stats, w_out);
+}
+extern "C" int ilqr_problem_closed_loop_noise_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, int with_feedforward,
+                                                  double* cost, double* stats, double* X, double* U, double* w_out) {
+    return closed_loop(p, n_samples, x0, nullptr, with_feedforward, cost, X, U, true, true, noise, stats, w_out);
 }
 
 extern "C" int ilqr_problem_get_K(ilqr_problem* p, double* K) { return get_gains(p, K, nullptr); }

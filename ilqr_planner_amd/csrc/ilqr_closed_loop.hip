@@ -48,6 +48,12 @@ __global__ __launch_bounds__(64) void k_closed_loop_coop(Bufs a, ClArgs c, int d
         const double* X0 = a.X[a.cur[bq]] + bq;
         UNR for (int i = 0; i < NX; i++) x[i] = c.x0 ? c.x0[g * NX + i] : X0[(size_t)i * Bp];
     }
+    const unsigned gb = c.b_off + (unsigned)b, gs = c.s_off + (unsigned)s;   // the counter of this lane's draws (padding lanes: any)
+    if (c.noise) {
+        double nz[NX];
+        const unsigned on = noise_draw<NX, false, false>(c.seed, gb, gs, NOISE_STEP_START, c.sigma_x0, NX, nullptr, nz);
+        UNR for (int i = 0; i < NX; i++) if ((on >> i) & 1u) x[i] += nz[i];
+    }
     double lim = 0;
     int st = 0;
     NOUNR for (int k0 = 0; k0 < T - 1; k0 += depth) {
@@ -70,6 +76,10 @@ __global__ __launch_bounds__(64) void k_closed_loop_coop(Bufs a, ClArgs c, int d
         NOUNR for (int j = 0; j < nk; j++) {
             const int k = k0 + j;
             const double* r = lds + ((size_t)j * NI + li) * STRIDE;
+            // the draw of this step depends on no state: issued first, it fills the latency of the control / dynamics chain below
+            double nz[NX];
+            unsigned on = 0;
+            if (c.noise) on = noise_draw<NX, false, false>(c.seed, gb, gs, (unsigned)k, c.sigma_w, NX, nullptr, nz);
             if (c.X && valid) { UNR for (int i = 0; i < NX; i++) c.X[(g * T + k) * NX + i] = x[i]; }
             cl_control<S>(r, SYM, FF, r + RS, r + RS + NX, 1, sc, x, u);
             if (c.U && valid) { UNR for (int i = 0; i < NU; i++) c.U[(g * (T - 1) + k) * NU + i] = u[i]; }
@@ -83,7 +93,8 @@ __global__ __launch_bounds__(64) void k_closed_loop_coop(Bufs a, ClArgs c, int d
                 st++;
             }
             dyn_step<S>(d, x, u, xn);
-            if (c.w) { UNR for (int i = 0; i < NX; i++) xn[i] += c.w[(g * (T - 1) + k) * NX + i]; }
+            if (c.noise) cl_disturb<NX, false>(c, g, k, T, NX, nullptr, on, nz, valid, xn);
+            else if (c.w) { UNR for (int i = 0; i < NX; i++) xn[i] += c.w[(g * (T - 1) + k) * NX + i]; }
             UNR for (int i = 0; i < NX; i++) x[i] = xn[i];
         }
     }

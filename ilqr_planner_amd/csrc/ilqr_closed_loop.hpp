@@ -6,8 +6,10 @@
 //   x_{k+1} = f(x_k, u_k) + w_k                                  dyn_step
 //   J       = sum_k limit terms(x_k)  +  sum over the step table of the keypoint terms(x_t, u_t)   (System::cost without AL terms)
 #pragma once
+#include "../../include/ilqr_hip.h"  // ILQR_MAX_NX, ILQR_CL_STATS
 #include "ilqr_closed_loop_plan.hpp"
 #include "ilqr_step.hpp"
+#include "ilqr_noise.hpp"
 
 namespace ilqr {
 
@@ -20,7 +22,29 @@ struct ClArgs {
     double* cost;       // [B][S]
     double* X;          // [B][S][T][n_x] or null
     double* U;          // [B][S][T-1][n_u] or null
+    // ilqr_problem_closed_loop_noise: the disturbances and the start perturbation are drawn in the kernel (ilqr_noise.hpp)
+    int noise = 0;                          // draw; with 0 the fields below are read by nothing
+    unsigned long long seed = 0;
+    unsigned int b_off = 0, s_off = 0;      // global index of this call's first instance / sample
+    double sigma_w[ILQR_MAX_NX] = {}, sigma_x0[ILQR_MAX_NX] = {};   // user's state layout; 0: no draw for the entry
+    double* w_out = nullptr;                // [B][S][T-1][n_x] or null: the disturbance every step added
 };
+
+// x_{k+1} += w_k: the caller's w, the draw (nz, on: noise_draw), or both; w_out gets what was added (0 where nothing was).  An entry without
+// either is not touched (no + 0.0).  One function for both kernels, like the rest of the step.
+template <int NX, bool MAP>
+ILQR_DEV void cl_disturb(const ClArgs& c, int g, int k, int T, int nxu, const int* usr, unsigned on, const double* nz, bool valid, double* xn) {
+    UNR for (int i = 0; i < NX; i++) {
+        const int iu = MAP ? usr[i] : i;
+        if (iu < 0) continue;
+        double wv = 0.0;
+        bool has = false;
+        if (c.w) { wv = c.w[(g * (T - 1) + k) * nxu + iu]; has = true; }
+        if ((on >> i) & 1u) { wv = has ? wv + nz[i] : nz[i]; has = true; }
+        if (has) xn[i] += wv;
+        if (c.w_out && valid) c.w_out[(g * (T - 1) + k) * nxu + iu] = has ? wv : 0.0;
+    }
+}
 
 // The control of one lane at one step.  rec: the step's gain record (entry (i, j) at kd_off, the feed-forward at column n_x); xb, ub: the plan's
 // state and control, entry i at xb[i * xs] (xs = Bp in the trajectory buffers, 1 in a staged record); sc: the alpha scaling rule of k_track.

@@ -687,6 +687,12 @@ __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap m
         const int iu = MAP ? mx.usr[i] : i;
         x[i] = (c.x0 && iu >= 0) ? c.x0[g * nxu + iu] : Xb[(size_t)i * Bp];
     }
+    const unsigned gb = c.b_off + (unsigned)b, gs = c.s_off + (unsigned)(g - b * c.S);   // the counter of this lane's draws
+    if (c.noise) {
+        double nz[NX];
+        const unsigned on = noise_draw<NX, MAP, true>(c.seed, gb, gs, NOISE_STEP_START, c.sigma_x0, nxu, mx.usr, nz);
+        UNR for (int i = 0; i < NX; i++) if ((on >> i) & 1u) x[i] += nz[i];
+    }
     double lim = 0, kpc = 0;
     int st = 0;  // step table walk, as in k_init_rollout
     for (int k = 0; k < T - 1; k++) {
@@ -700,8 +706,13 @@ __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap m
         }
         lim += cl_limits<S>(d, x);
         if (st < d.steps.n && d.steps.t[st] == k) { kpc = cl_kp_terms<S>(d, a, b, st, x, u, kpc); st++; }
+        // the draw of this step: behind the keypoint terms, so that it is not live across FK; it depends on no state and fills dyn_step's latency
+        double nz[NX];
+        unsigned on = 0;
+        if (c.noise) on = noise_draw<NX, MAP, true>(c.seed, gb, gs, (unsigned)k, c.sigma_w, nxu, mx.usr, nz);
         dyn_step<S>(d, x, u, xn);
-        if (c.w) {
+        if (c.noise) cl_disturb<NX, MAP>(c, g, k, T, nxu, mx.usr, on, nz, true, xn);
+        else if (c.w) {
             UNR for (int i = 0; i < NX; i++) { const int iu = MAP ? mx.usr[i] : i; if (iu >= 0) xn[i] += c.w[(g * (T - 1) + k) * nxu + iu]; }
         }
         UNR for (int i = 0; i < NX; i++) x[i] = xn[i];
@@ -716,6 +727,33 @@ __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap m
         kpc = cl_kp_terms<S>(d, a, b, st, x, zu, kpc);
     }
     c.cost[g] = lim + kpc;
+}
+
+// Per-instance statistics of the closed-loop costs: one lane per instance over cost[b][0 .. S-1] in sample order, in two passes, so the sums do
+// not depend on the batch size or on which kernel made the costs.  stats[b] = { mean, unbiased variance, min, max, n_bad }: n_bad counts the
+// samples whose cost is not finite, the other four are over the finite ones (variance 0 for a single one, all four NaN for none).
+__global__ __launch_bounds__(64) void k_closed_loop_stats(const double* __restrict__ cost, int B, int S, double* __restrict__ stats) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const double* cb = cost + (size_t)b * S;
+    int n = 0;
+    double sum = 0, lo = INFINITY, hi = -INFINITY;
+    for (int s = 0; s < S; s++) {
+        const double v = cb[s];
+        if (isfinite(v)) { n++; sum += v; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
+    }
+    const double mean = sum / n;
+    double ss = 0;
+    for (int s = 0; s < S; s++) {
+        const double v = cb[s];
+        if (isfinite(v)) ss += (v - mean) * (v - mean);
+    }
+    double* o = stats + (size_t)b * ILQR_CL_STATS;
+    o[0] = n ? mean : NAN;
+    o[1] = n > 1 ? ss / (n - 1) : (n ? 0.0 : NAN);
+    o[2] = n ? lo : NAN;
+    o[3] = n ? hi : NAN;
+    o[4] = (double)(S - n);
 }
 
 // f(X) for every (instance, timestep): one lane per pair (tuple<1> of ILQRRecursive::solve)
@@ -841,6 +879,9 @@ void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B,
         if (m) hipLaunchKernelGGL((k_closed_loop<S, true>), grid, block, 0, st, a, c, m->x, m->u);
         else hipLaunchKernelGGL((k_closed_loop<S, false>), grid, block, 0, st, a, c, IndexMap{}, IndexMap{});
     });
+}
+void launch_closed_loop_stats(const double* cost, int B, int S, double* stats, hipStream_t st) {
+    hipLaunchKernelGGL(k_closed_loop_stats, dim3((B + 63) / 64), dim3(64), 0, st, cost, B, S, stats);
 }
 void launch_fk_batch(const DevDesc* dd, int n, const double* q, double* pos, double* quat, double* jac, hipStream_t st) {
     hipLaunchKernelGGL(k_fk_batch, dim3((n + 63) / 64), dim3(64), 0, st, dd, n, q, pos, quat, jac);

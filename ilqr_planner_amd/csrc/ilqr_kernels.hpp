@@ -107,6 +107,7 @@ void launch_from_soa_scaled(const double* src, const double* alpha, const int* i
 void launch_get_gains(const double* kd, int kd_sym, const double* alpha, const int* iters, double* K_out, double* d_out, int B, int Bp, int T1, int nu, int nx, hipStream_t st);
 void launch_warm_start(const Bufs& a, double* U0, double* q0, double* dq0, int shift, int B, int T, int nx, int nu, int nd, hipStream_t st);
 void launch_track(const Bufs& a, const double* x_meas, int k, int with_ff, double* u_out, int B, int nx, int nu, hipStream_t st);
+void launch_closed_loop_stats(const double* cost, int B, int S, double* stats, hipStream_t st);  // k_closed_loop_stats: stats[B][ILQR_CL_STATS] of cost[B][S]
 void launch_fk_batch(const DevDesc* dd, int n, const double* q, double* pos, double* quat, double* jac, hipStream_t st);
 // The layout conversions of a chain of fewer than 7 joints (ilqr_dofmap.hpp): the same passes with every per-step vector of `outer`
 // vectors widened (upload, padding written as 0) or narrowed (download) through its map.  Rows of the natural side: outer * m.n_user.

@@ -253,7 +253,7 @@ int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_meas, int wit
 /* Closed loop of that law on the plan of the last Riccati solve: n_samples executions of every instance,
  *   x_0 = x0[b][s] (NULL: xbar_0);  u_k = ilqr_problem_track(k, x_k, with_feedforward);  x_{k+1} = f(x_k, u_k) + w[b][s][k] (NULL: none);
  *   cost[b][s] = sum_{k<T-1} cost(x_k, u_k, k) + cost(x_{T-1}, 0, T-1)     (the system's stage cost, no AL terms: what ilqr_solve_recursive reports),
- * with f the system's own step (dt = u_last^2 on the time systems).  Start states and disturbances are the caller's: no device random numbers.
+ * with f the system's own step (dt = u_last^2 on the time systems).  Start states and disturbances are the caller's (ilqr_problem_closed_loop_noise draws them on the device).
  * x0[B][S][n_x] or NULL, w[B][S][T-1][n_x] or NULL; cost[B][S]; X[B][S][T][n_x] or NULL; U[B][S][T-1][n_u] or NULL.
  * Fails unless ilqr_solve_recursive / ilqr_solve_al with nb_iter >= 1 has run since the problem's inputs last changed (the batch solvers leave no
  * gains), for n_samples < 1, for a null cost, and when B * n_samples * T * n_x reaches 2^31 (the kernels' 32-bit offsets).
@@ -262,6 +262,37 @@ int ilqr_problem_closed_loop(ilqr_problem* p, int n_samples, const double* x0, c
                              double* U);
 int ilqr_problem_closed_loop_dev(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost, double* X,
                                  double* U);
+/* The same rollout with the disturbances and the start-state perturbations drawn inside the kernels, and the costs reduced per instance on
+ * the device: no per-step array has to exist, and a call with only `stats` moves the plan in and 5 B doubles out.
+ *   x_0 = centre + sigma_x0 .* z,  centre = x0[b][s] (NULL: xbar_0);   x_{k+1} = f(x_k, u_k) + sigma_w .* z_k;   z ~ N(0, 1), independent.
+ * The generator is part of this contract, so that a caller can reproduce a draw:
+ *   Philox4x32-10: multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85; one round is
+ *       p0 = M0 c0, p1 = M1 c2;  c <- (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0));  then k0, k1 += the Weyl constants.
+ *   key = (seed & 0xffffffff, seed >> 32);  counter = (instance_offset + b, sample_offset + s, k, j): k = 0 .. T-2 is the step whose
+ *       successor is disturbed, k = 0xFFFFFFFF the start-state draw, j the pair index.
+ *   One call (r0, r1, r2, r3) gives two normals: u1 = ((double)((r1:r0) >> 11) + 0.5) 2^-53, u2 likewise from r3:r2,
+ *       z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2).
+ *   Pair j serves entries 2j and 2j + 1 of the state in the user's layout (for an odd n_x the last z1 is dropped; the padded entries of a
+ *       chain of fewer than 7 joints get nothing).  Entry i receives sigma[i] z, the product rounded on its own; an entry with sigma 0
+ *       receives nothing, and a pair whose sigmas are both 0 is not generated.
+ * The draw of (seed, global instance, global sample, step, entry) depends on nothing else: a cut-out of a batch, a shard or a range of samples,
+ * run with its offsets, reproduces the large call bit for bit.  Host builds use sin / cos, the device sincospi: they agree to rounding.
+ * cost[B][S] or NULL (the per-sample costs then stay in a workspace of the problem); stats[B][ILQR_CL_STATS] or NULL: per instance, over
+ * cost[b][0 .. S-1] in sample order, { mean, unbiased variance, min, max } of the finite costs (variance 0 for one, all four NaN for none) and
+ * n_bad, the number of costs that are not finite.  X, U as above; w_out[B][S][T-1][n_x] or NULL: the disturbance every step added.
+ * Refused: everything ilqr_problem_closed_loop refuses, a null noise, a negative or non-finite sigma, cost and stats both NULL,
+ * instance_offset + B or sample_offset + n_samples beyond 2^32.  The 32-bit bound depends on what is asked for: with X, U and w_out all NULL
+ * no per-step array exists and the bound is B * n_samples * n_x < 2^31; with any of them it is the one above. */
+#define ILQR_CL_STATS 5   /* mean, variance, min, max, n_bad */
+typedef struct {
+    unsigned long long seed;
+    unsigned int instance_offset, sample_offset;   /* this call's first global instance / sample */
+    double sigma_w[ILQR_MAX_NX], sigma_x0[ILQR_MAX_NX];   /* user's state layout; 0 = none */
+} ilqr_noise;
+int ilqr_problem_closed_loop_noise(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, int with_feedforward, double* cost,
+                                   double* stats, double* X, double* U, double* w_out);
+int ilqr_problem_closed_loop_noise_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, int with_feedforward, double* cost,
+                                       double* stats, double* X, double* U, double* w_out);
 
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];
