@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "ilqr_batch_dev.hpp"
+#include "ilqr_lanes.hpp"
 
 namespace ilqr {
 
@@ -203,18 +204,6 @@ __global__ __launch_bounds__(LPB) void k_cp_solve(Bufs a, CPArgs c) {
 // right-hand side eliminated along as an extra column = the forward substitution with the stored multipliers), so the two kernels
 // agree bit for bit.  (The earlier form -- one wave per instance, the system in LDS, a lane per column -- spent its time in the LDS
 // pipe: ~1000 64-bit LDS instructions per instance, 69 us for 8192 instances; this one 30 us, 14 of them the assembly.)
-template <int CTRL>
-__device__ __forceinline__ double cp_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double cp_fetch(int src_lane, double v) {
-    const int lo = __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
 template <class S, int KWP>
 __global__ __launch_bounds__(64) void k_cp_solve_w(Bufs a, CPArgs c) {
     constexpr int NX = S::NX, G = 64 / KWP;
@@ -264,11 +253,11 @@ __global__ __launch_bounds__(64) void k_cp_solve_w(Bufs a, CPArgs c) {
         const bool cand = r >= k;
         const double av = cand ? fabs(h[k]) : -1.0;
         double mx = av;
-        mx = fmax(mx, cp_dpp<0xB1>(mx));   // quad_perm [1,0,3,2]
-        mx = fmax(mx, cp_dpp<0x4E>(mx));   // quad_perm [2,3,0,1]
-        mx = fmax(mx, cp_dpp<0x141>(mx));  // row_half_mirror: the other quad of the half
-        mx = fmax(mx, cp_dpp<0x140>(mx));  // row_mirror: the other half of the 16-lane row
-        if (KWP == 32) mx = fmax(mx, cp_fetch(lane ^ 16, mx));
+        mx = fmax(mx, dpp_f64<0xB1>(mx));   // quad_perm [1,0,3,2]
+        mx = fmax(mx, dpp_f64<0x4E>(mx));   // quad_perm [2,3,0,1]
+        mx = fmax(mx, dpp_f64<0x141>(mx));  // row_half_mirror: the other quad of the half
+        mx = fmax(mx, dpp_f64<0x140>(mx));  // row_mirror: the other half of the 16-lane row
+        if (KWP == 32) mx = fmax(mx, bperm_f64((lane ^ 16) << 2, mx));
         const unsigned long long eq = __ballot((cand && av == mx) ? 1 : 0);
         const unsigned long long dn = __ballot((r == k && isnan(h[k])) ? 1 : 0);
         const unsigned eqg = (unsigned)(eq >> base) & (KWP == 32 ? 0xffffffffu : 0xffffu);
@@ -279,8 +268,8 @@ __global__ __launch_bounds__(64) void k_cp_solve_w(Bufs a, CPArgs c) {
         // between fetched and own values afterwards, and those selects cost more than the second round: 45 us against 30.)
         const int src = base + ((r == pr) ? k : ((r == k) ? pr : r));
         double prow[KWP + 1];
-        UNR for (int j = k; j <= KWP; j++) h[j] = cp_fetch(src, h[j]);
-        UNR for (int j = k; j <= KWP; j++) prow[j] = cp_fetch(base + k, h[j]);
+        UNR for (int j = k; j <= KWP; j++) h[j] = bperm_f64(src << 2, h[j]);
+        UNR for (int j = k; j <= KWP; j++) prow[j] = bperm_f64((base + k) << 2, h[j]);
         if (r > k) {
             const double m = h[k] / prow[k];
             UNR for (int j = k + 1; j <= KWP; j++) h[j] = fma(-m, prow[j], h[j]);
@@ -293,7 +282,7 @@ __global__ __launch_bounds__(64) void k_cp_solve_w(Bufs a, CPArgs c) {
                                                                             // several rows the compiler keeps a separate multiply)
         const double xi = s / h[i];
         if (r == i) mine = xi;
-        x[i] = cp_fetch(base + i, xi);
+        x[i] = bperm_f64((base + i) << 2, xi);
     }
     if (act) AT(c.dw, r, b) = mine;
 }
@@ -637,8 +626,7 @@ __global__ __launch_bounds__(256) void k_cpl_quad(Bufs a, CPArgs c) {
     for (int s0 = wv; s0 < nk; s0 += 8 * NW) {  // (k-steps beyond the end multiply zeros)
         UNR for (int j = 0; j < 8; j += 2) { kstep(s0 + j * NW, acc0); kstep(s0 + (j + 1) * NW, acc1); }
     }
-    c00 += __shfl_xor(c00, 16);
-    c00 += __shfl_xor(c00, 32);
+    c00 = cross_rows_sum(c00);
     UNR for (int r = 0; r < 4; r++) sPart[wv][r][l] = acc0[r] + acc1[r];
     sPart[wv][4][l] = c00;
     __syncthreads();
@@ -844,20 +832,17 @@ int batchcp_solve(BatchCPState& st, const DevDesc& h, Bufs& bufs, int nx, int nu
     }
     }  // !same
     const bool general = st.xc_general;  // cross-check path (ilqr_ctx_set_crosscheck)
-    if (KWP == 32) {  // wider bases on the time systems: the same kernels with 32 lanes per instance
-        if (h.kind == 3) return run_cp<Sys<3, 1>, 32>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
-        if (h.nd == 1) return run_cp<Sys<1, 1>, 32>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
-        return run_cp<Sys<1, 2>, 32>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
+    using TimeSys = SysList<Sys<3, 1>, Sys<1, 1>, Sys<1, 2>>;  // wider bases: the same kernels with 32 lanes per instance
+    using LtiSys = SysList<Sys<2, 1>, Sys<0, 1>, Sys<0, 2>>;   // the linear systems have shared tables (run_cpl) unless the general path is pinned
+    int rc = 1;
+    if (KWP == 32) {
+        if (TimeSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cp<decltype(s), 32>(st, h, bufs, nb_iter, early_stop, stream, err, ph); })) return rc;
+    } else {
+        if (!general && LtiSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cpl<decltype(s), 16>(st, h, bufs, psip, nb_iter, early_stop, stream, err, ph); })) return rc;
+        if (SysAll::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cp<decltype(s), 16>(st, h, bufs, nb_iter, early_stop, stream, err, ph); })) return rc;
     }
-    if (h.kind == 3) return run_cp<Sys<3, 1>, 16>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
-    if (h.kind == 2 && !general) return run_cpl<Sys<2, 1>, 16>(st, h, bufs, psip, nb_iter, early_stop, stream, err, ph);
-    if (h.kind == 2) return run_cp<Sys<2, 1>, 16>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
-    if (h.kind == 0 && h.nd == 1 && !general) return run_cpl<Sys<0, 1>, 16>(st, h, bufs, psip, nb_iter, early_stop, stream, err, ph);
-    if (h.kind == 0 && h.nd == 2 && !general) return run_cpl<Sys<0, 2>, 16>(st, h, bufs, psip, nb_iter, early_stop, stream, err, ph);
-    if (h.kind == 0 && h.nd == 1) return run_cp<Sys<0, 1>, 16>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
-    if (h.kind == 0 && h.nd == 2) return run_cp<Sys<0, 2>, 16>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
-    if (h.kind == 1 && h.nd == 1) return run_cp<Sys<1, 1>, 16>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
-    return run_cp<Sys<1, 2>, 16>(st, h, bufs, nb_iter, early_stop, stream, err, ph);
+    err = "ilqr_solve_batch_cp: unknown system kind";
+    return 1;
 }
 
 }  // namespace ilqr

@@ -835,13 +835,12 @@ int batchwide_solve(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nx, in
     if (h.n_kp <= 0) { err = "wide-basis batch solve: the system has no keypoint"; return 1; }
     if (!psi_host) Kw = N;
     if (Kw <= 0 || Kw > N) { err = "wide-basis batch solve: Kw must be in 1 .. (T-1) n_u"; return 1; }
-    if (h.kind == 0 && h.nd == 1) return run_wl_m<Sys<0, 1>>(st, h, bufs, psi_host, Kw, nb_iter, early_stop, u0_zero, stream, err);
-    if (h.kind == 0 && h.nd == 2) return run_wl_m<Sys<0, 2>>(st, h, bufs, psi_host, Kw, nb_iter, early_stop, u0_zero, stream, err);
-    if (h.kind == 2) return run_wl_m<Sys<2, 1>>(st, h, bufs, psi_host, Kw, nb_iter, early_stop, u0_zero, stream, err);
+    using LtiSys = SysList<Sys<0, 1>, Sys<0, 2>, Sys<2, 1>>;
+    using TimeSys = SysList<Sys<1, 1>, Sys<1, 2>, Sys<3, 1>>;
+    int rc = 1;
+    if (LtiSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_wl_m<decltype(s)>(st, h, bufs, psi_host, Kw, nb_iter, early_stop, u0_zero, stream, err); })) return rc;
     if (psi_host) { err = "wide-basis batch solve: on time systems only the identity basis (ilqr_solve_batch) is supported for Kw > 32"; return 1; }
-    if (h.kind == 1 && h.nd == 1) return run_wt_m<Sys<1, 1>>(st, h, bufs, nb_iter, early_stop, stream, err);
-    if (h.kind == 1 && h.nd == 2) return run_wt_m<Sys<1, 2>>(st, h, bufs, nb_iter, early_stop, stream, err);
-    if (h.kind == 3) return run_wt_m<Sys<3, 1>>(st, h, bufs, nb_iter, early_stop, stream, err);
+    if (TimeSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_wt_m<decltype(s)>(st, h, bufs, nb_iter, early_stop, stream, err); })) return rc;
     err = "wide-basis batch solve: unknown system kind";
     return 1;
 }

@@ -456,10 +456,9 @@ static bool wb_lti_m(WbStage stage, int B, int T, int nkp, Bufs& a, const WArgs&
 }
 
 bool wb_lti_launch(WbStage stage, int kind, int nd, int B, int T, int nkp, Bufs& a, const WArgs& c, const WBig& g, hipStream_t s) {
-    if (kind == 0 && nd == 1) return wb_lti_m<Sys<0, 1>>(stage, B, T, nkp, a, c, g, s);
-    if (kind == 0 && nd == 2) return wb_lti_m<Sys<0, 2>>(stage, B, T, nkp, a, c, g, s);
-    if (kind == 2) return wb_lti_m<Sys<2, 1>>(stage, B, T, nkp, a, c, g, s);
-    return false;
+    bool done = false;
+    SysList<Sys<0, 1>, Sys<0, 2>, Sys<2, 1>>::dispatch(kind, nd, [&](auto sys) { done = wb_lti_m<decltype(sys)>(stage, B, T, nkp, a, c, g, s); });
+    return done;
 }
 
 template <class S>
@@ -473,10 +472,9 @@ static bool wtb_m(int B, Bufs& a, const WTArgs& c, hipStream_t s) {
 }
 
 bool wb_time_solve_launch(int kind, int nd, int B, Bufs& a, const WTArgs& c, hipStream_t s) {
-    if (kind == 1 && nd == 1) return wtb_m<Sys<1, 1>>(B, a, c, s);
-    if (kind == 1 && nd == 2) return wtb_m<Sys<1, 2>>(B, a, c, s);
-    if (kind == 3) return wtb_m<Sys<3, 1>>(B, a, c, s);
-    return false;
+    bool done = false;
+    SysList<Sys<1, 1>, Sys<1, 2>, Sys<3, 1>>::dispatch(kind, nd, [&](auto sys) { done = wtb_m<decltype(sys)>(B, a, c, s); });
+    return done;
 }
 
 }  // namespace ilqr

@@ -148,12 +148,13 @@ static void launch_sys(const Bufs& a, const ClArgs& c, int B, const ClosedLoopPl
 }
 
 void launch_closed_loop_coop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const ClosedLoopPlan& pl, double* kpx, hipStream_t st) {
-    if (kind == 2) { if (a.kd_sym) launch_sys<Sys<2, 1>, true>(a, c, B, pl, kpx, st); else launch_sys<Sys<2, 1>, false>(a, c, B, pl, kpx, st); }
-    else if (kind == 3) launch_sys<Sys<3, 1>, false>(a, c, B, pl, kpx, st);
-    else if (kind == 0 && nd == 1) { if (a.kd_sym) launch_sys<Sys<0, 1>, true>(a, c, B, pl, kpx, st); else launch_sys<Sys<0, 1>, false>(a, c, B, pl, kpx, st); }
-    else if (kind == 0 && nd == 2) launch_sys<Sys<0, 2>, false>(a, c, B, pl, kpx, st);
-    else if (kind == 1 && nd == 1) launch_sys<Sys<1, 1>, false>(a, c, B, pl, kpx, st);
-    else launch_sys<Sys<1, 2>, false>(a, c, B, pl, kpx, st);
+    SysAll::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::NX == DOF) {  // the packed symmetric gain record exists for the single-integrator systems only
+            if (a.kd_sym) return launch_sys<S, true>(a, c, B, pl, kpx, st);
+        }
+        launch_sys<S, false>(a, c, B, pl, kpx, st);
+    });
 }
 
 }  // namespace ilqr

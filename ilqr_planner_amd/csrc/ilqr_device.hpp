@@ -76,6 +76,22 @@ struct Sys {
     static constexpr int NQ = JOINT ? NX : NF - ND_;
 };
 
+// The systems a launcher has kernels for, and the way from a run-time (kind, nd) to the matching instantiation.  A pair that is not in the
+// list runs nothing: dispatch says so.  Each Riccati launcher ties its list to its predicate of ilqr_plan.hpp with a static_assert (same_as).
+template <class... Ss>
+struct SysList {
+    static constexpr bool has(int kind, int nd) { return ((Ss::KIND == kind && Ss::ND == nd) || ...); }
+    // calls f(S{}) for the entry S that matches; false if none does
+    template <class F>
+    static bool dispatch(int kind, int nd, F&& f) {
+        return ((Ss::KIND == kind && Ss::ND == nd ? (f(Ss{}), true) : false) || ...);
+    }
+    // over the systems of THIS list: List holds exactly those that pred(kind, nd) accepts
+    template <class List, class P>
+    static constexpr bool same_as(P pred) { return ((List::has(Ss::KIND, Ss::ND) == pred(Ss::KIND, Ss::ND)) && ...); }
+};
+using SysAll = SysList<Sys<2, 1>, Sys<3, 1>, Sys<0, 1>, Sys<0, 2>, Sys<1, 1>, Sys<1, 2>>;
+
 #define ILQR_DEV __device__ __forceinline__
 // empty statement the optimiser cannot see through (device code; tests/tools/hostsim builds the same source with g++, which has no "v" constraint)
 #if defined(__HIP_DEVICE_COMPILE__)

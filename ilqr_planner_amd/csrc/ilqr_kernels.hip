@@ -179,10 +179,9 @@ constexpr int backward_ws_doubles() {
     return 3 * S::NX * S::NX + 5 * S::NU * S::NX + 3 * S::NU * S::NU + 4 * S::NX + 2 * S::NU;
 }
 int backward_ws_entries(int kind, int nd) {
-    if (kind == 2) return backward_ws_doubles<Sys<2, 1>>();
-    if (kind == 3) return backward_ws_doubles<Sys<3, 1>>();
-    if (kind == 0) return nd == 1 ? backward_ws_doubles<Sys<0, 1>>() : backward_ws_doubles<Sys<0, 2>>();
-    return nd == 1 ? backward_ws_doubles<Sys<1, 1>>() : backward_ws_doubles<Sys<1, 2>>();
+    int n = 0;
+    SysAll::dispatch(kind, nd, [&](auto s) { n = backward_ws_doubles<decltype(s)>(); });
+    return n;
 }
 
 template <class S, bool AL>
@@ -789,20 +788,11 @@ __global__ __launch_bounds__(64) void k_fk_batch(const DevDesc* dd, int n, const
 
 // ------------------------------------------------------------------------------------------------ launchers
 
-// the system ladder of the four launchers below: calls launch(S{}) with the Sys of (kind, nd)
-template <class L>
-static void with_sys(int kind, int nd, L&& launch) {
-    if (kind == 2) launch(Sys<2, 1>{});
-    else if (kind == 3) launch(Sys<3, 1>{});
-    else if (kind == 0 && nd == 1) launch(Sys<0, 1>{});
-    else if (kind == 0 && nd == 2) launch(Sys<0, 2>{});
-    else if (kind == 1 && nd == 1) launch(Sys<1, 1>{});
-    else launch(Sys<1, 2>{});
-}
+// the generic kernels exist for every system: SysAll (ilqr_device.hpp)
 
 void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
     if (f.n_kp <= 0) return;
-    with_sys(kind, nd, [&](auto s) {
+    SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
         if (f.shared) {  // f.n_kp = distinct steps, f.n_kp_all = keypoints
             hipLaunchKernelGGL((k_kp_terms<S>), dim3((B + 63) / 64, f.n_kp_all), dim3(64), 0, st, a);
@@ -813,7 +803,7 @@ void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, co
 }
 
 void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty) {
-    with_sys(kind, nd, [&](auto s) {
+    SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
         if (al) hipLaunchKernelGGL((k_init_rollout<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty);
         else hipLaunchKernelGGL((k_init_rollout<S, false>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty);
@@ -821,7 +811,7 @@ void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st
 }
 
 void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st) {
-    with_sys(kind, nd, [&](auto s) {
+    SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
         if (al) hipLaunchKernelGGL((k_backward<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a);
         else hipLaunchKernelGGL((k_backward<S, false>), dim3((B + 63) / 64), dim3(64), 0, st, a);
@@ -829,7 +819,7 @@ void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hi
 }
 
 void launch_forward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    with_sys(kind, nd, [&](auto s) {
+    SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
         if (al)
             hipLaunchKernelGGL((k_forward<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
@@ -842,12 +832,7 @@ void launch_forward_generic(int kind, int nd, bool al, const Bufs& a, int B, hip
 
 void launch_fx_all(int kind, int nd, const Bufs& a, int B, int T, double* out, hipStream_t st) {
     const dim3 grid((B + 63) / 64, T), block(64);
-    if (kind == 2) hipLaunchKernelGGL((k_fx_all<Sys<2, 1>>), grid, block, 0, st, a, out);
-    else if (kind == 3) hipLaunchKernelGGL((k_fx_all<Sys<3, 1>>), grid, block, 0, st, a, out);
-    else if (kind == 0 && nd == 1) hipLaunchKernelGGL((k_fx_all<Sys<0, 1>>), grid, block, 0, st, a, out);
-    else if (kind == 0 && nd == 2) hipLaunchKernelGGL((k_fx_all<Sys<0, 2>>), grid, block, 0, st, a, out);
-    else if (kind == 1 && nd == 1) hipLaunchKernelGGL((k_fx_all<Sys<1, 1>>), grid, block, 0, st, a, out);
-    else hipLaunchKernelGGL((k_fx_all<Sys<1, 2>>), grid, block, 0, st, a, out);
+    SysAll::dispatch(kind, nd, [&](auto s) { hipLaunchKernelGGL((k_fx_all<decltype(s)>), grid, block, 0, st, a, out); });
 }
 
 void launch_to_soa(const double* src, double* dst, int B, int Bp, int rows, hipStream_t st) {
@@ -874,7 +859,7 @@ void launch_track(const Bufs& a, const double* x_meas, int k, int with_ff, doubl
 }
 void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const DofMap* m, hipStream_t st) {
     const dim3 grid(((unsigned)B * c.S + 63) / 64), block(64);
-    with_sys(kind, nd, [&](auto s) {
+    SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
         if (m) hipLaunchKernelGGL((k_closed_loop<S, true>), grid, block, 0, st, a, c, m->x, m->u);
         else hipLaunchKernelGGL((k_closed_loop<S, false>), grid, block, 0, st, a, c, IndexMap{}, IndexMap{});

@@ -95,8 +95,7 @@ void launch_forward_wave(int kind, bool small, const Bufs& a, int B, hipStream_t
 void launch_apply_wave(int kind, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f);  // blend + AL bookkeeping + flip
 void launch_forward_lin(const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // PosOrn-2: k_forward_lin (cost pass of every step size)
 void launch_apply_lin(const Bufs& a, int B, int T, hipStream_t st);  // PosOrn-2: the winner re-rolled (k_blend) + flip
-void launch_forward_mfma(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: all step sizes of an instance as one matrix-core product per step (ilqr_kernels_fwdm.hip)
-void launch_forward_tm(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: launch_forward_mfma + k_select_x
+void launch_forward_tm(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: k_forward_mfma (all step sizes of an instance as one matrix-core product per step) + k_select_x (ilqr_kernels_fwdm.hip)
 void launch_apply_tm(int kind, int nd, bool dpp, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // time systems: re-roll of the winner, k_apply_dpp_tm (dpp) or k_apply_rows_tm
 void launch_al_update(int kind, int nd, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f);  // k_al_post: active-set weights (+ multiplier update)
 void launch_fx_all(int kind, int nd, const Bufs& a, int B, int T, double* out, hipStream_t st);

@@ -38,6 +38,7 @@
 // x = xbar + alpha (x(1) - xbar) with k_apply's expression, I_k from the multipliers before the update, lambda update on update
 // iterations, buffers flipped at the end (AL-ILQR.cpp:190, 202-208).
 #include "ilqr_kernels.hpp"
+#include "ilqr_lanes.hpp"
 #include "ilqr_step.hpp"
 
 namespace ilqr {
@@ -135,42 +136,14 @@ __device__ __forceinline__ void pivots(double (&s)[7], const double (&nm1)[7], d
 #undef OPS_
 }
 
-// DPP move of a double by 32-bit halves (quad_perm / row_half_mirror: 8-lane butterfly)
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// Sum over lanes 8m .. 8m+7, result in all eight.  Every addition is rounded on its own: left to contraction, the first one became
-// fma(a_l, x_l, a_l' x_l') in each lane -- another value in lane l than in its partner l', so the lanes of an instance disagreed in the last
-// bits of g (and could disagree on the sign of a g at zero), and no other kernel could restate the sum.  As written it is the tree
-// ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)) in every lane: con_g_oct (ilqr_kernels_wave.hip) gives the same bits.
-__device__ __forceinline__ double oct_sum(double v) {
-#pragma clang fp contract(off)
-    v = v + dpp64<0xB1>(v);   // quad_perm [1,0,3,2]
-    v = v + dpp64<0x4E>(v);   // quad_perm [2,3,0,1]
-    v = v + dpp64<0x141>(v);  // row_half_mirror
-    return v;
-}
 // g = a_r . x - b over the eight lanes of an instance: product, tree and subtraction each rounded once
 __device__ __forceinline__ double oct_row_g(double a_l, double x_l, double b) {
 #pragma clang fp contract(off)
     const double p = a_l * x_l;
-    return oct_sum(p) - b;
+    return oct_sum_rounded(p) - b;
 }
 
 __device__ __forceinline__ double ldg(const double* base, unsigned byte_off) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + byte_off); }
-// A ring value moved out of its slot by an instruction the compiler cannot fold away: the slot register is then free BEFORE the slot's next
-// load is issued, the loop-carried value and the load destination share one register, and no copy is left on the back edge.  (Without it
-// the old value stayed in place for the whole step, the new load went to a second register, and the copies that rotate the ring at the
-// end of the unrolled group waited for the loads issued ONE step earlier: s_waitcnt vmcnt(4) .. vmcnt(0) once per group.)
-__device__ __forceinline__ double ring_take(double v) {
-    double r;
-    asm volatile("v_mov_b64_e32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
-}
 __device__ __forceinline__ void stg(double* base, unsigned byte_off, double v) { *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + byte_off) = v; }
 
 }  // namespace

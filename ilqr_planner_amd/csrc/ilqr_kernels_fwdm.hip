@@ -27,6 +27,8 @@
 // winner's column writes its trajectory.  Instances whose prediction lost are re-rolled by k_apply_rows_tm (8 lanes per instance: this
 // kernel with every column on the accepted step size was measured against it and is slower, 0.29 against 0.21 ms).
 #include "ilqr_kernels.hpp"
+#include "ilqr_lanes.hpp"
+#include "ilqr_plan.hpp"
 #include "ilqr_step.hpp"
 
 namespace ilqr {
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(64) void k_forward_mfma(Bufs a, FwdArgs f) {
     constexpr int NS = (ND == 2) ? 4 : 3;  // k-steps: the 1st-order systems skip slot 2 (empty in every lane)
     auto slot = [](int q) { return (ND == 2 || q < 2) ? q : 3; };
 
-    // bounds of the slots (unweighted or empty: (+inf, -inf), which costs 0 for every x -- see LimRegs in ilqr_kernels_v2.hip)
+    // bounds of the slots (unweighted or empty: (+inf, -inf), which no x violates: it costs 0, as in k_backward_si_dpp)
     const int lim_on = d.limits_set;
     const double pen = d.penalty;
     double smx[4], smn[4];
@@ -240,10 +242,8 @@ __global__ __launch_bounds__(64) void k_forward_mfma(Bufs a, FwdArgs f) {
                     if (!act[i]) continue;  // uniform (an instance that is not at work still ran its products: on harmless data)
                     const double u0 = ub0[i] + D[i][0], u1 = ub1[i] + D[i][1], ut = ubt[i] + D[i][2];
                     if (want_dun) {  // uniform
-                        double n2 = __builtin_fma(D[i][1], D[i][1], D[i][0] * D[i][0]);
-                        n2 += __shfl_xor(n2, 16);
-                        n2 += __shfl_xor(n2, 32);
-                        dun[i] += sqrt(n2);
+                        const double n2 = __builtin_fma(D[i][1], D[i][1], D[i][0] * D[i][0]);
+                        dun[i] += sqrt(cross_rows_sum(n2));
                     }
                     put_out(j & 1, i, u0, u1);
                     if (at_kp) export_kp(i, k, u0, u1);
@@ -294,9 +294,7 @@ __global__ __launch_bounds__(64) void k_forward_mfma(Bufs a, FwdArgs f) {
 
     UNR for (int i = 0; i < TI; i++) {
         if (!act[i]) continue;
-        double v = lc[i];
-        v += __shfl_xor(v, 16);
-        v += __shfl_xor(v, 32);
+        const double v = cross_rows_sum(lc[i]);
         if (part && h == 0) {
             AT(a.lsc, c, b0 + i) = v;
             AT(a.dunA, c, b0 + i) = dun[i];
@@ -304,16 +302,70 @@ __global__ __launch_bounds__(64) void k_forward_mfma(Bufs a, FwdArgs f) {
     }
 }
 
+// Line-search decision for the alpha-parallel rollouts of k_forward_mfma, one lane per (instance, alpha): task cost at the
+// keypoints from the exported (x, u) + the limit cost; the first alpha whose cost is below the current one and not NaN wins,
+// else the last one tried (ILQRRecursive.cpp:101-155).  If the winner is the lane that wrote its trajectory speculatively
+// (the predicted winner) the buffers flip here, otherwise `pend` asks the APPLY pass to re-roll it.
 template <class S>
-static void launch_fwdm(const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    const dim3 grid(grid_x8((B + FM_TI - 1) / FM_TI)), block(64);
-    hipLaunchKernelGGL((k_forward_mfma<S>), grid, block, 0, st, a, f);
+__global__ __launch_bounds__(64) void k_select_x(Bufs a, FwdArgs f) {
+    constexpr int NX = S::NX, NU = S::NU;
+    const DevDesc& d = *a.desc;
+    const int lane = threadIdx.x, gi = lane >> 4, ai = lane & 15;
+    const int b = blockIdx.x * 4 + gi;
+    const int Bp = d.Bp, T = d.T, B = d.B;
+    const bool inst_ok = (b < B) && (a.active[b < B ? b : 0] != 0);
+    const int bb = (b < B) ? b : 0;
+    const bool part = inst_ok && ai < f.n_alpha;
+    double c = 0;
+    if (part) {
+        for (int kpi = 0; kpi < d.n_kp; kpi++) {
+            const int k = d.kp_t[kpi];
+            const double* o = a.kpx + ((size_t)kpi * 16 + ai) * (NX + NU) * Bp;
+            double xt[NX], ut[NU], tg[S::NF];
+            UNR for (int i = 0; i < NX; i++) xt[i] = AT(o, i, bb);
+            UNR for (int i = 0; i < NU; i++) ut[i] = (k < T - 1) ? AT(o, NX + i, bb) : 0.0;
+            UNR for (int i = 0; i < S::NF; i++) tg[i] = AT(a.kp_tg, kpi * S::NF + i, bb);
+            c += kp_cost<S>(d, kpi, tg, xt, ut);
+        }
+        c += AT(a.lsc, ai, bb);
+    }
+    const double cost0 = a.cost[bb];
+    const bool ok = part && !((c >= cost0) || isnan(c));
+    const unsigned m16 = (unsigned)((__ballot(ok ? 1 : 0) >> (gi * 16)) & 0xffffull);
+    const int w = m16 ? (__ffs(m16) - 1) : (f.n_alpha - 1);
+    const double wcost = __shfl(c, gi * 16 + w);
+    if (inst_ok && ai == 0) {
+        const double walpha = ldexp(1.0, -w);
+        const double wdun = AT(a.dunA, w, bb);
+        const int pr = a.pred[bb] < f.n_alpha ? a.pred[bb] : f.n_alpha - 1;
+        a.cost[bb] = wcost;
+        a.alpha[bb] = walpha;
+        a.iters[bb] = f.it + 1;
+        a.status[bb] = (isfinite(wcost) ? 0 : 1) | ((walpha <= d.alpha_floor) ? 2 : 0);
+        if (a.cost_trace) {
+            a.cost_trace[(size_t)f.it * Bp + bb] = wcost;
+            a.alpha_trace[(size_t)f.it * Bp + bb] = walpha;
+        }
+        if (w == pr) a.cur[bb] = 1 - a.cur[bb];  // the speculatively written trajectory is the accepted one
+        else a.pend[bb] = w + 1;
+        a.pred[bb] = w;
+        bool stop = f.early_stop && (walpha * sqrt(wdun) < d.stop_tol);
+        if (!f.al) stop = stop && (wcost < 1e-3);  // ILQRRecursive.cpp:174 vs AL-ILQR.cpp:225
+        if (stop) a.active[bb] = 0;
+    }
 }
 
-void launch_forward_mfma(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    if (kind == 3) launch_fwdm<Sys<3, 1>>(a, B, st, f);
-    else if (nd == 1) launch_fwdm<Sys<1, 1>>(a, B, st, f);
-    else launch_fwdm<Sys<1, 2>>(a, B, st, f);
+// the time systems: neither of the two linear line searches (ilqr_plan.hpp) takes them
+using TimeSys = SysList<Sys<3, 1>, Sys<1, 1>, Sys<1, 2>>;
+static_assert(SysAll::same_as<TimeSys>([](int kind, int nd) { return !forward_wave_supported(kind, nd, 16) && !forward_lin_supported(kind, nd, 16); }),
+              "the time-system forward pass covers what the linear line searches leave");
+
+void launch_forward_tm(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
+    TimeSys::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((k_forward_mfma<S>), dim3(grid_x8((B + FM_TI - 1) / FM_TI)), dim3(64), 0, st, a, f);
+        hipLaunchKernelGGL((k_select_x<S>), dim3((B + 3) / 4), dim3(64), 0, st, a, f);
+    });
 }
 
 }  // namespace ilqr

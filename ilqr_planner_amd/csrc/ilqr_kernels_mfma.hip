@@ -24,43 +24,14 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "ilqr_lanes.hpp"
 #include "ilqr_pivots.hpp"
+#include "ilqr_plan.hpp"
 #include "ilqr_step.hpp"
 
 namespace ilqr {
 
-#define LDS_ORDER() asm volatile("" ::: "memory")
 typedef double d4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double rcp_nr_m(double x) {  // 1/x to the last bit: v_rcp_f64 (24 good bits: measured 4.6e-8) and ONE cubic
-    const double r = __builtin_amdgcn_rcp(x);               // step r (1 + e + e^2), e = 1 - x r  -- max error 1.1e-16 over 2^20 samples, one
-    const double e = fma(-x, r, 1.0);                       // FMA less than two Newton steps (no IEEE division sequence)
-    return fma(fma(e, e, e), r, r);
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp64m(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false);  // (every lane has a source in these patterns: no "old" value, no copy)
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double oct_sum_m(double v) {  // sum over lanes 8m .. 8m+7, result in all eight
-    v += dpp64m<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp64m<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp64m<0x141>(v);  // row_half_mirror
-    return v;
-}
-__device__ __forceinline__ double row16_sum(double v) {  // sum over the 16 lanes of a DPP row, result in all sixteen
-    v = oct_sum_m(v);
-    v += dpp64m<0x140>(v);  // row_mirror
-    return v;
-}
-__device__ __forceinline__ double cross_rows_sum(double v) {  // sum over lanes c, c+16, c+32, c+48
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_m(double v) { return cross_rows_sum(row16_sum(v)); }
 
 
 template <class S, bool AL>
@@ -295,7 +266,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                 double part = sBtP[qi][qj] * sbc[qj];
                 const double part2 = sBtP[qi][q2] * sbc[q2];
                 part += second ? part2 : 0.0;
-                tot = oct_sum_m(qv ? part : 0.0);
+                tot = oct_sum(qv ? part : 0.0);
             }
             const int qjj = (TM && qj == NU - 1) ? 0 : qj;
             const double joint = (ND == 1) ? sBtP[qi][qjj] * dt : sBtP[qi][qjj] * hdt2 + sBtP[qi][DOF + qjj] * dt;
@@ -318,7 +289,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             for (int rr = 0; rr < m; rr++) {  // uniform; g = A [x;u] - b, w = lambda + I g
                 const double* Ar = a.conA + ((size_t)(a.per_step ? k : 0) * m + rr) * ns;
                 const double part = (isX ? Ar[vx] * xv : 0.0) + (isU ? Ar[NX + vu] * uv_ : 0.0);
-                const double g = wave_sum_m(part) - a.conb[(size_t)(a.per_step ? k : 0) * m + rr];
+                const double g = wave_sum(part) - a.conb[(size_t)(a.per_step ? k : 0) * m + rr];
                 const double Ik = sIs[rr], wv = slam[rr] + Ik * g;
                 const double axc = Ar[cj];
                 UNR for (int r = 0; r < 2; r++) {
@@ -378,19 +349,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
-template <class S>
-static void launch_mfma_sys(bool al, const Bufs& a, int B, hipStream_t st) {
-    const dim3 grid(grid_x8(B)), block(64);
-    if (al) hipLaunchKernelGGL((k_backward_mfma<S, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_backward_mfma<S, false>), grid, block, 0, st, a);
-}
+using MfmaSys = SysList<Sys<3, 1>, Sys<0, 1>, Sys<0, 2>, Sys<1, 1>, Sys<1, 2>>;
+static_assert(SysAll::same_as<MfmaSys>([](int kind, int nd) { return backward_mfma_supported(kind, nd, false, 0); }), "MfmaSys is backward_mfma_supported");
 
 void launch_backward_mfma(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st) {
-    if (kind == 3) launch_mfma_sys<Sys<3, 1>>(al, a, B, st);
-    else if (kind == 0 && nd == 1) launch_mfma_sys<Sys<0, 1>>(al, a, B, st);
-    else if (kind == 0 && nd == 2) launch_mfma_sys<Sys<0, 2>>(al, a, B, st);
-    else if (kind == 1 && nd == 1) launch_mfma_sys<Sys<1, 1>>(al, a, B, st);
-    else launch_mfma_sys<Sys<1, 2>>(al, a, B, st);
+    MfmaSys::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        const dim3 grid(grid_x8(B)), block(64);
+        if (al) hipLaunchKernelGGL((k_backward_mfma<S, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_backward_mfma<S, false>), grid, block, 0, st, a);
+    });
 }
 
 }  // namespace ilqr

@@ -5,11 +5,11 @@
 // staging); the only exchange per timestep is the all-gather of the state deviation through LDS.
 // Workgroup = one wave = 8 instances: all exchange is wave-local (LDS operations of a wave execute in order), no barrier.
 #include "ilqr_kernels.hpp"
+#include "ilqr_lanes.hpp"
+#include "ilqr_plan.hpp"
 #include "ilqr_step.hpp"
 
 namespace ilqr {
-
-#define LDS_ORDER() asm volatile("" ::: "memory")
 
 // ------------------------------------------------------------------------------------------------ linear line search
 //
@@ -427,13 +427,6 @@ __global__ __launch_bounds__(64) void k_apply_rows_tm(Bufs a, FwdArgs f) {
 //   row_shl:7 / row_shl:1 moves.  No LDS, nothing couples the waves; instances with nothing pending keep re-reading their first record (cache hits).
 #define AD_LO " row_mask:0xf bank_mask:0x3"
 #define AD_HI " row_mask:0xf bank_mask:0xc"
-template <int CTRL>
-__device__ __forceinline__ double ad_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 // this half's part of du_r: half 0 sum_{c<8} K[c] dx_c; half 1 the NHI - 1 remaining columns (broadcast lanes 8 ..) and al * K[NHI-1] (the feed-forward);
 // three accumulators in rotation (a DPP instruction reads its accumulator early: no register is touched again within two instructions)
 template <int NHI>
@@ -550,9 +543,9 @@ __global__ __launch_bounds__(64) void k_apply_dpp_tm(Bufs a, FwdArgs f) {
             if (k >= nsteps) continue;  // uniform; dummy step of the last group
             const double dxv = isS ? xv - xb : 0.0;
             const double part = ad_half_dot<NHI>(Kr, dxv, alpha);
-            const double du = part + ad_dpp<0x128>(part);   // row_ror:8: the other half's part; the same two numbers in both halves
+            const double du = part + dpp_f64<0x128>(part);   // row_ror:8: the other half's part; the same two numbers in both halves
             const double u = ub + du;
-            const double dts = ad_dpp<0x15F>(u);            // row_newbcast:15: the time control
+            const double dts = dpp_f64<0x15F>(u);            // row_newbcast:15: the time control
             const double dt = dts * dts;
             if (inst_ok) {
                 if (isS) *oX = xv;
@@ -561,8 +554,8 @@ __global__ __launch_bounds__(64) void k_apply_dpp_tm(Bufs a, FwdArgs f) {
             oX += sX_; oU += sU_;
             // ---- dynamics (SimulationInterface.cpp:19-31 with dt = u_last^2, PosOrnTimePlannerSys.cpp:149-184): k_apply_rows_tm's expressions per coordinate
             if (ND == 2) {
-                const double vv = ad_dpp<0x107>(xv);        // row_shl:7: dq_i to the lane of q_i
-                const double un = ad_dpp<0x101>(u);         // row_shl:1: u_i (lane 8 + i) to the lane of dq_i (lane 7 + i)
+                const double vv = dpp_f64<0x107>(xv);        // row_shl:7: dq_i to the lane of q_i
+                const double un = dpp_f64<0x101>(u);         // row_shl:1: u_i (lane 8 + i) to the lane of dq_i (lane 7 + i)
                 if (isQ) xv = xv + (dt * vv + dt * dt / 2 * u);
                 else if (isD) xv = xv + dt * un;
                 else if (isTm) xv = xv + dt;
@@ -581,6 +574,9 @@ __global__ __launch_bounds__(64) void k_apply_dpp_tm(Bufs a, FwdArgs f) {
 #undef AD_LO
 #undef AD_HI
 
+using LinSys = SysList<Sys<0, 2>>;  // PosOrn-2: launch_forward_lin and launch_apply_lin take no (kind, nd)
+static_assert(SysAll::same_as<LinSys>([](int kind, int nd) { return forward_lin_supported(kind, nd, 16); }), "LinSys is forward_lin_supported");
+
 void launch_forward_lin(const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {  // PosOrn-2
     using S = Sys<0, 2>;
     const dim3 grid(grid_x8((B + 7) / 8)), block(64);
@@ -594,18 +590,18 @@ void launch_apply_lin(const Bufs& a, int B, int T, hipStream_t st) {  // PosOrn-
     hipLaunchKernelGGL(k_flip, dim3((B + 255) / 256), dim3(256), 0, st, a);
 }
 
+// the time systems: neither of the two linear line searches (ilqr_plan.hpp) takes them
+using TimeSys = SysList<Sys<3, 1>, Sys<1, 1>, Sys<1, 2>>;
+static_assert(SysAll::same_as<TimeSys>([](int kind, int nd) { return !forward_wave_supported(kind, nd, 16) && !forward_lin_supported(kind, nd, 16); }),
+              "the re-roll covers what the linear line searches leave");
+
 void launch_apply_tm(int kind, int nd, bool dpp, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    if (dpp) {  // 16 lanes per instance on registers
-        const dim3 g4(grid_x8((B + 3) / 4)), blk(64);
-        if (kind == 3) hipLaunchKernelGGL((k_apply_dpp_tm<Sys<3, 1>>), g4, blk, 0, st, a, f);
-        else if (nd == 1) hipLaunchKernelGGL((k_apply_dpp_tm<Sys<1, 1>>), g4, blk, 0, st, a, f);
-        else hipLaunchKernelGGL((k_apply_dpp_tm<Sys<1, 2>>), g4, blk, 0, st, a, f);
-        return;
-    }
-    const dim3 grid(grid_x8((B + 7) / 8)), block(64);
-    if (kind == 3) hipLaunchKernelGGL((k_apply_rows_tm<Sys<3, 1>>), grid, block, 0, st, a, f);
-    else if (nd == 1) hipLaunchKernelGGL((k_apply_rows_tm<Sys<1, 1>>), grid, block, 0, st, a, f);
-    else hipLaunchKernelGGL((k_apply_rows_tm<Sys<1, 2>>), grid, block, 0, st, a, f);
+    TimeSys::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        const dim3 block(64);
+        if (dpp) hipLaunchKernelGGL((k_apply_dpp_tm<S>), dim3(grid_x8((B + 3) / 4)), block, 0, st, a, f);  // 16 lanes per instance on registers
+        else hipLaunchKernelGGL((k_apply_rows_tm<S>), dim3(grid_x8((B + 7) / 8)), block, 0, st, a, f);
+    });
 }
 
 }  // namespace ilqr

@@ -23,6 +23,8 @@
 // Hazards of the inline-assembly DPP blocks as explained there: every statement starts with the two wait states a DPP read needs after a VALU
 // write of any of its operands.
 #include "ilqr_kernels.hpp"
+#include "ilqr_lanes.hpp"
+#include "ilqr_plan.hpp"
 #include "ilqr_step.hpp"
 
 namespace ilqr {
@@ -31,33 +33,14 @@ namespace {
 
 #define RW_ALL_ " row_mask:0xf bank_mask:0xf"
 
-__device__ __forceinline__ double rw_rcp(double x) {
-    const double r = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r, 1.0);
-    return fma(fma(e, e, e), r, r);
-}
-template <int L>
-__device__ __forceinline__ double rw_bcast(double v) {  // lane L of the DPP row to all sixteen (compiler-visible: hazards handled by the compiler)
-    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + L, 0xf, 0xf, false);
-}
-__device__ __forceinline__ double rw_shr7(double v) { return __builtin_amdgcn_update_dpp(0.0, v, 0x117, 0xf, 0xf, false); }  // lane l <- lane l - 7 (0 below)
-__device__ __forceinline__ double rw_shl7(double v) { return __builtin_amdgcn_update_dpp(0.0, v, 0x107, 0xf, 0xf, false); }  // lane l <- lane l + 7 (0 above)
-template <int CTRL>
-__device__ __forceinline__ double rw_dpp32(double v) {
-    return __builtin_amdgcn_update_dpp(0.0, v, CTRL, 0xf, 0xf, false);
-}
-__device__ __forceinline__ double rw_row_sum(double v) {  // sum over the 16 lanes of the DPP row, result in all sixteen
-    v += rw_dpp32<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += rw_dpp32<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += rw_dpp32<0x141>(v);  // row_half_mirror
-    v += rw_dpp32<0x140>(v);  // row_mirror
+// sum over the 16 lanes of the DPP row, result in all sixteen.  Not row16_sum (ilqr_lanes.hpp): on its moves by halves seven of the eight
+// k_backward_rows come out as another instruction stream than on these compiler-visible moves, which this kernel was measured with
+__device__ __forceinline__ double rw_row_sum(double v) {
+    v += dppz_f64<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dppz_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+    v += dppz_f64<0x141>(v);  // row_half_mirror
+    v += dppz_f64<0x140>(v);  // row_mirror
     return v;
-}
-
-__device__ __forceinline__ double rw_take(double v) {
-    double r;
-    asm volatile("v_mov_b64_e32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
 }
 
 // acc[c] += bcast_L(src[c]) * mul for N consecutive columns starting at acc / src (N = 8, 7 or 1): one statement, two wait states first
@@ -219,8 +202,8 @@ __global__ __launch_bounds__(64) void k_backward_rows(Bufs a) {
     for (int k0 = T - 2; k0 >= 0; k0 -= PF) {
       UNR for (int jj = 0; jj < PF; jj++) {
         const int k = k0 - jj;
-        // (ring values leave their slots by an opaque move before the slot's next load is issued: see ring_take in ilqr_kernels_dpp.hip)
-        const double xv = xm * rw_take(xr[jj]), uv = (isC ? 1.0 : 0.0) * rw_take(ur[jj]), lamv = AL ? rw_take(lmr[jj]) : 0.0, isv = AL ? rw_take(isr[jj]) : 0.0;
+        // (ring values leave their slots by an opaque move before the slot's next load is issued: see ring_take in ilqr_lanes.hpp)
+        const double xv = xm * ring_take(xr[jj]), uv = (isC ? 1.0 : 0.0) * ring_take(ur[jj]), lamv = AL ? ring_take(lmr[jj]) : 0.0, isv = AL ? ring_take(isr[jj]) : 0.0;
         __builtin_amdgcn_sched_barrier(0);
         fetch(jj, k - PF);
         // the gain image of the step before this one (in time) leaves now: LDS -> registers here, registers -> memory after the pivots
@@ -246,7 +229,7 @@ __global__ __launch_bounds__(64) void k_backward_rows(Bufs a) {
             continue;
         }
         // ---- 1. step sizes, the time column b of B (PosOrnTimePlannerSys.cpp:161-162,176: the velocity AFTER the step)
-        const double dts = TM ? rw_bcast<15>(uv) : 0.0;
+        const double dts = TM ? dppz_bcast<15>(uv) : 0.0;
         const double dt = TM ? dts * dts : d.dt;
         const double c1 = (ND == 1) ? dt : dt * dt / 2, c2 = (ND == 1) ? 0.0 : dt;  // B = [c1 I ; c2 I] on the joint block
         double bq = 0.0;
@@ -254,7 +237,7 @@ __global__ __launch_bounds__(64) void k_backward_rows(Bufs a) {
             if (ND == 1) {
                 bq = 2 * dts * uv;                                   // q rows: lane i is also control lane i
             } else {
-                const double uq = rw_shl7(uv), dq = rw_shl7(xv);     // q rows: u_i and dq_i live 7 lanes up
+                const double uq = dppz_shl7(uv), dq = dppz_shl7(xv);     // q rows: u_i and dq_i live 7 lanes up
                 const double dqn = dq + dt * uq;
                 const double bqq = 2 * dts * dqn + 2 * dts * dts * dts * uq;
                 bq = (l < DOF) ? bqq : 2 * dts * uv;                 // v rows: lane 7 + i is control lane i
@@ -270,7 +253,7 @@ __global__ __launch_bounds__(64) void k_backward_rows(Bufs a) {
             const double vdt = vm * dt, jc1 = jm * c1, jc2 = jm * c2, jdt = jm * dt;
             UNR for (int c = 0; c < NC; c++) {
                 if (ND == 2) {
-                    const double sh = rw_shr7(Pt[c]);
+                    const double sh = dppz_shr7(Pt[c]);
                     AtP[c] = fma(vdt, sh, Pt[c]);
                     BtP[c] = fma(jc1, sh, jc2 * Pt[c]);
                 } else {
@@ -281,13 +264,13 @@ __global__ __launch_bounds__(64) void k_backward_rows(Bufs a) {
         }
         double brep[NX > 0 ? NX : 1];
         if (TM) {
-#define BR_(R) if (R < NX) brep[R] = rw_bcast<R>(bq);
+#define BR_(R) if (R < NX) brep[R] = dppz_bcast<R>(bq);
             BR_(0) BR_(1) BR_(2) BR_(3) BR_(4) BR_(5) BR_(6) BR_(7) BR_(8) BR_(9) BR_(10) BR_(11) BR_(12) BR_(13) BR_(14)
 #undef BR_
             double Pb = 0;
             UNR for (int r = 0; r < NX; r++) Pb = fma(Pt[r], brep[r], Pb);      // (P b)_l = (b'P)_l by the symmetry of P
             const double bp = rw_row_sum(bq * Pt[NX]);                          // b . p
-#define TB_(C) if (C < NX) BtP[C] = fma(tmk, rw_bcast<C>(Pb), BtP[C]);   // the time control's row, in lane 15
+#define TB_(C) if (C < NX) BtP[C] = fma(tmk, dppz_bcast<C>(Pb), BtP[C]);   // the time control's row, in lane 15
             TB_(0) TB_(1) TB_(2) TB_(3) TB_(4) TB_(5) TB_(6) TB_(7) TB_(8) TB_(9) TB_(10) TB_(11) TB_(12) TB_(13) TB_(14)
 #undef TB_
             BtP[NX] = fma(tmk, bp, BtP[NX]);
@@ -384,18 +367,16 @@ __global__ __launch_bounds__(64) void k_backward_rows(Bufs a) {
 #undef CLANE
 }
 
-template <class S>
-static void launch_rows_sys(bool al, const Bufs& a, int B, hipStream_t st) {
-    const dim3 grid(grid_x8((B + 3) / 4)), block(64);
-    if (al) hipLaunchKernelGGL((k_backward_rows<S, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_backward_rows<S, false>), grid, block, 0, st, a);
-}
+using RowsSys = SysList<Sys<3, 1>, Sys<0, 2>, Sys<1, 1>, Sys<1, 2>>;
+static_assert(SysAll::same_as<RowsSys>([](int kind, int nd) { return backward_rows_supported(kind, nd, false, 0); }), "RowsSys is backward_rows_supported");
 
 void launch_backward_rows(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st) {
-    if (kind == 3) launch_rows_sys<Sys<3, 1>>(al, a, B, st);
-    else if (kind == 0) launch_rows_sys<Sys<0, 2>>(al, a, B, st);
-    else if (nd == 1) launch_rows_sys<Sys<1, 1>>(al, a, B, st);
-    else launch_rows_sys<Sys<1, 2>>(al, a, B, st);
+    RowsSys::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        const dim3 grid(grid_x8((B + 3) / 4)), block(64);
+        if (al) hipLaunchKernelGGL((k_backward_rows<S, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_backward_rows<S, false>), grid, block, 0, st, a);
+    });
 }
 
 }  // namespace ilqr

@@ -2,6 +2,7 @@
 //   k_forward_wg      forward pass of the linear line search, one 8-wave workgroup per 16 instances, 32 lanes per instance
 //   k_select          line-search decision: task cost of every step size from the exported keypoint deviations (one lane per alpha)
 //   k_apply, k_flip   accepted trajectory x(alpha) = xbar + alpha (x(1) - xbar) and the AL bookkeeping in one pass; buffer flip
+//   k_al_post         the AL bookkeeping alone, for every system: the pipelines whose forward pass leaves the accepted trajectory in place
 //   k_init_roll_lti, k_init_finish   initial rollout with one lane per (instance, coordinate)
 //
 // The forward pass.  k_forward_lin (ilqr_kernels_rows.hip) gives each instance 8 lanes: B = 4096 is then 512 single-wave
@@ -11,7 +12,7 @@
 // 1 KiB of contiguous memory -- and B = 4096 becomes 2048 waves, two per SIMD.  Per step and lane:
 //     partial = K[r][c0] dx[c0] + K[r][c1] dx[c1]          (c1 = 7 is the feed-forward column: dx[7] := 1)
 //     du[r]   = sum over the row's 4 lanes                 (two DPP quad permutes, no LDS)
-//     du[c0], du[c1] <- ds_bpermute from the rows c0, c1   (the transpose the product needs; LDS crossbar, no LDS memory)
+//     du[c0], du[c1] <- bperm_f64 from the rows c0, c1     (the transpose the product needs; LDS crossbar, no LDS memory)
 //     dx[c]  += dt du[c]                                    every lane keeps its two columns of the state deviation
 // xbar, ubar come in and x(1), u(1) go out through LDS in blocks of 8 timesteps, loaded / stored by the whole workgroup as full
 // 128-byte lines (see k_forward_wg).  The keypoint cost (FK) is not evaluated here: at keypoint steps the deviation (dx, du) is
@@ -20,34 +21,11 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "ilqr_lanes.hpp"
+#include "ilqr_plan.hpp"
 #include "ilqr_step.hpp"
 
 namespace ilqr {
-
-#define LDS_ORDER() asm volatile("" ::: "memory")
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false);  // every lane is written: no "old" operand, no copy
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// sum over the 4 lanes of a quad, result in all 4 (quad_perm [1,0,3,2] then [2,3,0,1])
-__device__ __forceinline__ double quad_sum(double v) {
-    v += dpp_f64<0xB1>(v);
-    v += dpp_f64<0x4E>(v);
-    return v;
-}
-__device__ __forceinline__ double bperm_f64(int byte_addr, double v) {
-    const int lo = __builtin_amdgcn_ds_bpermute(byte_addr, __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute(byte_addr, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
-// Workgroup barrier that only drains LDS traffic (__syncthreads() also emits s_waitcnt vmcnt(0): it would wait for the gain
-// prefetches issued 7 steps ahead).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // One workgroup = 8 waves = 16 consecutive instances; a wave owns two of them (32 lanes each, see the file header).
 //   gains        : read by the owning wave straight from HBM, one 16-byte load per lane and step (a wave's two records are
@@ -93,7 +71,7 @@ __global__ __launch_bounds__(FW_IW * 32) void k_forward_wg(Bufs a, FwdArgs f) {
     const int c1c = c1ok ? c1 : NX - 1;
     const bool colst = inst_ok && (r8 == 0);               // row 0 publishes x (its 4 lanes hold all 7 columns)
     const bool rowst = inst_ok && (jl == 0) && (r8 < NU);  // the first lane of a row publishes u
-    const int src0 = (g * 32 + c0 * 4) * 4, src1 = (g * 32 + c1c * 4) * 4;  // byte addresses for ds_bpermute
+    const int src0 = (g * 32 + c0 * 4) * 4, src1 = (g * 32 + c1c * 4) * 4;  // byte addresses for bperm_f64
 
     const double dt = d.dt, dt1 = c1ok ? dt : 0.0;
     const int lim_on = d.limits_set;
@@ -276,7 +254,7 @@ __global__ __launch_bounds__(FW_IW * 32) void k_forward_wg(Bufs a, FwdArgs f) {
 //   Memory: a wave may have 64 vector-memory instructions in flight, so what bounds the chain is instructions per step x latency / 64 (measured with
 //   8 per step: 0.23 us per step at any ring depth).  Hence 4 per step: the gain row as two 16-byte loads per lane (the halves take the two halves of
 //   the row), xbar_r | ubar_r as ONE load (half 0 / half 1), x(1)_r | u(1)_r as ONE store.  Ring of PF = 8 steps; a slot is refilled after its last
-//   use, so the loop-carried value and the load share a register (see ring_take in ilqr_kernels_dpp.hip for what happens otherwise).
+//   use, so the loop-carried value and the load share a register (see ring_take in ilqr_lanes.hpp for what happens otherwise).
 // Outputs as k_forward_wg: x(1), u(1) into the other buffer, (dx, du) at the keypoint steps, the limit cost of every step size, sum ||du||.
 // (Measured and dropped: this kernel, the decision and the next sweep's keypoint derivatives as ONE launch, a wave carrying its four instances through the
 // three phases -- bit-identical, and no faster at any batch size (C2, B = 256: 2.472 against 2.463 ms per solve): what the two launches cost is made up
@@ -295,13 +273,6 @@ __device__ __forceinline__ double fd_half_dot(const double (&K)[4], double x, do
                  : [x] "v"(x), [one] "v"(one), [k0] "v"(K[0]), [k1] "v"(K[1]), [k2] "v"(K[2]), [k3] "v"(K[3]));
 #undef D_
     return (s0 + s1) + s2;
-}
-// sum over lanes 8m .. 8m+7, result in all eight (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror)
-__device__ __forceinline__ double fd_oct_sum(double v) {
-    v += dpp_f64<0xB1>(v);
-    v += dpp_f64<0x4E>(v);
-    v += dpp_f64<0x141>(v);
-    return v;
 }
 
 // LIM / ES: limits set / early stop asked for -- template parameters because a branch instruction costs a lone wave 20-30 clocks whether taken or not
@@ -382,7 +353,7 @@ __device__ __forceinline__ bool forward_dpp_body(const Bufs& a, const FwdArgs& f
             const double du = part + dpp_f64<0x128>(part);   /* row_ror:8: the other half's part */                \
             if (st) *qV = vb + (h ? du : dx);                                                                      \
             qV += Vstep;                                                                                           \
-            if (ES) dun += __builtin_amdgcn_sqrt(fd_oct_sum(row ? du * du : 0.0));   /* ||du_k(1)|| */             \
+            if (ES) dun += __builtin_amdgcn_sqrt(oct_sum(row ? du * du : 0.0));   /* ||du_k(1)|| */             \
             if (LIM && __builtin_expect(__ballot((seg_bad(vb) & sx) ? 1 : 0) != 0ull, 0)) limits_all(vb);          \
             if (CHK && k == kp_next) {   /* hand the deviation of this step to k_select */                         \
                 double* o = kpdev + (size_t)kpi * (NX + NU) * Bp;                                                  \
@@ -415,7 +386,7 @@ __device__ __forceinline__ bool forward_dpp_body(const Bufs& a, const FwdArgs& f
     }
     // limit cost per step size: the seven coordinates of an instance (half 0), lane 0 writes
     UNR for (int i = 0; i < NA; i++) {
-        const double sA = LIM ? fd_oct_sum(row ? pc[i] : 0.0) : 0.0;
+        const double sA = LIM ? oct_sum(row ? pc[i] : 0.0) : 0.0;
         if (inst_ok && l == 0) AT(a.lsc, i, bb) = sA;
     }
     if (inst_ok && l == 0) a.dun[bb] = dun;
@@ -429,6 +400,9 @@ __global__ __launch_bounds__(64) void k_forward_dpp(Bufs a, FwdArgs f) { (void)f
 // The decision of k_select once every lane holds the task cost of its step size: limit cost added, the first step size (descending) below the current
 // cost wins, else the last one tried (ILQRRecursive.cpp:101-155); bookkeeping by the instance's first lane.  Returns the winner's index (uniform over
 // the instance's 16 lanes); *stopped = the instance left the iteration (early stop).
+// (The bookkeeping block is spelled out here, in k_forward, k_forward_lin and k_select_x, and the AL row update in k_apply and k_al_post: taken
+// from one shared inlined function, each of these kernels but k_apply compiled to another instruction stream, k_select_x with a private segment
+// and k_al_post with more registers.)
 template <int NA>
 __device__ __forceinline__ int select_decide(const Bufs& a, const FwdArgs& f, const DevDesc& d, int bb, bool inst_ok, bool mine, int gi, int al, int n_alpha, double c,
                                              bool* stopped = nullptr) {
@@ -461,7 +435,7 @@ __device__ __forceinline__ int select_decide(const Bufs& a, const FwdArgs& f, co
 }
 
 // Line-search decision of iteration f.it, one lane per (instance, alpha): task cost of x(alpha) = xbar + alpha dx at the keypoint
-// steps + the limit cost k_forward_w32 accumulated; the first alpha (descending) whose cost is below the current one wins, else
+// steps + the limit cost the rollout (k_forward_wg / k_forward_dpp) accumulated; the first alpha (descending) whose cost is below the current one wins, else
 // the last one tried (ILQRRecursive.cpp:101-155).  Writes cost/alpha/iters/status/traces, `pend` for k_blend/k_flip, and the
 // early-stop flag.
 // KW = 2: the keypoints are dealt to the two waves of the workgroup (keypoint kpi to wave kpi mod 2) -- the kernel is one chain of dependent
@@ -576,6 +550,32 @@ __global__ __launch_bounds__(256) void k_apply(Bufs a, FwdArgs f) {
         }
     }
 }
+// The same AL bookkeeping on a trajectory that is already in place, one lane per (instance, k), for the instances that ran iteration
+// f.it: the active-set weights penalty * I_k the next backward sweep needs (AL-ILQR.cpp:21-44,190 -- every trial overwrites them, so
+// only the accepted trial's values survive in the reference too) and, every lag_update_step iterations, the multiplier update
+// (AL-ILQR.cpp:202-208).  Keeps the rollout kernels of the other pipelines free of AL; at it = -1 it follows the LTI initial rollout.
+template <class S>
+__global__ __launch_bounds__(256) void k_al_post(Bufs a, FwdArgs f) {
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    const int k = blockIdx.y;
+    if (b >= d.B) return;
+    if (a.iters[b] != f.it + 1) return;
+    const int Bp = d.Bp;
+    const int cur = a.cur[b];
+    double x[S::NX], u[S::NU];
+    UNR for (int i = 0; i < S::NX; i++) x[i] = AT(a.X[cur], k * S::NX + i, b);
+    UNR for (int i = 0; i < S::NU; i++) u[i] = AT(a.U[cur], k * S::NU + i, b);
+    for (int r = 0; r < a.m; r++) {
+        const double g = con_g<S>(a, k, r, x, u);
+        const double lam = AT(a.lambda, k * a.m + r, b);
+        AT(a.Is, k * a.m + r, b) = f.penalty_roll * ((g < 0 && lam == 0) ? 0.0 : 1.0);
+        if (f.do_update) {
+            const double v = lam + f.penalty_update * g;
+            AT(a.lambda, k * a.m + r, b) = v > 0 ? v : 0;
+        }
+    }
+}
 __global__ void k_flip_ran(Bufs a) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.desc->B) return;
@@ -671,28 +671,29 @@ __global__ __launch_bounds__(64) void k_init_finish(Bufs a) {
     a.status[b] = isfinite(cost) ? 0 : 1;
 }
 
-template <class S>
-static void launch_init_lti_sys(const Bufs& a, int B, hipStream_t st) {
-    hipLaunchKernelGGL((k_init_roll_lti<S>), dim3((B + 255) / 256, DOF + S::TM), dim3(256), 0, st, a);
-    hipLaunchKernelGGL((k_init_finish<S>), dim3((B + 63) / 64), dim3(64), 0, st, a);
-}
+static_assert(SysAll::same_as<SysAll>([](int kind, int nd) { return init_lti_supported(kind, nd); }), "k_init_roll_lti: every system");
 void launch_init_lti(int kind, int nd, const Bufs& a, int B, hipStream_t st) {
-    if (kind == 2) launch_init_lti_sys<Sys<2, 1>>(a, B, st);
-    else if (kind == 3) launch_init_lti_sys<Sys<3, 1>>(a, B, st);
-    else if (kind == 1 && nd == 1) launch_init_lti_sys<Sys<1, 1>>(a, B, st);
-    else if (kind == 1) launch_init_lti_sys<Sys<1, 2>>(a, B, st);
-    else if (nd == 1) launch_init_lti_sys<Sys<0, 1>>(a, B, st);
-    else launch_init_lti_sys<Sys<0, 2>>(a, B, st);
+    SysAll::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((k_init_roll_lti<S>), dim3((B + 255) / 256, DOF + S::TM), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((k_init_finish<S>), dim3((B + 63) / 64), dim3(64), 0, st, a);
+    });
+}
+void launch_al_update(int kind, int nd, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f) {
+    SysAll::dispatch(kind, nd, [&](auto s) {
+        hipLaunchKernelGGL((k_al_post<decltype(s)>), dim3((B + 255) / 256, T - 1), dim3(256), 0, st, a, f);
+    });
 }
 
-template <class S>
-static void launch_apply_wave_sys(const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f) {
-    hipLaunchKernelGGL((k_apply<S>), dim3((B + 15) / 16, (T + 15) / 16), dim3(256), 0, st, a, f);
-    hipLaunchKernelGGL(k_flip_ran, dim3((B + 255) / 256), dim3(256), 0, st, a);
-}
+// the single-integrator systems of this file's forward pass, decision and apply pass (their launchers take no nd: it is 1)
+using WaveSys = SysList<Sys<2, 1>, Sys<0, 1>>;
+static_assert(SysAll::same_as<WaveSys>([](int kind, int nd) { return forward_wave_supported(kind, nd, 16); }), "WaveSys is forward_wave_supported");
+
 void launch_apply_wave(int kind, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f) {
-    if (kind == 2) launch_apply_wave_sys<Sys<2, 1>>(a, B, T, st, f);
-    else launch_apply_wave_sys<Sys<0, 1>>(a, B, T, st, f);
+    WaveSys::dispatch(kind, 1, [&](auto s) {
+        hipLaunchKernelGGL((k_apply<decltype(s)>), dim3((B + 15) / 16, (T + 15) / 16), dim3(256), 0, st, a, f);
+        hipLaunchKernelGGL(k_flip_ran, dim3((B + 255) / 256), dim3(256), 0, st, a);
+    });
 }
 
 template <class S, int NA>
@@ -737,8 +738,7 @@ static void launch_forward_wave_sys(bool small, const Bufs& a, int B, hipStream_
     }
 }
 void launch_forward_wave(int kind, bool small, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    if (kind == 2) launch_forward_wave_sys<Sys<2, 1>>(small, a, B, st, f);
-    else launch_forward_wave_sys<Sys<0, 1>>(small, a, B, st, f);
+    WaveSys::dispatch(kind, 1, [&](auto s) { launch_forward_wave_sys<decltype(s)>(small, a, B, st, f); });
 }
 
 }  // namespace ilqr

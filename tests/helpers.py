@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +15,17 @@ if ROOT not in sys.path:
 from oracle import oracle as orc  # noqa: E402  (tests are allowed to use the oracle)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def build_hostsim(lib):
+    """The lane-per-instance kernels and the C-ABI orchestration built with g++ into the shared library `lib`: the sources and include paths
+    of tests/tools/hostsim/build.sh, without sanitizers.  Returns `lib`."""
+    hostsim = os.path.join(ROOT, "tests", "tools", "hostsim")
+    src = os.path.join(ROOT, "ilqr_planner_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-I" + hostsim, "-I" + src, "-Wno-unused-result", "-x", "c++",
+                           os.path.join(src, "ilqr_kernels.hip"), os.path.join(src, "ilqr_capi.cpp"), os.path.join(src, "urdf_chain.cpp"),
+                           os.path.join(hostsim, "stubs.cpp"), "-o", str(lib)])
+    return str(lib)
 
 
 def urdf_text():

@@ -5,16 +5,14 @@ import os
 import subprocess
 import sys
 
+from tests.helpers import build_hostsim
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOSTSIM = os.path.join(ROOT, "tests", "tools", "hostsim")
-SRC = os.path.join(ROOT, "ilqr_planner_amd", "csrc")
 
 
 def test_closed_loop_noise_on_host_build(tmp_path):
-    lib = str(tmp_path / "libilqr_hostsim.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-I" + HOSTSIM, "-I" + SRC, "-Wno-unused-result", "-x", "c++",
-                           os.path.join(SRC, "ilqr_kernels.hip"), os.path.join(SRC, "ilqr_capi.cpp"), os.path.join(SRC, "urdf_chain.cpp"),
-                           os.path.join(HOSTSIM, "stubs.cpp"), "-o", lib])
+    lib = build_hostsim(tmp_path / "libilqr_hostsim.so")
     r = subprocess.run([sys.executable, os.path.join(HOSTSIM, "closed_loop_noise_checks.py"), lib], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
     assert r.stdout.strip().splitlines()[-1] == "closed loop noise: ok"

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+from tests.helpers import build_hostsim
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOSTSIM = os.path.join(ROOT, "tests", "tools", "hostsim")
 SRC = os.path.join(ROOT, "ilqr_planner_amd", "csrc")
@@ -21,10 +23,7 @@ def test_dofmap_table(tmp_path):
 
 
 def test_narrow_chains_on_host_build(tmp_path):
-    lib = str(tmp_path / "libilqr_hostsim.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-I" + HOSTSIM, "-I" + SRC, "-Wno-unused-result", "-x", "c++",
-                           os.path.join(SRC, "ilqr_kernels.hip"), os.path.join(SRC, "ilqr_capi.cpp"), os.path.join(SRC, "urdf_chain.cpp"),
-                           os.path.join(HOSTSIM, "stubs.cpp"), "-o", lib])
+    lib = build_hostsim(tmp_path / "libilqr_hostsim.so")
     r = subprocess.run([sys.executable, os.path.join(HOSTSIM, "narrow_chain_checks.py"), lib], capture_output=True, text=True, timeout=900,
                        cwd=ROOT)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]

@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+from tests.helpers import build_hostsim
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOSTSIM = os.path.join(ROOT, "tests", "tools", "hostsim")
 SRC = os.path.join(ROOT, "ilqr_planner_amd", "csrc")
@@ -21,16 +23,8 @@ def test_step_table(tmp_path):
     assert r.stdout.strip().splitlines()[-1] == "ok"
 
 
-def _host_build(tmp_path):
-    lib = str(tmp_path / "libilqr_hostsim.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-I" + HOSTSIM, "-I" + SRC, "-Wno-unused-result", "-x", "c++",
-                           os.path.join(SRC, "ilqr_kernels.hip"), os.path.join(SRC, "ilqr_capi.cpp"), os.path.join(SRC, "urdf_chain.cpp"),
-                           os.path.join(HOSTSIM, "stubs.cpp"), "-o", lib])
-    return lib
-
-
 def test_shared_steps_on_host_build(tmp_path):
-    lib = _host_build(tmp_path)
+    lib = build_hostsim(tmp_path / "libilqr_hostsim.so")
     r = subprocess.run([sys.executable, os.path.join(HOSTSIM, "shared_step_checks.py"), lib], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
     assert r.stdout.strip().splitlines()[-1] == "shared steps: ok"
@@ -39,7 +33,7 @@ def test_shared_steps_on_host_build(tmp_path):
 def test_mixtures_device_against_host_loop_on_host_build(tmp_path):
     """tests/cpp/shared_steps_main.cpp linked against the host build (its generic kernels; the LQT entry points refused): an object frame, a
     dead zone, a joint and two PosOrn keypoints with different targets on one step, solved through the lowering and over the virtuals."""
-    lib = _host_build(tmp_path)
+    lib = build_hostsim(tmp_path / "libilqr_hostsim.so")
     host = os.path.join(SRC, "host")
     exe = str(tmp_path / "shared_steps")
     subprocess.check_call(["g++", "-O1", "-std=c++17", os.path.join(ROOT, "tests", "cpp", "shared_steps_main.cpp"), os.path.join(host, "ilqr_host.cpp"),
