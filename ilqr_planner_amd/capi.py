@@ -19,6 +19,8 @@ SYS_POS_ORN, SYS_POS_ORN_TIME, SYS_JOINT, SYS_JOINT_TIME = 0, 1, 2, 3
 STATUS_OK, STATUS_NONFINITE, STATUS_ALPHA_FLOOR = 0, 1, 2
 LQT_MAX_NX, LQT_MAX_NU = 16, 8
 CL_STATS = 5  # mean, variance, min, max, n_bad (ILQR_CL_STATS)
+KP_ERR, KP_STATS, CL_OUTCOME = 5, 12, 4  # ILQR_KP_ERR (pos, orn, vel, angvel, time), ILQR_KP_STATS (mean[5], max[5], n_miss, n_bad), ILQR_CL_OUTCOME
+KP_ERR_POS, KP_ERR_ORN, KP_ERR_VEL, KP_ERR_ANGVEL, KP_ERR_TIME = range(5)
 PROF_ROLLOUT, PROF_BACKWARD, PROF_FORWARD, PROF_OTHER, PROF_APPLY = 0, 1, 2, 3, 4
 
 # every symbol include/ilqr_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -34,6 +36,7 @@ EXPORTS = [
     "ilqr_profile_enable", "ilqr_profile_reset", "ilqr_profile_get", "ilqr_chain_from_urdf", "ilqr_urdf_last_error",
     "ilqr_problem_reset_multipliers", "ilqr_problem_warm_start", "ilqr_problem_track", "ilqr_problem_track_dev",
     "ilqr_problem_closed_loop", "ilqr_problem_closed_loop_dev", "ilqr_problem_closed_loop_noise", "ilqr_problem_closed_loop_noise_dev",
+    "ilqr_problem_closed_loop_report", "ilqr_problem_closed_loop_report_dev",
     "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
@@ -98,7 +101,20 @@ class Noise(C.Structure):
                 ("sigma_x0", C.c_double * MAX_NX)]
 
 
+class Tol(C.Structure):
+    """Mirror of ilqr_cl_tol."""
+
+    _fields_ = [("kp_tol", (C.c_double * KP_ERR) * MAX_KP), ("lim_tol", C.c_double)]
+
+
+class Report(C.Structure):
+    """Mirror of ilqr_cl_report: four pointers (host or device), 0 / None where the output is not asked for."""
+
+    _fields_ = [("kp_err", C.c_void_p), ("kp_stats", C.c_void_p), ("lim_cost", C.c_void_p), ("outcome", C.c_void_p)]
+
+
 ClosedLoopNoise = collections.namedtuple("ClosedLoopNoise", "cost stats X U w")
+ClosedLoopReport = collections.namedtuple("ClosedLoopReport", "cost stats kp_err kp_stats lim_cost outcome X U w")
 
 _lib = None
 
@@ -144,6 +160,8 @@ def load():
     L.ilqr_problem_closed_loop_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
     L.ilqr_problem_closed_loop_noise.argtypes = [vp, C.c_int, C.POINTER(Noise), dp, C.c_int, dp, dp, dp, dp, dp]
     L.ilqr_problem_closed_loop_noise_dev.argtypes = [vp, C.c_int, C.POINTER(Noise), vp, C.c_int, vp, vp, vp, vp, vp]
+    L.ilqr_problem_closed_loop_report.argtypes = [vp, C.c_int, C.POINTER(Noise), dp, dp, C.c_int, C.POINTER(Tol), dp, dp, C.POINTER(Report)]
+    L.ilqr_problem_closed_loop_report_dev.argtypes = [vp, C.c_int, C.POINTER(Noise), vp, vp, C.c_int, C.POINTER(Tol), vp, vp, C.POINTER(Report)]
     L.ilqr_solve_recursive.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.ilqr_solve_al.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]
     L.ilqr_solve_batch_cp.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
@@ -344,7 +362,7 @@ class BatchProblem:
         self.ctx, self.L, self.desc, self.B = ctx, ctx.L, desc, int(batch)
         self.dims = Dims()
         self.L.ilqr_dims_of(C.byref(desc), C.byref(self.dims))
-        self.T = desc.horizon
+        self.T, self.n_kp = desc.horizon, int(desc.n_kp)
         self.h = C.c_void_p()
         ctx.check(self.L.ilqr_problem_create(ctx.h, C.byref(desc), self.B, C.byref(self.h)))
         ctx._problems.add(self)
@@ -530,6 +548,71 @@ class BatchProblem:
         self.ctx.check(self.L.ilqr_problem_closed_loop_noise_dev(self.h, int(samples), C.byref(noise) if noise is not None else None, x0_ptr or None,
                                                                  int(bool(with_feedforward)), cost_ptr or None, stats_ptr or None, X_ptr or None,
                                                                  U_ptr or None, w_ptr or None))
+
+    def tol(self, kp_tol=None, lim_tol=0.0):
+        """The ilqr_cl_tol of a report: kp_tol a scalar (every keypoint and group), 5 values (every keypoint) or [n_kp][5]; negative = that group
+        is not judged, None = nothing is judged.  lim_tol >= 0."""
+        t = Tol()
+        v = np.broadcast_to(np.asarray(-1.0 if kp_tol is None else kp_tol, dtype=np.float64), (self.n_kp, KP_ERR))
+        for k in range(MAX_KP):
+            for g in range(KP_ERR):
+                t.kp_tol[k][g] = v[k, g] if k < self.n_kp else -1.0
+        t.lim_tol = float(lim_tol)
+        return t
+
+    def closed_loop_report(self, samples=None, seed=None, sigma_w=None, sigma_x0=None, x0=None, w=None, with_feedforward: bool = False,
+                           kp_tol=None, lim_tol=None, instance_offset=0, sample_offset=0, want_cost: bool = True, want_stats: bool = True,
+                           want_kp_err: bool = True, want_kp_stats: bool = True, want_lim_cost: bool = True, want_outcome: bool = True,
+                           want_X: bool = False, want_U: bool = False, want_w: bool = False):
+        """The closed loop with a report of what every execution did (ilqr_problem_closed_loop_report; definitions in include/ilqr_hip.h):
+        kp_err [B][S][n_kp][5] (pos, orn, vel, angvel, time), kp_stats [B][n_kp][12] (mean[5], max[5], n_miss, n_bad), lim_cost [B][S] and
+        outcome [B][4] (n_ok, n_miss, n_lim, n_bad).  seed given: the draw of closed_loop_noise (x0 its centre); w given: the caller's
+        disturbances; neither: none.  kp_tol: see tol(); with kp_tol and lim_tol both None no tolerance is passed and the two reductions are
+        not asked for.  X, U, w are not outputs of the C call: where they are wanted they come from closed_loop_noise / closed_loop with the same
+        inputs, which run the same rollout bit for bit.  Returns a ClosedLoopReport; what was not asked for is None."""
+        S = samples
+        for arr in (x0, w):
+            if S is None and arr is not None:
+                S = np.shape(arr)[1]
+        S = 1 if S is None else int(S)
+        n = max(S, 0)
+        x0 = _f64(x0, (self.B, n, self.dims.n_x)) if x0 is not None else None
+        w = _f64(w, (self.B, n, self.T - 1, self.dims.n_x)) if w is not None else None
+        nz = self.noise(seed, sigma_w, sigma_x0, instance_offset, sample_offset) if seed is not None else None
+        judged = kp_tol is not None or lim_tol is not None
+        tol = self.tol(kp_tol, 0.0 if lim_tol is None else lim_tol) if judged else None
+        cost = np.empty((self.B, n)) if want_cost else None
+        stats = np.empty((self.B, CL_STATS)) if want_stats else None
+        kp_err = np.empty((self.B, n, self.n_kp, KP_ERR)) if want_kp_err else None
+        kp_stats = np.empty((self.B, self.n_kp, KP_STATS)) if want_kp_stats and judged else None
+        lim_cost = np.empty((self.B, n)) if want_lim_cost else None
+        outcome = np.empty((self.B, CL_OUTCOME)) if want_outcome and judged else None
+        rp = Report(*(a.ctypes.data if a is not None else None for a in (kp_err, kp_stats, lim_cost, outcome)))
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_report(self.h, S, C.byref(nz) if nz is not None else None, _dp(x0), _dp(w),
+                                                              int(bool(with_feedforward)), C.byref(tol) if tol is not None else None, _dp(cost),
+                                                              _dp(stats), C.byref(rp)))
+        X = U = wo = None
+        if want_X or want_U or want_w:
+            if nz is not None:
+                r = self.closed_loop_noise(S, seed, sigma_w, sigma_x0, x0, with_feedforward, instance_offset, sample_offset, want_stats=False,
+                                           want_X=want_X, want_U=want_U, want_w=want_w)
+                X, U, wo = r.X, r.U, r.w
+            else:
+                _, X, U = self.closed_loop(x0, w, S, with_feedforward, want_X=want_X, want_U=want_U)
+                wo = w if want_w else None
+        return ClosedLoopReport(cost, stats, kp_err, kp_stats, lim_cost, outcome, X, U, wo)
+
+    def closed_loop_report_dev(self, samples: int, noise, x0_ptr, w_ptr, with_feedforward: bool, tol, cost_ptr=None, stats_ptr=None,
+                               kp_err_ptr=None, kp_stats_ptr=None, lim_cost_ptr=None, outcome_ptr=None):
+        """Device pointers (0 / None where ilqr_problem_closed_loop_report takes NULL), asynchronous on the context's stream; noise: self.noise(..)
+        or None, tol: self.tol(..) or None."""
+        rp = Report(kp_err_ptr or None, kp_stats_ptr or None, lim_cost_ptr or None, outcome_ptr or None)
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_report_dev(self.h, int(samples), C.byref(noise) if noise is not None else None,
+                                                                  x0_ptr or None, w_ptr or None, int(bool(with_feedforward)),
+                                                                  C.byref(tol) if tol is not None else None, cost_ptr or None, stats_ptr or None,
+                                                                  C.byref(rp)))
 
     def close(self):
         if self.h:

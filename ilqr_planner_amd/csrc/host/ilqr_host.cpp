@@ -1495,6 +1495,25 @@ BatchResult ILQRRecursive::solveBatch(const BatchInputs& in, int nb_iter, bool l
     return run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) { check(ilqr_solve_recursive(p, nb_iter, line_search, early_stop)); }, nullptr);
 }
 
+// ilqr_problem_closed_loop_report for the same executions: the rollout is repeated (same inputs, same bits), so that what closed_loop_of
+// returns without tolerances stays exactly what it was
+static void closed_loop_report_of(ilqr_problem* p, sys::System& s, int B, const ClosedLoopInputs& cl, const ilqr_noise* nz, ClosedLoopResult& o) {
+    o.n_kp = (int)s.deviceKeypoints().size();
+    const size_t n = (size_t)B * cl.S, nk = (size_t)o.n_kp;
+    ilqr_cl_tol tol{};
+    const size_t nt = cl.kp_tol.size();
+    if (nt > 1 && nt != ILQR_KP_ERR && nt != nk * ILQR_KP_ERR)
+        throw std::runtime_error("[closed_loop_batch] kp_tol must be a scalar, have 5 entries or be nb_keypoints x 5");
+    for (size_t k = 0; k < ILQR_MAX_KP; k++)
+        for (size_t g = 0; g < ILQR_KP_ERR; g++)
+            tol.kp_tol[k][g] = (k >= nk || nt == 0) ? -1.0 : (nt == 1 ? cl.kp_tol[0] : (nt == ILQR_KP_ERR ? cl.kp_tol[g] : cl.kp_tol[k * ILQR_KP_ERR + g]));
+    tol.lim_tol = cl.lim_tol;
+    o.kp_err.resize(n * nk * ILQR_KP_ERR); o.kp_stats.resize((size_t)B * nk * ILQR_KP_STATS); o.lim_cost.resize(n); o.outcome.resize((size_t)B * ILQR_CL_OUTCOME);
+    ilqr_cl_report rp{o.kp_err.data(), o.kp_stats.data(), o.lim_cost.data(), o.outcome.data()};
+    check(ilqr_problem_closed_loop_report(p, cl.S, nz, cl.x0.empty() ? nullptr : cl.x0.data(), cl.w.empty() ? nullptr : cl.w.data(), cl.with_feedforward ? 1 : 0,
+                                          &tol, nullptr, nullptr, &rp));
+}
+
 // ilqr_problem_closed_loop on the problem a batched solve has just finished with
 static void closed_loop_of(ilqr_problem* p, sys::System& s, int B, const ClosedLoopInputs& cl, ClosedLoopResult& o) {
     o.B = B; o.S = cl.S; o.T = s.getHorizon(); o.n_x = s.getNbStateVar(); o.n_u = s.getNbCtrlVar();
@@ -1515,6 +1534,7 @@ static void closed_loop_of(ilqr_problem* p, sys::System& s, int B, const ClosedL
         }
         check(ilqr_problem_closed_loop_noise(p, cl.S, &nz, cl.x0.empty() ? nullptr : cl.x0.data(), cl.with_feedforward ? 1 : 0, o.cost.data(), o.stats.data(),
                                              o.X.data(), o.U.data(), nullptr));
+        if (cl.has_tol) closed_loop_report_of(p, s, B, cl, &nz, o);
         return;
     }
     check(ilqr_problem_closed_loop(p, cl.S, cl.x0.empty() ? nullptr : cl.x0.data(), cl.w.empty() ? nullptr : cl.w.data(), cl.with_feedforward ? 1 : 0,
@@ -1533,6 +1553,7 @@ static void closed_loop_of(ilqr_problem* p, sys::System& s, int B, const ClosedL
         double* st = o.stats.data() + (size_t)b * ILQR_CL_STATS;
         st[0] = nf ? mean : NAN; st[1] = nf > 1 ? ss / (nf - 1) : (nf ? 0.0 : NAN); st[2] = nf ? lo : NAN; st[3] = nf ? hi : NAN; st[4] = cl.S - nf;
     }
+    if (cl.has_tol) closed_loop_report_of(p, s, B, cl, nullptr, o);
 }
 
 std::pair<BatchResult, ClosedLoopResult> ILQRRecursive::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool line_search,

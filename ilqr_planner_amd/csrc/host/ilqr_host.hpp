@@ -482,11 +482,19 @@ struct ClosedLoopInputs {
     bool has_seed = false;
     unsigned long long seed = 0;
     std::vector<double> sigma_w, sigma_x0;   // one value (every entry) or n_x values; empty: 0
+    // tolerances given: the executions are also reported on (ilqr_problem_closed_loop_report, the definitions of include/ilqr_hip.h)
+    bool has_tol = false;
+    std::vector<double> kp_tol;   // one value (every keypoint and group), ILQR_KP_ERR values (every keypoint) or n_kp x ILQR_KP_ERR; negative: not
+                                  // judged; empty: nothing is judged
+    double lim_tol = 0;
 };
 struct ClosedLoopResult {
     int B = 0, S = 0, T = 0, n_x = 0, n_u = 0;
     std::vector<double> cost, X, U;  // [B][S], [B][S][T][n_x], [B][S][T-1][n_u]
     std::vector<double> stats;       // [B][5]: mean, unbiased variance, min, max of the finite costs in sample order, and the number that are not finite
+    // with tolerances (ClosedLoopInputs::has_tol), else empty: [B][S][n_kp][5], [B][n_kp][12], [B][S], [B][4]
+    int n_kp = 0;
+    std::vector<double> kp_err, kp_stats, lim_cost, outcome;
 };
 
 struct Constraint {  // AL-ILQR.h:20-23

@@ -97,9 +97,19 @@ static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& 
 // numpy -> ClosedLoopInputs: x0 [B][S][n_x] or None, w [B][S][T-1][n_x] or None; samples: S where neither array gives it
 static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const py::object& w, const py::object& samples, bool with_ff,
                                                    const py::object& seed = py::none(), const py::object& sigma_w = py::none(),
-                                                   const py::object& sigma_x0 = py::none()) {
+                                                   const py::object& sigma_x0 = py::none(), const py::object& kp_tol = py::none(),
+                                                   const py::object& lim_tol = py::none()) {
     solver::ClosedLoopInputs cl;
     cl.with_feedforward = with_ff;
+    if (!kp_tol.is_none() || !lim_tol.is_none()) {  // either one asks for the report
+        cl.has_tol = true;
+        if (!kp_tol.is_none()) {
+            arr_t a = arr_t::ensure(kp_tol);
+            if (!a || a.ndim() > 2) throw std::runtime_error("[closed_loop_batch] kp_tol must be a scalar, have 5 entries or be nb_keypoints x 5");
+            cl.kp_tol.assign(a.data(), a.data() + a.size());
+        }
+        cl.lim_tol = lim_tol.is_none() ? 0.0 : lim_tol.cast<double>();
+    }
     if (!seed.is_none()) {
         if (!w.is_none()) throw std::runtime_error("[closed_loop_batch] give either w or seed (with seed the disturbances are drawn on the device), not both");
         cl.has_seed = true;
@@ -310,7 +320,16 @@ PYBIND11_MODULE(PyLQR, m) {
         .def_property_readonly("cost", [](const solver::ClosedLoopResult& r) { return shaped(r.cost, {r.B, r.S}); })
         .def_property_readonly("X", [](const solver::ClosedLoopResult& r) { return shaped(r.X, {r.B, r.S, r.T, r.n_x}); })
         .def_property_readonly("U", [](const solver::ClosedLoopResult& r) { return shaped(r.U, {r.B, r.S, r.T - 1, r.n_u}); })
-        .def_property_readonly("stats", [](const solver::ClosedLoopResult& r) { return shaped(r.stats, {r.B, ILQR_CL_STATS}); });
+        .def_property_readonly("stats", [](const solver::ClosedLoopResult& r) { return shaped(r.stats, {r.B, ILQR_CL_STATS}); })
+        // filled when closed_loop_batch is given kp_tol or lim_tol, else None
+        .def_property_readonly("kp_err", [](const solver::ClosedLoopResult& r) -> py::object {
+            return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.kp_err, {r.B, r.S, r.n_kp, ILQR_KP_ERR})); })
+        .def_property_readonly("kp_stats", [](const solver::ClosedLoopResult& r) -> py::object {
+            return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.kp_stats, {r.B, r.n_kp, ILQR_KP_STATS})); })
+        .def_property_readonly("lim_cost", [](const solver::ClosedLoopResult& r) -> py::object {
+            return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.lim_cost, {r.B, r.S})); })
+        .def_property_readonly("outcome", [](const solver::ClosedLoopResult& r) -> py::object {
+            return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.outcome, {r.B, ILQR_CL_OUTCOME})); });
     py::class_<solver::Constraint>(m_sol, "Constraint").def(py::init<>()).def_readwrite("A", &solver::Constraint::A).def_readwrite("b", &solver::Constraint::b);
     py::class_<solver::ILQRRecursive>(m_sol, "ILQRRecursive")
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
@@ -324,12 +343,13 @@ PYBIND11_MODULE(PyLQR, m) {
         .def("closed_loop_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
                 const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
-                const py::object& sigma_x0) {
-                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0), nb_iter, ls, es);
+                const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol) {
+                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol), nb_iter,
+                                             ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
              py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(), py::arg("w") = py::none(), py::arg("with_feedforward") = false,
-             py::arg("samples") = py::none(), py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none());
+             py::arg("samples") = py::none(), py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none());
     py::class_<solver::AL_ILQR>(m_sol, "AL_ILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const std::vector<solver::Constraint>&, const std::vector<Vec>&>(), py::arg("s"), py::arg("inequality"),
              py::arg("initLambda"))
@@ -343,14 +363,14 @@ PYBIND11_MODULE(PyLQR, m) {
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
                 const py::object& kp, const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed,
-                const py::object& sigma_w, const py::object& sigma_x0) {
-                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0), nb_iter, lag, pen, sc, ls,
-                                             es);
+                const py::object& sigma_w, const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol) {
+                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol), nb_iter,
+                                             lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(),
              py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none(), py::arg("seed") = py::none(),
-             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none());
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none());
     // bindings.cpp:778-782
     py::class_<solver::BatchILQR>(m_sol, "BatchILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("Q"))

@@ -52,6 +52,8 @@ struct ilqr_problem {
     size_t cl_cost_elems = 0;
     double* cl_kpx = nullptr;  // closed_loop: state | control of every sample at the step-table entries (k_closed_loop_coop -> k_closed_loop_kp)
     size_t cl_kpx_elems = 0;
+    double* cl_rep = nullptr;  // closed_loop_report through device pointers: kp_err | lim_cost where the caller asks only for their reductions
+    size_t cl_rep_elems = 0;
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
     BatchCPState cp;
     BatchWideState cpw;
@@ -456,6 +458,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     for (void* q : p->allocs) (void)hipFree(q);
     if (p->staging) (void)hipFree(p->staging);
     if (p->cl_kpx) (void)hipFree(p->cl_kpx);
+    if (p->cl_rep) (void)hipFree(p->cl_rep);
     if (p->cl_cost) (void)hipFree(p->cl_cost);
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
@@ -943,8 +946,11 @@ extern "C" int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_me
 // Closed loop of the tracking law on the last plan (ilqr_closed_loop.hpp): n_samples executions per instance.  Which kernel runs is decided by
 // plan_closed_loop; chains of fewer than 7 joints take the generic kernel's mapped variant.
 // nz: ilqr_problem_closed_loop_noise (noisy) -- the draws of ilqr_noise.hpp in place of w, and stats / w_out.
+// report: ilqr_problem_closed_loop_report -- the same rollout with the states of the step-table entries and the limit share kept (ClArgs::kpx,
+// lim_cost), then k_closed_loop_kp_err and the two reductions; cost may be null, and noisy is "a noise was given".
 static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w, int with_ff, double* cost, double* X, double* U, bool dev,
-                       bool noisy = false, const ilqr_noise* nz = nullptr, double* stats = nullptr, double* w_out = nullptr) {
+                       bool noisy = false, const ilqr_noise* nz = nullptr, double* stats = nullptr, double* w_out = nullptr, bool report = false,
+                       const ilqr_cl_tol* tol = nullptr, const ilqr_cl_report* out = nullptr) {
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
     if (!p->has_gains)
@@ -956,24 +962,40 @@ static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w
         for (int i = 0; i < nxu; i++)
             if (!(nz->sigma_w[i] >= 0) || !std::isfinite(nz->sigma_w[i]) || !(nz->sigma_x0[i] >= 0) || !std::isfinite(nz->sigma_x0[i]))
                 return fail(c, "closed loop: every sigma_w and sigma_x0 must be finite and >= 0");
-        if (!cost && !stats) return fail(c, "cost and stats are both null pointers");
+        if (!report && !cost && !stats) return fail(c, "cost and stats are both null pointers");
         if ((unsigned long long)nz->instance_offset + (unsigned long long)p->B > (1ull << 32) ||
             (unsigned long long)nz->sample_offset + (unsigned long long)S > (1ull << 32))
             return fail(c, "closed loop: instance_offset + B or sample_offset + n_samples exceeds 2^32 (the generator's counter)");
-    } else if (!cost) return fail(c, "cost is a null pointer");
+    } else if (!report && !cost) return fail(c, "cost is a null pointer");
+    const int n_kp = p->hdesc.steps.kp[p->hdesc.steps.n];
+    ilqr_cl_report rp = {};
+    if (report) {
+        if (noisy && w) return fail(c, "closed loop report: noise and w are both given (the draw or the caller's disturbances, not both)");
+        if (!out || (!out->kp_err && !out->kp_stats && !out->lim_cost && !out->outcome))
+            return fail(c, "closed loop report: every report output is a null pointer");
+        rp = *out;
+        if (tol) {
+            bool nan = std::isnan(tol->lim_tol);
+            for (int k = 0; k < n_kp; k++)
+                for (int g = 0; g < ILQR_KP_ERR; g++) nan = nan || std::isnan(tol->kp_tol[k][g]);
+            if (nan) return fail(c, "closed loop report: a tolerance is NaN");
+            if (tol->lim_tol < 0) return fail(c, "closed loop report: lim_tol must be >= 0");
+        } else if (rp.kp_stats || rp.outcome)
+            return fail(c, "closed loop report: tol is a null pointer while kp_stats or outcome is asked for");
+    }
     const size_t n = (size_t)p->B * S;
     const size_t n_x0 = x0 ? n * nxu : 0, n_w = w ? n * (T - 1) * nxu : 0, n_X = X ? n * T * nxu : 0, n_U = U ? n * (T - 1) * nuu : 0;
     const size_t n_wo = w_out ? n * (T - 1) * nxu : 0, n_st = stats ? (size_t)p->B * ILQR_CL_STATS : 0;
     // the kernels address the caller's arrays with 32-bit element offsets
-    if (noisy && !X && !U && !w_out) {  // no per-step array: x0 and cost are the longest
+    if ((noisy || report) && !X && !U && !w_out && !w) {  // no per-step array: x0 and cost are the longest
         if (n * (size_t)nxu >= ((size_t)1 << 31))
             return fail(c, "closed loop: B * n_samples * n_x overflows the kernels' 32-bit offsets (split the samples over several calls)");
     } else if (n * T * (size_t)(nxu > nuu ? nxu : nuu) >= ((size_t)1 << 31))
         return fail(c, "closed loop: B * n_samples * T * n_x overflows the kernels' 32-bit offsets (split the samples over several calls)");
     HIPCHK(c, hipSetDevice(c->device));
     const ClosedLoopPlan pl = plan_closed_loop(p->desc.kind, p->desc.nb_deriv, S, p->B, c->n_simd, c->xc_generic || p->mapped);
-    if (pl.coop) {
-        if (!launch_closed_loop_coop) return fail(c, "closed loop: the cooperative kernels are not part of this build (pin the generic kernels)");
+    if (pl.coop && !launch_closed_loop_coop) return fail(c, "closed loop: the cooperative kernels are not part of this build (pin the generic kernels)");
+    if (pl.coop || report) {  // the report reads the states of the step-table entries from either kernel
         const size_t need = (size_t)(p->hdesc.steps.n > 0 ? p->hdesc.steps.n : 1) * (p->dims.n_x + p->dims.n_u) * n;
         if (p->cl_kpx_elems < need) {
             if (p->cl_kpx) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p->cl_kpx)); p->cl_kpx = nullptr; p->cl_kpx_elems = 0; }
@@ -996,8 +1018,23 @@ static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w
         }
         a.cost = p->cl_cost;
     }
-    if (!dev) {  // staging: x0 | w | cost | X | U | w_out | stats
-        if (ensure_staging(p, n_x0 + n_w + n + n_X + n_U + n_wo + n_st)) return 1;
+    // report: kp_err feeds both reductions, lim_cost the outcome; what the caller does not ask for itself lives in a workspace
+    const bool want_ke = rp.kp_err || rp.kp_stats || rp.outcome, want_lc = rp.lim_cost || rp.outcome;
+    const size_t n_ke = want_ke ? n * n_kp * ILQR_KP_ERR : 0, n_lc = want_lc ? n : 0;
+    const size_t n_ks = rp.kp_stats ? (size_t)p->B * n_kp * ILQR_KP_STATS : 0, n_oc = rp.outcome ? (size_t)p->B * ILQR_CL_OUTCOME : 0;
+    ilqr_cl_report dr = rp;  // the device side of the four outputs
+    if (report && dev) {
+        const size_t ws_ke = rp.kp_err ? 0 : n_ke, ws_lc = rp.lim_cost ? 0 : n_lc;
+        if (p->cl_rep_elems < ws_ke + ws_lc) {
+            if (p->cl_rep) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p->cl_rep)); p->cl_rep = nullptr; p->cl_rep_elems = 0; }
+            HIPCHK(c, hipMalloc((void**)&p->cl_rep, (ws_ke + ws_lc) * sizeof(double)));
+            p->cl_rep_elems = ws_ke + ws_lc;
+        }
+        if (!rp.kp_err) dr.kp_err = p->cl_rep;
+        if (!rp.lim_cost) dr.lim_cost = p->cl_rep + ws_ke;
+    }
+    if (!dev) {  // staging: x0 | w | cost | X | U | w_out | stats | kp_err | lim_cost | kp_stats | outcome
+        if (ensure_staging(p, n_x0 + n_w + n + n_X + n_U + n_wo + n_st + n_ke + n_lc + n_ks + n_oc)) return 1;
         double* s = p->staging;
         if (x0) { HIPCHK(c, hipMemcpyAsync(s, x0, n_x0 * sizeof(double), hipMemcpyHostToDevice, c->stream)); a.x0 = s; }
         s += n_x0;
@@ -1011,10 +1048,21 @@ static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w
         if (w_out) a.w_out = s;
         s += n_wo;
         if (stats) dstats = s;
+        s += n_st;
+        dr.kp_err = s; s += n_ke;
+        dr.lim_cost = s; s += n_lc;
+        dr.kp_stats = s; s += n_ks;
+        dr.outcome = s;
     }
+    if (report) { a.kpx = pl.coop ? nullptr : p->cl_kpx; a.lim_cost = want_lc ? dr.lim_cost : nullptr; }
     if (pl.coop) launch_closed_loop_coop(p->desc.kind, p->desc.nb_deriv, p->bufs, a, p->B, pl, p->cl_kpx, c->stream);
     else launch_closed_loop(p->desc.kind, p->desc.nb_deriv, p->bufs, a, p->B, p->mapped ? &p->map : nullptr, c->stream);
     if (stats) launch_closed_loop_stats(a.cost, p->B, S, dstats, c->stream);
+    if (report) {
+        if (want_ke) launch_closed_loop_kp_err(p->desc.kind, p->desc.nb_deriv, p->bufs, p->B, S, n_kp, p->cl_kpx, dr.kp_err, c->stream);
+        if (rp.kp_stats) launch_closed_loop_kp_stats(dr.kp_err, *tol, p->B, S, n_kp, dr.kp_stats, c->stream);
+        if (rp.outcome) launch_closed_loop_outcome(a.cost, dr.kp_err, dr.lim_cost, *tol, p->B, S, n_kp, dr.outcome, c->stream);
+    }
     HIPCHK(c, hipGetLastError());
     if (!dev) {
         if (cost) HIPCHK(c, hipMemcpyAsync(cost, a.cost, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1022,6 +1070,10 @@ static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w
         if (w_out) HIPCHK(c, hipMemcpyAsync(w_out, a.w_out, n_wo * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, n_X * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (U) HIPCHK(c, hipMemcpyAsync(U, a.U, n_U * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (rp.kp_err && n_ke) HIPCHK(c, hipMemcpyAsync(rp.kp_err, dr.kp_err, n_ke * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (rp.lim_cost) HIPCHK(c, hipMemcpyAsync(rp.lim_cost, dr.lim_cost, n_lc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (rp.kp_stats && n_ks) HIPCHK(c, hipMemcpyAsync(rp.kp_stats, dr.kp_stats, n_ks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (rp.outcome) HIPCHK(c, hipMemcpyAsync(rp.outcome, dr.outcome, n_oc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return 0;
@@ -1042,6 +1094,15 @@ extern "C" int ilqr_problem_closed_loop_noise(ilqr_problem* p, int n_samples, co
 extern "C" int ilqr_problem_closed_loop_noise_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, int with_feedforward,
                                                   double* cost, double* stats, double* X, double* U, double* w_out) {
     return closed_loop(p, n_samples, x0, nullptr, with_feedforward, cost, X, U, true, true, noise, stats, w_out);
+}
+
+extern "C" int ilqr_problem_closed_loop_report(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
+                                               int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out) {
+    return closed_loop(p, n_samples, x0, w, with_feedforward, cost, nullptr, nullptr, false, noise != nullptr, noise, stats, nullptr, true, tol, out);
+}
+extern "C" int ilqr_problem_closed_loop_report_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
+                                                   int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out) {
+    return closed_loop(p, n_samples, x0, w, with_feedforward, cost, nullptr, nullptr, true, noise != nullptr, noise, stats, nullptr, true, tol, out);
 }
 
 extern "C" int ilqr_problem_get_K(ilqr_problem* p, double* K) { return get_gains(p, K, nullptr); }

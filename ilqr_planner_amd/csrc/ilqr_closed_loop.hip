@@ -106,6 +106,7 @@ __global__ __launch_bounds__(64) void k_closed_loop_coop(Bufs a, ClArgs c, int d
         UNR for (int i = 0; i < NX; i++) o[(size_t)i * BS] = x[i];
         UNR for (int i = 0; i < NU; i++) o[(size_t)(NX + i) * BS] = 0.0;
     }
+    if (c.lim_cost) c.lim_cost[g] = lim;  // uniform: only the report asks
     c.cost[g] = lim;
 }
 

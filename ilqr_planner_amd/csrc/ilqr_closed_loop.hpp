@@ -28,6 +28,10 @@ struct ClArgs {
     unsigned int b_off = 0, s_off = 0;      // global index of this call's first instance / sample
     double sigma_w[ILQR_MAX_NX] = {}, sigma_x0[ILQR_MAX_NX] = {};   // user's state layout; 0: no draw for the entry
     double* w_out = nullptr;                // [B][S][T-1][n_x] or null: the disturbance every step added
+    // ilqr_problem_closed_loop_report: both null in every other call
+    double* kpx = nullptr;                  // generic kernel: the state at every step-table entry, in the cooperative kernel's layout
+                                            // [steps.n][n_x + n_u][B * S] (the x rows only); the cooperative kernel has its own argument
+    double* lim_cost = nullptr;             // [B][S]: the limit terms of the execution, summed over the steps
 };
 
 // x_{k+1} += w_k: the caller's w, the draw (nz, on: noise_draw), or both; w_out gets what was added (0 where nothing was).  An entry without
@@ -82,10 +86,28 @@ ILQR_DEV double cl_kp_terms(const DevDesc& d, const Bufs& a, int b, int st, cons
     return acc;
 }
 
+// report: the state of pair g at step-table entry st into c.kpx, the rows the cooperative kernel stores its state in
+template <int NX, int NU>
+ILQR_DEV void cl_store_kpx(const ClArgs& c, const DevDesc& d, int st, int g, const double* x) {
+    const size_t BS = (size_t)d.B * c.S;
+    double* o = c.kpx + (size_t)st * (NX + NU) * BS + g;
+    UNR for (int i = 0; i < NX; i++) o[(size_t)i * BS] = x[i];
+}
+
 // generic kernel (ilqr_kernels.hip); m: the maps of a chain of fewer than 7 joints, or null
 void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const DofMap* m, hipStream_t st);
 // cooperative kernels (ilqr_closed_loop.hip), 7-joint layouts only; kpx: [steps.n][n_x + n_u][B * S] workspace.  A weak declaration: the host
 // builds of the generic kernel set link without that file, and a launch that needs it there is an error (closed_loop, ilqr_capi.cpp).
 __attribute__((weak)) void launch_closed_loop_coop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const ClosedLoopPlan& pl, double* kpx, hipStream_t st);
+
+
+// ilqr_problem_closed_loop_report (ilqr_kernels.hip), after either rollout.  kpx: the workspace above, filled by the rollout.
+// k_closed_loop_kp_err: kp_err[B][S][n_kp][ILQR_KP_ERR] of the states in kpx
+void launch_closed_loop_kp_err(int kind, int nd, const Bufs& a, int B, int S, int n_kp, const double* kpx, double* kp_err, hipStream_t st);
+// k_closed_loop_kp_stats: kp_stats[B][n_kp][ILQR_KP_STATS] of kp_err (tol travels as a kernel argument)
+void launch_closed_loop_kp_stats(const double* kp_err, const ilqr_cl_tol& tol, int B, int S, int n_kp, double* kp_stats, hipStream_t st);
+// k_closed_loop_outcome: outcome[B][ILQR_CL_OUTCOME] of cost, kp_err and lim_cost
+void launch_closed_loop_outcome(const double* cost, const double* kp_err, const double* lim_cost, const ilqr_cl_tol& tol, int B, int S, int n_kp,
+                                double* outcome, hipStream_t st);
 
 }  // namespace ilqr

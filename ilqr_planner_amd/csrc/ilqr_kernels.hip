@@ -704,7 +704,11 @@ __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap m
             UNR for (int i = 0; i < NU; i++) { const int iu = MAP ? mu.usr[i] : i; if (iu >= 0) c.U[(g * (T - 1) + k) * nuu + iu] = u[i]; }
         }
         lim += cl_limits<S>(d, x);
-        if (st < d.steps.n && d.steps.t[st] == k) { kpc = cl_kp_terms<S>(d, a, b, st, x, u, kpc); st++; }
+        if (st < d.steps.n && d.steps.t[st] == k) {
+            if (c.kpx) cl_store_kpx<NX, NU>(c, d, st, g, x);  // uniform: only the report asks
+            kpc = cl_kp_terms<S>(d, a, b, st, x, u, kpc);
+            st++;
+        }
         // the draw of this step: behind the keypoint terms, so that it is not live across FK; it depends on no state and fills dyn_step's latency
         double nz[NX];
         unsigned on = 0;
@@ -723,9 +727,120 @@ __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap m
     if (st < d.steps.n && d.steps.t[st] == T - 1) {
         double zu[NU];
         UNR for (int i = 0; i < NU; i++) zu[i] = 0;
+        if (c.kpx) cl_store_kpx<NX, NU>(c, d, st, g, x);
         kpc = cl_kp_terms<S>(d, a, b, st, x, zu, kpc);
     }
+    if (c.lim_cost) c.lim_cost[g] = lim;
     c.cost[g] = lim + kpc;
+}
+
+// ---- ilqr_problem_closed_loop_report: what the executions did at the keypoints and against the limits (definitions: include/ilqr_hip.h)
+
+ILQR_DEV double cl_norm3(const double* e) { return sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]); }
+
+// The five errors of every (pair g = b * S + s, keypoint): one lane per (g, keypoint), g fastest (blockIdx.y = keypoint), so the reads of
+// kpx -- [steps.n][n_x + n_u][B * S], the states either rollout stored -- coalesce.  The residual is kp_cost's: fx_of through the keypoint's
+// frame, then kp_diff (a joint keypoint: target - x); no dead zone.  Device layout: the padded entries of a chain of fewer than 7 joints
+// are 0 in the state and in the target and contribute 0.  Serves both rollouts, so their reports agree by construction.
+template <class S>
+__global__ __launch_bounds__(64) void k_closed_loop_kp_err(Bufs a, int n_samples, const double* __restrict__ kpx, double* __restrict__ kp_err) {
+    constexpr int NX = S::NX, NU = S::NU;
+    const DevDesc& d = *a.desc;
+    const size_t BS = (size_t)d.B * n_samples;
+    const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const int kpi = blockIdx.y, n_kp = d.steps.kp[d.steps.n];
+    if (g >= BS || kpi >= n_kp) return;
+    const int b = (int)(g / (size_t)n_samples), Bp = d.Bp;
+    int st = 0;  // the step-table entry that holds keypoint kpi
+    while (st + 1 < d.steps.n && d.steps.kp[st + 1] <= kpi) st++;
+    const double* o = kpx + (size_t)st * (NX + NU) * BS + g;
+    double x[NX], tg[S::NF];
+    UNR for (int i = 0; i < NX; i++) x[i] = o[(size_t)i * BS];
+    UNR for (int i = 0; i < S::NF; i++) tg[i] = AT(a.kp_tg, kpi * S::NF + i, b);
+    double err[ILQR_KP_ERR] = {0, 0, 0, 0, 0};
+    if (!S::JOINT && S::ND == 1 && d.kp_joint[kpi]) {  // joint-space keypoint of a hybrid sequence: e = target - x (kp_cost)
+        double ss = 0;
+        UNR for (int i = 0; i < DOF; i++) ss += (tg[i] - x[i]) * (tg[i] - x[i]);
+        err[ILQR_KP_ERR_POS] = sqrt(ss);
+        if (S::TM) err[ILQR_KP_ERR_TIME] = fabs(tg[NX - 1] - x[NX - 1]);
+    } else {
+        double fxv[S::NF], e[S::NQ];
+        fx_of<S, false>(d, x, fxv, nullptr, kpi);
+        kp_diff<S>(tg, fxv, e);
+        if (S::JOINT) {
+            double ss = 0;
+            UNR for (int i = 0; i < DOF; i++) ss += e[i] * e[i];
+            err[ILQR_KP_ERR_POS] = sqrt(ss);
+        } else {
+            err[ILQR_KP_ERR_POS] = cl_norm3(e);
+            err[ILQR_KP_ERR_ORN] = cl_norm3(e + 3);
+            if (S::ND == 2) {
+                err[ILQR_KP_ERR_VEL] = cl_norm3(e + 6);
+                err[ILQR_KP_ERR_ANGVEL] = cl_norm3(e + 9);
+            }
+        }
+        if (S::TM) err[ILQR_KP_ERR_TIME] = fabs(e[S::NQ - 1]);
+    }
+    double* out = kp_err + (g * (size_t)n_kp + kpi) * ILQR_KP_ERR;
+    UNR for (int j = 0; j < ILQR_KP_ERR; j++) out[j] = err[j];
+}
+
+// an execution with errors err[ILQR_KP_ERR] misses the keypoint whose tolerances are tol[ILQR_KP_ERR]: strict, a negative tolerance is not judged
+ILQR_DEV bool cl_kp_miss(const double* err, const double* tol) {
+    bool m = false;
+    UNR for (int j = 0; j < ILQR_KP_ERR; j++) m = m || (!(tol[j] < 0) && err[j] > tol[j]);
+    return m;
+}
+
+// kp_stats[b][k] = { mean[5], max[5], n_miss, n_bad } of kp_err[b][0 .. S-1][k]: one lane per (instance, keypoint) over the samples in sample
+// order (blockIdx.y = keypoint), like k_closed_loop_stats and for its reason: the sums do not depend on the batch size or on the kernel pin.
+__global__ __launch_bounds__(64) void k_closed_loop_kp_stats(const double* __restrict__ kp_err, ilqr_cl_tol tol, int B, int S, int n_kp,
+                                                            double* __restrict__ kp_stats) {
+    const int b = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y;
+    if (b >= B || k >= n_kp) return;
+    double sum[ILQR_KP_ERR], hi[ILQR_KP_ERR], tk[ILQR_KP_ERR];
+    UNR for (int j = 0; j < ILQR_KP_ERR; j++) { sum[j] = 0; hi[j] = -INFINITY; tk[j] = tol.kp_tol[k][j]; }
+    int n = 0, n_miss = 0;
+    for (int s = 0; s < S; s++) {
+        const double* e = kp_err + (((size_t)b * S + s) * n_kp + k) * ILQR_KP_ERR;
+        double v[ILQR_KP_ERR];
+        bool good = true;
+        UNR for (int j = 0; j < ILQR_KP_ERR; j++) { v[j] = e[j]; good = good && isfinite(v[j]); }
+        if (!good) continue;
+        n++;
+        UNR for (int j = 0; j < ILQR_KP_ERR; j++) { sum[j] += v[j]; hi[j] = v[j] > hi[j] ? v[j] : hi[j]; }
+        if (cl_kp_miss(v, tk)) n_miss++;
+    }
+    double* o = kp_stats + ((size_t)b * n_kp + k) * ILQR_KP_STATS;
+    UNR for (int j = 0; j < ILQR_KP_ERR; j++) { o[j] = n ? sum[j] / n : NAN; o[ILQR_KP_ERR + j] = n ? hi[j] : NAN; }
+    o[2 * ILQR_KP_ERR] = (double)n_miss;
+    o[2 * ILQR_KP_ERR + 1] = (double)(S - n);
+}
+
+// outcome[b] = { n_ok, n_miss, n_lim, n_bad }: one lane per instance over its samples
+__global__ __launch_bounds__(64) void k_closed_loop_outcome(const double* __restrict__ cost, const double* __restrict__ kp_err,
+                                                           const double* __restrict__ lim_cost, ilqr_cl_tol tol, int B, int S, int n_kp,
+                                                           double* __restrict__ outcome) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    int n_ok = 0, n_miss = 0, n_lim = 0, n_bad = 0;
+    for (int s = 0; s < S; s++) {
+        const size_t g = (size_t)b * S + s;
+        if (!isfinite(cost[g])) { n_bad++; continue; }
+        bool miss = false;
+        for (int k = 0; k < n_kp; k++) {
+            const double* e = kp_err + (g * n_kp + k) * ILQR_KP_ERR;
+            double v[ILQR_KP_ERR];
+            UNR for (int j = 0; j < ILQR_KP_ERR; j++) v[j] = e[j];
+            miss = miss || cl_kp_miss(v, tol.kp_tol[k]);
+        }
+        const bool lim = lim_cost[g] > tol.lim_tol;
+        n_miss += miss ? 1 : 0;
+        n_lim += lim ? 1 : 0;
+        n_ok += (!miss && !lim) ? 1 : 0;
+    }
+    double* o = outcome + (size_t)b * ILQR_CL_OUTCOME;
+    o[0] = (double)n_ok; o[1] = (double)n_miss; o[2] = (double)n_lim; o[3] = (double)n_bad;
 }
 
 // Per-instance statistics of the closed-loop costs: one lane per instance over cost[b][0 .. S-1] in sample order, in two passes, so the sums do
@@ -867,6 +982,19 @@ void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B,
 }
 void launch_closed_loop_stats(const double* cost, int B, int S, double* stats, hipStream_t st) {
     hipLaunchKernelGGL(k_closed_loop_stats, dim3((B + 63) / 64), dim3(64), 0, st, cost, B, S, stats);
+}
+void launch_closed_loop_kp_err(int kind, int nd, const Bufs& a, int B, int S, int n_kp, const double* kpx, double* kp_err, hipStream_t st) {
+    if (n_kp <= 0) return;
+    const dim3 grid((unsigned)(((size_t)B * S + 63) / 64), n_kp), block(64);
+    SysAll::dispatch(kind, nd, [&](auto s) { hipLaunchKernelGGL((k_closed_loop_kp_err<decltype(s)>), grid, block, 0, st, a, S, kpx, kp_err); });
+}
+void launch_closed_loop_kp_stats(const double* kp_err, const ilqr_cl_tol& tol, int B, int S, int n_kp, double* kp_stats, hipStream_t st) {
+    if (n_kp <= 0) return;
+    hipLaunchKernelGGL(k_closed_loop_kp_stats, dim3((B + 63) / 64, n_kp), dim3(64), 0, st, kp_err, tol, B, S, n_kp, kp_stats);
+}
+void launch_closed_loop_outcome(const double* cost, const double* kp_err, const double* lim_cost, const ilqr_cl_tol& tol, int B, int S, int n_kp,
+                                double* outcome, hipStream_t st) {
+    hipLaunchKernelGGL(k_closed_loop_outcome, dim3((B + 63) / 64), dim3(64), 0, st, cost, kp_err, lim_cost, tol, B, S, n_kp, outcome);
 }
 void launch_fk_batch(const DevDesc* dd, int n, const double* q, double* pos, double* quat, double* jac, hipStream_t st) {
     hipLaunchKernelGGL(k_fk_batch, dim3((n + 63) / 64), dim3(64), 0, st, dd, n, q, pos, quat, jac);

@@ -293,6 +293,60 @@ int ilqr_problem_closed_loop_noise(ilqr_problem* p, int n_samples, const ilqr_no
                                    double* stats, double* X, double* U, double* w_out);
 int ilqr_problem_closed_loop_noise_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, int with_feedforward, double* cost,
                                        double* stats, double* X, double* U, double* w_out);
+/* The same rollout, reporting what every execution did at the keypoints and against the limits -- per sample and reduced per instance on
+ * the device; no per-step array has to exist.  The disturbances are the draw above (noise non-NULL), the caller's w[B][S][T-1][n_x] (w
+ * non-NULL; both given is refused) or none (both NULL).  A noise whose sigmas are all 0 with n_samples = 1 reports on the plan itself.
+ * Keypoint errors.  For keypoint k of the descriptor (0 .. n_kp-1, the descriptor's index, not a step-table entry) on step t_k and the
+ *   execution's state x at that step, e is the residual the keypoint's cost term is built from -- f(x) seen through the keypoint's object
+ *   frame, then Keypoint::diff (its rule that an all-zero f(x) gives a zero pose residual included) -- WITHOUT the dead zone, which is itself a
+ *   tolerance.  Five numbers, ILQR_KP_ERR_*:
+ *     POS     ||e[0:3]||_2 (m);  a joint keypoint (the ILQR_SYS_JOINT* kinds, or kp_joint[k]): ||joint-position part of e||_2 (rad) over the user's joints
+ *     ORN     ||e[3:6]||_2 (rad: the angle of the reference's log map);  joint keypoint: 0
+ *     VEL     ||e[6:9]||_2 for nb_deriv = 2, else 0;  joint keypoint: 0
+ *     ANGVEL  ||e[9:12]||_2 for nb_deriv = 2, else 0;  joint keypoint: 0
+ *     TIME    |last entry of e| on the time systems, else 0
+ * Limit share.  lim_cost[b][s] = the sum over k = 0 .. T-1 of the limit terms of the stage cost at x_k, both limit sets with their
+ *   multiplicities: the part of cost[b][s] that is not a keypoint term.  It is 0.0 exactly when no weighted bound was crossed.
+ * Tolerances (ilqr_cl_tol).  An execution misses keypoint k if err[k][g] > kp_tol[k][g] for some judged group g; a negative kp_tol[k][g] means
+ *   that g is not judged.  It violates the limits if lim_cost > lim_tol (lim_tol >= 0).  Every comparison is strict.
+ * Outputs (ilqr_cl_report); each may be NULL, but not all four:
+ *   kp_err[B][S][n_kp][ILQR_KP_ERR]     the errors of every sample
+ *   kp_stats[B][n_kp][ILQR_KP_STATS]    { mean[5], max[5], n_miss, n_bad } over the samples of instance b in sample order: a sample is bad for
+ *                                       keypoint k if one of its five errors is not finite; means and maxima are over the good samples (NaN for
+ *                                       none); n_miss counts the good samples that miss keypoint k
+ *   lim_cost[B][S]
+ *   outcome[B][ILQR_CL_OUTCOME]         { n_ok, n_miss, n_lim, n_bad }: n_bad counts the samples whose cost is not finite (stats[b][4]); among
+ *                                       the others n_miss counts those that miss at least one keypoint, n_lim those with lim_cost > lim_tol, n_ok
+ *                                       those with neither.  n_ok / n_samples is the plan's success rate.
+ * cost[B][S], stats[B][ILQR_CL_STATS]: as above, each may be NULL (the costs then stay in a workspace of the problem); they and the rollout
+ * are bit for bit those of the entry points above for the same inputs.  tol may be NULL when neither kp_stats nor outcome is asked for.
+ * Refused: everything the entry points above refuse (a null cost is not: see before), noise and w both given, all four report pointers NULL,
+ * a NaN tolerance, lim_tol < 0, tol NULL while kp_stats or outcome is asked for.  32-bit bound: no per-step output exists, so without w it is
+ * B * n_samples * n_x < 2^31, with w the bound of the caller's w.
+ * _dev: every array is a device pointer (noise, tol and out themselves are structs in host memory, read before the call returns);
+ * asynchronous on the context's stream. */
+#define ILQR_KP_ERR 5
+#define ILQR_KP_ERR_POS 0
+#define ILQR_KP_ERR_ORN 1
+#define ILQR_KP_ERR_VEL 2
+#define ILQR_KP_ERR_ANGVEL 3
+#define ILQR_KP_ERR_TIME 4
+#define ILQR_KP_STATS 12     /* mean[5], max[5], n_miss, n_bad */
+#define ILQR_CL_OUTCOME 4    /* n_ok, n_miss, n_lim, n_bad */
+typedef struct {
+    double kp_tol[ILQR_MAX_KP][ILQR_KP_ERR]; /* execution misses keypoint k if err[k][g] > kp_tol[k][g] for some judged g; negative: g is not judged */
+    double lim_tol;                          /* execution violates the limits if lim_cost > lim_tol; >= 0 */
+} ilqr_cl_tol;
+typedef struct {
+    double* kp_err;    /* [B][S][n_kp][ILQR_KP_ERR] or NULL */
+    double* kp_stats;  /* [B][n_kp][ILQR_KP_STATS] or NULL */
+    double* lim_cost;  /* [B][S] or NULL */
+    double* outcome;   /* [B][ILQR_CL_OUTCOME] or NULL */
+} ilqr_cl_report;
+int ilqr_problem_closed_loop_report(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
+                                    int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out);
+int ilqr_problem_closed_loop_report_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
+                                        int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out);
 
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];
