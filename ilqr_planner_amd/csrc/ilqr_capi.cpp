@@ -143,13 +143,13 @@ extern "C" int ilqr_ctx_set_split(ilqr_ctx* c, int on) {
 }
 
 static_assert((int)SweepPin::Mfma == ILQR_XC_SWEEP_MFMA && (int)SweepPin::Rows == ILQR_XC_SWEEP_ROWS && (int)FwdPin::Wg == ILQR_XC_FWD_WG &&
-              (int)FwdPin::Dpp == ILQR_XC_FWD_DPP && (int)RerollPin::Rows == ILQR_XC_REROLL_ROWS && (int)RerollPin::Dpp == ILQR_XC_REROLL_DPP,
+              (int)FwdPin::Dpp == ILQR_XC_FWD_DPP && (int)FwdPin::WgLds == ILQR_XC_FWD_WG_LDS && (int)RerollPin::Rows == ILQR_XC_REROLL_ROWS && (int)RerollPin::Dpp == ILQR_XC_REROLL_DPP,
               "variant pins of ilqr_plan.hpp and include/ilqr_hip.h");
 
 extern "C" int ilqr_ctx_set_crosscheck(ilqr_ctx* c, int generic_kernels, int cp_lane_solve, int cp_general, int sweep, int forward, int reroll) {
     if (!c) return 1;
     if (sweep < 0 || sweep > 2) return fail(c, "ilqr_ctx_set_crosscheck: sweep must be ILQR_XC_AUTO, ILQR_XC_SWEEP_MFMA or ILQR_XC_SWEEP_ROWS");
-    if (forward < 0 || forward > 2) return fail(c, "ilqr_ctx_set_crosscheck: forward must be ILQR_XC_AUTO, ILQR_XC_FWD_WG or ILQR_XC_FWD_DPP");
+    if (forward < 0 || forward > 3) return fail(c, "ilqr_ctx_set_crosscheck: forward must be ILQR_XC_AUTO, ILQR_XC_FWD_WG, ILQR_XC_FWD_DPP or ILQR_XC_FWD_WG_LDS");
     if (reroll < 0 || reroll > 2) return fail(c, "ilqr_ctx_set_crosscheck: reroll must be ILQR_XC_AUTO, ILQR_XC_REROLL_ROWS or ILQR_XC_REROLL_DPP");
     c->xc_sweep = (SweepPin)sweep;
     c->xc_forward = (FwdPin)forward;
@@ -707,6 +707,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     f.shared = has_shared_step(p->hdesc.steps) ? 1 : 0;
     f.n_kp_all = p->desc.n_kp;
     f.fused = pl.fused ? 1 : 0;
+    f.fwd_lds = pl.fwd_lds ? 1 : 0;
     f.limits = p->desc.limits_set ? 1 : 0;
     for (int k = 0; k < p->desc.n_kp; k++) f.kp_ext |= p->desc.kp_dist[k] | p->desc.kp_has_frame[k] | p->desc.kp_has_Ru[k] | p->desc.kp_joint[k];
     for (int h = 0; h < nh; h++) {

@@ -70,6 +70,7 @@ struct FwdArgs {
     int limits;   // the descriptor's limits_set (host copy: selects kernel instantiations)
     int fused;    // the acceptance of the line search is applied by the next sweep (k_backward_si_dpp<.., true>): until then the accepted
                   // trajectory of an instance with pend > 0 is xbar + alpha (x(1) - xbar) over its two buffers
+    int fwd_lds;  // Forward::WaveWg runs its predecessor k_forward_wg (the pin ILQR_XC_FWD_WG_LDS) instead of k_forward_reg: same bits
 };
 
 // Fused acceptance in the cooperative sweep: what k_apply would have used at the end of the PREVIOUS iteration
@@ -91,7 +92,7 @@ void launch_init_lti(int kind, int nd, const Bufs& a, int B, hipStream_t st);  /
 void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw);  // rows in registers, DPP broadcasts (ilqr_kernels_dpp.hip)
 void launch_backward_rows(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // row-per-lane register sweep (ilqr_kernels_rowsweep.hip); needs launch_kp_derivs first
 void launch_backward_mfma(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // needs launch_kp_derivs first
-void launch_forward_wave(int kind, bool small, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // k_forward_dpp (small) or k_forward_wg, + k_select
+void launch_forward_wave(int kind, bool small, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // k_forward_dpp (small) or k_forward_reg (k_forward_wg if f.fwd_lds), + k_select
 void launch_apply_wave(int kind, const Bufs& a, int B, int T, hipStream_t st, const FwdArgs& f);  // blend + AL bookkeeping + flip
 void launch_forward_lin(const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // PosOrn-2: k_forward_lin (cost pass of every step size)
 void launch_apply_lin(const Bufs& a, int B, int T, hipStream_t st);  // PosOrn-2: the winner re-rolled (k_blend) + flip

@@ -1,5 +1,7 @@
 // ilqr_kernels_wave.hip -- the single-integrator fast path around the backward sweep (PosOrn / JointSpace, nb_deriv = 1):
-//   k_forward_wg      forward pass of the linear line search, one 8-wave workgroup per 16 instances, 32 lanes per instance
+//   k_forward_reg     forward pass of the linear line search for large batches: 16 lanes per instance on registers, a 4-wave workgroup per 16 instances
+//   k_forward_wg      its predecessor (one 8-wave workgroup per 16 instances, 32 lanes per instance), kept under a pin as its bitwise reference
+//   k_forward_dpp     the same pass for small batches: a bare chain, one wave per workgroup (agrees with the two above to rounding)
 //   k_select          line-search decision: task cost of every step size from the exported keypoint deviations (one lane per alpha)
 //   k_apply, k_flip   accepted trajectory x(alpha) = xbar + alpha (x(1) - xbar) and the AL bookkeeping in one pass; buffer flip
 //   k_al_post         the AL bookkeeping alone, for every system: the pipelines whose forward pass leaves the accepted trajectory in place
@@ -397,6 +399,239 @@ __global__ __launch_bounds__(64) void k_forward_dpp(Bufs a, FwdArgs f) { (void)f
 #undef FD_LO
 #undef FD_HI
 
+// ------------------------------------------------------------------------------------------------ large batches, on registers
+// k_forward_wg waits on the LDS pipe of its CU (three reads, four ds_bpermute and up to three writes per wave-step from eight waves, two
+// workgroup barriers per 8 steps): 0.5 us per step at any batch size.  k_forward_reg is the rollout of k_forward_dpp -- 16 lanes per instance,
+// lane (h, r) holds coordinate r and half h of gain row r, dx_c comes out of lane c's register by a DPP broadcast, no barrier -- with the
+// memory shape of a large batch, and with k_forward_wg's arithmetic restated term by term: it gives k_forward_wg's bits
+// (tests/test_gpu_forward_reg.py), where k_forward_dpp sums in another order.
+//   arithmetic   t_j = fma(K_r,2j, dx_2j, K_r,2j+1 dx_2j+1) (t_3 = fma(K_r6, dx_6, d_r 1)), du_r = (t_0 + t_1) + (t_2 + t_3): half 0 forms t_0 + t_1,
+//                half 1 t_2 + t_3, they meet by row_ror:8 (the top addition commutes).  The broadcasts are the compiler-visible moves: an FMA with
+//                a DPP operand onto a zeroed accumulator would turn a product of -0 into +0.  dx' = fma(dt, du, dx), as k_forward_wg's
+//                `dx + dt * du` is contracted.  The limit cost of a stage is accumulated per column pair and summed (pc_0 + pc_1) + (pc_2 + pc_3) as
+//                there, lane l of an instance taking step size 2^-l with the pair's values broadcast to it; ||du|| as there.
+//   gains        the four records of a wave are one contiguous run (4 x 288 bytes packed, 4 x 448 plain): loaded linearly, lane p its 16-byte
+//                pieces p and 64 + p (two loads per wave-step), kept in a register ring of FR_PF steps, dropped two steps ahead of their use into a
+//                double-buffered image in the wave's own LDS, from which each lane picks its four entries one step ahead.  LDS operations of a wave
+//                execute in order: no barrier.
+//   xbar | ubar  one load per wave-step (half 0 the state, half 1 the control).  A workgroup is FR_WAVES = 4 waves with 16 consecutive instances, so
+//                the four waves that share every 128-byte line of the [row][b] arrays sit on one CU.
+//   x(1) | u(1)  dropped into an LDS block per group of FR_PF steps and stored by the workgroup as full lines behind ONE barrier per group (see
+//                block_store): the only coupling of the waves.
+// Measured (profiles/fwd_reg_variations.txt): groups of 6, 10 and 12 steps against 8; one-wave workgroups against four (with the per-wave stores of the first form).
+constexpr int FR_WAVES = 4;   // waves per workgroup: 16 instances, one 128-byte line per row segment
+constexpr int FR_PF = 8;      // steps per group = depth of the gain ring = steps per store block
+// The number of step sizes is a run-time value here (f.n_alpha): it only gates the store of the limit costs, the limit branch evaluates all sixteen lanes anyway.
+template <bool LIM, bool ES, bool SYM>
+__global__ __launch_bounds__(FR_WAVES * 64) void k_forward_reg(Bufs a, FwdArgs f) {
+#pragma clang fp contract(off)  // every fused operation below is written as one
+    constexpr int NX = 7, NU = 7, ROWP = kd_rowp(NX), PF = FR_PF, IPW = 4;
+    static_assert(ROWP == 8, "record row = 7 gains + feed-forward");
+    static_assert(PF >= 2 && PF % 2 == 0, "image parity = slot parity");
+    constexpr int RSD = SYM ? KD_SYM_RS : NU * ROWP;  // doubles per record
+    constexpr int NPC = IPW * RSD / 2;                // 16-byte pieces of the wave's four records: 72 or 112
+    static_assert(NPC > 64 && NPC <= 128, "two pieces per lane");
+    __shared__ __attribute__((aligned(16))) double sK[FR_WAVES][2][IPW * RSD];
+    // x(1) | u(1) of a group of PF steps, [step][row][instance] with the row padded by two (bank spread), double-buffered: see block_store
+    constexpr int NR = NX + NU, IWG = FR_WAVES * IPW, OSTR = IWG + 2, NT = FR_WAVES * 64, NOUT = PF * NR * IWG, NRND = (NOUT + NT - 1) / NT;
+    __shared__ double sOut[2][PF * NR * OSTR];
+    const DevDesc& d = *a.desc;
+    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, g = lane >> 4, l = lane & 15, h = l >> 3, r8 = l & 7;
+    const int b0 = (xcd_tile() * FR_WAVES + wv) * IPW;  // the wave's first instance
+    const int b = b0 + g;
+    const int Bp = d.Bp, T = d.T, B = d.B;
+    const bool inst_ok = (b < B) && (a.active[b < B ? b : 0] != 0);
+    {   // workgroup-uniform exit (the waves meet at a barrier per group): every wave looks at all the workgroup's instances
+        const int bi = b0 - wv * IPW + (lane & (IWG - 1));
+        const bool any = (bi < B) && (a.active[bi < B ? bi : 0] != 0);
+        if (__ballot(any ? 1 : 0) == 0ull) return;
+    }
+    const int bb = (b < B) ? b : 0;
+    const bool row = r8 < NX;              // lanes (h, 7) shadow row 6: never the source of a broadcast
+    const int r = row ? r8 : NX - 1;
+    const bool st = inst_ok && row;        // this lane stores (x in half 0, u in half 1)
+    const bool sx = st && h == 0;          // ... and holds a state coordinate
+    const int cur = a.cur[bb];
+    const double dt = d.dt, pen = d.penalty;
+    const int lw = LIM ? d.lw[r] : 0;
+    const double mx = lw ? d.smax[r] : INFINITY, mn = lw ? d.smin[r] : -INFINITY;
+    const int n_kp = d.n_kp;
+    int kpi = 0, kp_next = (n_kp > 0) ? d.kp_t[0] : -1;
+
+    const size_t Vstep = (size_t)NX * Bp;
+    const double* pV = (h ? a.U[cur] : a.X[cur]) + (size_t)r * Bp + bb;      // xbar_r (half 0) | ubar_r (half 1): same stride
+    // x(1), u(1) leave as full 128-byte lines: the waves drop a group's values into sOut, and after one barrier the workgroup stores the group,
+    // thread tid the entries q NT + tid = (segment = (step, row), instance tid mod 16).  Stored by each wave as its own 32-byte pieces of every line
+    // they cost more than the rollout saves (measured: DESIGN 5.3).  One barrier per group is enough: a buffer is written again two groups
+    // later, behind the next barrier, which every wave reaches with its reads of the buffer done.
+    static_assert(IWG == 16, "a row segment of the workgroup's instances is one 128-byte line");
+    const int tid = wv * 64 + lane, l_inst = tid & (IWG - 1), l_bi = b0 - wv * IPW + l_inst, l_b = l_bi < B ? l_bi : 0;
+    const bool l_ok = (l_bi < B) && (a.active[l_b] != 0);
+    double* l_dst[NRND];   // the entry's place at step 0 of the group in the instance's other buffer
+    int l_s[NRND], l_src[NRND];
+    {
+        const int l_cur = a.cur[l_b];
+        UNR for (int q = 0; q < NRND; q++) {
+            const int e = q * NT + tid, seg = (e < NOUT ? e : 0) / IWG, s_ = seg / NR, rw = seg % NR;
+            l_s[q] = e < NOUT ? s_ : PF;   // PF: no entry
+            l_src[q] = seg * OSTR + l_inst;
+            l_dst[q] = (rw < NX ? a.X[1 - l_cur] + (size_t)rw * Bp : a.U[1 - l_cur] + (size_t)(rw - NX) * Bp) + (size_t)s_ * Vstep + l_b;
+        }
+    }
+    const int ow = (h * NX + r) * OSTR + wv * IPW + g;   // this lane's entry of a step in sOut (the shadow lane writes row 6's value again)
+    auto block_store = [&](int buf, int k0) {
+        UNR for (int q = 0; q < NRND; q++) {
+            const double v = sOut[buf][l_src[q]];
+            if (l_ok && l_s[q] < PF && k0 + l_s[q] < T - 1) l_dst[q][(size_t)k0 * Vstep] = v;
+        }
+    };
+    const double xT = a.X[cur][((size_t)(T - 1) * NX + r) * Bp + bb];         // terminal xbar
+    // gains: a wave-uniform base that walks the horizon + the lane's byte offsets of its two pieces (a lane without a second piece re-reads its first)
+    const char* kb = reinterpret_cast<const char*>(a.KD + (size_t)b0 * RSD);
+    const size_t Kstep = (size_t)Bp * RSD * sizeof(double);
+    const int p1 = (64 + lane < NPC) ? 64 + lane : lane;
+    const unsigned ko0 = lane * 16u, ko1 = p1 * 16u;
+    double* const img = &sK[wv][0][0];
+    constexpr int IMG = IPW * RSD;
+    // the lane's four entries of row r in a record's image: columns 4h .. 4h+3 (column 7 = d_r)
+    int ro[4];
+    UNR for (int j = 0; j < 4; j++) ro[j] = g * RSD + (SYM ? kd_sym_off(r, 4 * h + j) : r * ROWP + 4 * h + j);
+
+    double ga[PF], gb[PF], gc[PF], gd[PF], vr[PF];  // (scalar arrays: an array of double2 is not split into registers)
+    auto fetch_g = [&](int slot, int kk) {  // unconditional; the base stops at the last control step
+        // nontemporal: a record is read once.  Measured: the solve is 0.2 ms shorter, part of it in the sweep that follows -- presumably because the records no
+        // longer displace the x(1), u(1) it reads from the caches (a hypothesis: DESIGN 5.3)
+        typedef double d2v __attribute__((ext_vector_type(2)));
+        const d2v v0 = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(kb + ko0)), v1 = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(kb + ko1));
+        ga[slot] = v0.x; gb[slot] = v0.y; gc[slot] = v1.x; gd[slot] = v1.y;
+        kb += (kk < T - 2) ? Kstep : 0;     // uniform: a scalar select, not a branch
+    };
+    auto fetch_v = [&](int slot, int kk) {
+        vr[slot] = *pV;
+        pV += (kk < T - 2) ? Vstep : 0;
+    };
+    // pieces of ring slot -> image buf (the lane without a second piece writes its first again); they leave the slot by an opaque move, so that
+    // the slot's next load shares its registers (ring_take, ilqr_lanes.hpp)
+    auto stage = [&](int slot, int buf) {
+        const double ta = ring_take(ga[slot]), tb = ring_take(gb[slot]), tc = ring_take(gc[slot]), td = ring_take(gd[slot]);
+        *reinterpret_cast<double2*>(img + buf * IMG + 2 * lane) = make_double2(ta, tb);
+        *reinterpret_cast<double2*>(img + buf * IMG + 2 * p1) = make_double2(tc, td);
+    };
+    auto pick = [&](int buf, double (&K)[4]) {  // this lane's entries out of image buf
+        if (SYM) {
+            UNR for (int j = 0; j < 4; j++) K[j] = img[buf * IMG + ro[j]];
+        } else {
+            const double2 v0 = *reinterpret_cast<const double2*>(img + buf * IMG + ro[0]), v1 = *reinterpret_cast<const double2*>(img + buf * IMG + ro[2]);
+            K[0] = v0.x; K[1] = v0.y; K[2] = v1.x; K[3] = v1.y;
+        }
+    };
+    UNR for (int q = 0; q < PF; q++) { fetch_g(q, q); fetch_v(q, q); __builtin_amdgcn_sched_barrier(0); }
+    double Kc[4];                           // the entries of the step being computed
+    stage(0, 0);
+    LDS_ORDER();
+    pick(0, Kc);
+    stage(1, 1);
+    LDS_ORDER();
+    __builtin_amdgcn_sched_barrier(0);
+    fetch_g(0, PF);
+    fetch_g(1, PF + 1);
+
+    double dx = 0, dun = 0, pc[4] = {0, 0, 0, 0};
+    // k_forward_wg's limit cost of a column pair (c0, c1) for one step size (inspectJointLimit, System.cpp:163-179): cost(c0) + cost(c1) with
+    // cost = (q pen) q, as that kernel's contraction fuses it -- cost(c1) rounded, cost(c0) the product of the FMA
+    // (Read off the ISA of k_forward_wg<1 | 11 | 16> as AMD clang 22.0.0git / ROCm 7.2.0 compiles it, as is dx' = fma(dt, du, dx) below: the old source
+    // leaves both to -ffp-contract=fast.  A compiler that contracts it otherwise shows in tests/test_gpu_forward_reg.py: test_limits and
+    // test_step_sizes[urdf] for this expression, every case for the dynamics; then restate what the new ISA does here.)
+    auto pair_cost = [&](double v0, double mx0, double mn0, double v1, double mx1, double mn1) -> double {
+        const double q0 = fmax(v0 - mx0, 0.0) + fmax(mn0 - v0, 0.0), q1 = fmax(v1 - mx1, 0.0) + fmax(mn1 - v1, 0.0);
+        return fma(q0 * pen, q0, (q1 * pen) * q1);
+    };
+    const double myA = ldexp(1.0, -l);      // the step size of this lane
+    // bounds of the column pairs (uniform); pair 3 is column 6 and the feed-forward column (dx := 1, weight 0)
+    double pmx[8], pmn[8];
+    UNR for (int c = 0; c < 8; c++) {
+        const int lwc = (LIM && c < NX) ? d.lw[c < NX ? c : 0] : 0;
+        pmx[c] = lwc ? d.smax[c < NX ? c : 0] : INFINITY;
+        pmn[c] = lwc ? d.smin[c < NX ? c : 0] : -INFINITY;
+    }
+    // the stage's limit cost for every step size; xb: xbar_r in the lanes of half 0
+#define FR_PAIR_(J, C1, DX1)                                                                                                        \
+    pc[J] += pair_cost(fma(myA, dppz_bcast<2 * J>(dx), dppz_bcast<2 * J>(xb)), pmx[2 * J], pmn[2 * J],                              \
+                       fma(myA, DX1, dppz_bcast<C1>(xb)), pmx[2 * J + 1], pmn[2 * J + 1]);
+    auto limits_all = [&](double xb) {
+        FR_PAIR_(0, 1, dppz_bcast<1>(dx)) FR_PAIR_(1, 3, dppz_bcast<3>(dx)) FR_PAIR_(2, 5, dppz_bcast<5>(dx)) FR_PAIR_(3, 6, 1.0)
+    };
+    auto seg_bad = [&](double xb) -> bool {  // the segment [xbar, x(1)] of this coordinate leaves [mn, mx]
+        const double e = xb + dx;
+        return (fmax(xb, e) > mx) | (fmin(xb, e) < mn);
+    };
+    const bool ev = (r8 & 1) == 0, last2 = r8 >= 6;
+    double* kpdev = a.kpdev;
+
+#define FR_STEP_(JJ, CHK)                                                                                          \
+    {                                                                                                              \
+        const int k = k0 + JJ;                                                                                     \
+        double Kn[4];                                                                                              \
+        pick((JJ + 1) & 1, Kn);                          /* the entries of step k + 1 */                           \
+        LDS_ORDER();                                                                                               \
+        stage((JJ + 2) % PF, JJ & 1);                    /* step k + 2 over the image of step k */                 \
+        LDS_ORDER();                                                                                               \
+        __builtin_amdgcn_sched_barrier(0);               /* the slot is free: only now its next load */            \
+        fetch_g((JJ + 2) % PF, k + 2 + PF);                                                                        \
+        if (!CHK || k < T - 1) {                                                                                   \
+            const double vb = ring_take(vr[JJ]);         /* xbar_r | ubar_r */                                     \
+            const double x0 = dpp_bcast_halves<0, 4>(dx), x1 = dpp_bcast_halves<1, 5>(dx);                         \
+            const double x2 = dpp_bcast_halves<2, 6>(dx), x3 = dpp_bcast_halves<3, -1>(dx, 1.0);                   \
+            const double part = fma(Kc[0], x0, Kc[1] * x1) + fma(Kc[2], x2, Kc[3] * x3);                           \
+            const double du = part + dpp_f64<0x128>(part);   /* row_ror:8: the other half's part */                \
+            sOut[ob][JJ * NR * OSTR + ow] = vb + (h ? du : dx);   /* x(1)_r | u(1)_r */                            \
+            if (ES) {                                    /* ||du_k(1)||: s_j = fma(du_2j, du_2j, du_2j+1^2), s_3 = du_6^2 */ \
+                const double o = dpp_f64<0xB1>(du);      /* the pair's other row */                                \
+                const double pa = ev ? du : o, pb = ev ? o : du;                                                   \
+                double s = fma(pa, pa, last2 ? 0.0 : pb * pb);                                                     \
+                s = s + dpp_f64<0x4E>(s);                /* (s_0 + s_1), (s_2 + s_3) */                            \
+                s = s + dpp_f64<0x141>(s);                                                                         \
+                dun += __builtin_amdgcn_sqrt(s);                                                                   \
+            }                                                                                                      \
+            if (LIM && __builtin_expect(__ballot((seg_bad(vb) & sx) ? 1 : 0) != 0ull, 0)) limits_all(vb);          \
+            if (CHK && k == kp_next) {   /* hand the deviation of this step to k_select */                         \
+                double* o = kpdev + (size_t)kpi * (NX + NU) * Bp;                                                  \
+                if (st) AT(o, h * NX + r, bb) = h ? du : dx;                                                       \
+                kpi++;                                                                                             \
+                kp_next = (kpi < n_kp) ? __builtin_amdgcn_readfirstlane(d.kp_t[kpi]) : -1;                         \
+            }                                                                                                      \
+            dx = fma(dt, du, dx);   /* deviation dynamics (both halves) */                                         \
+        }                                                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                         \
+        fetch_v(JJ, k + PF);                                                                                       \
+        UNR for (int j = 0; j < 4; j++) Kc[j] = Kn[j];                                                             \
+    }
+    // one copy of the group (k_forward_dpp runs a second one without the two tests where no keypoint step and no end of the horizon falls into the
+    // group: here the values that leave either copy would each keep registers of their own across the other, and the copies that bring the ring
+    // back together at the end of a group wait for nearly every load in flight)
+    for (int k0 = 0, ob = 0; k0 < T - 1; k0 += PF, ob ^= 1) {
+        UNR for (int jj = 0; jj < PF; jj++) FR_STEP_(jj, true)
+        lds_barrier();   // the group's x(1), u(1) of every wave are in sOut[ob]
+        block_store(ob, k0);
+    }
+#undef FR_STEP_
+    {   // terminal state
+        if (sx) a.X[1 - cur][((size_t)(T - 1) * NX + r) * Bp + bb] = xT + dx;   // one 32-byte piece per line, once
+        if (LIM && __ballot((seg_bad(xT) & sx) ? 1 : 0) != 0ull) limits_all(xT);
+        if (kp_next == T - 1 && sx) {
+            double* o = kpdev + (size_t)kpi * (NX + NU) * Bp;
+            AT(o, r, bb) = dx;
+        }
+    }
+#undef FR_PAIR_
+    // limit cost per step size (lane l: 2^-l) and sum ||du||
+    const double sA = LIM ? (pc[0] + pc[1]) + (pc[2] + pc[3]) : 0.0;
+    const int na = f.n_alpha <= 1 ? 1 : f.n_alpha <= 11 ? 11 : 16;   // the rows k_forward_wg<1 | 11 | 16> writes (k_select reads n_alpha of them)
+    if (inst_ok && l < na) AT(a.lsc, l, bb) = sA;
+    if (inst_ok && l == 0) a.dun[bb] = dun;
+}
+
 // The decision of k_select once every lane holds the task cost of its step size: limit cost added, the first step size (descending) below the current
 // cost wins, else the last one tried (ILQRRecursive.cpp:101-155); bookkeeping by the instance's first lane.  Returns the winner's index (uniform over
 // the instance's 16 lanes); *stopped = the instance left the iteration (early stop).
@@ -718,22 +953,42 @@ static void launch_forward_dpp(const Bufs& a, dim3 grid, hipStream_t st, const F
         else hipLaunchKernelGGL((k_forward_dpp<NA, false, false>), grid, block, 0, st, a, f);
     }
 }
+static void launch_forward_reg(const Bufs& a, dim3 grid, hipStream_t st, const FwdArgs& f) {
+    const dim3 block(FR_WAVES * 64);
+#define FR_LAUNCH_(LIM, ES)                                                                             \
+    do {                                                                                                \
+        if (a.kd_sym) hipLaunchKernelGGL((k_forward_reg<LIM, ES, true>), grid, block, 0, st, a, f);  \
+        else hipLaunchKernelGGL((k_forward_reg<LIM, ES, false>), grid, block, 0, st, a, f);          \
+    } while (0)
+    if (f.limits) {
+        if (f.early_stop) FR_LAUNCH_(true, true);
+        else FR_LAUNCH_(true, false);
+    } else {
+        if (f.early_stop) FR_LAUNCH_(false, true);
+        else FR_LAUNCH_(false, false);
+    }
+#undef FR_LAUNCH_
+}
 // the rollout itself knows no keypoint function (single-integrator dynamics); the decision kernel is per system kind
 template <class S>
 static void launch_forward_wave_sys(bool small, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
-    const dim3 grid(grid_x8((B + FW_IW - 1) / FW_IW)), block(FW_IW * 32);
+    const dim3 grid(grid_x8((B + FW_IW - 1) / FW_IW)), block(FW_IW * 32);  // k_forward_wg: 16 instances per workgroup
+    const dim3 rgrid(grid_x8((B + 4 * FR_WAVES - 1) / (4 * FR_WAVES)));    // large batches: k_forward_reg, or k_forward_wg under its pin (f.fwd_lds)
     const dim3 sgrid(grid_x8((B + 3) / 4));  // small batches: 16 lanes per instance, one wave per workgroup (k_forward_dpp)
     if (f.n_alpha <= 1) {
         if (small) launch_forward_dpp<1>(a, sgrid, st, f);
-        else hipLaunchKernelGGL((k_forward_wg<1>), grid, block, 0, st, a, f);
+        else if (f.fwd_lds) hipLaunchKernelGGL((k_forward_wg<1>), grid, block, 0, st, a, f);
+        else launch_forward_reg(a, rgrid, st, f);
         launch_select<S, 1>(a, B, st, f);
     } else if (f.n_alpha <= 11) {
         if (small) launch_forward_dpp<11>(a, sgrid, st, f);
-        else hipLaunchKernelGGL((k_forward_wg<11>), grid, block, 0, st, a, f);
+        else if (f.fwd_lds) hipLaunchKernelGGL((k_forward_wg<11>), grid, block, 0, st, a, f);
+        else launch_forward_reg(a, rgrid, st, f);
         launch_select<S, 11>(a, B, st, f);
     } else {
         if (small) launch_forward_dpp<16>(a, sgrid, st, f);
-        else hipLaunchKernelGGL((k_forward_wg<16>), grid, block, 0, st, a, f);
+        else if (f.fwd_lds) hipLaunchKernelGGL((k_forward_wg<16>), grid, block, 0, st, a, f);
+        else launch_forward_reg(a, rgrid, st, f);
         launch_select<S, 16>(a, B, st, f);
     }
 }

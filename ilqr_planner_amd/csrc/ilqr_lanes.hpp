@@ -31,6 +31,12 @@ __device__ __forceinline__ double dppz_f64(double v) {
 }
 template <int L>
 __device__ __forceinline__ double dppz_bcast(double v) { return dppz_f64<0x150 + L>(v); }  // lane L of the DPP row to all sixteen
+// lane LO of the DPP row to its lanes 0 .. 7, lane HI to its lanes 8 .. 15 (bank masks: a bank is four lanes); HI < 0: `other` there instead
+template <int LO, int HI>
+__device__ __forceinline__ double dpp_bcast_halves(double v, double other = 0.0) {
+    const double hi = HI < 0 ? other : __builtin_amdgcn_update_dpp(0.0, v, 0x150 + (HI < 0 ? 0 : HI), 0xf, 0xc, false);
+    return __builtin_amdgcn_update_dpp(hi, v, 0x150 + LO, 0xf, 0x3, false);
+}
 __device__ __forceinline__ double dppz_shr7(double v) { return dppz_f64<0x117>(v); }  // lane l <- lane l - 7 (0 below)
 __device__ __forceinline__ double dppz_shl7(double v) { return dppz_f64<0x107>(v); }  // lane l <- lane l + 7 (0 above)
 // v of the lane at byte address 4 * lane (ds_bpermute: LDS crossbar, no LDS memory)

@@ -22,7 +22,7 @@ constexpr bool backward_mfma_supported(int kind, int /*nd*/, bool al, int m) { r
 constexpr bool backward_rows_supported(int kind, int nd, bool al, int m) {
     return kind != 2 && !(kind == 0 && nd == 1) && (!al || m <= 16);
 }
-// k_forward_wg / k_forward_dpp: the linear line search of the single-integrator systems, one lane row per step size (at most 16)
+// k_forward_reg / k_forward_wg / k_forward_dpp: the linear line search of the single-integrator systems, one lane row per step size (at most 16)
 constexpr bool forward_wave_supported(int kind, int nd, int n_alpha) { return (kind == 0 || kind == 2) && nd == 1 && n_alpha <= 16; }
 // k_forward_lin: the linear line search of PosOrn-2, at most 16 step sizes
 constexpr bool forward_lin_supported(int kind, int nd, int n_alpha) { return kind == 0 && nd == 2 && n_alpha <= 16; }
@@ -45,7 +45,7 @@ constexpr int si_lanes(int launched_B, int n_simd) { return (launched_B + 3) / 4
 
 // Variant pins of ilqr_ctx_set_crosscheck: AUTO (0) = by batch size; the values are the ILQR_XC_* constants of include/ilqr_hip.h
 enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2 };
-enum class FwdPin { Auto = 0, Wg = 1, Dpp = 2 };
+enum class FwdPin { Auto = 0, Wg = 1, Dpp = 2, WgLds = 3 };  // WgLds: Wg with k_forward_wg, the predecessor of k_forward_reg (same bits)
 enum class RerollPin { Auto = 0, Rows = 1, Dpp = 2 };
 
 struct PlanIn {
@@ -72,7 +72,7 @@ struct PlanIn {
 
 enum class Init { Lti, Generic };                          // k_init_roll_lti + k_init_finish, or k_init_rollout
 enum class Sweep { SiDpp, Mfma, Rows, Generic };           // k_backward_si_dpp, k_backward_mfma, k_backward_rows, k_backward (+ workspace)
-enum class Forward { WaveWg, WaveDpp, Lin, Mfma, Generic };  // k_forward_wg / k_forward_dpp + k_select, k_forward_lin, k_forward_mfma + k_select_x, k_forward
+enum class Forward { WaveWg, WaveDpp, Lin, Mfma, Generic };  // k_forward_reg (k_forward_wg if fwd_lds) / k_forward_dpp + k_select, k_forward_lin, k_forward_mfma + k_select_x, k_forward
 enum class Apply {
     None,
     Wave,        // k_apply + k_flip_ran every iteration
@@ -90,6 +90,7 @@ struct RiccatiPlan {
     Sweep sweep = Sweep::Generic;
     int si_lanes[2] = {16, 16};   // Sweep::SiDpp: lanes per instance of the whole batch or of each half (split)
     Forward forward = Forward::Generic;
+    bool fwd_lds = false;         // Forward::WaveWg under the pin FwdPin::WgLds: k_forward_wg instead of k_forward_reg
     Apply apply = Apply::None;
     bool al_update = false;       // k_al_post after every line search (the wave path does it in k_apply or the fused sweep)
     bool fused = false;           // the sweep applies the previous line search's winner itself (ilqr_kernels_dpp.hip)
@@ -120,6 +121,7 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     if (coop_fwd && forward_wave_supported(kind, nd, p.n_alpha)) {
         const bool dpp = in.forward == FwdPin::Dpp || (in.forward == FwdPin::Auto && (in.B + 3) / 4 <= 3 * in.n_simd / 4);
         p.forward = dpp ? Forward::WaveDpp : Forward::WaveWg;
+        p.fwd_lds = in.forward == FwdPin::WgLds;  // the large-batch pass at any batch size, as its predecessor wrote it
     } else if (coop_fwd && forward_lin_supported(kind, nd, p.n_alpha)) {
         p.forward = Forward::Lin;
     } else if (coop_fwd) {

@@ -161,12 +161,13 @@ int ilqr_ctx_synchronize(ilqr_ctx* ctx);
  * stream, one kernel at a time -- what a profiler run wants.  Default: on (1).  on = 2 splits every cooperative path (experiments only: measured
  * slower on the single-integrator systems).  Any other value fails with an error text.  (No reference counterpart: the reference has no batch.) */
 int ilqr_ctx_set_split(ilqr_ctx* ctx, int on);
-/* Variant pins of ilqr_ctx_set_crosscheck: AUTO = by batch size; each pair of variants agrees to rounding, not bit for bit */
+/* Variant pins of ilqr_ctx_set_crosscheck: AUTO = by batch size; the variants of a pin agree to rounding, not bit for bit, unless said otherwise */
 #define ILQR_XC_AUTO 0
 #define ILQR_XC_SWEEP_MFMA 1   /* sweep of the 2nd-order / time systems: one instance per wave on the f64 matrix cores (AUTO: up to 2 n_simd instances) */
 #define ILQR_XC_SWEEP_ROWS 2   /*   ... 16 lanes per instance with the rows in registers (AUTO: beyond) */
-#define ILQR_XC_FWD_WG 1       /* forward pass of the single-integrator systems: the bandwidth-built k_forward_wg (AUTO: beyond 3 n_simd instances) */
-#define ILQR_XC_FWD_DPP 2      /*   ... the latency-built k_forward_dpp (AUTO: up to 3 n_simd) */
+#define ILQR_XC_FWD_WG 1       /* forward pass of the single-integrator systems: the large-batch k_forward_reg (AUTO: beyond 3 n_simd instances) */
+#define ILQR_XC_FWD_DPP 2      /*   ... the latency-built k_forward_dpp (AUTO: up to 3 n_simd); agrees with the others to rounding */
+#define ILQR_XC_FWD_WG_LDS 3   /*   ... k_forward_wg, the predecessor of k_forward_reg, at any batch size: the same bits as ILQR_XC_FWD_WG (never AUTO) */
 #define ILQR_XC_REROLL_ROWS 1  /* re-roll of the line-search winner on the time systems: k_apply_rows_tm (AUTO: beyond n_simd instances) */
 #define ILQR_XC_REROLL_DPP 2   /*   ... k_apply_dpp_tm (AUTO: up to n_simd) */
 /* Cross-check kernel variants for parity tests (no reference counterpart; the library reads no environment variable -- these are context state,
