@@ -192,6 +192,11 @@ def _f64(x, shape=None):
     return a
 
 
+def _out(want, *shape):
+    """An output array of a call, or None where it is not asked for."""
+    return np.empty(shape) if want else None
+
+
 def chain_from_urdf(urdf_text: str, base: str, tip: str, tool_rpy=None, tool_xyz=None):
     """URDF text -> chain dict (seg_joint, seg_xyz, seg_R, seg_axis, dof, lower, upper) via the C++ reader in the library."""
     L = load()
@@ -485,21 +490,26 @@ class BatchProblem:
         self.ctx.check(self.L.ilqr_problem_track(self.h, int(k), _dp(x), int(bool(with_feedforward)), _dp(u)))
         return u
 
-    def closed_loop(self, x0=None, w=None, samples=None, with_feedforward: bool = False, want_X: bool = True, want_U: bool = True):
-        """Closed loop of the tracking law on the last Riccati solve's plan (ilqr_problem_closed_loop): x0 [B][S][n_x] or None (the plan's start),
-        w [B][S][T-1][n_x] or None (no disturbance); samples: S, needed only where neither array gives it.  Returns (cost [B][S],
-        X [B][S][T][n_x] or None, U [B][S][T-1][n_u] or None)."""
+    def _cl_inputs(self, samples, x0, w=None):
+        """(S, n, x0, w) of a closed-loop call: S is `samples`, else what x0 or w gives, else 1; n = max(S, 0) sizes the arrays (the library
+        refuses S < 1; they must merely exist); x0 and w are coerced to their shapes."""
         S = samples
         for arr in (x0, w):
             if S is None and arr is not None:
                 S = np.shape(arr)[1]
         S = 1 if S is None else int(S)
-        n = max(S, 0)  # (the library refuses S < 1; the arrays below must merely exist)
+        n = max(S, 0)
         x0 = _f64(x0, (self.B, n, self.dims.n_x)) if x0 is not None else None
         w = _f64(w, (self.B, n, self.T - 1, self.dims.n_x)) if w is not None else None
+        return S, n, x0, w
+
+    def closed_loop(self, x0=None, w=None, samples=None, with_feedforward: bool = False, want_X: bool = True, want_U: bool = True):
+        """Closed loop of the tracking law on the last Riccati solve's plan (ilqr_problem_closed_loop): x0 [B][S][n_x] or None (the plan's start),
+        w [B][S][T-1][n_x] or None (no disturbance); samples: S, needed only where neither array gives it.  Returns (cost [B][S],
+        X [B][S][T][n_x] or None, U [B][S][T-1][n_u] or None)."""
+        S, n, x0, w = self._cl_inputs(samples, x0, w)
         cost = np.empty((self.B, n))
-        X = np.empty((self.B, n, self.T, self.dims.n_x)) if want_X else None
-        U = np.empty((self.B, n, self.T - 1, self.dims.n_u)) if want_U else None
+        X, U = _out(want_X, self.B, n, self.T, self.dims.n_x), _out(want_U, self.B, n, self.T - 1, self.dims.n_u)
         self.ctx.crosscheck_from_env()
         self.ctx.check(self.L.ilqr_problem_closed_loop(self.h, S, _dp(x0), _dp(w), int(bool(with_feedforward)), _dp(cost), _dp(X), _dp(U)))
         return cost, X, U
@@ -527,14 +537,10 @@ class BatchProblem:
         the draw of (seed, instance_offset + b, sample_offset + s, step, entry) is the definition in include/ilqr_hip.h.  x0 [B][S][n_x] or None
         is the centre of the start perturbation.  Returns a ClosedLoopNoise of cost [B][S], stats [B][5] (mean, variance, min, max of the
         finite costs, n_bad), X, U, w [B][S][T-1][n_x]; what was not asked for is None."""
-        S = int(samples)
-        n = max(S, 0)
-        x0 = _f64(x0, (self.B, n, self.dims.n_x)) if x0 is not None else None
-        cost = np.empty((self.B, n)) if want_cost else None
-        stats = np.empty((self.B, CL_STATS)) if want_stats else None
-        X = np.empty((self.B, n, self.T, self.dims.n_x)) if want_X else None
-        U = np.empty((self.B, n, self.T - 1, self.dims.n_u)) if want_U else None
-        w = np.empty((self.B, n, self.T - 1, self.dims.n_x)) if want_w else None
+        S, n, x0, _ = self._cl_inputs(int(samples), x0)
+        cost, stats = _out(want_cost, self.B, n), _out(want_stats, self.B, CL_STATS)
+        X, U = _out(want_X, self.B, n, self.T, self.dims.n_x), _out(want_U, self.B, n, self.T - 1, self.dims.n_u)
+        w = _out(want_w, self.B, n, self.T - 1, self.dims.n_x)
         nz = self.noise(seed, sigma_w, sigma_x0, instance_offset, sample_offset)
         self.ctx.crosscheck_from_env()
         self.ctx.check(self.L.ilqr_problem_closed_loop_noise(self.h, S, C.byref(nz), _dp(x0), int(bool(with_feedforward)), _dp(cost), _dp(stats),
@@ -570,23 +576,13 @@ class BatchProblem:
         disturbances; neither: none.  kp_tol: see tol(); with kp_tol and lim_tol both None no tolerance is passed and the two reductions are
         not asked for.  X, U, w are not outputs of the C call: where they are wanted they come from closed_loop_noise / closed_loop with the same
         inputs, which run the same rollout bit for bit.  Returns a ClosedLoopReport; what was not asked for is None."""
-        S = samples
-        for arr in (x0, w):
-            if S is None and arr is not None:
-                S = np.shape(arr)[1]
-        S = 1 if S is None else int(S)
-        n = max(S, 0)
-        x0 = _f64(x0, (self.B, n, self.dims.n_x)) if x0 is not None else None
-        w = _f64(w, (self.B, n, self.T - 1, self.dims.n_x)) if w is not None else None
+        S, n, x0, w = self._cl_inputs(samples, x0, w)
         nz = self.noise(seed, sigma_w, sigma_x0, instance_offset, sample_offset) if seed is not None else None
         judged = kp_tol is not None or lim_tol is not None
         tol = self.tol(kp_tol, 0.0 if lim_tol is None else lim_tol) if judged else None
-        cost = np.empty((self.B, n)) if want_cost else None
-        stats = np.empty((self.B, CL_STATS)) if want_stats else None
-        kp_err = np.empty((self.B, n, self.n_kp, KP_ERR)) if want_kp_err else None
-        kp_stats = np.empty((self.B, self.n_kp, KP_STATS)) if want_kp_stats and judged else None
-        lim_cost = np.empty((self.B, n)) if want_lim_cost else None
-        outcome = np.empty((self.B, CL_OUTCOME)) if want_outcome and judged else None
+        cost, stats = _out(want_cost, self.B, n), _out(want_stats, self.B, CL_STATS)
+        kp_err, kp_stats = _out(want_kp_err, self.B, n, self.n_kp, KP_ERR), _out(want_kp_stats and judged, self.B, self.n_kp, KP_STATS)
+        lim_cost, outcome = _out(want_lim_cost, self.B, n), _out(want_outcome and judged, self.B, CL_OUTCOME)
         rp = Report(*(a.ctypes.data if a is not None else None for a in (kp_err, kp_stats, lim_cost, outcome)))
         self.ctx.crosscheck_from_env()
         self.ctx.check(self.L.ilqr_problem_closed_loop_report(self.h, S, C.byref(nz) if nz is not None else None, _dp(x0), _dp(w),

@@ -1523,37 +1523,36 @@ static void closed_loop_of(ilqr_problem* p, sys::System& s, int B, const ClosedL
     if (!cl.w.empty() && cl.w.size() != n * (o.T - 1) * o.n_x) throw std::runtime_error("[closed_loop_batch] w must be B x S x (horizon-1) x nb_state_var");
     o.cost.resize(n); o.X.resize(n * o.T * o.n_x); o.U.resize(n * (o.T - 1) * o.n_u);
     o.stats.resize((size_t)B * ILQR_CL_STATS);
+    const double *x0 = cl.x0.empty() ? nullptr : cl.x0.data(), *w = cl.w.empty() ? nullptr : cl.w.data();
+    const int ff = cl.with_feedforward ? 1 : 0;
+    ilqr_noise nz{};
     if (cl.has_seed) {
-        if (!cl.w.empty()) throw std::runtime_error("[closed_loop_batch] give either w or seed (with seed the disturbances are drawn on the device), not both");
-        ilqr_noise nz{};
+        if (w) throw std::runtime_error("[closed_loop_batch] give either w or seed (with seed the disturbances are drawn on the device), not both");
         nz.seed = cl.seed;
         for (int which = 0; which < 2; which++) {
             const std::vector<double>& sg = which ? cl.sigma_x0 : cl.sigma_w;
             if (sg.size() > 1 && (int)sg.size() != o.n_x) throw std::runtime_error("[closed_loop_batch] sigma_w and sigma_x0 must be a scalar or have nb_state_var entries");
             for (int i = 0; i < o.n_x && !sg.empty(); i++) (which ? nz.sigma_x0 : nz.sigma_w)[i] = sg.size() == 1 ? sg[0] : sg[i];
         }
-        check(ilqr_problem_closed_loop_noise(p, cl.S, &nz, cl.x0.empty() ? nullptr : cl.x0.data(), cl.with_feedforward ? 1 : 0, o.cost.data(), o.stats.data(),
-                                             o.X.data(), o.U.data(), nullptr));
-        if (cl.has_tol) closed_loop_report_of(p, s, B, cl, &nz, o);
-        return;
+        check(ilqr_problem_closed_loop_noise(p, cl.S, &nz, x0, ff, o.cost.data(), o.stats.data(), o.X.data(), o.U.data(), nullptr));
+    } else {
+        check(ilqr_problem_closed_loop(p, cl.S, x0, w, ff, o.cost.data(), o.X.data(), o.U.data()));
+        // the statistics of k_closed_loop_stats, restated on the host: the costs are already here.  Same two passes in sample order, but the device
+        // may contract (v - mean)^2 into the sum: the two agree to rounding, not bit for bit (min, max and n_bad are exact on both)
+        for (int b = 0; b < B; b++) {
+            const double* cb = o.cost.data() + (size_t)b * cl.S;
+            int nf = 0;
+            double sum = 0, lo = INFINITY, hi = -INFINITY, ss = 0;
+            for (int s2 = 0; s2 < cl.S; s2++)
+                if (std::isfinite(cb[s2])) { nf++; sum += cb[s2]; lo = std::min(lo, cb[s2]); hi = std::max(hi, cb[s2]); }
+            const double mean = sum / nf;
+            for (int s2 = 0; s2 < cl.S; s2++)
+                if (std::isfinite(cb[s2])) ss += (cb[s2] - mean) * (cb[s2] - mean);
+            double* st = o.stats.data() + (size_t)b * ILQR_CL_STATS;
+            st[0] = nf ? mean : NAN; st[1] = nf > 1 ? ss / (nf - 1) : (nf ? 0.0 : NAN); st[2] = nf ? lo : NAN; st[3] = nf ? hi : NAN; st[4] = cl.S - nf;
+        }
     }
-    check(ilqr_problem_closed_loop(p, cl.S, cl.x0.empty() ? nullptr : cl.x0.data(), cl.w.empty() ? nullptr : cl.w.data(), cl.with_feedforward ? 1 : 0,
-                                   o.cost.data(), o.X.data(), o.U.data()));
-    // the statistics of k_closed_loop_stats, restated on the host: the costs are already here.  Same two passes in sample order, but the device may
-    // contract (v - mean)^2 into the sum: the two agree to rounding, not bit for bit (min, max and n_bad are exact on both)
-    for (int b = 0; b < B; b++) {
-        const double* cb = o.cost.data() + (size_t)b * cl.S;
-        int nf = 0;
-        double sum = 0, lo = INFINITY, hi = -INFINITY, ss = 0;
-        for (int s2 = 0; s2 < cl.S; s2++)
-            if (std::isfinite(cb[s2])) { nf++; sum += cb[s2]; lo = std::min(lo, cb[s2]); hi = std::max(hi, cb[s2]); }
-        const double mean = sum / nf;
-        for (int s2 = 0; s2 < cl.S; s2++)
-            if (std::isfinite(cb[s2])) ss += (cb[s2] - mean) * (cb[s2] - mean);
-        double* st = o.stats.data() + (size_t)b * ILQR_CL_STATS;
-        st[0] = nf ? mean : NAN; st[1] = nf > 1 ? ss / (nf - 1) : (nf ? 0.0 : NAN); st[2] = nf ? lo : NAN; st[3] = nf ? hi : NAN; st[4] = cl.S - nf;
-    }
-    if (cl.has_tol) closed_loop_report_of(p, s, B, cl, nullptr, o);
+    if (cl.has_tol) closed_loop_report_of(p, s, B, cl, cl.has_seed ? &nz : nullptr, o);
 }
 
 std::pair<BatchResult, ClosedLoopResult> ILQRRecursive::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool line_search,

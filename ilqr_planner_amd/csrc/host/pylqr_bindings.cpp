@@ -111,7 +111,6 @@ static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const p
         cl.lim_tol = lim_tol.is_none() ? 0.0 : lim_tol.cast<double>();
     }
     if (!seed.is_none()) {
-        if (!w.is_none()) throw std::runtime_error("[closed_loop_batch] give either w or seed (with seed the disturbances are drawn on the device), not both");
         cl.has_seed = true;
         cl.seed = seed.cast<unsigned long long>();
         for (int which = 0; which < 2; which++) {

@@ -24,6 +24,20 @@
 
 using namespace ilqr;
 
+// A device buffer of doubles that only grows: the staging area and the workspaces of the closed loop.  A call whose need is covered allocates nothing.
+struct DevScratch {
+    double* ptr = nullptr;
+    size_t elems = 0;
+    int reserve(ilqr_ctx* c, size_t n) {
+        if (elems >= n) return 0;
+        if (ptr) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(ptr)); ptr = nullptr; elems = 0; }  // kernels in flight may still read it
+        HIPCHK(c, hipMalloc((void**)&ptr, n * sizeof(double)));
+        elems = n;
+        return 0;
+    }
+    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; elems = 0; }
+};
+
 struct ilqr_problem {
     ilqr_ctx* ctx = nullptr;
     ilqr_problem_desc desc;  // as given: the user's dof
@@ -43,17 +57,13 @@ struct ilqr_problem {
     double* lambda0 = nullptr;                // initial multipliers, kept for ilqr_problem_reset_multipliers
     bool con_state_only = false;              // no constraint row touches the controls (enables the closed-form sweep)
     int trace_iters = 0;
-    double* staging = nullptr;  // device staging for host<->device natural-layout transfers
-    size_t staging_elems = 0;
+    DevScratch staging;  // device staging for host<->device natural-layout transfers
     int last_nb_iter = 0;
     bool has_controls = false, has_state = false;
     bool has_gains = false;  // a Riccati solve with nb_iter >= 1 has run since the inputs last changed: X, U, KD are one plan (closed_loop)
-    double* cl_cost = nullptr; // closed_loop_noise without a cost array: the per-sample costs k_closed_loop_stats reduces
-    size_t cl_cost_elems = 0;
-    double* cl_kpx = nullptr;  // closed_loop: state | control of every sample at the step-table entries (k_closed_loop_coop -> k_closed_loop_kp)
-    size_t cl_kpx_elems = 0;
-    double* cl_rep = nullptr;  // closed_loop_report through device pointers: kp_err | lim_cost where the caller asks only for their reductions
-    size_t cl_rep_elems = 0;
+    DevScratch cl_cost;  // closed_loop_noise without a cost array: the per-sample costs k_closed_loop_stats reduces
+    DevScratch cl_kpx;   // closed_loop: state | control of every sample at the step-table entries (k_closed_loop_coop -> k_closed_loop_kp)
+    DevScratch cl_rep;   // closed_loop_report through device pointers: kp_err | lim_cost where the caller asks only for their reductions
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
     BatchCPState cp;
     BatchWideState cpw;
@@ -358,14 +368,6 @@ static int dalloc(ilqr_problem* p, T** ptr, size_t n, bool zero = true) {
     return 0;
 }
 
-static int ensure_staging(ilqr_problem* p, size_t elems) {
-    if (p->staging_elems >= elems) return 0;
-    if (p->staging) { HIPCHK(p->ctx, hipStreamSynchronize(p->ctx->stream)); HIPCHK(p->ctx, hipFree(p->staging)); p->staging = nullptr; }
-    HIPCHK(p->ctx, hipMalloc((void**)&p->staging, elems * sizeof(double)));
-    p->staging_elems = elems;
-    return 0;
-}
-
 extern "C" int ilqr_problem_create(ilqr_ctx* c, const ilqr_problem_desc* d, int batch, ilqr_problem** out) {
     if (!c) return 1;
     if (!d || !out || batch <= 0) return fail(c, "bad arguments");
@@ -456,10 +458,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
     for (void* q : p->allocs) (void)hipFree(q);
-    if (p->staging) (void)hipFree(p->staging);
-    if (p->cl_kpx) (void)hipFree(p->cl_kpx);
-    if (p->cl_rep) (void)hipFree(p->cl_rep);
-    if (p->cl_cost) (void)hipFree(p->cl_cost);
+    for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_cost}) b->release();
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
     delete p;
@@ -472,9 +471,9 @@ static int upload(ilqr_problem* p, const double* src, bool src_is_dev, double* d
     const size_t n = (size_t)p->B * rows;
     const double* dsrc = src;
     if (!src_is_dev) {
-        if (ensure_staging(p, n)) return 1;
-        HIPCHK(c, hipMemcpyAsync(p->staging, src, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        dsrc = p->staging;
+        if (p->staging.reserve(c, n)) return 1;
+        HIPCHK(c, hipMemcpyAsync(p->staging.ptr, src, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        dsrc = p->staging.ptr;
     }
     if (m) launch_to_soa_map(dsrc, dst, p->B, p->Bp, outer, *m, c->stream);
     else launch_to_soa(dsrc, dst, p->B, p->Bp, rows, c->stream);
@@ -853,8 +852,8 @@ static int download(ilqr_problem* p, int mode, const double* s0, const double* s
     const size_t n = (size_t)p->B * rows;
     double* ddst = dst;
     if (!dst_is_dev) {
-        if (ensure_staging(p, n)) return 1;
-        ddst = p->staging;
+        if (p->staging.reserve(c, n)) return 1;
+        ddst = p->staging.ptr;
     }
     if (m) launch_from_soa_cur_map(s0, s1, p->bufs.cur, ddst, p->B, p->Bp, outer, *m, c->stream);
     else if (mode == GET_CUR) launch_from_soa_cur(s0, s1, p->bufs.cur, ddst, p->B, p->Bp, rows, c->stream);
@@ -862,7 +861,7 @@ static int download(ilqr_problem* p, int mode, const double* s0, const double* s
     else launch_from_soa(s0, ddst, p->B, p->Bp, rows, c->stream);
     HIPCHK(c, hipGetLastError());
     if (!dst_is_dev) {
-        HIPCHK(c, hipMemcpyAsync(dst, p->staging, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dst, p->staging.ptr, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return 0;
@@ -887,15 +886,15 @@ static int get_gains(ilqr_problem* p, double* K, double* d) {
     if (!dst) return fail(c, "null output pointer");
     const int T1 = p->T - 1, nu = p->dims.n_u, nx = p->dims.n_x;
     const size_t n = (size_t)p->B * T1 * p->udims.n_u * (K ? p->udims.n_x : 1);
-    if (ensure_staging(p, n)) return 1;
+    if (p->staging.reserve(c, n)) return 1;
     if (p->mapped)
-        launch_get_gains_map(p->bufs.KD, p->bufs.kd_sym, p->bufs.alpha, p->bufs.iters, K ? p->staging : nullptr, K ? nullptr : p->staging, p->B, p->Bp, T1, p->map,
+        launch_get_gains_map(p->bufs.KD, p->bufs.kd_sym, p->bufs.alpha, p->bufs.iters, K ? p->staging.ptr : nullptr, K ? nullptr : p->staging.ptr, p->B, p->Bp, T1, p->map,
                              c->stream);
     else
-        launch_get_gains(p->bufs.KD, p->bufs.kd_sym, p->bufs.alpha, p->bufs.iters, K ? p->staging : nullptr, K ? nullptr : p->staging, p->B, p->Bp, T1, nu, nx,
+        launch_get_gains(p->bufs.KD, p->bufs.kd_sym, p->bufs.alpha, p->bufs.iters, K ? p->staging.ptr : nullptr, K ? nullptr : p->staging.ptr, p->B, p->Bp, T1, nu, nx,
                          c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(dst, p->staging, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, p->staging.ptr, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -922,10 +921,10 @@ static int track(ilqr_problem* p, int k, const double* x_meas, int with_ff, doub
     const double* xs = x_meas;
     double* us = u_out;
     if (!dev) {
-        if (ensure_staging(p, nxb + nub)) return 1;
-        HIPCHK(c, hipMemcpyAsync(p->staging, x_meas, nxb * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        xs = p->staging;
-        us = p->staging + nxb;
+        if (p->staging.reserve(c, nxb + nub)) return 1;
+        HIPCHK(c, hipMemcpyAsync(p->staging.ptr, x_meas, nxb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        xs = p->staging.ptr;
+        us = p->staging.ptr + nxb;
     }
     if (p->mapped) launch_track_map(p->bufs, xs, k, with_ff, us, p->B, p->map, c->stream);
     else launch_track(p->bufs, xs, k, with_ff, us, p->B, p->dims.n_x, p->dims.n_u, c->stream);
@@ -943,167 +942,219 @@ extern "C" int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_me
     return track(p, k, x_meas, with_feedforward, u_out, true);
 }
 
-
+// ------------------------------------------------------------------------------------------------ closed loop
 // Closed loop of the tracking law on the last plan (ilqr_closed_loop.hpp): n_samples executions per instance.  Which kernel runs is decided by
-// plan_closed_loop; chains of fewer than 7 joints take the generic kernel's mapped variant.
-// nz: ilqr_problem_closed_loop_noise (noisy) -- the draws of ilqr_noise.hpp in place of w, and stats / w_out.
-// report: ilqr_problem_closed_loop_report -- the same rollout with the states of the step-table entries and the limit share kept (ClArgs::kpx,
-// lim_cost), then k_closed_loop_kp_err and the two reductions; cost may be null, and noisy is "a noise was given".
-static int closed_loop(ilqr_problem* p, int S, const double* x0, const double* w, int with_ff, double* cost, double* X, double* U, bool dev,
-                       bool noisy = false, const ilqr_noise* nz = nullptr, double* stats = nullptr, double* w_out = nullptr, bool report = false,
-                       const ilqr_cl_tol* tol = nullptr, const ilqr_cl_report* out = nullptr) {
-    if (!p) return 1;
+// plan_closed_loop; chains of fewer than 7 joints take the generic kernel's mapped variant.  Each of the six entry points fills a ClRequest, and
+// closed_loop does its jobs in turn: cl_check (every refusal), cl_bind (the memory the kernels see every array in), cl_launch and, for host
+// pointers, ClStaging::fetch.
+struct ClRequest {
+    int S = 0;
+    const double *x0 = nullptr, *w = nullptr;  // [B][S][n_x], [B][S][T-1][n_x] or null
+    int with_ff = 0;
+    double *cost = nullptr, *X = nullptr, *U = nullptr;
+    bool dev = false;  // every array is a device pointer, and the call is asynchronous
+    // draw the disturbances (ilqr_noise.hpp).  The entry point's own flag, not "a noise is given": ilqr_problem_closed_loop_noise sets it always
+    // (and a null noise is refused), ilqr_problem_closed_loop_report where a noise is given
+    bool noisy = false;
+    const ilqr_noise* noise = nullptr;
+    double *stats = nullptr, *w_out = nullptr;
+    // ilqr_problem_closed_loop_report: the same rollout with the states of the step-table entries and the limit share kept (ClArgs::kpx,
+    // lim_cost), then k_closed_loop_kp_err and the two reductions; cost may be null
+    bool report = false;
+    const ilqr_cl_tol* tol = nullptr;
+    const ilqr_cl_report* out = nullptr;
+};
+
+// Every refusal, before anything is allocated or launched; the caller sees the first condition that fails.
+static int cl_check(const ilqr_problem* p, const ClRequest& rq) {
     ilqr_ctx* c = p->ctx;
     if (!p->has_gains)
         return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) since the problem's inputs last changed");
-    if (S < 1) return fail(c, "n_samples must be >= 1");
+    if (rq.S < 1) return fail(c, "n_samples must be >= 1");
     const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u;
-    if (noisy) {
+    if (rq.noisy) {
+        const ilqr_noise* nz = rq.noise;
         if (!nz) return fail(c, "noise is a null pointer");
         for (int i = 0; i < nxu; i++)
             if (!(nz->sigma_w[i] >= 0) || !std::isfinite(nz->sigma_w[i]) || !(nz->sigma_x0[i] >= 0) || !std::isfinite(nz->sigma_x0[i]))
                 return fail(c, "closed loop: every sigma_w and sigma_x0 must be finite and >= 0");
-        if (!report && !cost && !stats) return fail(c, "cost and stats are both null pointers");
+        if (!rq.report && !rq.cost && !rq.stats) return fail(c, "cost and stats are both null pointers");
         if ((unsigned long long)nz->instance_offset + (unsigned long long)p->B > (1ull << 32) ||
-            (unsigned long long)nz->sample_offset + (unsigned long long)S > (1ull << 32))
+            (unsigned long long)nz->sample_offset + (unsigned long long)rq.S > (1ull << 32))
             return fail(c, "closed loop: instance_offset + B or sample_offset + n_samples exceeds 2^32 (the generator's counter)");
-    } else if (!report && !cost) return fail(c, "cost is a null pointer");
-    const int n_kp = p->hdesc.steps.kp[p->hdesc.steps.n];
-    ilqr_cl_report rp = {};
-    if (report) {
-        if (noisy && w) return fail(c, "closed loop report: noise and w are both given (the draw or the caller's disturbances, not both)");
+    } else if (!rq.report && !rq.cost) return fail(c, "cost is a null pointer");
+    if (rq.report) {
+        const ilqr_cl_tol* tol = rq.tol;
+        const ilqr_cl_report* out = rq.out;
+        if (rq.noisy && rq.w) return fail(c, "closed loop report: noise and w are both given (the draw or the caller's disturbances, not both)");
         if (!out || (!out->kp_err && !out->kp_stats && !out->lim_cost && !out->outcome))
             return fail(c, "closed loop report: every report output is a null pointer");
-        rp = *out;
         if (tol) {
             bool nan = std::isnan(tol->lim_tol);
-            for (int k = 0; k < n_kp; k++)
+            for (int k = 0; k < p->hdesc.steps.kp[p->hdesc.steps.n]; k++)
                 for (int g = 0; g < ILQR_KP_ERR; g++) nan = nan || std::isnan(tol->kp_tol[k][g]);
             if (nan) return fail(c, "closed loop report: a tolerance is NaN");
             if (tol->lim_tol < 0) return fail(c, "closed loop report: lim_tol must be >= 0");
-        } else if (rp.kp_stats || rp.outcome)
+        } else if (out->kp_stats || out->outcome)
             return fail(c, "closed loop report: tol is a null pointer while kp_stats or outcome is asked for");
     }
-    const size_t n = (size_t)p->B * S;
-    const size_t n_x0 = x0 ? n * nxu : 0, n_w = w ? n * (T - 1) * nxu : 0, n_X = X ? n * T * nxu : 0, n_U = U ? n * (T - 1) * nuu : 0;
-    const size_t n_wo = w_out ? n * (T - 1) * nxu : 0, n_st = stats ? (size_t)p->B * ILQR_CL_STATS : 0;
     // the kernels address the caller's arrays with 32-bit element offsets
-    if ((noisy || report) && !X && !U && !w_out && !w) {  // no per-step array: x0 and cost are the longest
+    const size_t n = (size_t)p->B * rq.S;
+    if ((rq.noisy || rq.report) && !rq.X && !rq.U && !rq.w_out && !rq.w) {  // no per-step array: x0 and cost are the longest
         if (n * (size_t)nxu >= ((size_t)1 << 31))
             return fail(c, "closed loop: B * n_samples * n_x overflows the kernels' 32-bit offsets (split the samples over several calls)");
     } else if (n * T * (size_t)(nxu > nuu ? nxu : nuu) >= ((size_t)1 << 31))
         return fail(c, "closed loop: B * n_samples * T * n_x overflows the kernels' 32-bit offsets (split the samples over several calls)");
-    HIPCHK(c, hipSetDevice(c->device));
-    const ClosedLoopPlan pl = plan_closed_loop(p->desc.kind, p->desc.nb_deriv, S, p->B, c->n_simd, c->xc_generic || p->mapped);
-    if (pl.coop && !launch_closed_loop_coop) return fail(c, "closed loop: the cooperative kernels are not part of this build (pin the generic kernels)");
-    if (pl.coop || report) {  // the report reads the states of the step-table entries from either kernel
-        const size_t need = (size_t)(p->hdesc.steps.n > 0 ? p->hdesc.steps.n : 1) * (p->dims.n_x + p->dims.n_u) * n;
-        if (p->cl_kpx_elems < need) {
-            if (p->cl_kpx) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p->cl_kpx)); p->cl_kpx = nullptr; p->cl_kpx_elems = 0; }
-            HIPCHK(c, hipMalloc((void**)&p->cl_kpx, need * sizeof(double)));
-            p->cl_kpx_elems = need;
-        }
-    }
-    ClArgs a;
-    a.S = S; a.with_ff = with_ff ? 1 : 0; a.x0 = x0; a.w = w; a.cost = cost; a.X = X; a.U = U;
-    if (noisy) {
-        a.noise = 1; a.seed = nz->seed; a.b_off = nz->instance_offset; a.s_off = nz->sample_offset; a.w_out = w_out;
-        for (int i = 0; i < nxu; i++) { a.sigma_w[i] = nz->sigma_w[i]; a.sigma_x0[i] = nz->sigma_x0[i]; }
-    }
-    double* dstats = stats;
-    if (dev && !cost) {  // the per-sample costs live in a workspace of the problem
-        if (p->cl_cost_elems < n) {
-            if (p->cl_cost) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p->cl_cost)); p->cl_cost = nullptr; p->cl_cost_elems = 0; }
-            HIPCHK(c, hipMalloc((void**)&p->cl_cost, n * sizeof(double)));
-            p->cl_cost_elems = n;
-        }
-        a.cost = p->cl_cost;
-    }
-    // report: kp_err feeds both reductions, lim_cost the outcome; what the caller does not ask for itself lives in a workspace
-    const bool want_ke = rp.kp_err || rp.kp_stats || rp.outcome, want_lc = rp.lim_cost || rp.outcome;
-    const size_t n_ke = want_ke ? n * n_kp * ILQR_KP_ERR : 0, n_lc = want_lc ? n : 0;
-    const size_t n_ks = rp.kp_stats ? (size_t)p->B * n_kp * ILQR_KP_STATS : 0, n_oc = rp.outcome ? (size_t)p->B * ILQR_CL_OUTCOME : 0;
-    ilqr_cl_report dr = rp;  // the device side of the four outputs
-    if (report && dev) {
-        const size_t ws_ke = rp.kp_err ? 0 : n_ke, ws_lc = rp.lim_cost ? 0 : n_lc;
-        if (p->cl_rep_elems < ws_ke + ws_lc) {
-            if (p->cl_rep) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p->cl_rep)); p->cl_rep = nullptr; p->cl_rep_elems = 0; }
-            HIPCHK(c, hipMalloc((void**)&p->cl_rep, (ws_ke + ws_lc) * sizeof(double)));
-            p->cl_rep_elems = ws_ke + ws_lc;
-        }
-        if (!rp.kp_err) dr.kp_err = p->cl_rep;
-        if (!rp.lim_cost) dr.lim_cost = p->cl_rep + ws_ke;
-    }
-    if (!dev) {  // staging: x0 | w | cost | X | U | w_out | stats | kp_err | lim_cost | kp_stats | outcome
-        if (ensure_staging(p, n_x0 + n_w + n + n_X + n_U + n_wo + n_st + n_ke + n_lc + n_ks + n_oc)) return 1;
-        double* s = p->staging;
-        if (x0) { HIPCHK(c, hipMemcpyAsync(s, x0, n_x0 * sizeof(double), hipMemcpyHostToDevice, c->stream)); a.x0 = s; }
-        s += n_x0;
-        if (w) { HIPCHK(c, hipMemcpyAsync(s, w, n_w * sizeof(double), hipMemcpyHostToDevice, c->stream)); a.w = s; }
-        s += n_w;
-        a.cost = s; s += n;
-        if (X) a.X = s;
-        s += n_X;
-        if (U) a.U = s;
-        s += n_U;
-        if (w_out) a.w_out = s;
-        s += n_wo;
-        if (stats) dstats = s;
-        s += n_st;
-        dr.kp_err = s; s += n_ke;
-        dr.lim_cost = s; s += n_lc;
-        dr.kp_stats = s; s += n_ks;
-        dr.outcome = s;
-    }
-    if (report) { a.kpx = pl.coop ? nullptr : p->cl_kpx; a.lim_cost = want_lc ? dr.lim_cost : nullptr; }
-    if (pl.coop) launch_closed_loop_coop(p->desc.kind, p->desc.nb_deriv, p->bufs, a, p->B, pl, p->cl_kpx, c->stream);
-    else launch_closed_loop(p->desc.kind, p->desc.nb_deriv, p->bufs, a, p->B, p->mapped ? &p->map : nullptr, c->stream);
-    if (stats) launch_closed_loop_stats(a.cost, p->B, S, dstats, c->stream);
-    if (report) {
-        if (want_ke) launch_closed_loop_kp_err(p->desc.kind, p->desc.nb_deriv, p->bufs, p->B, S, n_kp, p->cl_kpx, dr.kp_err, c->stream);
-        if (rp.kp_stats) launch_closed_loop_kp_stats(dr.kp_err, *tol, p->B, S, n_kp, dr.kp_stats, c->stream);
-        if (rp.outcome) launch_closed_loop_outcome(a.cost, dr.kp_err, dr.lim_cost, *tol, p->B, S, n_kp, dr.outcome, c->stream);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (!dev) {
-        if (cost) HIPCHK(c, hipMemcpyAsync(cost, a.cost, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (stats) HIPCHK(c, hipMemcpyAsync(stats, dstats, n_st * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (w_out) HIPCHK(c, hipMemcpyAsync(w_out, a.w_out, n_wo * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, n_X * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (U) HIPCHK(c, hipMemcpyAsync(U, a.U, n_U * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (rp.kp_err && n_ke) HIPCHK(c, hipMemcpyAsync(rp.kp_err, dr.kp_err, n_ke * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (rp.lim_cost) HIPCHK(c, hipMemcpyAsync(rp.lim_cost, dr.lim_cost, n_lc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (rp.kp_stats && n_ks) HIPCHK(c, hipMemcpyAsync(rp.kp_stats, dr.kp_stats, n_ks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (rp.outcome) HIPCHK(c, hipMemcpyAsync(rp.outcome, dr.outcome, n_oc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
     return 0;
 }
+
+// The staging area of a host-pointer call, laid out by one cursor: every slice is the next n doubles.  cl_bind walks it twice, first without a
+// base, which gives the size to reserve (nothing is copied or noted), then over the reserved area: the size cannot disagree with the walk.
+struct ClStaging {
+    ilqr_ctx* c;
+    double* base;
+    size_t used = 0;
+    bool failed = false;  // a copy in has failed: the context holds the error
+    struct Back { double* host; const double* dev; size_t n; } back[9];  // at most cost, stats, w_out, X, U and the four report outputs
+    int n_back = 0;
+    int copy(void* dst, const void* src, size_t n, hipMemcpyKind kind) { HIPCHK(c, hipMemcpyAsync(dst, src, n * sizeof(double), kind, c->stream)); return 0; }
+    double* take(size_t n) { used += n; return base ? base + (used - n) : nullptr; }
+    const double* take_in(const double* host, size_t n) {  // ... filled with the caller's input
+        double* s = take(n);
+        if (base && copy(s, host, n, hipMemcpyHostToDevice)) failed = true;
+        return s;
+    }
+    double* take_out(double* host, size_t n) {  // ... which fetch copies to `host`, where there is one
+        double* s = take(n);
+        if (base && host && n) back[n_back++] = {host, s, n};
+        return s;
+    }
+    int fetch() {
+        for (int i = 0; i < n_back; i++)
+            if (copy(back[i].host, back[i].dev, back[i].n, hipMemcpyDeviceToHost)) return 1;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+};
+
+struct ClBound {  // what the kernels see
+    ClArgs a;
+    double* stats = nullptr;  // the device side of stats
+    ilqr_cl_report dr = {};   // ... and of the four report outputs
+};
+
+// Per array: the caller's device pointer, a slice of staging (host pointers), or a workspace of the problem (what the caller does not ask for
+// but a kernel reads).  rq has passed cl_check.
+static int cl_bind(ilqr_problem* p, const ClRequest& rq, const ClosedLoopPlan& pl, ClStaging& stg, ClBound& b) {
+    ilqr_ctx* c = p->ctx;
+    const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u;
+    const size_t n = (size_t)p->B * rq.S;
+    const ilqr_cl_report rp = rq.report ? *rq.out : ilqr_cl_report{};
+    const int n_kp = p->hdesc.steps.kp[p->hdesc.steps.n];
+    const bool want_ke = rp.kp_err || rp.kp_stats || rp.outcome, want_lc = rp.lim_cost || rp.outcome;  // kp_err feeds both reductions, lim_cost the outcome
+    const size_t n_ke = want_ke ? n * n_kp * ILQR_KP_ERR : 0, n_lc = want_lc ? n : 0;
+    if (pl.coop || rq.report)  // the report reads the states of the step-table entries from either kernel
+        if (p->cl_kpx.reserve(c, (size_t)(p->hdesc.steps.n > 0 ? p->hdesc.steps.n : 1) * (p->dims.n_x + p->dims.n_u) * n)) return 1;
+    ClArgs& a = b.a;
+    a.S = rq.S; a.with_ff = rq.with_ff ? 1 : 0; a.x0 = rq.x0; a.w = rq.w; a.cost = rq.cost; a.X = rq.X; a.U = rq.U; a.w_out = rq.w_out;
+    if (rq.noisy) {
+        a.noise = 1; a.seed = rq.noise->seed; a.b_off = rq.noise->instance_offset; a.s_off = rq.noise->sample_offset;
+        for (int i = 0; i < nxu; i++) { a.sigma_w[i] = rq.noise->sigma_w[i]; a.sigma_x0[i] = rq.noise->sigma_x0[i]; }
+    }
+    b.stats = rq.stats;
+    b.dr = rp;
+    if (rq.dev) {
+        if (!rq.cost) {  // the per-sample costs live in a workspace: stats and outcome read them there
+            if (p->cl_cost.reserve(c, n)) return 1;
+            a.cost = p->cl_cost.ptr;
+        }
+        if (rq.report) {  // kp_err | lim_cost where the caller asks only for their reductions
+            const size_t ws_ke = rp.kp_err ? 0 : n_ke, ws_lc = rp.lim_cost ? 0 : n_lc;
+            if (p->cl_rep.reserve(c, ws_ke + ws_lc)) return 1;
+            if (!rp.kp_err) b.dr.kp_err = p->cl_rep.ptr;
+            if (!rp.lim_cost) b.dr.lim_cost = p->cl_rep.ptr + ws_ke;
+        }
+    } else {
+        if (rq.x0) a.x0 = stg.take_in(rq.x0, n * nxu);
+        if (rq.w) a.w = stg.take_in(rq.w, n * (T - 1) * nxu);
+        a.cost = stg.take_out(rq.cost, n);  // always staged: stats and outcome read it
+        if (rq.stats) b.stats = stg.take_out(rq.stats, (size_t)p->B * ILQR_CL_STATS);
+        if (rq.w_out) a.w_out = stg.take_out(rq.w_out, n * (T - 1) * nxu);
+        if (rq.X) a.X = stg.take_out(rq.X, n * T * nxu);
+        if (rq.U) a.U = stg.take_out(rq.U, n * (T - 1) * nuu);
+        if (rq.report) {
+            b.dr.kp_err = stg.take_out(rp.kp_err, n_ke);
+            b.dr.lim_cost = stg.take_out(rp.lim_cost, n_lc);
+            b.dr.kp_stats = stg.take_out(rp.kp_stats, rp.kp_stats ? (size_t)p->B * n_kp * ILQR_KP_STATS : 0);
+            b.dr.outcome = stg.take_out(rp.outcome, rp.outcome ? (size_t)p->B * ILQR_CL_OUTCOME : 0);
+        }
+        if (stg.failed) return 1;
+    }
+    if (rq.report) { a.kpx = pl.coop ? nullptr : p->cl_kpx.ptr; a.lim_cost = want_lc ? b.dr.lim_cost : nullptr; }
+    return 0;
+}
+
+static void cl_launch(ilqr_problem* p, const ClRequest& rq, const ClosedLoopPlan& pl, const ClBound& b) {
+    const int kind = p->desc.kind, nd = p->desc.nb_deriv, B = p->B, S = rq.S, n_kp = p->hdesc.steps.kp[p->hdesc.steps.n];
+    hipStream_t st = p->ctx->stream;
+    if (pl.coop) launch_closed_loop_coop(kind, nd, p->bufs, b.a, B, pl, p->cl_kpx.ptr, st);
+    else launch_closed_loop(kind, nd, p->bufs, b.a, B, p->mapped ? &p->map : nullptr, st);
+    if (rq.stats) launch_closed_loop_stats(b.a.cost, B, S, b.stats, st);
+    if (!rq.report) return;
+    const ilqr_cl_report& rp = *rq.out;
+    if (rp.kp_err || rp.kp_stats || rp.outcome) launch_closed_loop_kp_err(kind, nd, p->bufs, B, S, n_kp, p->cl_kpx.ptr, b.dr.kp_err, st);
+    if (rp.kp_stats) launch_closed_loop_kp_stats(b.dr.kp_err, *rq.tol, B, S, n_kp, b.dr.kp_stats, st);
+    if (rp.outcome) launch_closed_loop_outcome(b.a.cost, b.dr.kp_err, b.dr.lim_cost, *rq.tol, B, S, n_kp, b.dr.outcome, st);
+}
+
+static int closed_loop(ilqr_problem* p, const ClRequest& rq) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    if (cl_check(p, rq)) return 1;
+    HIPCHK(c, hipSetDevice(c->device));
+    const ClosedLoopPlan pl = plan_closed_loop(p->desc.kind, p->desc.nb_deriv, rq.S, p->B, c->n_simd, c->xc_generic || p->mapped);
+    if (pl.coop && !launch_closed_loop_coop) return fail(c, "closed loop: the cooperative kernels are not part of this build (pin the generic kernels)");
+    ClBound b;
+    if (!rq.dev) {  // the sizing walk
+        ClStaging size{c, nullptr};
+        if (cl_bind(p, rq, pl, size, b) || p->staging.reserve(c, size.used)) return 1;
+    }
+    ClStaging stg{c, rq.dev ? nullptr : p->staging.ptr};
+    if (cl_bind(p, rq, pl, stg, b)) return 1;
+    cl_launch(p, rq, pl, b);
+    HIPCHK(c, hipGetLastError());
+    return rq.dev ? 0 : stg.fetch();
+}
+
 extern "C" int ilqr_problem_closed_loop(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost, double* X,
                                         double* U) {
-    return closed_loop(p, n_samples, x0, w, with_feedforward, cost, X, U, false);
+    return closed_loop(p, {.S = n_samples, .x0 = x0, .w = w, .with_ff = with_feedforward, .cost = cost, .X = X, .U = U});
 }
 extern "C" int ilqr_problem_closed_loop_dev(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost,
                                             double* X, double* U) {
-    return closed_loop(p, n_samples, x0, w, with_feedforward, cost, X, U, true);
+    return closed_loop(p, {.S = n_samples, .x0 = x0, .w = w, .with_ff = with_feedforward, .cost = cost, .X = X, .U = U, .dev = true});
 }
 
 extern "C" int ilqr_problem_closed_loop_noise(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, int with_feedforward,
                                               double* cost, double* stats, double* X, double* U, double* w_out) {
-    return closed_loop(p, n_samples, x0, nullptr, with_feedforward, cost, X, U, false, true, noise, stats, w_out);
+    return closed_loop(p, {.S = n_samples, .x0 = x0, .with_ff = with_feedforward, .cost = cost, .X = X, .U = U, .noisy = true, .noise = noise,
+                           .stats = stats, .w_out = w_out});
 }
 extern "C" int ilqr_problem_closed_loop_noise_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, int with_feedforward,
                                                   double* cost, double* stats, double* X, double* U, double* w_out) {
-    return closed_loop(p, n_samples, x0, nullptr, with_feedforward, cost, X, U, true, true, noise, stats, w_out);
+    return closed_loop(p, {.S = n_samples, .x0 = x0, .with_ff = with_feedforward, .cost = cost, .X = X, .U = U, .dev = true, .noisy = true,
+                           .noise = noise, .stats = stats, .w_out = w_out});
 }
 
 extern "C" int ilqr_problem_closed_loop_report(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
                                                int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out) {
-    return closed_loop(p, n_samples, x0, w, with_feedforward, cost, nullptr, nullptr, false, noise != nullptr, noise, stats, nullptr, true, tol, out);
+    return closed_loop(p, {.S = n_samples, .x0 = x0, .w = w, .with_ff = with_feedforward, .cost = cost, .noisy = noise != nullptr, .noise = noise,
+                           .stats = stats, .report = true, .tol = tol, .out = out});
 }
 extern "C" int ilqr_problem_closed_loop_report_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
                                                    int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out) {
-    return closed_loop(p, n_samples, x0, w, with_feedforward, cost, nullptr, nullptr, true, noise != nullptr, noise, stats, nullptr, true, tol, out);
+    return closed_loop(p, {.S = n_samples, .x0 = x0, .w = w, .with_ff = with_feedforward, .cost = cost, .dev = true, .noisy = noise != nullptr,
+                           .noise = noise, .stats = stats, .report = true, .tol = tol, .out = out});
 }
 
 extern "C" int ilqr_problem_get_K(ilqr_problem* p, double* K) { return get_gains(p, K, nullptr); }
@@ -1140,16 +1191,16 @@ extern "C" int ilqr_problem_get_fX(ilqr_problem* p, double* fX) {
     ilqr_ctx* c = p->ctx;
     if (!fX) return fail(c, "null output pointer");
     const size_t n = (size_t)p->B * p->T * p->dims.n_f;
-    if (ensure_staging(p, n)) return 1;
+    if (p->staging.reserve(c, n)) return 1;
     {
         ProfScope ps(c, ILQR_PROF_OTHER);
-        launch_fx_all(p->desc.kind, p->desc.nb_deriv, p->bufs, p->B, p->T, p->staging, c->stream);
+        launch_fx_all(p->desc.kind, p->desc.nb_deriv, p->bufs, p->B, p->T, p->staging.ptr, c->stream);
     }
     prof_mark(c, -1);
     HIPCHK(c, hipGetLastError());
     const bool narrow = p->udims.n_f != p->dims.n_f;  // f(x) = x of a joint-space system of fewer than 7 joints: the state map
     std::vector<double> wide(narrow ? n : 0);
-    HIPCHK(c, hipMemcpyAsync(narrow ? wide.data() : fX, p->staging, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(narrow ? wide.data() : fX, p->staging.ptr, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (narrow) {
         const IndexMap& mx = p->map.x;
