@@ -36,7 +36,7 @@ EXPORTS = [
     "ilqr_profile_enable", "ilqr_profile_reset", "ilqr_profile_get", "ilqr_chain_from_urdf", "ilqr_urdf_last_error",
     "ilqr_problem_reset_multipliers", "ilqr_problem_warm_start", "ilqr_problem_track", "ilqr_problem_track_dev",
     "ilqr_problem_closed_loop", "ilqr_problem_closed_loop_dev", "ilqr_problem_closed_loop_noise", "ilqr_problem_closed_loop_noise_dev",
-    "ilqr_problem_closed_loop_report", "ilqr_problem_closed_loop_report_dev",
+    "ilqr_problem_closed_loop_report", "ilqr_problem_closed_loop_report_dev", "ilqr_problem_closed_loop_cov", "ilqr_problem_closed_loop_cov_dev",
     "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
@@ -113,6 +113,13 @@ class Report(C.Structure):
     _fields_ = [("kp_err", C.c_void_p), ("kp_stats", C.c_void_p), ("lim_cost", C.c_void_p), ("outcome", C.c_void_p)]
 
 
+class Cov(C.Structure):
+    """Mirror of ilqr_cl_cov: five pointers (host or device), 0 / None where the output is not asked for."""
+
+    _fields_ = [("Sigma", C.c_void_p), ("kp_Sigma", C.c_void_p), ("kp_var", C.c_void_p), ("u_var", C.c_void_p), ("lim_z", C.c_void_p)]
+
+
+ClosedLoopCov = collections.namedtuple("ClosedLoopCov", "Sigma kp_Sigma kp_var u_var lim_z")
 ClosedLoopNoise = collections.namedtuple("ClosedLoopNoise", "cost stats X U w")
 ClosedLoopReport = collections.namedtuple("ClosedLoopReport", "cost stats kp_err kp_stats lim_cost outcome X U w")
 
@@ -162,6 +169,8 @@ def load():
     L.ilqr_problem_closed_loop_noise_dev.argtypes = [vp, C.c_int, C.POINTER(Noise), vp, C.c_int, vp, vp, vp, vp, vp]
     L.ilqr_problem_closed_loop_report.argtypes = [vp, C.c_int, C.POINTER(Noise), dp, dp, C.c_int, C.POINTER(Tol), dp, dp, C.POINTER(Report)]
     L.ilqr_problem_closed_loop_report_dev.argtypes = [vp, C.c_int, C.POINTER(Noise), vp, vp, C.c_int, C.POINTER(Tol), vp, vp, C.POINTER(Report)]
+    L.ilqr_problem_closed_loop_cov.argtypes = [vp, dp, dp, C.POINTER(Cov)]
+    L.ilqr_problem_closed_loop_cov_dev.argtypes = [vp, dp, dp, C.POINTER(Cov)]
     L.ilqr_solve_recursive.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.ilqr_solve_al.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]
     L.ilqr_solve_batch_cp.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
@@ -609,6 +618,30 @@ class BatchProblem:
                                                                   x0_ptr or None, w_ptr or None, int(bool(with_feedforward)),
                                                                   C.byref(tol) if tol is not None else None, cost_ptr or None, stats_ptr or None,
                                                                   C.byref(rp)))
+
+    def _sigma(self, sig):
+        """A sigma of a covariance call: None (zeros, passed as NULL), a scalar (every entry) or n_x values in the user's state layout."""
+        return None if sig is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sig, dtype=np.float64), (self.dims.n_x,)))
+
+    def closed_loop_cov(self, sigma_w=None, sigma_x0=None, want_Sigma: bool = False, want_kp_Sigma: bool = True, want_kp_var: bool = True,
+                        want_u_var: bool = True, want_lim_z: bool = True):
+        """The state covariance of the closed loop under the noise model of closed_loop_noise, propagated analytically on the device
+        (ilqr_problem_closed_loop_cov; definitions in include/ilqr_hip.h): Sigma [B][T][n_x][n_x], kp_Sigma [B][n_kp][n_x][n_x], kp_var
+        [B][n_kp][5] (pos, orn, vel, angvel, time), u_var [B][T-1][n_u], lim_z [B].  Returns a ClosedLoopCov; what was not asked for is None."""
+        nx = self.dims.n_x
+        Sigma, kp_Sigma = _out(want_Sigma, self.B, self.T, nx, nx), _out(want_kp_Sigma, self.B, self.n_kp, nx, nx)
+        kp_var, u_var = _out(want_kp_var, self.B, self.n_kp, KP_ERR), _out(want_u_var, self.B, self.T - 1, self.dims.n_u)
+        lim_z = _out(want_lim_z, self.B)
+        cv = Cov(*(a.ctypes.data if a is not None else None for a in (Sigma, kp_Sigma, kp_var, u_var, lim_z)))
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_cov(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)), C.byref(cv)))
+        return ClosedLoopCov(Sigma, kp_Sigma, kp_var, u_var, lim_z)
+
+    def closed_loop_cov_dev(self, sigma_w=None, sigma_x0=None, Sigma_ptr=None, kp_Sigma_ptr=None, kp_var_ptr=None, u_var_ptr=None, lim_z_ptr=None):
+        """Device pointers (0 / None where the output is not asked for), asynchronous on the context's stream; the sigmas are host values."""
+        cv = Cov(Sigma_ptr or None, kp_Sigma_ptr or None, kp_var_ptr or None, u_var_ptr or None, lim_z_ptr or None)
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_cov_dev(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)), C.byref(cv)))
 
     def close(self):
         if self.h:

@@ -1555,6 +1555,33 @@ static void closed_loop_of(ilqr_problem* p, sys::System& s, int B, const ClosedL
     if (cl.has_tol) closed_loop_report_of(p, s, B, cl, cl.has_seed ? &nz : nullptr, o);
 }
 
+void closed_loop_cov_sigma_error() { throw std::runtime_error("[closed_loop_batch] sigma_w and sigma_x0 must be a scalar or have nb_state_var entries"); }
+
+// ilqr_problem_closed_loop_cov on the problem a batched solve has just finished with
+static void closed_loop_cov_of(ilqr_problem* p, sys::System& s, int B, const ClosedLoopCovInputs& cv, ClosedLoopCovResult& o) {
+    o.B = B; o.T = s.getHorizon(); o.n_x = s.getNbStateVar(); o.n_u = s.getNbCtrlVar(); o.n_kp = (int)s.deviceKeypoints().size();
+    std::vector<double> sg[2];
+    for (int which = 0; which < 2; which++) {
+        const std::vector<double>& in = which ? cv.sigma_x0 : cv.sigma_w;
+        if (in.size() > 1 && (int)in.size() != o.n_x) closed_loop_cov_sigma_error();
+        for (int i = 0; i < o.n_x && !in.empty(); i++) sg[which].push_back(in.size() == 1 ? in[0] : in[i]);
+    }
+    const size_t nn = (size_t)o.n_x * o.n_x;
+    if (cv.want_Sigma) o.Sigma.resize((size_t)B * o.T * nn);
+    o.kp_Sigma.resize((size_t)B * o.n_kp * nn); o.kp_var.resize((size_t)B * o.n_kp * ILQR_CL_COV_KP);
+    o.u_var.resize((size_t)B * (o.T - 1) * o.n_u); o.lim_z.resize((size_t)B);
+    ilqr_cl_cov out{cv.want_Sigma ? o.Sigma.data() : nullptr, o.kp_Sigma.data(), o.kp_var.data(), o.u_var.data(), o.lim_z.data()};
+    check(ilqr_problem_closed_loop_cov(p, sg[0].empty() ? nullptr : sg[0].data(), sg[1].empty() ? nullptr : sg[1].data(), &out));
+}
+
+std::pair<BatchResult, ClosedLoopCovResult> ILQRRecursive::closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool line_search,
+                                                                              bool early_stop) {
+    ClosedLoopCovResult o;
+    BatchResult r = run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) { check(ilqr_solve_recursive(p, nb_iter, line_search, early_stop)); },
+                              [&](ilqr_problem* p) { closed_loop_cov_of(p, *s, in.B, cv, o); });
+    return {std::move(r), std::move(o)};
+}
+
 std::pair<BatchResult, ClosedLoopResult> ILQRRecursive::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool line_search,
                                                                         bool early_stop) {
     ClosedLoopResult o;
@@ -1597,6 +1624,13 @@ std::pair<BatchResult, ClosedLoopResult> AL_ILQR::closedLoopBatch(const BatchInp
                                                                   double scaling, bool line_search, bool early_stop) {
     ClosedLoopResult o;
     BatchResult r = solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, [&](ilqr_problem* p) { closed_loop_of(p, *s, in.B, cl, o); });
+    return {std::move(r), std::move(o)};
+}
+
+std::pair<BatchResult, ClosedLoopCovResult> AL_ILQR::closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, int lag, double penalty,
+                                                                        double scaling, bool line_search, bool early_stop) {
+    ClosedLoopCovResult o;
+    BatchResult r = solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, [&](ilqr_problem* p) { closed_loop_cov_of(p, *s, in.B, cv, o); });
     return {std::move(r), std::move(o)};
 }
 

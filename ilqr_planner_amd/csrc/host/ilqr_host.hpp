@@ -497,6 +497,19 @@ struct ClosedLoopResult {
     std::vector<double> kp_err, kp_stats, lim_cost, outcome;
 };
 
+// The covariance of that closed loop under the noise model of ClosedLoopInputs::seed, propagated analytically (ilqr_problem_closed_loop_cov)
+struct ClosedLoopCovInputs {
+    std::vector<double> sigma_w, sigma_x0;   // one value (every entry) or n_x values; empty: 0
+    bool want_Sigma = false;                 // the covariance at every step (B T n_x^2 doubles)
+};
+// the one place of closed_loop_cov_batch's rule for a sigma (a scalar or nb_state_var entries) and of its error text, which is closed_loop_batch's
+[[noreturn]] void closed_loop_cov_sigma_error();
+struct ClosedLoopCovResult {
+    int B = 0, T = 0, n_x = 0, n_u = 0, n_kp = 0;
+    std::vector<double> Sigma;                           // [B][T][n_x][n_x], empty unless asked for
+    std::vector<double> kp_Sigma, kp_var, u_var, lim_z;  // [B][n_kp][n_x][n_x], [B][n_kp][5], [B][T-1][n_u], [B]
+};
+
 struct Constraint {  // AL-ILQR.h:20-23
     Mat A;
     Vec b;
@@ -523,6 +536,9 @@ public:
     // solveBatch, then the closed loop on its plan, in one stateless call
     std::pair<BatchResult, ClosedLoopResult> closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool line_search = true,
                                                              bool early_stop = true);
+    // solveBatch, then the analytic covariance of the closed loop on its plan
+    std::pair<BatchResult, ClosedLoopCovResult> closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool line_search = true,
+                                                                   bool early_stop = true);
 
 private:
     std::shared_ptr<sys::System> s;
@@ -538,6 +554,8 @@ public:
                            bool early_stop = false);
     std::pair<BatchResult, ClosedLoopResult> closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, int lag_update_step, double penalty,
                                                              double scaling_factor, bool line_search = true, bool early_stop = false);
+    std::pair<BatchResult, ClosedLoopCovResult> closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, int lag_update_step,
+                                                                   double penalty, double scaling_factor, bool line_search = true, bool early_stop = false);
 
 private:
     BatchResult solveBatchThen(const BatchInputs& in, int nb_iter, int lag_update_step, double penalty, double scaling_factor, bool line_search, bool early_stop,

@@ -138,6 +138,20 @@ static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const p
     return cl;
 }
 
+// numpy -> ClosedLoopCovInputs: a sigma is None, a scalar or nb_state_var entries
+static solver::ClosedLoopCovInputs closed_loop_cov_inputs(const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
+    solver::ClosedLoopCovInputs cv;
+    cv.want_Sigma = want_Sigma;
+    for (int which = 0; which < 2; which++) {
+        const py::object& sg = which ? sigma_x0 : sigma_w;
+        if (sg.is_none()) continue;
+        arr_t a = arr_t::ensure(sg);
+        if (!a || a.ndim() > 1) solver::closed_loop_cov_sigma_error();   // (the length is checked where nb_state_var is known)
+        (which ? cv.sigma_x0 : cv.sigma_w).assign(a.data(), a.data() + a.size());
+    }
+    return cv;
+}
+
 PYBIND11_MODULE(PyLQR, m) {
     m.doc() = "PyLQR: the reference's Python surface over the MI355X-native batched iLQR hot path (libilqr_hip.so)";
 
@@ -329,6 +343,13 @@ PYBIND11_MODULE(PyLQR, m) {
             return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.lim_cost, {r.B, r.S})); })
         .def_property_readonly("outcome", [](const solver::ClosedLoopResult& r) -> py::object {
             return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.outcome, {r.B, ILQR_CL_OUTCOME})); });
+    py::class_<solver::ClosedLoopCovResult>(m_sol, "ClosedLoopCovResult")
+        .def_property_readonly("Sigma", [](const solver::ClosedLoopCovResult& r) -> py::object {   // None unless want_Sigma
+            return r.Sigma.empty() ? py::object(py::none()) : py::object(shaped(r.Sigma, {r.B, r.T, r.n_x, r.n_x})); })
+        .def_property_readonly("kp_Sigma", [](const solver::ClosedLoopCovResult& r) { return shaped(r.kp_Sigma, {r.B, r.n_kp, r.n_x, r.n_x}); })
+        .def_property_readonly("kp_var", [](const solver::ClosedLoopCovResult& r) { return shaped(r.kp_var, {r.B, r.n_kp, ILQR_CL_COV_KP}); })
+        .def_property_readonly("u_var", [](const solver::ClosedLoopCovResult& r) { return shaped(r.u_var, {r.B, r.T - 1, r.n_u}); })
+        .def_property_readonly("lim_z", [](const solver::ClosedLoopCovResult& r) { return shaped(r.lim_z, {r.B}); });
     py::class_<solver::Constraint>(m_sol, "Constraint").def(py::init<>()).def_readwrite("A", &solver::Constraint::A).def_readwrite("b", &solver::Constraint::b);
     py::class_<solver::ILQRRecursive>(m_sol, "ILQRRecursive")
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
@@ -348,7 +369,14 @@ PYBIND11_MODULE(PyLQR, m) {
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
              py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(), py::arg("w") = py::none(), py::arg("with_feedforward") = false,
-             py::arg("samples") = py::none(), py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none());
+             py::arg("samples") = py::none(), py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none())
+        .def("closed_loop_cov_batch",
+             [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
+                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
+                 return self.closedLoopCovBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, ls, es);
+             },
+             py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
+             py::arg("kp_targets") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false);
     py::class_<solver::AL_ILQR>(m_sol, "AL_ILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const std::vector<solver::Constraint>&, const std::vector<Vec>&>(), py::arg("s"), py::arg("inequality"),
              py::arg("initLambda"))
@@ -369,7 +397,15 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(),
              py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none(), py::arg("seed") = py::none(),
-             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none());
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none())
+        .def("closed_loop_cov_batch",
+             [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
+                const py::object& kp, const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
+                 return self.closedLoopCovBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, lag, pen, sc, ls, es);
+             },
+             py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
+             py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false);
     // bindings.cpp:778-782
     py::class_<solver::BatchILQR>(m_sol, "BatchILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("Q"))

@@ -18,6 +18,7 @@
 
 #include "ilqr_batchcp.hpp"
 #include "ilqr_closed_loop.hpp"
+#include "ilqr_closed_loop_cov.hpp"
 #include "ilqr_ctx.hpp"
 #include "ilqr_kernels.hpp"
 #include "ilqr_plan.hpp"
@@ -64,6 +65,8 @@ struct ilqr_problem {
     DevScratch cl_cost;  // closed_loop_noise without a cost array: the per-sample costs k_closed_loop_stats reduces
     DevScratch cl_kpx;   // closed_loop: state | control of every sample at the step-table entries (k_closed_loop_coop -> k_closed_loop_kp)
     DevScratch cl_rep;   // closed_loop_report through device pointers: kp_err | lim_cost where the caller asks only for their reductions
+    DevScratch cl_cov_ws;   // closed_loop_cov: the per-lane matrices of the generic kernel k_cl_cov
+    DevScratch cl_cov_kps;  // closed_loop_cov through device pointers: kp_Sigma where the caller asks only for kp_var
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
     BatchCPState cp;
     BatchWideState cpw;
@@ -458,7 +461,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
     for (void* q : p->allocs) (void)hipFree(q);
-    for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_cost}) b->release();
+    for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_cost, &p->cl_cov_ws, &p->cl_cov_kps}) b->release();
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
     delete p;
@@ -1155,6 +1158,73 @@ extern "C" int ilqr_problem_closed_loop_report_dev(ilqr_problem* p, int n_sample
                                                    int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out) {
     return closed_loop(p, {.S = n_samples, .x0 = x0, .w = w, .with_ff = with_feedforward, .cost = cost, .dev = true, .noisy = noise != nullptr,
                            .noise = noise, .stats = stats, .report = true, .tol = tol, .out = out});
+}
+
+// The covariance of that closed loop, propagated analytically (ilqr_closed_loop_cov.hpp).  Which kernel runs is decided by plan_closed_loop_cov.
+// kp_var is formed from kp_Sigma by a kernel of its own, so kp_Sigma always exists where kp_var is asked for: the caller's array, a slice of
+// staging, or the problem's workspace.
+static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out, bool dev) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u, B = p->B, n_kp = p->hdesc.steps.kp[p->hdesc.steps.n];
+    for (int i = 0; i < nxu; i++)
+        for (const double* sg : {sigma_w, sigma_x0})
+            if (sg && (!(sg[i] >= 0) || !std::isfinite(sg[i]))) return fail(c, "closed loop: every sigma_w and sigma_x0 must be finite and >= 0");
+    if (!out || (!out->Sigma && !out->kp_Sigma && !out->kp_var && !out->u_var && !out->lim_z))
+        return fail(c, "closed loop cov: every output is a null pointer");
+    const size_t nn = (size_t)nxu * nxu, n_S = (size_t)B * T * nn, n_kS = (size_t)B * n_kp * nn;
+    if (const char* why = cl_cov_size_refusal(B, T, n_kp, nxu, out->Sigma != nullptr, out->kp_Sigma != nullptr)) return fail(c, why);
+    if (!p->has_gains)   // (behind the bounds on the call itself: those do not depend on the state of the problem)
+        return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) since the problem's inputs last changed");
+    HIPCHK(c, hipSetDevice(c->device));
+    const ClosedLoopCovPlan pl = plan_closed_loop_cov(p->desc.kind, p->desc.nb_deriv, B, c->n_simd, c->xc_generic || p->mapped);
+    if (pl.rows && !launch_closed_loop_cov_rows) return fail(c, "closed loop cov: the row kernel is not part of this build (pin the generic kernels)");
+
+    ClCovArgs a;
+    for (int i = 0; i < p->dims.n_x; i++) {
+        const int iu = p->mapped ? p->map.x.usr[i] : i;
+        if (iu < 0) continue;
+        a.sw2[i] = sigma_w ? sigma_w[iu] * sigma_w[iu] : 0.0;
+        a.sx02[i] = sigma_x0 ? sigma_x0[iu] * sigma_x0[iu] : 0.0;
+    }
+    const bool want_kS = (out->kp_Sigma || out->kp_var) && n_kp > 0;
+    const size_t n_kv = (size_t)B * n_kp * ILQR_CL_COV_KP, n_uv = (size_t)B * (T - 1) * nuu;
+    double* kp_var = out->kp_var;
+    a.Sigma = out->Sigma; a.kp_Sigma = out->kp_Sigma; a.u_var = out->u_var; a.lim_z = out->lim_z;
+    auto bind = [&](ClStaging& stg) {  // the staging slices of a host-pointer call (ClStaging: first the sizing walk, then the real one)
+        if (out->Sigma) a.Sigma = stg.take_out(out->Sigma, n_S);
+        a.kp_Sigma = want_kS ? stg.take_out(out->kp_Sigma, n_kS) : nullptr;
+        if (out->kp_var) kp_var = stg.take_out(out->kp_var, n_kv);
+        if (out->u_var) a.u_var = stg.take_out(out->u_var, n_uv);
+        if (out->lim_z) a.lim_z = stg.take_out(out->lim_z, (size_t)B);
+    };
+    if (!dev) {
+        ClStaging size{c, nullptr};
+        bind(size);
+        if (p->staging.reserve(c, size.used)) return 1;
+    } else if (want_kS && !out->kp_Sigma) {
+        if (p->cl_cov_kps.reserve(c, n_kS)) return 1;
+        a.kp_Sigma = p->cl_cov_kps.ptr;
+    }
+    ClStaging stg{c, dev ? nullptr : p->staging.ptr};
+    if (!dev) bind(stg);
+    if (!want_kS) a.kp_Sigma = nullptr;
+    if (!pl.rows) {
+        if (p->cl_cov_ws.reserve(c, (size_t)cl_cov_ws_entries(p->desc.kind, p->desc.nb_deriv) * p->Bp)) return 1;
+        a.ws = p->cl_cov_ws.ptr;
+    }
+    const int kind = p->desc.kind, nd = p->desc.nb_deriv;
+    if (pl.rows) launch_closed_loop_cov_rows(kind, nd, p->bufs, a, B, c->stream);
+    else launch_closed_loop_cov(kind, nd, p->bufs, a, B, p->mapped ? &p->map : nullptr, c->stream);
+    if (out->kp_var) launch_closed_loop_cov_kp(kind, nd, p->bufs, B, n_kp, p->mapped ? p->map.dof : DOF, a.kp_Sigma, kp_var, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return dev ? 0 : stg.fetch();
+}
+extern "C" int ilqr_problem_closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out) {
+    return closed_loop_cov(p, sigma_w, sigma_x0, out, false);
+}
+extern "C" int ilqr_problem_closed_loop_cov_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out) {
+    return closed_loop_cov(p, sigma_w, sigma_x0, out, true);
 }
 
 extern "C" int ilqr_problem_get_K(ilqr_problem* p, double* K) { return get_gains(p, K, nullptr); }

@@ -43,4 +43,28 @@ inline ClosedLoopPlan plan_closed_loop(int kind, int nd, int S, int B, int n_sim
     return p;
 }
 
+// Which kernel propagates the closed-loop covariance (ilqr_problem_closed_loop_cov, ilqr_closed_loop_cov.hpp).  Chains of fewer than 7 joints
+// (the caller passes them as generic_pin, as for plan_closed_loop) and the generic pin take k_cl_cov, one lane per instance; everything else
+// k_cl_cov_rows, 16 lanes per instance.  The two sum in different orders: they agree to rounding, not bit for bit.
+struct ClosedLoopCovPlan {
+    bool rows = false;   // k_cl_cov_rows; otherwise the generic k_cl_cov
+};
+
+// B and n_simd are part of the interface for a crossover by launch size; none has been measured, so they do not enter the decision.
+inline ClosedLoopCovPlan plan_closed_loop_cov(int kind, int nd, int B, int n_simd, bool generic_pin) {
+    ClosedLoopCovPlan p;
+    (void)B; (void)n_simd;
+    p.rows = !generic_pin && cl_nx(kind, nd) <= 15;
+    return p;
+}
+
+// The refusals of ilqr_problem_closed_loop_cov that depend on the call's sizes alone: the error text, or null where the call is within both
+// bounds.  n_x: the user's.  Pure, so that the bounds are checked without a problem of 2^31 entries (tests/cpp/closed_loop_cov_plan_main.cpp).
+inline const char* cl_cov_size_refusal(long long B, long long T, long long n_kp, long long n_x, bool want_Sigma, bool want_kp_Sigma) {
+    const long long lim = 1ll << 31;
+    if (want_Sigma && B * T * n_x * n_x >= lim) return "closed loop cov: B * T * n_x^2 reaches 2^31 (ask for kp_Sigma, or split the batch)";
+    if (want_kp_Sigma && B * n_kp * n_x * n_x >= lim) return "closed loop cov: B * n_kp * n_x^2 reaches 2^31 (split the batch)";
+    return nullptr;
+}
+
 }  // namespace ilqr

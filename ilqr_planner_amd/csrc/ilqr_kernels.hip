@@ -11,6 +11,7 @@
 //   forward pass + line search src/solver/ILQRRecursive.cpp:101-176 (AL: src/solver/AL-ILQR.cpp:149-227)
 // A_k, B_k are never stored: they are rebuilt from (x_k, u_k) exactly as forwardPass builds them.
 #include "ilqr_closed_loop.hpp"
+#include "ilqr_closed_loop_cov.hpp"
 #include "ilqr_kernels.hpp"
 #include "ilqr_step.hpp"
 
@@ -870,6 +871,178 @@ __global__ __launch_bounds__(64) void k_closed_loop_stats(const double* __restri
     o[4] = (double)(S - n);
 }
 
+// ---- ilqr_problem_closed_loop_cov: the covariance of the closed loop, propagated analytically (ilqr_closed_loop_cov.hpp)
+
+// One lane per instance walks the steps.  Sigma, M = F Sigma, G = K Sigma, a row of H = M K' and the time column of B live in an explicit
+// per-lane workspace (c.ws, entry e of instance b at ws[e Bp + b], as k_backward's): 225 doubles of Sigma alone would spill.  The lower
+// triangle of Sigma' is computed and mirrored, so the workspace -- and every Sigma_k stored from it -- is exactly symmetric.  MAP: a chain of
+// fewer than 7 joints; the gain entries of padded rows and columns are read as 0, so the padding takes no part (its Sigma stays 0).
+template <class S>
+constexpr int cl_cov_ws_doubles() { return 2 * S::NX * S::NX + S::NU * S::NX + S::NU + S::NX; }
+int cl_cov_ws_entries(int kind, int nd) {
+    int n = 0;
+    SysAll::dispatch(kind, nd, [&](auto s) { n = cl_cov_ws_doubles<decltype(s)>(); });
+    return n;
+}
+
+template <class S, bool MAP>
+__global__ __launch_bounds__(64) void k_cl_cov(Bufs a, ClCovArgs c, IndexMap mx, IndexMap mu) {
+    constexpr int NX = S::NX, NU = S::NU, ND = S::ND, TM = S::TM;
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= d.B) return;
+    const int Bp = d.Bp, T = d.T, cur = a.cur[b];
+    const int nxu = MAP ? mx.n_user : NX, nuu = MAP ? mu.n_user : NU;
+    const int sym = a.kd_sym, rowp = kd_rowp(NX), rs = kd_rs(sym, NU, rowp);
+    const double* Xb = a.X[cur] + b;  // entry `row` of the plan: Xb[row * Bp]
+    const double* Ub = a.U[cur] + b;
+    double* const w = c.ws + b;
+    constexpr int oS = 0, oM = oS + NX * NX, oG = oM + NX * NX, oH = oG + NU * NX, oC = oH + NU, oEnd = oC + NX;
+    static_assert(oEnd == cl_cov_ws_doubles<S>(), "workspace layout");
+#define WS(o, i, j, C) w[(size_t)((o) + (i) * (C) + (j)) * Bp]
+#define WV(o, i) w[(size_t)((o) + (i)) * Bp]
+    auto xu = [&](int i) { return MAP ? mx.usr[i] : i; };   // user index of device state entry i, < 0: padding
+    auto uu = [&](int i) { return MAP ? mu.usr[i] : i; };
+    auto ctl = [](int r) { return r < DOF ? r : ((ND == 2 && r < 2 * DOF) ? r - DOF : NU - 1); };   // the control of row r (the time row: the time control)
+    NOUNR for (int i = 0; i < NX; i++)
+        NOUNR for (int j = 0; j < NX; j++) WS(oS, i, j, NX) = (i == j) ? c.sx02[i] : 0.0;
+    double zmin = INFINITY;
+    int st = 0;  // step table walk
+    for (int k = 0; k < T; k++) {
+        // ---- what is read off Sigma_k: the outputs, the margin to the bounds
+        if (c.Sigma) {
+            double* o = c.Sigma + ((size_t)b * T + k) * nxu * nxu;
+            NOUNR for (int i = 0; i < NX; i++)
+                NOUNR for (int j = 0; j < NX; j++)
+                    if (xu(i) >= 0 && xu(j) >= 0) o[xu(i) * nxu + xu(j)] = WS(oS, i, j, NX);
+        }
+        if (st < d.steps.n && d.steps.t[st] == k) {
+            if (c.kp_Sigma) {
+                const int n_kp = d.steps.kp[d.steps.n];
+                for (int kpi = d.steps.kp[st]; kpi < d.steps.kp[st + 1]; kpi++) {
+                    double* o = c.kp_Sigma + ((size_t)b * n_kp + kpi) * nxu * nxu;
+                    NOUNR for (int i = 0; i < NX; i++)
+                        NOUNR for (int j = 0; j < NX; j++)
+                            if (xu(i) >= 0 && xu(j) >= 0) o[xu(i) * nxu + xu(j)] = WS(oS, i, j, NX);
+                }
+            }
+            st++;
+        }
+        NOUNR for (int i = 0; i < NX; i++) {
+            const double sii = WS(oS, i, i, NX);
+            if (!(sii > 0)) continue;
+            const double xi = Xb[((size_t)k * NX + i) * Bp], sd = sqrt(sii);
+            if (d.limits_set && d.lw[i] != 0) zmin = fmin(zmin, fmin(d.smax[i] - xi, xi - d.smin[i]) / sd);
+            if (d.lim2 && d.lw2[i] != 0) zmin = fmin(zmin, fmin(d.smax2[i] - xi, xi - d.smin2[i]) / sd);
+        }
+        if (k == T - 1) break;
+        // ---- the step
+        const double* rec = KD_REC(a.KD, Bp, rs, k, b);
+        auto K = [&](int i, int j) { return (MAP && (mu.usr[i] < 0 || mx.usr[j] < 0)) ? 0.0 : rec[kd_off(sym, rowp, i, j)]; };
+        const double* u = Ub + (size_t)k * NU * Bp;  // u_i = u[i Bp]
+        const double dts = TM ? u[(size_t)(NU - 1) * Bp] : 0.0;
+        const double dt = TM ? dts * dts : d.dt;
+        const double b1 = (ND == 1) ? dt : dt * dt / 2;   // B on the position rows; dt on the velocity rows
+        NOUNR for (int r = 0; r < NX; r++) {
+            const bool is_q = r < DOF, is_v = ND == 2 && r >= DOF && r < 2 * DOF, is_t = TM && r == NX - 1;
+            const double ui = is_t ? 0.0 : u[(size_t)ctl(r) * Bp], vi = (ND == 2 && is_q) ? Xb[((size_t)k * NX + DOF + r) * Bp] : 0.0;
+            WV(oC, r) = TM ? cov_time_col<ND>(is_q, is_v, is_t, dts, ui, vi) : 0.0;
+        }
+        // G = K Sigma, u_var = diag(G K')
+        NOUNR for (int i = 0; i < NU; i++) {
+            NOUNR for (int cc = 0; cc < NX; cc++) {
+                double s = 0;
+                NOUNR for (int j = 0; j < NX; j++) s += K(i, j) * WS(oS, j, cc, NX);
+                WS(oG, i, cc, NX) = s;
+            }
+            if (c.u_var && uu(i) >= 0) {
+                double s = 0;
+                NOUNR for (int cc = 0; cc < NX; cc++) s += WS(oG, i, cc, NX) * K(i, cc);
+                c.u_var[((size_t)b * (T - 1) + k) * nuu + uu(i)] = s;
+            }
+        }
+        // M = F Sigma
+        NOUNR for (int r = 0; r < NX; r++) {
+            const bool is_q = r < DOF, is_t = TM && r == NX - 1;
+            const double br = is_t ? 0.0 : (is_q ? b1 : dt), cr = WV(oC, r);
+            NOUNR for (int cc = 0; cc < NX; cc++) {
+                double m = WS(oS, r, cc, NX);
+                if (ND == 2 && is_q) m += dt * WS(oS, DOF + r, cc, NX);
+                if (!is_t) m += br * WS(oG, ctl(r), cc, NX);
+                if (TM) m += cr * WS(oG, NU - 1, cc, NX);
+                WS(oM, r, cc, NX) = m;
+            }
+        }
+        // Sigma' = M F' + diag(sigma_w^2): the lower triangle, mirrored
+        NOUNR for (int r = 0; r < NX; r++) {
+            NOUNR for (int i = 0; i < NU; i++) {
+                double s = 0;
+                NOUNR for (int j = 0; j < NX; j++) s += WS(oM, r, j, NX) * K(i, j);
+                WV(oH, i) = s;
+            }
+            NOUNR for (int cc = 0; cc <= r; cc++) {
+                const bool is_q = cc < DOF, is_t = TM && cc == NX - 1;
+                double v = WS(oM, r, cc, NX);
+                if (ND == 2 && is_q) v += dt * WS(oM, r, DOF + cc, NX);
+                if (!is_t) v += (is_q ? b1 : dt) * WV(oH, ctl(cc));
+                if (TM) v += WV(oC, cc) * WV(oH, NU - 1);
+                if (cc == r) v += c.sw2[r];
+                WS(oS, r, cc, NX) = v;
+                WS(oS, cc, r, NX) = v;
+            }
+        }
+    }
+#undef WS
+#undef WV
+    if (c.lim_z) c.lim_z[b] = zmin;
+}
+
+// kp_var[b][kpi][g]: the trace of group g's 3 x 3 block of Jf Sigma_t Jf' (include/ilqr_hip.h), one lane per (instance, keypoint), from
+// kp_Sigma [B][n_kp][n_x][n_x] on the USER's dimensions (dof joints: position j at j, velocity at dof + j, the time at ND dof) and the
+// geometric Jacobian at the plan's state of the keypoint's step (the object frame rotates a block and keeps its trace: not applied).
+// Serves both propagation kernels.
+template <class S>
+__global__ __launch_bounds__(64) void k_cl_cov_kp(Bufs a, int dof, const double* __restrict__ kp_Sigma, double* __restrict__ kp_var) {
+    constexpr int NX = S::NX, ND = S::ND;
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    const int kpi = blockIdx.y, n_kp = d.steps.kp[d.steps.n];
+    if (b >= d.B || kpi >= n_kp) return;
+    const int Bp = d.Bp, nxu = ND * dof + S::TM;
+    const double* Sg = kp_Sigma + ((size_t)b * n_kp + kpi) * nxu * nxu;
+    double var[ILQR_CL_COV_KP] = {0, 0, 0, 0, 0};
+    bool joint = S::JOINT;
+    if (!S::JOINT && ND == 1) joint = d.kp_joint[kpi] != 0;
+    if (joint) {
+        double s = 0;
+        for (int j = 0; j < dof; j++) s += Sg[j * nxu + j];
+        var[ILQR_KP_ERR_POS] = s;
+    } else {
+        const double* X = a.X[a.cur[b]];
+        double q[DOF], p3[3], qt[4], J[6][DOF];
+        UNR for (int i = 0; i < DOF; i++) q[i] = AT(X, d.kp_t[kpi] * NX + i, b);
+        fk<true>(d.chain, q, p3, qt, J);
+        // trace(Jh S Jh') = sum_ij S[i][j] (Jh'Jh)[i][j] for the upper (translation) and the lower (rotation) half Jh of J: one pass over the
+        // block of Sigma with an entry at a time in flight (the products J S J' held in registers next to FK spilled)
+        UNR for (int blk = 0; blk < ND; blk++) {
+            const double* Sb = Sg + (size_t)blk * dof * (nxu + 1);   // the (blk, blk) block of Sigma
+            double tp = 0, tq = 0;
+            UNR for (int i = 0; i < DOF; i++) {
+                UNR for (int j = 0; j < DOF; j++) {
+                    const double sij = (i < dof && j < dof) ? Sb[i * nxu + j] : 0.0;
+                    tp += sij * (J[0][i] * J[0][j] + J[1][i] * J[1][j] + J[2][i] * J[2][j]);
+                    tq += sij * (J[3][i] * J[3][j] + J[4][i] * J[4][j] + J[5][i] * J[5][j]);
+                }
+            }
+            var[blk == 0 ? ILQR_KP_ERR_POS : ILQR_KP_ERR_VEL] = tp;
+            var[blk == 0 ? ILQR_KP_ERR_ORN : ILQR_KP_ERR_ANGVEL] = tq;
+        }
+    }
+    if (S::TM) var[ILQR_KP_ERR_TIME] = Sg[(nxu - 1) * nxu + nxu - 1];
+    double* o = kp_var + ((size_t)b * n_kp + kpi) * ILQR_CL_COV_KP;
+    UNR for (int g = 0; g < ILQR_CL_COV_KP; g++) o[g] = var[g];
+}
+
 // f(X) for every (instance, timestep): one lane per pair (tuple<1> of ILQRRecursive::solve)
 template <class S>
 __global__ __launch_bounds__(64) void k_fx_all(Bufs a, double* __restrict__ out /* natural [B][T][NF] */) {
@@ -979,6 +1152,19 @@ void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B,
         if (m) hipLaunchKernelGGL((k_closed_loop<S, true>), grid, block, 0, st, a, c, m->x, m->u);
         else hipLaunchKernelGGL((k_closed_loop<S, false>), grid, block, 0, st, a, c, IndexMap{}, IndexMap{});
     });
+}
+void launch_closed_loop_cov(int kind, int nd, const Bufs& a, const ClCovArgs& c, int B, const DofMap* m, hipStream_t st) {
+    const dim3 grid((B + 63) / 64), block(64);
+    SysAll::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if (m) hipLaunchKernelGGL((k_cl_cov<S, true>), grid, block, 0, st, a, c, m->x, m->u);
+        else hipLaunchKernelGGL((k_cl_cov<S, false>), grid, block, 0, st, a, c, IndexMap{}, IndexMap{});
+    });
+}
+void launch_closed_loop_cov_kp(int kind, int nd, const Bufs& a, int B, int n_kp, int dof, const double* kp_Sigma, double* kp_var, hipStream_t st) {
+    if (n_kp <= 0) return;
+    const dim3 grid((B + 63) / 64, n_kp), block(64);
+    SysAll::dispatch(kind, nd, [&](auto s) { hipLaunchKernelGGL((k_cl_cov_kp<decltype(s)>), grid, block, 0, st, a, dof, kp_Sigma, kp_var); });
 }
 void launch_closed_loop_stats(const double* cost, int B, int S, double* stats, hipStream_t st) {
     hipLaunchKernelGGL(k_closed_loop_stats, dim3((B + 63) / 64), dim3(64), 0, st, cost, B, S, stats);

@@ -349,6 +349,50 @@ int ilqr_problem_closed_loop_report(ilqr_problem* p, int n_samples, const ilqr_n
 int ilqr_problem_closed_loop_report_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
                                         int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out);
 
+/* The Gaussian answer to the same question, without samples: the state covariance of the executions of ilqr_problem_closed_loop_noise
+ * (x0 = NULL, no feed-forward term: the covariance about the mean does not depend on it to first order), propagated analytically,
+ *   Sigma_0 = diag(sigma_x0^2),   Sigma_{k+1} = F_k Sigma_k F_k' + diag(sigma_w^2),   F_k = A_k + B_k K_k,
+ * with K_k the gain ilqr_problem_get_K returns and A_k, B_k the exact Jacobian of the system's step at the plan (xbar_k, ubar_k):
+ *   nb_deriv = 1: A = I, B = dt I on the joint rows;   nb_deriv = 2: A = [[I, dt I], [0, I]], B = [[dt^2/2 I], [dt I]];
+ *   time systems: dt = s^2 with s = ubar_k's last entry; the time row of A is 1 on the time entry, and the column of B for the last control is
+ *   d step / d s: 2 s u_i on the joint rows (nb_deriv = 1), 2 s v_i + 2 s^3 u_i on the position rows with v the velocity BEFORE the step and
+ *   2 s u_i on the velocity rows (nb_deriv = 2), 2 s on the time row.  (The reference's solver uses the velocity after the step there; that
+ *   is its quirk, not the Jacobian, and is not used here.)
+ * On the constant-dt systems the closed loop is linear and the recursion is exact: the sample covariance of ilqr_problem_closed_loop_noise's X
+ * converges to Sigma.  On the time systems it is the first-order answer about the plan.
+ * sigma_w[n_x], sigma_x0[n_x]: the user's state layout, as in ilqr_noise; NULL: zeros.  Outputs (ilqr_cl_cov), each may be NULL, but not all:
+ *   Sigma[B][T][n_x][n_x]        Sigma_0 holds sigma_x0^2 exactly; every Sigma_k is stored exactly symmetric (one triangle, mirrored)
+ *   kp_Sigma[B][n_kp][n_x][n_x]  Sigma at the step of keypoint k of the descriptor
+ *   kp_var[B][n_kp][ILQR_CL_COV_KP]  the first-order variance of the task-space deviation at keypoint k, by the groups of
+ *                                ilqr_problem_closed_loop_report: the trace of group g's 3 x 3 block of Jf Sigma_t Jf', Jf = blkdiag(J, J) bordered
+ *                                by 1 for the time state, J the geometric Jacobian at xbar_t (m^2, rad^2, (m/s)^2, (rad/s)^2, s^2; an object
+ *                                frame rotates a block and keeps its trace; dead zones play no part).  A joint keypoint (the ILQR_SYS_JOINT*
+ *                                kinds, or kp_joint[k]): POS = the trace of the joint-position block of Sigma_t over the user's joints, ORN =
+ *                                VEL = ANGVEL = 0.  VEL = ANGVEL = 0 for nb_deriv = 1; TIME = Sigma_t[time][time], 0 off the time systems.
+ *   u_var[B][T-1][n_u]           diag(K_k Sigma_k K_k'): the variance of the commanded controls
+ *   lim_z[B]                     how many standard deviations the plan keeps from its bounds: the minimum over k = 0 .. T-1 and the state
+ *                                entries i with a weighted bound in either limit set and Sigma_k[i][i] > 0 of
+ *                                min(smax_i - xbar_k,i, xbar_k,i - smin_i) / sqrt(Sigma_k[i][i]) (the bounds of that set); +inf if there is no
+ *                                such (k, i), negative where the plan itself lies outside a bound.
+ * Two kernels serve the call (under ilqr_ctx_set_crosscheck's generic_kernels pin and for chains of fewer than 7 joints: one lane per instance;
+ * otherwise rows of Sigma in the registers of 16 lanes).  They sum in different orders: their results agree to rounding, not bit for bit; the
+ * second keeps a lane's whole row inside the recursion and makes Sigma symmetric where it is stored.  No expected cost: the limit terms
+ * are not smooth, and `stats` of ilqr_problem_closed_loop_noise stays the answer for cost.
+ * Refused: what ilqr_problem_closed_loop refuses about the state of the problem, a negative or non-finite sigma, out NULL or all five outputs
+ * NULL, B T n_x^2 >= 2^31 when Sigma is asked for, B n_kp n_x^2 >= 2^31 when kp_Sigma is.
+ * _dev: the arrays inside `out` are device pointers (the sigmas and out itself are read on the host before the call returns); asynchronous on
+ * the context's stream. */
+#define ILQR_CL_COV_KP ILQR_KP_ERR   /* POS, ORN, VEL, ANGVEL, TIME: the groups of ilqr_problem_closed_loop_report */
+typedef struct {
+    double* Sigma;     /* [B][T][n_x][n_x] or NULL */
+    double* kp_Sigma;  /* [B][n_kp][n_x][n_x] or NULL: Sigma at the step of descriptor keypoint k */
+    double* kp_var;    /* [B][n_kp][ILQR_CL_COV_KP] or NULL */
+    double* u_var;     /* [B][T-1][n_u] or NULL: diag(K_k Sigma_k K_k') */
+    double* lim_z;     /* [B] or NULL */
+} ilqr_cl_cov;
+int ilqr_problem_closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out);
+int ilqr_problem_closed_loop_cov_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out);
+
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];
  * any output may be NULL.  Host pointers. */
