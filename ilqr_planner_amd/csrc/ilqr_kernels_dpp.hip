@@ -149,27 +149,42 @@ __device__ __forceinline__ void stg(double* base, unsigned byte_off, double v) {
 }  // namespace
 
 // UNIF: every control weight is the same (R = r I, the common case): then N' = D M - I equals N = M D - I entry by entry
-template <int LPI, int MR, bool FUSED, bool UNIF>
-__global__ __launch_bounds__(64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
+//
+// WG: the workgroup form for large batches.  SW_WAVES = 4 waves with 16 consecutive instances per workgroup, so the four waves that share
+// every 128-byte line of the [row][b] arrays (a wave of 4 instances touches 32 bytes of each of the 14 lines of a step, 28 when it loads)
+// sit on ONE CU, as in k_forward_reg, instead of wherever the dispatcher puts four one-wave workgroups.  Nothing couples the waves: no
+// barrier, no shared LDS, every wave runs the lone wave's code on its own image -- same bits (tests/test_gpu_sweep_wg.py).  Measured on C3
+// at B = 4096 (profiles/sweep_wg_variations.txt): 6.09 against 6.30 ms per solve.  Staging the accepted x, u of a group of PF steps in an
+// LDS block and storing full lines behind one barrier per group, as k_forward_reg does, was built and measured too: 6.37 ms -- the barrier
+// costs a latency-bound chain 13 us per launch (6.11 with the barrier taken out, which is not a correct kernel), more than the lines save.
+// 16 lanes per instance and the fused acceptance only.
+constexpr int SW_WAVES = 4;
+template <int LPI, int MR, bool FUSED, bool UNIF, bool WG = false>
+__global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
     constexpr int N = 7, IPW = 64 / LPI;
+    constexpr int NWV = WG ? SW_WAVES : 1;
+    static_assert(!WG || (LPI == 16 && FUSED), "the workgroup form: 4 instances per wave, 16 per workgroup = one 128-byte line per row segment");
     constexpr int MRR = MR > 0 ? MR : 1;
     constexpr int ROWP = kd_rowp(N), RS = UNIF ? KD_SYM_RS : N * ROWP;  // uniform R: K is symmetric, the record holds its upper triangle (ilqr_kernels.hpp)
     static_assert(ROWP == 8, "a gain row is the lane's eight doubles {K_r0..K_r6, d_r}");
     static_assert(LPI == 8 || LPI == 16, "");
     // two images of the wave's gain records (written at the end of a step, sent out during the next) + one dump slot per lane behind each
     constexpr int NPQ_ = (IPW * (RS / 2) + 63) / 64, IMG = (IPW * RS > 128 * NPQ_) ? IPW * RS : 128 * NPQ_;
-    __shared__ __attribute__((aligned(16))) double sK[2][IMG + 64];
+    __shared__ __attribute__((aligned(16))) double sKw[NWV][2][IMG + 64];
     const DevDesc& d = *a.desc;
-    const int lane = threadIdx.x, g = lane / LPI, l = lane % LPI;
+    const int wv = WG ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0;
+    double (*const sK)[IMG + 64] = sKw[wv];
+    const int lane = WG ? (int)threadIdx.x & 63 : (int)threadIdx.x, g = lane / LPI, l = lane % LPI;
     const int r = l & 7;                 // row of the matrices / component of the vectors this lane owns (7 = padding: all zeros)
     const bool low = l < 8;              // LPI = 16: the half that stores (the other half holds a second copy)
-    const int b = xcd_tile() * IPW + g;
+    const int b0 = (xcd_tile() * NWV + wv) * IPW;  // the wave's first instance
+    const int b = b0 + g;
     const int Bp = d.Bp, T = d.T;
     const bool ok = (b < d.B) && a.active[b < d.B ? b : 0];
     const int bb = (b < d.B) ? b : 0;    // clamp so that every address stays valid; stores are guarded
     const int pendw = (FUSED && b < d.B) ? a.pend[bb] : 0;
     const bool acc = pendw > 0;
-    if (__ballot((ok || acc) ? 1 : 0) == 0ull) return;  // wave-uniform
+    if (__ballot((ok || acc) ? 1 : 0) == 0ull) return;  // wave-uniform (the waves of a workgroup never meet)
 
     const bool isV = r < N;
     const int v = isV ? r : 0;
@@ -239,7 +254,7 @@ __global__ __launch_bounds__(64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
         }
         if (l == 0) { sK[0][g * RS + KD_SYM_RS - 1] = 0; sK[1][g * RS + KD_SYM_RS - 1] = 0; }  // the pad entry of the record
     }
-    double* Kout = KD_REC(a.KD, Bp, RS, T - 2, xcd_tile() * IPW);  // (the gains of a big batch pass 4 GiB: 64-bit pointer)
+    double* Kout = KD_REC(a.KD, Bp, RS, T - 2, b0);  // (the gains of a big batch pass 4 GiB: 64-bit pointer)
     const ptrdiff_t Kstep = (ptrdiff_t)Bp * RS;
 
     int kpi = d.n_kp - 1;
@@ -438,16 +453,19 @@ __global__ __launch_bounds__(64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
     }
 }
 
-template <int LPI, bool FUSED, bool UNIF>
+template <int LPI, bool FUSED, bool UNIF, bool WG = false>
 static void launch_dpp2(bool al, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
-    const dim3 grid(grid_x8((B + 64 / LPI - 1) / (64 / LPI))), block(64);
-    if (!al || a.m == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 0, FUSED, UNIF>), grid, block, 0, st, a, sw);
-    else if (a.m <= 1) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 1, FUSED, UNIF>), grid, block, 0, st, a, sw);
-    else hipLaunchKernelGGL((k_backward_si_dpp<LPI, 4, FUSED, UNIF>), grid, block, 0, st, a, sw);
+    constexpr int IWG = (WG ? SW_WAVES : 1) * (64 / LPI);  // instances per workgroup
+    const dim3 grid(grid_x8((B + IWG - 1) / IWG)), block(WG ? SW_WAVES * 64 : 64);
+    if (!al || a.m == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 0, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
+    else if (a.m <= 1) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 1, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
+    else hipLaunchKernelGGL((k_backward_si_dpp<LPI, 4, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
 }
 
 void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
-    if (lpi == 16) {
+    if (lpi == 16 && fused && sw.si_wg) {  // the workgroup form (RiccatiPlan::si_wg): instantiated for the fused acceptance only
+        if (uniform_R) launch_dpp2<16, true, true, true>(al, a, B, st, sw); else launch_dpp2<16, true, false, true>(al, a, B, st, sw);
+    } else if (lpi == 16) {
         if (fused) { if (uniform_R) launch_dpp2<16, true, true>(al, a, B, st, sw); else launch_dpp2<16, true, false>(al, a, B, st, sw); }
         else { if (uniform_R) launch_dpp2<16, false, true>(al, a, B, st, sw); else launch_dpp2<16, false, false>(al, a, B, st, sw); }
     } else {

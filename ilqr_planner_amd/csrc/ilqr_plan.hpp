@@ -42,9 +42,15 @@ inline int n_alpha_of(bool line_search, double alpha_floor) {
 // then bound by one wave's instruction stream, which is shorter with 4 instances per wave), 8 beyond (half the instructions per instance).
 // Measured crossover between 4096 and 8192 instances on 1024 SIMDs.  Both groupings are bit-identical (test_sweep_lane_groupings_agree).
 constexpr int si_lanes(int launched_B, int n_simd) { return (launched_B + 3) / 4 <= n_simd ? 16 : 8; }
+// Workgroup form of k_backward_si_dpp (four waves = 16 consecutive instances per workgroup: the waves that share a 128-byte line of x, u on one
+// CU), decided on the LAUNCHED (half-)batch, for the 16-lane grouping only: from this many instances on.  Both forms give the same bits
+// (tests/test_gpu_sweep_wg.py), so the threshold is a pure speed choice.  Measured on C3 (profiles/sweep_wg_batch_scan.txt, ms per solve, lone
+// waves against workgroups): B = 256 5.19 / 5.16, 1024 5.35 / 5.33, 2048 5.63 / 5.46, 3072 6.21 / 6.16, 4096 6.27 / 6.07 -- never slower at a
+// measured size; smaller batches were not measured and stay on lone waves.
+constexpr int SI_WG_MIN_BATCH = 256;
 
 // Variant pins of ilqr_ctx_set_crosscheck: AUTO (0) = by batch size; the values are the ILQR_XC_* constants of include/ilqr_hip.h
-enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2 };
+enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2, SiWave = 4, SiWg = 5 };  // SiWave / SiWg: the form of k_backward_si_dpp (same bits); AUTO elsewhere.  (3 is no pin: ilqr_ctx_set_crosscheck refuses it)
 enum class FwdPin { Auto = 0, Wg = 1, Dpp = 2, WgLds = 3 };  // WgLds: Wg with k_forward_wg, the predecessor of k_forward_reg (same bits)
 enum class RerollPin { Auto = 0, Rows = 1, Dpp = 2 };
 
@@ -89,6 +95,7 @@ struct RiccatiPlan {
     bool init_al_update = false;  // k_al_post at it = -1 after the LTI rollout (active-set weights of the initial trajectory)
     Sweep sweep = Sweep::Generic;
     int si_lanes[2] = {16, 16};   // Sweep::SiDpp: lanes per instance of the whole batch or of each half (split)
+    bool si_wg[2] = {false, false};  // Sweep::SiDpp with 16 lanes: the workgroup form (SI_WG_MIN_BATCH, or the pins SiWave / SiWg), per launched half
     Forward forward = Forward::Generic;
     bool fwd_lds = false;         // Forward::WaveWg under the pin FwdPin::WgLds: k_forward_wg instead of k_forward_reg
     Apply apply = Apply::None;
@@ -112,7 +119,8 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     // waves (measured: B = 2048 600 against 548 us, B = 4096 597 against 1040)
     if (cooperative && in.off32 && backward_si_supported(kind, nd, in.al, in.m, in.per_step, in.con_state_only)) p.sweep = Sweep::SiDpp;
     else if (cooperative && backward_mfma_supported(kind, nd, in.al, in.m)) {
-        const bool rows = in.sweep == SweepPin::Rows || (in.sweep == SweepPin::Auto && in.B > 2 * in.n_simd);
+        const bool pinned = in.sweep == SweepPin::Mfma || in.sweep == SweepPin::Rows;  // (SiWave / SiWg pin nothing here)
+        const bool rows = in.sweep == SweepPin::Rows || (!pinned && in.B > 2 * in.n_simd);
         p.sweep = rows && backward_rows_supported(kind, nd, in.al, in.m) ? Sweep::Rows : Sweep::Mfma;
     }
 
@@ -158,6 +166,11 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     const int b0 = p.split ? split_first_half(in.B) : in.B;
     p.si_lanes[0] = si_lanes(b0, in.n_simd);
     p.si_lanes[1] = si_lanes(in.B - b0, in.n_simd);
+    // the 8-lane grouping (B > 4 n_simd) stays on the one-wave form, whatever the pin says
+    const int launched[2] = {b0, in.B - b0};
+    for (int h = 0; h < 2; h++)
+        p.si_wg[h] = p.sweep == Sweep::SiDpp && p.si_lanes[h] == 16 &&
+                     (in.sweep == SweepPin::SiWg || (in.sweep != SweepPin::SiWave && launched[h] >= SI_WG_MIN_BATCH));
     return p;
 }
 

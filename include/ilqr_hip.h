@@ -165,6 +165,8 @@ int ilqr_ctx_set_split(ilqr_ctx* ctx, int on);
 #define ILQR_XC_AUTO 0
 #define ILQR_XC_SWEEP_MFMA 1   /* sweep of the 2nd-order / time systems: one instance per wave on the f64 matrix cores (AUTO: up to 2 n_simd instances) */
 #define ILQR_XC_SWEEP_ROWS 2   /*   ... 16 lanes per instance with the rows in registers (AUTO: beyond) */
+#define ILQR_XC_SWEEP_SI_WAVE 4 /* sweep of the single-integrator systems: k_backward_si_dpp on lone waves at any batch size: the same bits as AUTO (3 is no sweep pin: refused) */
+#define ILQR_XC_SWEEP_SI_WG 5   /*   ... in its workgroup form (16 lanes per instance only; AUTO: from 256 launched instances): the same bits as AUTO */
 #define ILQR_XC_FWD_WG 1       /* forward pass of the single-integrator systems: the large-batch k_forward_reg (AUTO: beyond 3 n_simd instances) */
 #define ILQR_XC_FWD_DPP 2      /*   ... the latency-built k_forward_dpp (AUTO: up to 3 n_simd); agrees with the others to rounding */
 #define ILQR_XC_FWD_WG_LDS 3   /*   ... k_forward_wg, the predecessor of k_forward_reg, at any batch size: the same bits as ILQR_XC_FWD_WG (never AUTO) */
@@ -177,7 +179,7 @@ int ilqr_ctx_set_split(ilqr_ctx* ctx, int on);
  * variant each (ILQR_XC_*); a value out of range fails with an error text.  All 0 = the product path.
  * With all three pins at ILQR_XC_AUTO the product path picks between numerically different (rounding-level) kernels by batch size and the
  * device's SIMD count: the same instance can give different bits in batches (or shards) of different sizes.  With all three pinned, the
- * remaining size-dependent choices (the lane grouping of the single-integrator sweep, the two-stream split) are bit-identical. */
+ * remaining size-dependent choices (the lane grouping and the workgroup form of the single-integrator sweep, the two-stream split) are bit-identical. */
 int ilqr_ctx_set_crosscheck(ilqr_ctx* ctx, int generic_kernels, int cp_lane_solve, int cp_general, int sweep, int forward, int reroll);
 const char* ilqr_version(void);
 
