@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libilqr_hip.so")
 
 MAX_SEG, MAX_KP, MAX_NX, MAX_NU, MAX_NF, MAX_NQ = 24, 8, 15, 8, 15, 13
 SYS_POS_ORN, SYS_POS_ORN_TIME, SYS_JOINT, SYS_JOINT_TIME = 0, 1, 2, 3
-STATUS_OK, STATUS_NONFINITE, STATUS_ALPHA_FLOOR = 0, 1, 2
+STATUS_OK, STATUS_NONFINITE, STATUS_ALPHA_FLOOR, STATUS_SWEEP_IO = 0, 1, 2, 4  # ILQR_STATUS_* (bits of the per-instance status word)
 LQT_MAX_NX, LQT_MAX_NU = 16, 8
 CL_STATS = 5  # mean, variance, min, max, n_bad (ILQR_CL_STATS)
 KP_ERR, KP_STATS, CL_OUTCOME = 5, 12, 4  # ILQR_KP_ERR (pos, orn, vel, angvel, time), ILQR_KP_STATS (mean[5], max[5], n_miss, n_bad), ILQR_CL_OUTCOME
@@ -313,10 +313,10 @@ class Context:
     def synchronize(self):
         self.check(self.L.ilqr_ctx_synchronize(self.h))
 
-    _PINS = {"sweep": {None: 0, "mfma": 1, "rows": 2, "siwave": 4, "siwg": 5}, "forward": {None: 0, "wg": 1, "dpp": 2, "wglds": 3}, "reroll": {None: 0, "rows": 1, "dpp": 2}}  # ILQR_XC_*
+    _PINS = {"sweep": {None: 0, "mfma": 1, "rows": 2, "siwave": 4, "siwg": 5, "siwgio": 6}, "forward": {None: 0, "wg": 1, "dpp": 2, "wglds": 3}, "reroll": {None: 0, "rows": 1, "dpp": 2}}  # ILQR_XC_*
 
     def set_crosscheck(self, generic_kernels=False, cp_lane_solve=False, cp_general=False, sweep=None, forward=None, reroll=None):
-        """Cross-check kernel variants (ilqr_ctx_set_crosscheck); context state, in force until changed.  sweep "mfma"|"rows"|"siwave"|"siwg", forward "wg"|"dpp"|"wglds",
+        """Cross-check kernel variants (ilqr_ctx_set_crosscheck); context state, in force until changed.  sweep "mfma"|"rows"|"siwave"|"siwg"|"siwgio", forward "wg"|"dpp"|"wglds",
         reroll "rows"|"dpp"; None = by batch size."""
         pins = []
         for name, v in (("sweep", sweep), ("forward", forward), ("reroll", reroll)):
@@ -327,7 +327,7 @@ class Context:
 
     def crosscheck_from_env(self):
         """TEST PLUMBING of this Python wrapper (the library itself reads no environment variable): the parity tests select the cross-check
-        variants per test case through ILQR_HIP_PATH=v1, ILQR_CP_SOLVE=lane, ILQR_CP=general, ILQR_SWEEP=mfma|rows|siwave|siwg, ILQR_FWD=wg|dpp|wglds, ILQR_APPLY=rows|dpp; every solve of BatchProblem passes them on."""
+        variants per test case through ILQR_HIP_PATH=v1, ILQR_CP_SOLVE=lane, ILQR_CP=general, ILQR_SWEEP=mfma|rows|siwave|siwg|siwgio, ILQR_FWD=wg|dpp|wglds, ILQR_APPLY=rows|dpp; every solve of BatchProblem passes them on."""
         env = os.environ
         self.set_crosscheck(env.get("ILQR_HIP_PATH") == "v1", env.get("ILQR_CP_SOLVE") == "lane", env.get("ILQR_CP") == "general",
                             sweep=env.get("ILQR_SWEEP") or None, forward=env.get("ILQR_FWD") or None, reroll=env.get("ILQR_APPLY") or None)

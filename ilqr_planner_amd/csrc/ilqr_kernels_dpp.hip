@@ -37,6 +37,7 @@
 // FUSED / AL bookkeeping exactly as before: the acceptance of the previous line search rides in the load path,
 // x = xbar + alpha (x(1) - xbar) with k_apply's expression, I_k from the multipliers before the update, lambda update on update
 // iterations, buffers flipped at the end (AL-ILQR.cpp:190, 202-208).
+#include "../../include/ilqr_hip.h"
 #include "ilqr_kernels.hpp"
 #include "ilqr_lanes.hpp"
 #include "ilqr_step.hpp"
@@ -143,6 +144,16 @@ __device__ __forceinline__ double oct_row_g(double a_l, double x_l, double b) {
     return oct_sum_rounded(p) - b;
 }
 
+// LDS byte address of a __shared__ object (for inline assembly)
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)p; }
+// Flag words in LDS: plain ds_read / ds_write kept in place by compiler barriers.  (Not `volatile`: through a generic pointer that is a flat
+// access, which counts in vmcnt too and made every step of the chain wait for its prefetched loads -- vmcnt(0).)
+typedef __attribute__((address_space(3))) int lds_int;
+__device__ __forceinline__ int flag_read(const int* p) { LDS_ORDER(); const int v = *(const lds_int*)p; LDS_ORDER(); return v; }
+__device__ __forceinline__ void flag_write(int* p, int v) { LDS_ORDER(); *(lds_int*)p = v; LDS_ORDER(); }
+// Bounded wait of a chain wave for the I/O wave's "consumed" word (LDS byte address `addr`, last read as `seen`) to reach `need`: polls at
+// most SW_POLL_CHAIN times with s_sleep 1 between the polls and returns 1 if it gave up.  One asm statement: no control flow for the compiler.
+__device__ __forceinline__ int wait_consumed(int seen, unsigned addr, int need);
 __device__ __forceinline__ double ldg(const double* base, unsigned byte_off) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + byte_off); }
 __device__ __forceinline__ void stg(double* base, unsigned byte_off, double v) { *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + byte_off) = v; }
 
@@ -158,22 +169,71 @@ __device__ __forceinline__ void stg(double* base, unsigned byte_off, double v) {
 // LDS block and storing full lines behind one barrier per group, as k_forward_reg does, was built and measured too: 6.37 ms -- the barrier
 // costs a latency-bound chain 13 us per launch (6.11 with the barrier taken out, which is not a correct kernel), more than the lines save.
 // 16 lanes per instance and the fused acceptance only.
+//
+// IO: the workgroup form with a fifth wave that executes no Riccati arithmetic and carries the stores of the four chain waves (bit 0: the
+// gain records, bit 1: the accepted x, u as whole 128-byte lines: 16 instances x 8 bytes of one row).  A chain wave writes the gain image of
+// its n-th step (n = 1 .. T - 1) into slot (n - 1) mod SW_RING of its ring in LDS, drops its blended x | u into the same slot of the
+// workgroup's x | u ring (one ds_write per lane: the low half of an instance's 16 lanes holds x, the copy in the high half u) and then stores
+// n into its word of sFl ("produced").  The I/O wave polls the four words; once every live chain wave has produced step n it reads the four
+// images and the 14 x 16 block into registers, stores n into the workgroup's "consumed" word and sends the images where SEND_ sends them
+// (the same 16-byte pieces, the same pst / kfull masks) and x, u as row segments, each lane under its own instance's blend and into its own
+// instance's buffer.  A chain wave reads "consumed" at the start of the first step n of a group of PF steps and, at that step's end, needs
+// consumed >= n + PF - SW_RING: that frees the slots of steps n .. n + PF, i.e. the group's images, its remaining x | u and the x | u of the
+// next group's first step, which is written ahead of that group's check.  One check per group (a check per step cost the chain
+// more than the stores it was relieved of: profiles/sweep_io_variations.txt).  Flags are plain LDS words written after the data they announce
+// (a wave's LDS operations execute in order); one workgroup barrier before the loop (every wave has read active, pend and cur of the 16
+// instances before a chain wave can finish and rewrite them), none inside.  Every wait is bounded (SW_POLL_CHAIN / SW_POLL_IO polls with
+// s_sleep between them, more than 20 ms = a hundred launches): a wave that gives up clears `active` and sets ILQR_STATUS_SWEEP_IO on its
+// instances and ends.  Two waves share a SIMD: at most 256 VGPRs, so not for MR = 4.  Same bits (tests/test_gpu_sweep_io.py).  Measured on C3
+// at B = 4096 (profiles/sweep_io_ab_bench.txt): 5.99 against 6.08 ms per solve.
 constexpr int SW_WAVES = 4;
-template <int LPI, int MR, bool FUSED, bool UNIF, bool WG = false>
-__global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
+constexpr int SW_RING = 8;             // slots per ring: two groups of PF steps, which lets the chain waves run 4 steps ahead of the I/O wave (with 4 slots: none)
+constexpr int SW_POLL_CHAIN = 1 << 20; // polls of s_sleep 1 (64 clocks) + an LDS round trip: 28 ms at 2.4 GHz from the sleeps alone
+constexpr int SW_POLL_IO = 1 << 18;    // polls of s_sleep 4 (256 clocks) + an LDS round trip: 28 ms at 2.4 GHz from the sleeps alone
+namespace {
+__device__ __forceinline__ int wait_consumed(int seen, unsigned addr, int need) {
+    int v = seen, cons, cnt;
+    asm volatile(
+        "s_mov_b32 %[cnt], 0\n"
+        "1:\n\t"
+        "v_readfirstlane_b32 %[cons], %[v]\n\t"
+        "s_cmp_ge_i32 %[cons], %[need]\n\t"
+        "s_cbranch_scc1 2f\n\t"
+        "s_cmp_ge_u32 %[cnt], %[lim]\n\t"
+        "s_cbranch_scc1 2f\n\t"
+        "s_sleep 1\n\t"
+        "ds_read_b32 %[v], %[addr]\n\t"
+        "s_add_u32 %[cnt], %[cnt], 1\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "s_branch 1b\n"
+        "2:"
+        : [v] "+v"(v), [cons] "=&s"(cons), [cnt] "=&s"(cnt)
+        : [addr] "v"(addr), [need] "s"(need), [lim] "s"(SW_POLL_CHAIN)
+        : "memory", "scc");
+    return __builtin_amdgcn_readfirstlane(cons < need ? 1 : 0);  // (uniform by construction; the compiler takes asm results for divergent)
+}
+}  // namespace
+template <int LPI, int MR, bool FUSED, bool UNIF, bool WG = false, int IO = 0>
+__global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
     constexpr int N = 7, IPW = 64 / LPI;
     constexpr int NWV = WG ? SW_WAVES : 1;
+    constexpr bool IOK = (IO & 1) != 0, IOX = (IO & 2) != 0;  // the I/O wave sends the gain records / stores the accepted x, u
+    constexpr int NIMG = IOK ? SW_RING : 2, XRING = SW_RING, XROW = 18;
     static_assert(!WG || (LPI == 16 && FUSED), "the workgroup form: 4 instances per wave, 16 per workgroup = one 128-byte line per row segment");
+    static_assert(!IO || (WG && MR <= 1), "the I/O wave: workgroup form, at most one constraint row (256 VGPRs at two waves on a SIMD)");
     constexpr int MRR = MR > 0 ? MR : 1;
     constexpr int ROWP = kd_rowp(N), RS = UNIF ? KD_SYM_RS : N * ROWP;  // uniform R: K is symmetric, the record holds its upper triangle (ilqr_kernels.hpp)
     static_assert(ROWP == 8, "a gain row is the lane's eight doubles {K_r0..K_r6, d_r}");
     static_assert(LPI == 8 || LPI == 16, "");
     // two images of the wave's gain records (written at the end of a step, sent out during the next) + one dump slot per lane behind each
     constexpr int NPQ_ = (IPW * (RS / 2) + 63) / 64, IMG = (IPW * RS > 128 * NPQ_) ? IPW * RS : 128 * NPQ_;
-    __shared__ __attribute__((aligned(16))) double sKw[NWV][2][IMG + 64];
+    __shared__ __attribute__((aligned(16))) double sKw[NWV][NIMG][IMG + 64];
+    // IOX: the accepted x | u of a step, [row 0 .. 6 x, 7 .. 13 u, 14 dump][instance of the workgroup], row stride XROW (banks)
+    __shared__ double sXU[IOX ? XRING : 1][IOX ? 2 * N + 1 : 1][IOX ? XROW : 1];
+    __shared__ int sFl[IO ? NWV + 1 : 1];  // produced (per chain wave), consumed
     const DevDesc& d = *a.desc;
     const int wv = WG ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0;
-    double (*const sK)[IMG + 64] = sKw[wv];
+    double (*const sK)[IMG + 64] = sKw[wv < NWV ? wv : 0];
     const int lane = WG ? (int)threadIdx.x & 63 : (int)threadIdx.x, g = lane / LPI, l = lane % LPI;
     const int r = l & 7;                 // row of the matrices / component of the vectors this lane owns (7 = padding: all zeros)
     const bool low = l < 8;              // LPI = 16: the half that stores (the other half holds a second copy)
@@ -184,7 +244,87 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
     const int bb = (b < d.B) ? b : 0;    // clamp so that every address stays valid; stores are guarded
     const int pendw = (FUSED && b < d.B) ? a.pend[bb] : 0;
     const bool acc = pendw > 0;
-    if (__ballot((ok || acc) ? 1 : 0) == 0ull) return;  // wave-uniform (the waves of a workgroup never meet)
+    if (IO) {
+        constexpr int RS_ = UNIF ? KD_SYM_RS : N * kd_rowp(N), PCS_ = RS_ / 2, NPQ2 = (IPW * PCS_ + 63) / 64;
+        if (wv == NWV) {  // ---- the I/O wave: lane j looks at instance j mod 16 of the workgroup
+            const int bi = xcd_tile() * (NWV * IPW) + (lane & 15);
+            const bool in = bi < d.B;
+            const int bbi = in ? bi : 0;
+            const bool oki = in && a.active[bbi];
+            const int pwi = in ? a.pend[bbi] : 0;
+            const int curi = a.cur[bbi];
+            __syncthreads();  // every wave has read active, pend and cur of the 16 instances; the flags are zero
+            const unsigned okm16 = (unsigned)__ballot((oki && lane < 16) ? 1 : 0);
+            const unsigned livem = (unsigned)__ballot(((oki || pwi > 0) && lane < 16) ? 1 : 0);  // the chain waves' early exit, per wave
+            if (livem == 0u) return;
+            bool live[NWV], kfull[NWV], pst[NWV][NPQ2];
+            UNR for (int w = 0; w < NWV; w++) {
+                live[w] = ((livem >> (w * IPW)) & 15u) != 0u;
+                kfull[w] = ((okm16 >> (w * IPW)) & 15u) == 15u;
+                UNR for (int q = 0; q < NPQ2; q++) {
+                    const int c = lane + 64 * q, gi = (c / PCS_ < IPW) ? c / PCS_ : 0;
+                    pst[w][q] = c < IPW * PCS_ && ((okm16 >> (w * IPW + gi)) & 1u);
+                }
+            }
+            const bool want = (lane < NWV) ? ((livem >> (lane * IPW)) & 15u) != 0u : false;  // lane w polls chain wave w's word
+            const int T1 = d.T - 1, Bpi = d.Bp;
+            double* Ko = KD_REC(a.KD, Bpi, RS_, T1 - 1, xcd_tile() * (NWV * IPW));
+            const ptrdiff_t Ks = (ptrdiff_t)Bpi * RS_;
+            // accepted x, u: lane j stores rows (j / 16) + 4 q of instance j mod 16, into the buffer its x(1), u(1) were read from
+            const bool blendi = pwi > 1;
+            const unsigned bufoi = (unsigned)((a.X[1] - a.X[0]) * (ptrdiff_t)sizeof(double));
+            const unsigned Vs = (unsigned)N * Bpi * 8u;
+            unsigned oXi = (unsigned)(1 - curi) * bufoi + ((unsigned)((T1 - 1) * N) * Bpi + bbi) * 8u;
+            for (int n = 1; n <= T1; n++) {
+                for (int spins = 0;; spins++) {
+                    const int pv = flag_read(&sFl[lane < NWV ? lane : 0]);
+                    if (__ballot((want && pv < n) ? 1 : 0) == 0ull) break;
+                    if (spins >= SW_POLL_IO) {  // a chain wave never produced step n: give up on the workgroup's instances
+                        if (lane < 16 && in) { a.active[bbi] = 0; atomicOr(&a.status[bbi], ILQR_STATUS_SWEEP_IO); }
+                        return;
+                    }
+                    __builtin_amdgcn_s_sleep(4);
+                }
+                LDS_ORDER();
+                double kqa[NWV][NPQ2], kqb[NWV][NPQ2], xu[4];
+                if (IOK) {
+                    UNR for (int w = 0; w < NWV; w++) UNR for (int q = 0; q < NPQ2; q++) {
+                        const double2 t2 = reinterpret_cast<const double2*>(sKw[w][(n - 1) % SW_RING])[lane + 64 * q];
+                        kqa[w][q] = t2.x; kqb[w][q] = t2.y;
+                    }
+                }
+                if (IOX) { UNR for (int q = 0; q < 4; q++) xu[q] = sXU[(n - 1) % XRING][(4 * q + (lane >> 4)) < 2 * N ? 4 * q + (lane >> 4) : 2 * N][lane & 15]; }
+                flag_write(&sFl[NWV], n);  // consumed: the slots of step n are free
+                if (IOK) {
+                    UNR for (int w = 0; w < NWV; w++) {
+                        if (!live[w]) continue;
+                        double2* dst = reinterpret_cast<double2*>(Ko + w * (IPW * RS_)) + lane;
+                        if (kfull[w]) {
+                            UNR for (int q = 0; q + 1 < NPQ2; q++) dst[64 * q] = make_double2(kqa[w][q], kqb[w][q]);
+                            if (lane + 64 * (NPQ2 - 1) < IPW * PCS_) dst[64 * (NPQ2 - 1)] = make_double2(kqa[w][NPQ2 - 1], kqb[w][NPQ2 - 1]);
+                        } else {
+                            UNR for (int q = 0; q < NPQ2; q++) if (pst[w][q]) dst[64 * q] = make_double2(kqa[w][q], kqb[w][q]);
+                        }
+                    }
+                    Ko -= Ks;
+                }
+                if (IOX) {
+                    if (blendi) {
+                        UNR for (int q = 0; q < 4; q++) {
+                            const int row = 4 * q + (lane >> 4);
+                            if (row < N) stg(a.X[0], oXi + (unsigned)row * Bpi * 8u, xu[q]);
+                            else if (row < 2 * N) stg(a.U[0], oXi + (unsigned)(row - N) * Bpi * 8u, xu[q]);
+                        }
+                    }
+                    oXi -= Vs;
+                }
+            }
+            return;
+        }
+        if (lane == 0) { sFl[wv] = 0; if (wv == 0) sFl[NWV] = 0; }
+        __syncthreads();
+    }
+    if (__ballot((ok || acc) ? 1 : 0) == 0ull) return;  // wave-uniform (the waves of a workgroup never meet in the loop)
 
     const bool isV = r < N;
     const int v = isV ? r : 0;
@@ -252,7 +392,7 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
             UNR for (int j = 0; j < N; j++) wo[j] = (j >= v) ? g * RS + kd_sym_tri(v, j) : IMG + lane;
             wod = g * RS + KD_SYM_D + v;
         }
-        if (l == 0) { sK[0][g * RS + KD_SYM_RS - 1] = 0; sK[1][g * RS + KD_SYM_RS - 1] = 0; }  // the pad entry of the record
+        if (l == 0) { UNR for (int i = 0; i < NIMG; i++) sK[i][g * RS + KD_SYM_RS - 1] = 0; }  // the pad entry of the record
     }
     double* Kout = KD_REC(a.KD, Bp, RS, T - 2, b0);  // (the gains of a big batch pass 4 GiB: 64-bit pointer)
     const ptrdiff_t Kstep = (ptrdiff_t)Bp * RS;
@@ -310,7 +450,12 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
     unsigned oW = (unsigned)r1 * bufo + ((unsigned)((T - 2) * N + v) * Bp + bb) * 8u;
     unsigned oLw = ((unsigned)(T - 2) * m * Bp + bb) * 8u;
 
+    static_assert(SW_RING % PF == 0, "a step's slot is the group's first slot + its place in the group");
+    const unsigned fl_cons = lds_addr(&sFl[IO ? NWV : 0]);
+    int gave_up = 0;  // uniform
+    const int xcol = wv * IPW + g, xrow = isV ? (low ? v : N + v) : 2 * N;  // IOX: where this lane drops its x (low half) or u (the copy)
     for (int k0 = T - 2; k0 >= 0; k0 -= PF) {
+      const int sl0 = IOK ? (T - 2 - k0) % SW_RING : 0, xs0 = IOX ? (T - 2 - k0) % XRING : 0;  // uniform: the slots of the group's first step
       UNR for (int jj = 0; jj < PF; jj++) {
         const int k = k0 - jj;
         double xv = ring_take(xr[jj]), uv = ring_take(ur[jj]);
@@ -326,12 +471,15 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
         }
         __builtin_amdgcn_sched_barrier(0);  // the slots are free: only now their next loads
         fetch(jj, k - PF);
+        const int consumed = (IO && jj == 0) ? flag_read(&sFl[IO ? NWV : 0]) : 0;  // read here, needed at the step's end
         // the image of the step before this one (in time) leaves now: LDS -> registers here, registers -> memory after the pivots
         const bool kprev = k < T - 2;
         double kqa[NPQ], kqb[NPQ];  // (two arrays of doubles: an array of double2 -- or anything a lambda captures by reference -- goes to scratch)
-        UNR for (int q = 0; q < NPQ; q++) {  // unconditional: stays inside the (padded) array
-            const double2 t2 = reinterpret_cast<const double2*>(sK[(jj + 1) & 1])[lane + 64 * q];
-            kqa[q] = t2.x; kqb[q] = t2.y;
+        if (!IOK) {
+            UNR for (int q = 0; q < NPQ; q++) {  // unconditional: stays inside the (padded) array
+                const double2 t2 = reinterpret_cast<const double2*>(sK[(jj + 1) & 1])[lane + 64 * q];
+                kqa[q] = t2.x; kqb[q] = t2.y;
+            }
         }
 #define SEND_()                                                                                                         \
         {                                                                                                               \
@@ -344,11 +492,12 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
             }                                                                                                           \
         }
         if (k < 0) {  // uniform: dummy step of the last group; the one right behind the last real step sends its image out
-            if (k == -1) SEND_()
+            if (!IOK && k == -1) SEND_()
             continue;
         }
         if (FUSED) {
-            if (wr) { stg(Xb, oW, xv); stg(Ub, oW, uv); }
+            if (IOX) sXU[xs0 + jj][xrow][xcol] = low ? xv : uv;  // the I/O wave stores them as lines, under the instance's own blend
+            else if (wr) { stg(Xb, oW, xv); stg(Ub, oW, uv); }
             oW -= Vstep;
         }
         const double Qu = Rv * uv + dt * p;  // Qu = R u + B'p
@@ -357,7 +506,7 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
         UNR for (int j = 0; j < N; j++) s[j] = fma(dt2, P[j], Dd[j]);
         double myrc = 0.0;
         pivots<LPI>(s, nm1, myrc);
-        if (kprev) SEND_()
+        if (!IOK && kprev) SEND_()
         const double nrc = -myrc;
         // row r of S^-1 is M = nrc s.  With uniform control weights M is never formed: N = M D - I = (nrc D) s - I, and the two
         // products with M run on s and are scaled afterwards.
@@ -384,17 +533,27 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
         // doubled the launch (measured: 381 -> 194 us at B = 8192 with these stores removed).  The rows go into a wave-local LDS image of
         // the wave's records as they lie in memory; the image leaves during the NEXT step as 16-byte pieces of whole lines (1 KiB
         // contiguous per instruction), so neither the LDS round trip nor the stores sit on this step's chain.
+        if (IO && jj == 0) {  // once per group of PF steps n .. n + PF - 1 (n = T - 1 - k), behind the x | u write of step n and ahead of every other
+            // write of the group and of the x | u write of step n + PF, which opens the next group ahead of that group's check: the last of these
+            // slots, step n + PF's, is free once step n + PF - SW_RING is consumed (the x | u slot of step n itself was covered by the check of
+            // the group before, or is the ring's first use).
+            // No branch for the compiler to see: the bounded poll is one asm statement that falls through at once in the common case, and
+            // a wave that gave up finishes this group on slots it may not own and then leaves the loop (below).
+            const int need = __builtin_amdgcn_readfirstlane(T - 1 - k + PF - SW_RING);
+            gave_up |= wait_consumed(consumed, fl_cons, need);
+        }
         if (UNIF) {  // packed symmetric record: row r contributes K_rr .. K_r6 and d_r; everything else (and every lane without a row) writes its dump slot -- no mask
-            double* img = sK[jj & 1];
+            double* img = sK[IOK ? sl0 + jj : jj & 1];
             UNR for (int j = 0; j < N; j++) img[wo[j]] = Kr[j];
             img[wod] = dv;
         } else if (isV && low) {
-            double2* w = reinterpret_cast<double2*>(&sK[jj & 1][g * RS + v * ROWP]);
+            double2* w = reinterpret_cast<double2*>(&sK[IOK ? sl0 + jj : jj & 1][g * RS + v * ROWP]);
             w[0] = make_double2(Kr[0], Kr[1]);
             w[1] = make_double2(Kr[2], Kr[3]);
             w[2] = make_double2(Kr[4], Kr[5]);
             w[3] = make_double2(Kr[6], dv);
         }
+        if (IO) flag_write(&sFl[wv], T - 1 - k);  // produced: after the data it announces
         Kout -= Kstep;
         // ---- stage derivatives l_xx (row r), l_x (component r), accumulated onto -D N / dt^2
         double Pn[N], lx = 0;
@@ -443,8 +602,13 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
         p = lx + p - (Qu + Dv * dv) * idt - reg * (Dv * Md - dv) * idt;
         if (FUSED && MR > 0) oLw -= Lstep;
       }
+      if (IO) k0 = gave_up ? 0 : k0;  // (a select on the loop counter, no branch: the loop ends here)
     }
-    if ((T - 2) % PF == PF - 1) {  // the last real step closed its group: no dummy step sent its image out
+    if (IO && gave_up) {  // the I/O wave is gone: the wave's instances are out of the solve, whatever was stored for them
+        if (l == 0 && b < d.B) { a.active[bb] = 0; atomicOr(&a.status[bb], ILQR_STATUS_SWEEP_IO); }
+        return;
+    }
+    if (!IOK && (T - 2) % PF == PF - 1) {  // the last real step closed its group: no dummy step sent its image out
         UNR for (int q = 0; q < NPQ; q++) if (pst[q]) reinterpret_cast<double2*>(Kout + Kstep)[lane + 64 * q] = reinterpret_cast<const double2*>(sK[(PF - 1) & 1])[lane + 64 * q];
     }
     if (FUSED && acc && l == 0) {  // the acceptance is complete: the other buffer is the instance's trajectory now
@@ -453,17 +617,20 @@ __global__ __launch_bounds__(WG ? SW_WAVES * 64 : 64) void k_backward_si_dpp(Buf
     }
 }
 
-template <int LPI, bool FUSED, bool UNIF, bool WG = false>
+constexpr int SW_IO = 3;  // what the I/O wave carries: the gain records and the accepted x, u (the stages that were measured: profiles/sweep_io_variations.txt)
+template <int LPI, bool FUSED, bool UNIF, bool WG = false, int IO = 0>
 static void launch_dpp2(bool al, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
     constexpr int IWG = (WG ? SW_WAVES : 1) * (64 / LPI);  // instances per workgroup
-    const dim3 grid(grid_x8((B + IWG - 1) / IWG)), block(WG ? SW_WAVES * 64 : 64);
-    if (!al || a.m == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 0, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
-    else if (a.m <= 1) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 1, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
-    else hipLaunchKernelGGL((k_backward_si_dpp<LPI, 4, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
+    const dim3 grid(grid_x8((B + IWG - 1) / IWG)), block(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64);
+    if (!al || a.m == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 0, FUSED, UNIF, WG, IO>), grid, block, 0, st, a, sw);
+    else if (a.m <= 1) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 1, FUSED, UNIF, WG, IO>), grid, block, 0, st, a, sw);
+    else if constexpr (IO == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 4, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
 }
 
 void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
-    if (lpi == 16 && fused && sw.si_wg) {  // the workgroup form (RiccatiPlan::si_wg): instantiated for the fused acceptance only
+    if (lpi == 16 && fused && sw.si_wg && sw.si_io && (!al || a.m <= 1)) {  // ... with the I/O wave (RiccatiPlan::si_io): at most one constraint row
+        if (uniform_R) launch_dpp2<16, true, true, true, SW_IO>(al, a, B, st, sw); else launch_dpp2<16, true, false, true, SW_IO>(al, a, B, st, sw);
+    } else if (lpi == 16 && fused && sw.si_wg) {  // the workgroup form (RiccatiPlan::si_wg): instantiated for the fused acceptance only
         if (uniform_R) launch_dpp2<16, true, true, true>(al, a, B, st, sw); else launch_dpp2<16, true, false, true>(al, a, B, st, sw);
     } else if (lpi == 16) {
         if (fused) { if (uniform_R) launch_dpp2<16, true, true>(al, a, B, st, sw); else launch_dpp2<16, true, false>(al, a, B, st, sw); }

@@ -48,9 +48,19 @@ constexpr int si_lanes(int launched_B, int n_simd) { return (launched_B + 3) / 4
 // waves against workgroups): B = 256 5.19 / 5.16, 1024 5.35 / 5.33, 2048 5.63 / 5.46, 3072 6.21 / 6.16, 4096 6.27 / 6.07 -- never slower at a
 // measured size; smaller batches were not measured and stay on lone waves.
 constexpr int SI_WG_MIN_BATCH = 256;
+// The workgroup form with an I/O wave (a fifth wave that stores the gain records and the accepted x, u of the four chain waves, the latter as whole
+// 128-byte lines, so that these stores leave the chains' instruction streams; 16 lanes per instance and at most one constraint row: two waves
+// share a SIMD, 256 VGPRs), decided on the LAUNCHED (half-)batch: from this many instances on.  Same bits as the other forms
+// (tests/test_gpu_sweep_io.py), so the threshold is a pure speed choice.  Measured on C3 (profiles/sweep_io_batch_scan.txt, ms per solve, four
+// waves against four waves and the I/O wave): B = 256 5.14 / 5.07, 1024 5.31 / 5.25, 2048 5.45 / 5.40, 3072 6.13 / 6.02, 4096 6.09 / 5.98 -- never
+// slower at a measured size; smaller batches were not measured and stay on lone waves, as for SI_WG_MIN_BATCH.  The halves of a split solve
+// (ilqr_ctx_set_split(2)) were not measured either and keep the four-wave form under AUTO: the form's 99 KB of LDS allow one workgroup per CU, so
+// two halves of 4096 instances on two streams could no longer share the CUs as the 20 KB workgroups of the four-wave form do.  The pin forces it there too.
+constexpr int SI_IO_MIN_BATCH = 256;
+constexpr bool si_io_supported(bool al, int m) { return !al || m <= 1; }
 
 // Variant pins of ilqr_ctx_set_crosscheck: AUTO (0) = by batch size; the values are the ILQR_XC_* constants of include/ilqr_hip.h
-enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2, SiWave = 4, SiWg = 5 };  // SiWave / SiWg: the form of k_backward_si_dpp (same bits); AUTO elsewhere.  (3 is no pin: ilqr_ctx_set_crosscheck refuses it)
+enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2, SiWave = 4, SiWg = 5, SiWgIo = 6 };  // SiWave / SiWg / SiWgIo: the form of k_backward_si_dpp (same bits); AUTO elsewhere.  (3 is no pin: ilqr_ctx_set_crosscheck refuses it)
 enum class FwdPin { Auto = 0, Wg = 1, Dpp = 2, WgLds = 3 };  // WgLds: Wg with k_forward_wg, the predecessor of k_forward_reg (same bits)
 enum class RerollPin { Auto = 0, Rows = 1, Dpp = 2 };
 
@@ -96,6 +106,7 @@ struct RiccatiPlan {
     Sweep sweep = Sweep::Generic;
     int si_lanes[2] = {16, 16};   // Sweep::SiDpp: lanes per instance of the whole batch or of each half (split)
     bool si_wg[2] = {false, false};  // Sweep::SiDpp with 16 lanes: the workgroup form (SI_WG_MIN_BATCH, or the pins SiWave / SiWg), per launched half
+    bool si_io[2] = {false, false};  // ... with the I/O wave (SI_IO_MIN_BATCH on an unsplit solve, or the pin SiWgIo; never under SiWave / SiWg): only where si_wg, at most one AL row
     Forward forward = Forward::Generic;
     bool fwd_lds = false;         // Forward::WaveWg under the pin FwdPin::WgLds: k_forward_wg instead of k_forward_reg
     Apply apply = Apply::None;
@@ -119,7 +130,7 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     // waves (measured: B = 2048 600 against 548 us, B = 4096 597 against 1040)
     if (cooperative && in.off32 && backward_si_supported(kind, nd, in.al, in.m, in.per_step, in.con_state_only)) p.sweep = Sweep::SiDpp;
     else if (cooperative && backward_mfma_supported(kind, nd, in.al, in.m)) {
-        const bool pinned = in.sweep == SweepPin::Mfma || in.sweep == SweepPin::Rows;  // (SiWave / SiWg pin nothing here)
+        const bool pinned = in.sweep == SweepPin::Mfma || in.sweep == SweepPin::Rows;  // (SiWave / SiWg / SiWgIo pin nothing here)
         const bool rows = in.sweep == SweepPin::Rows || (!pinned && in.B > 2 * in.n_simd);
         p.sweep = rows && backward_rows_supported(kind, nd, in.al, in.m) ? Sweep::Rows : Sweep::Mfma;
     }
@@ -168,9 +179,12 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     p.si_lanes[1] = si_lanes(in.B - b0, in.n_simd);
     // the 8-lane grouping (B > 4 n_simd) stays on the one-wave form, whatever the pin says
     const int launched[2] = {b0, in.B - b0};
-    for (int h = 0; h < 2; h++)
-        p.si_wg[h] = p.sweep == Sweep::SiDpp && p.si_lanes[h] == 16 &&
-                     (in.sweep == SweepPin::SiWg || (in.sweep != SweepPin::SiWave && launched[h] >= SI_WG_MIN_BATCH));
+    for (int h = 0; h < 2; h++) {
+        const bool wg_pin = in.sweep == SweepPin::SiWg || in.sweep == SweepPin::SiWgIo;  // (SiWgIo acts as SiWg where the I/O wave is not supported)
+        p.si_wg[h] = p.sweep == Sweep::SiDpp && p.si_lanes[h] == 16 && (wg_pin || (in.sweep != SweepPin::SiWave && launched[h] >= SI_WG_MIN_BATCH));
+        p.si_io[h] = p.si_wg[h] && si_io_supported(in.al, in.m) &&
+                     (in.sweep == SweepPin::SiWgIo || (in.sweep != SweepPin::SiWg && !p.split && launched[h] >= SI_IO_MIN_BATCH));
+    }
     return p;
 }
 

@@ -47,6 +47,8 @@ extern "C" {
 #define ILQR_STATUS_OK 0
 #define ILQR_STATUS_NONFINITE 1   /* accepted cost is NaN/Inf (the reference prints -nan and carries on) */
 #define ILQR_STATUS_ALPHA_FLOOR 2 /* last line search bottomed out at alpha <= alpha_floor (accept-anyway rule) */
+#define ILQR_STATUS_SWEEP_IO 4    /* a wave of the sweep's I/O-wave form gave up a bounded wait on its partner (a protocol error, never seen): the instance was \
+                                     made inactive, no later kernel touches it and its outputs are not a solution.  Sticky until the next solve. */
 
 typedef struct ilqr_ctx ilqr_ctx;
 typedef struct ilqr_problem ilqr_problem;
@@ -166,7 +168,10 @@ int ilqr_ctx_set_split(ilqr_ctx* ctx, int on);
 #define ILQR_XC_SWEEP_MFMA 1   /* sweep of the 2nd-order / time systems: one instance per wave on the f64 matrix cores (AUTO: up to 2 n_simd instances) */
 #define ILQR_XC_SWEEP_ROWS 2   /*   ... 16 lanes per instance with the rows in registers (AUTO: beyond) */
 #define ILQR_XC_SWEEP_SI_WAVE 4 /* sweep of the single-integrator systems: k_backward_si_dpp on lone waves at any batch size: the same bits as AUTO (3 is no sweep pin: refused) */
-#define ILQR_XC_SWEEP_SI_WG 5   /*   ... in its workgroup form (16 lanes per instance only; AUTO: from 256 launched instances): the same bits as AUTO */
+#define ILQR_XC_SWEEP_SI_WG 5   /*   ... in its four-wave workgroup form without the I/O wave (16 lanes per instance only): the same bits as AUTO */
+#define ILQR_XC_SWEEP_SI_WG_IO 6 /*  ... in its workgroup form with the I/O wave, a fifth wave that stores the chain waves' gain records and their accepted x, u, the \
+                                     latter as whole 128-byte lines (16 lanes per instance, at most one constraint row; ILQR_XC_SWEEP_SI_WG elsewhere; AUTO: from \
+                                     256 launched instances of an unsplit solve): the same bits as AUTO */
 #define ILQR_XC_FWD_WG 1       /* forward pass of the single-integrator systems: the large-batch k_forward_reg (AUTO: beyond 3 n_simd instances) */
 #define ILQR_XC_FWD_DPP 2      /*   ... the latency-built k_forward_dpp (AUTO: up to 3 n_simd); agrees with the others to rounding */
 #define ILQR_XC_FWD_WG_LDS 3   /*   ... k_forward_wg, the predecessor of k_forward_reg, at any batch size: the same bits as ILQR_XC_FWD_WG (never AUTO) */
