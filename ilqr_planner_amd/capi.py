@@ -37,7 +37,7 @@ EXPORTS = [
     "ilqr_problem_reset_multipliers", "ilqr_problem_warm_start", "ilqr_problem_track", "ilqr_problem_track_dev",
     "ilqr_problem_closed_loop", "ilqr_problem_closed_loop_dev", "ilqr_problem_closed_loop_noise", "ilqr_problem_closed_loop_noise_dev",
     "ilqr_problem_closed_loop_report", "ilqr_problem_closed_loop_report_dev", "ilqr_problem_closed_loop_cov", "ilqr_problem_closed_loop_cov_dev",
-    "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck",
+    "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck", "ilqr_problem_gains",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
     "ilqr_lqt_get_d",
@@ -161,6 +161,7 @@ def load():
     L.ilqr_problem_set_constraints.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
     L.ilqr_problem_reset_multipliers.argtypes = [vp]
     L.ilqr_problem_warm_start.argtypes = [vp, C.c_int]
+    L.ilqr_problem_gains.argtypes = [vp]
     L.ilqr_problem_track.argtypes = [vp, C.c_int, dp, C.c_int, dp]
     L.ilqr_problem_track_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.ilqr_problem_closed_loop.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp]
@@ -492,6 +493,13 @@ class BatchProblem:
     # ---- receding horizon / tracking
     def warm_start(self, shift: int = 0):
         self.ctx.check(self.L.ilqr_problem_warm_start(self.h, int(shift)))
+
+    def gains(self):
+        """Gains about the plan the problem holds (ilqr_problem_gains): one backward sweep about X(), U(), whichever solver left them -- the batch
+        solvers and a 0-iteration solve_recursive included.  Afterwards K(), d() are that sweep's (d unscaled, alpha() all ones) and track and the
+        closed-loop calls run on them; X, U, cost, iters, status, lam and the trace are untouched.  Asynchronous on the context's stream."""
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_gains(self.h))
 
     def track(self, k: int, x_meas, with_feedforward: bool = False):
         x = _f64(x_meas, (self.B, self.dims.n_x))

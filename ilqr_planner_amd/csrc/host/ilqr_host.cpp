@@ -1443,14 +1443,15 @@ static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter,
     r.X.resize((size_t)B * T * dm.n_x);
     r.U.resize((size_t)B * nU);
     r.cost.resize(B); r.alpha.resize(B); r.iters.resize(B); r.status.resize(B);
+    check(ilqr_problem_get_alpha(g.p, r.alpha.data()));  // the solver's last step size: ilqr_problem_gains puts 1 there
+    if (in.plan_gains) check(ilqr_problem_gains(g.p));   // K, d about the plan the solve leaves, before any of them is read
     check(ilqr_problem_get_X(g.p, r.X.data()));
     check(ilqr_problem_get_U(g.p, r.U.data()));
     check(ilqr_problem_get_cost(g.p, r.cost.data()));
-    check(ilqr_problem_get_alpha(g.p, r.alpha.data()));
     check(ilqr_problem_get_iters(g.p, r.iters.data()));
     check(ilqr_problem_get_status(g.p, r.status.data()));
     if (in.want_fX) { r.fX.resize((size_t)B * T * dm.n_f); check(ilqr_problem_get_fX(g.p, r.fX.data())); }
-    if (gains && in.want_gains && nb_iter > 0) {
+    if ((gains && in.want_gains && nb_iter > 0) || in.plan_gains) {
         r.K.resize((size_t)B * nU * dm.n_x);
         r.d.resize((size_t)B * nU);
         check(ilqr_problem_get_K(g.p, r.K.data()));
@@ -1714,7 +1715,8 @@ BatchILQRCP::BatchILQRCP(const std::shared_ptr<sys::System>& s_, const Mat& Q_, 
 BatchILQRCP::BatchILQRCP(const std::shared_ptr<sys::System>& s_, const Mat& psi) : s(s_), PSI(psi), custom_Q(false) {}
 
 // psi == nullptr: BatchILQR (identity basis, never materialised)
-static BatchResult batch_gauss_newton(sys::System& s, const Mat* psi, const Mat* Q, const BatchInputs& in, int nb_iter, bool early_stop) {
+static BatchResult batch_gauss_newton(sys::System& s, const Mat* psi, const Mat* Q, const BatchInputs& in, int nb_iter, bool early_stop,
+                                      const std::function<void(ilqr_problem*)>& then = nullptr) {
     const int T = s.getHorizon(), nu = s.getNbCtrlVar();
     if (psi && psi->rows != (T - 1) * nu) throw std::runtime_error("[BatchILQRCP] psi must have (horizon-1)*nb_ctrl_var rows");
     // the sparse form of the reference stacks a target block per keypoint of the concatenated list, every sub-system's target into each of a
@@ -1733,23 +1735,45 @@ static BatchResult batch_gauss_newton(sys::System& s, const Mat* psi, const Mat*
             }
     }
     BatchInputs in2 = in;
-    in2.want_gains = false;
+    in2.want_gains = false;  // the batch solvers leave no gains: K, d are read only where plan_gains asks ilqr_problem_gains for them
     return run_batch(s, in2, nb_iter, false, &d, nullptr,
                      [&](ilqr_problem* p) {
                          if (psi) check(ilqr_solve_batch_cp(p, psi->d.data(), psi->cols, nb_iter, early_stop));
                          else check(ilqr_solve_batch(p, nb_iter, early_stop));
                      },
-                     nullptr);
+                     then);
+}
+
+// the batch solve, the gains about its plan (ilqr_problem_gains), then the closed loop / its covariance on them
+template <class In, class Out, class Fn>
+static std::pair<BatchResult, Out> batch_then(sys::System& s, const Mat* psi, const Mat* Q, const BatchInputs& in, const In& cin, int nb_iter, bool early_stop, Fn fn) {
+    Out o;
+    BatchInputs in2 = in;
+    in2.plan_gains = true;
+    BatchResult r = batch_gauss_newton(s, psi, Q, in2, nb_iter, early_stop, [&](ilqr_problem* p) { fn(p, s, in.B, cin, o); });
+    return {std::move(r), std::move(o)};
 }
 
 BatchResult BatchILQRCP::solveBatch(const BatchInputs& in, int nb_iter, bool early_stop) {
     return batch_gauss_newton(*s, &PSI, custom_Q ? &Q : nullptr, in, nb_iter, early_stop);
+}
+std::pair<BatchResult, ClosedLoopResult> BatchILQRCP::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool early_stop) {
+    return batch_then<ClosedLoopInputs, ClosedLoopResult>(*s, &PSI, custom_Q ? &Q : nullptr, in, cl, nb_iter, early_stop, closed_loop_of);
+}
+std::pair<BatchResult, ClosedLoopCovResult> BatchILQRCP::closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool early_stop) {
+    return batch_then<ClosedLoopCovInputs, ClosedLoopCovResult>(*s, &PSI, custom_Q ? &Q : nullptr, in, cv, nb_iter, early_stop, closed_loop_cov_of);
 }
 
 BatchILQR::BatchILQR(const std::shared_ptr<sys::System>& s_, const Mat& Q_) : s(s_), Q(Q_), custom_Q(true) {}
 BatchILQR::BatchILQR(const std::shared_ptr<sys::System>& s_) : s(s_), custom_Q(false) {}
 BatchResult BatchILQR::solveBatch(const BatchInputs& in, int nb_iter, bool early_stop) {
     return batch_gauss_newton(*s, nullptr, custom_Q ? &Q : nullptr, in, nb_iter, early_stop);
+}
+std::pair<BatchResult, ClosedLoopResult> BatchILQR::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool early_stop) {
+    return batch_then<ClosedLoopInputs, ClosedLoopResult>(*s, nullptr, custom_Q ? &Q : nullptr, in, cl, nb_iter, early_stop, closed_loop_of);
+}
+std::pair<BatchResult, ClosedLoopCovResult> BatchILQR::closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool early_stop) {
+    return batch_then<ClosedLoopCovInputs, ClosedLoopCovResult>(*s, nullptr, custom_Q ? &Q : nullptr, in, cv, nb_iter, early_stop, closed_loop_cov_of);
 }
 Vec BatchILQR::solve(int nb_iter, const Vec& u0, bool early_stop, CallBackMessage* cb) {  // BatchILQR.cpp:110-173
     if (!s->builtin()) return solve_batch_over_virtuals(*s, nullptr, custom_Q ? Q : s->getQMatrix(true), nb_iter, u0, early_stop, cb);  // user-defined System

@@ -469,6 +469,9 @@ struct BatchInputs {
     std::vector<std::vector<double>> kp_targets;    // per keypoint: [B][n_f] in f(x) order
     std::vector<double> U0;                         // [B][T-1][n_u]  (or [T-1][n_u], broadcast)
     bool want_fX = true, want_gains = true;
+    // K, d of the result are the gains about the plan the solve leaves (ilqr_problem_gains: one sweep about the returned X, U, feed-forward
+    // unscaled), for any solver -- the batch solvers, which leave none of their own, included; the closed loops then run on them
+    bool plan_gains = false;
 };
 
 // Closed loop of the tracking law on the plan a batched Riccati solve leaves (ilqr_problem_closed_loop): S executions per instance.
@@ -571,6 +574,9 @@ public:
     explicit BatchILQR(const std::shared_ptr<sys::System>& s);
     Vec solve(int nb_iter, const Vec& u0, bool early_stop = true, CallBackMessage* cb = nullptr);
     BatchResult solveBatch(const BatchInputs& in, int nb_iter, bool early_stop = true);
+    // solveBatch, the gains about its plan (ilqr_problem_gains), then the closed loop / its analytic covariance on them
+    std::pair<BatchResult, ClosedLoopResult> closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool early_stop = true);
+    std::pair<BatchResult, ClosedLoopCovResult> closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool early_stop = true);
 
 private:
     std::shared_ptr<sys::System> s;
@@ -584,6 +590,9 @@ public:
     BatchILQRCP(const std::shared_ptr<sys::System>& s, const Mat& psi);
     Vec solve(int nb_iter, const Vec& u0, bool early_stop = true, CallBackMessage* cb = nullptr);
     BatchResult solveBatch(const BatchInputs& in, int nb_iter, bool early_stop = true);
+    // solveBatch, the gains about its plan (ilqr_problem_gains), then the closed loop / its analytic covariance on them
+    std::pair<BatchResult, ClosedLoopResult> closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool early_stop = true);
+    std::pair<BatchResult, ClosedLoopCovResult> closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool early_stop = true);
 
 private:
     std::shared_ptr<sys::System> s;

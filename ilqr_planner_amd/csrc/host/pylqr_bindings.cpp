@@ -64,6 +64,12 @@ static py::array_t<double> shaped(const std::vector<double>& v, std::vector<py::
     return a;
 }
 
+// solve_batch(..., plan_gains = True): K, d of the result are the gains about the plan the solve leaves (ilqr_problem_gains)
+static solver::BatchInputs plan_gains(solver::BatchInputs in, bool on) {
+    in.plan_gains = on;
+    return in;
+}
+
 // numpy -> BatchInputs: U0 [B][T-1][n_u] or [T-1][n_u]; q0/dq0 [B][dof] or None; kp_targets list of [B][n_f] or None
 static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& q0, const py::object& dq0, const py::object& kp_targets, bool flat_u = false) {
     solver::BatchInputs in;
@@ -355,28 +361,28 @@ PYBIND11_MODULE(PyLQR, m) {
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
         .def("solve", &solver::ILQRRecursive::solve, py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
-             [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp) {
-                 return self.solveBatch(batch_inputs(U0, q0, dq0, kp), nb_iter, ls, es);
+             [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg) {
+                 return self.solveBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
-             py::arg("kp_targets") = py::none())
+             py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
         .def("closed_loop_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
                 const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
-                const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol) {
-                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol), nb_iter,
+                const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol, bool pg) {
+                 return self.closedLoopBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol), nb_iter,
                                              ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
              py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(), py::arg("w") = py::none(), py::arg("with_feedforward") = false,
-             py::arg("samples") = py::none(), py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none())
+             py::arg("samples") = py::none(), py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none(), py::arg("plan_gains") = false)
         .def("closed_loop_cov_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
-                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
-                 return self.closedLoopCovBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, ls, es);
+                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg) {
+                 return self.closedLoopCovBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
-             py::arg("kp_targets") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false);
+             py::arg("kp_targets") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("plan_gains") = false);
     py::class_<solver::AL_ILQR>(m_sol, "AL_ILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const std::vector<solver::Constraint>&, const std::vector<Vec>&>(), py::arg("s"), py::arg("inequality"),
              py::arg("initLambda"))
@@ -384,38 +390,57 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("line_search"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
-                const py::object& kp) { return self.solveBatch(batch_inputs(U0, q0, dq0, kp), nb_iter, lag, pen, sc, ls, es); },
+                const py::object& kp, bool pg) { return self.solveBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), nb_iter, lag, pen, sc, ls, es); },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
-             py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none())
+             py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
                 const py::object& kp, const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed,
-                const py::object& sigma_w, const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol) {
-                 return self.closedLoopBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol), nb_iter,
+                const py::object& sigma_w, const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol, bool pg) {
+                 return self.closedLoopBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol), nb_iter,
                                              lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(),
              py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none(), py::arg("seed") = py::none(),
-             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none())
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none(), py::arg("plan_gains") = false)
         .def("closed_loop_cov_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
-                const py::object& kp, const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
-                 return self.closedLoopCovBatch(batch_inputs(U0, q0, dq0, kp), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, lag, pen, sc, ls, es);
+                const py::object& kp, const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg) {
+                 return self.closedLoopCovBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
-             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false);
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("plan_gains") = false);
     // bindings.cpp:778-782
     py::class_<solver::BatchILQR>(m_sol, "BatchILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("Q"))
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
         .def("solve", &solver::BatchILQR::solve, py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
-             [](solver::BatchILQR& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp) {
-                 return self.solveBatch(batch_inputs(u0, q0, dq0, kp, true), nb_iter, es);
+             [](solver::BatchILQR& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg) {
+                 return self.solveBatch(plan_gains(batch_inputs(u0, q0, dq0, kp, true), pg), nb_iter, es);
              },
-             py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none());
+             py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
+        // the arguments of solve_batch, then the closed-loop arguments of ILQRRecursive's methods; always on the gains about the solve's plan
+        .def("closed_loop_batch",
+             [](solver::BatchILQR& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
+                const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
+                const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol) {
+                 return self.closedLoopBatch(batch_inputs(u0, q0, dq0, kp, true), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol),
+                                             nb_iter, es);
+             },
+             py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
+             py::arg("x0") = py::none(), py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none(),
+             py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(),
+             py::arg("lim_tol") = py::none())
+        .def("closed_loop_cov_batch",
+             [](solver::BatchILQR& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
+                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
+                 return self.closedLoopCovBatch(batch_inputs(u0, q0, dq0, kp, true), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, es);
+             },
+             py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false);
     // bindings.cpp:862-869: positional arguments only, no defaults
     py::class_<solver::LQT>(m_sol, "LQT")
         .def(py::init<const Mat&, const Mat&, const std::vector<Mat>&, const Vec&, float, int>())
@@ -430,8 +455,27 @@ PYBIND11_MODULE(PyLQR, m) {
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("psi"))
         .def("solve", &solver::BatchILQRCP::solve, py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
-             [](solver::BatchILQRCP& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp) {
-                 return self.solveBatch(batch_inputs(u0, q0, dq0, kp, true), nb_iter, es);
+             [](solver::BatchILQRCP& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg) {
+                 return self.solveBatch(plan_gains(batch_inputs(u0, q0, dq0, kp, true), pg), nb_iter, es);
              },
-             py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none());
+             py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
+        // the arguments of solve_batch, then the closed-loop arguments of ILQRRecursive's methods; always on the gains about the solve's plan
+        .def("closed_loop_batch",
+             [](solver::BatchILQRCP& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
+                const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
+                const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol) {
+                 return self.closedLoopBatch(batch_inputs(u0, q0, dq0, kp, true), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol),
+                                             nb_iter, es);
+             },
+             py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
+             py::arg("x0") = py::none(), py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none(),
+             py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(),
+             py::arg("lim_tol") = py::none())
+        .def("closed_loop_cov_batch",
+             [](solver::BatchILQRCP& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
+                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
+                 return self.closedLoopCovBatch(batch_inputs(u0, q0, dq0, kp, true), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, es);
+             },
+             py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false);
 }

@@ -61,7 +61,8 @@ struct ilqr_problem {
     DevScratch staging;  // device staging for host<->device natural-layout transfers
     int last_nb_iter = 0;
     bool has_controls = false, has_state = false;
-    bool has_gains = false;  // a Riccati solve with nb_iter >= 1 has run since the inputs last changed: X, U, KD are one plan (closed_loop)
+    bool has_gains = false;  // a Riccati solve with nb_iter >= 1 or ilqr_problem_gains has run since the inputs last changed: X, U, KD are one plan (closed_loop)
+    bool has_plan = false;   // one of the four solvers has run since the inputs last changed: X, U are a plan ilqr_problem_gains can sweep about
     DevScratch cl_cost;  // closed_loop_noise without a cost array: the per-sample costs k_closed_loop_stats reduces
     DevScratch cl_kpx;   // closed_loop: state | control of every sample at the step-table entries (k_closed_loop_coop -> k_closed_loop_kp)
     DevScratch cl_rep;   // closed_loop_report through device pointers: kp_err | lim_cost where the caller asks only for their reductions
@@ -489,7 +490,7 @@ static int upload(ilqr_problem* p, const double* src, bool src_is_dev, double* d
 static int set_init_state(ilqr_problem* p, const double* q0, const double* dq0, bool dev) {
     if (!p) return 1;
     if (!q0) return fail(p->ctx, "q0 is required");
-    p->has_gains = false;
+    p->has_gains = p->has_plan = false;
     const IndexMap* qm = p->mapped ? &p->qmap : nullptr;
     if (upload(p, q0, dev, (double*)p->bufs.q0, p->desc.dof, qm, 1)) return 1;
     if (dq0) {
@@ -506,7 +507,7 @@ extern "C" int ilqr_problem_set_init_state_dev(ilqr_problem* p, const double* q0
 static int set_kp(ilqr_problem* p, int k, const double* tg, bool dev) {
     if (!p) return 1;
     if (k < 0 || k >= p->desc.n_kp || !tg) return fail(p->ctx, "bad keypoint index / null target");
-    p->has_gains = false;
+    p->has_gains = p->has_plan = false;
     double* dst = (double*)p->bufs.kp_tg + (size_t)k * p->dims.n_f * p->Bp;
     if (p->mapped && (p->desc.kind == ILQR_SYS_JOINT || p->desc.kind == ILQR_SYS_JOINT_TIME))  // the target is a state
         return upload(p, tg, dev, dst, p->udims.n_f, &p->map.x, 1);
@@ -522,7 +523,7 @@ extern "C" int ilqr_problem_set_keypoint_targets_dev(ilqr_problem* p, int k, con
 static int set_controls(ilqr_problem* p, const double* U0, bool dev) {
     if (!p) return 1;
     if (!U0) return fail(p->ctx, "U0 is required");
-    p->has_gains = false;
+    p->has_gains = p->has_plan = false;
     if (upload(p, U0, dev, (double*)p->bufs.U0, (p->T - 1) * p->udims.n_u, p->mapped ? &p->map.u : nullptr, p->T - 1)) return 1;
     p->has_controls = true;
     p->u0_zero = false;
@@ -541,7 +542,7 @@ extern "C" int ilqr_problem_set_constraints(ilqr_problem* p, int m, int per_step
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
     if (m <= 0 || !A || !b) return fail(c, "bad constraint arguments");
-    p->has_gains = false;
+    p->has_gains = p->has_plan = false;
     const int ns = p->dims.n_x + p->dims.n_u, T = p->T, nsu = p->udims.n_x + p->udims.n_u;
     const size_t nk = per_step ? (size_t)(T - 1) : 1;
     if (p->bufs.m != m || p->bufs.per_step != per_step || !p->conA) {
@@ -593,7 +594,7 @@ extern "C" int ilqr_problem_set_constraints(ilqr_problem* p, int m, int per_step
 extern "C" int ilqr_problem_reset_multipliers(ilqr_problem* p) {
     if (!p) return 1;
     if (p->bufs.m <= 0) return fail(p->ctx, "no constraints set");
-    p->has_gains = false;
+    p->has_gains = p->has_plan = false;
     HIPCHK(p->ctx, hipMemcpyAsync(p->bufs.lambda, p->lambda0, sizeof(double) * (size_t)(p->T - 1) * p->bufs.m * p->Bp,
                                   hipMemcpyDeviceToDevice, p->ctx->stream));
     return 0;
@@ -654,6 +655,67 @@ static PlanIn plan_input(const ilqr_problem* p, bool al, int nb_iter, int line_s
     return in;
 }
 
+// ---- one or two independent halves ("lanes" of the launch schedule).  Instances never interact, so the halves of a large batch are
+// two complete solves on two streams; the second one starts one sweep later, so that its latency-bound sweep runs under the other
+// half's bandwidth-bound forward pass.  Results do not depend on the split (bit for bit: tests/test_gpu_fullsize.py).
+struct Half { Bufs bufs; int B; hipStream_t st; };
+static int split_begin(ilqr_problem* p, bool split, Half hv[2], int& nh) {
+    ilqr_ctx* c = p->ctx;
+    nh = 1;
+    if (!split) {
+        hv[0].bufs = p->bufs; hv[0].B = p->B; hv[0].st = c->stream;
+        return 0;
+    }
+    for (int i = 0; i < 2; i++) {
+        if (!c->half_stream[i]) HIPCHK(c, hipStreamCreateWithFlags(&c->half_stream[i], hipStreamNonBlocking));
+        if (!c->ev_half_done[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_half_done[i], hipEventDisableTiming));
+    }
+    if (!c->ev_begin) HIPCHK(c, hipEventCreateWithFlags(&c->ev_begin, hipEventDisableTiming));
+    if (!c->ev_stagger) HIPCHK(c, hipEventCreateWithFlags(&c->ev_stagger, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_begin, c->stream));  // inputs (and the trace fill) are ordered on the caller's stream
+    nh = 2;
+    for (int i = 0; i < 2; i++) {
+        HIPCHK(c, hipStreamWaitEvent(c->half_stream[i], c->ev_begin, 0));
+        hv[i].bufs = half_bufs(p, i); hv[i].B = p->half_B[i]; hv[i].st = c->half_stream[i];
+    }
+    return 0;
+}
+// Join on EVERY exit path: an early return between split_begin and the end of the call (a failed launch or event call on one half) must not
+// leave work queued on a half stream that the context's stream never waits for -- the caller's next call would race with it.
+struct SplitJoin {
+    ilqr_ctx* c; bool on;
+    ~SplitJoin() {
+        if (!on) return;
+        for (int i = 0; i < 2; i++)
+            if (hipEventRecord(c->ev_half_done[i], c->half_stream[i]) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_half_done[i], 0) != hipSuccess)
+                (void)hipStreamSynchronize(c->half_stream[i]);  // last resort: drain it here
+    }
+};
+
+// What k_kp_derivs needs of a launch (and what every FwdArgs of a plan shares): the step table's sizes and which keypoint code is instantiated.
+static FwdArgs plan_fwd_args(const ilqr_problem* p, const RiccatiPlan& pl) {
+    FwdArgs f;
+    std::memset(&f, 0, sizeof(f));
+    f.n_alpha = pl.n_alpha; f.n_kp = p->hdesc.steps.n;
+    f.shared = has_shared_step(p->hdesc.steps) ? 1 : 0;
+    f.n_kp_all = p->desc.n_kp;
+    f.fused = pl.fused ? 1 : 0;
+    f.fwd_lds = pl.fwd_lds ? 1 : 0;
+    f.limits = p->desc.limits_set ? 1 : 0;
+    for (int k = 0; k < p->desc.n_kp; k++) f.kp_ext |= p->desc.kp_dist[k] | p->desc.kp_has_frame[k] | p->desc.kp_has_Ru[k] | p->desc.kp_joint[k];
+    return f;
+}
+// The sweep of the plan on half h (the whole batch: h = 0)
+static void launch_sweep(const ilqr_problem* p, const RiccatiPlan& pl, int h, bool al, const Bufs& bf, int B, hipStream_t st, SweepArgs& sw) {
+    const int kind = p->desc.kind, nd = p->desc.nb_deriv;
+    switch (pl.sweep) {
+        case Sweep::SiDpp: sw.si_wg = pl.si_wg[h] ? 1 : 0; sw.si_io = pl.si_io[h] ? 1 : 0; launch_backward_si_dpp(al, pl.fused, pl.kd_sym == 1, pl.si_lanes[h], bf, B, st, sw); break;
+        case Sweep::Rows: launch_backward_rows(kind, nd, al, bf, B, st); break;
+        case Sweep::Mfma: launch_backward_mfma(kind, nd, al, bf, B, st); break;
+        case Sweep::Generic: launch_backward_generic(kind, nd, al, bf, B, st); break;
+    }
+}
+
 static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double penalty0, double scaling, int line_search, int early_stop) {
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
@@ -663,56 +725,19 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     HIPCHK(c, hipSetDevice(c->device));
     if (ensure_trace(p, nb_iter)) return 1;
     p->last_nb_iter = nb_iter;
-    p->has_gains = false;  // until this solve's launches are queued; a 0-iteration solve re-rolls X from U0 and leaves the gains of another plan
+    p->has_gains = p->has_plan = false;  // until this solve's launches are queued; a 0-iteration solve re-rolls X from U0 and leaves the gains of another plan
     const int kind = p->desc.kind, nd = p->desc.nb_deriv, T = p->T;
     const RiccatiPlan pl = plan_riccati(plan_input(p, al, nb_iter, line_search));
     if (pl.kd_sym != KD_SYM_KEEP) p->bufs.kd_sym = pl.kd_sym;  // before half_bufs: it sizes the half's offset into KD
     if (pl.needs_ws && !p->bufs.ws)
         if (dalloc(p, &p->bufs.ws, (size_t)backward_ws_entries(kind, nd) * p->Bp, false)) return 1;
 
-    // ---- one or two independent halves ("lanes" of the launch schedule).  Instances never interact, so the halves of a large batch are
-    // two complete solves on two streams; the second one starts one sweep later, so that its latency-bound sweep runs under the other
-    // half's bandwidth-bound forward pass.  Results do not depend on the split (bit for bit: tests/test_gpu_fullsize.py).
-    struct Half { Bufs bufs; int B; hipStream_t st; };
     Half hv[2];
     int nh = 1;
-    if (pl.split) {
-        for (int i = 0; i < 2; i++) {
-            if (!c->half_stream[i]) HIPCHK(c, hipStreamCreateWithFlags(&c->half_stream[i], hipStreamNonBlocking));
-            if (!c->ev_half_done[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_half_done[i], hipEventDisableTiming));
-        }
-        if (!c->ev_begin) HIPCHK(c, hipEventCreateWithFlags(&c->ev_begin, hipEventDisableTiming));
-        if (!c->ev_stagger) HIPCHK(c, hipEventCreateWithFlags(&c->ev_stagger, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->ev_begin, c->stream));  // inputs (and the trace fill) are ordered on the caller's stream
-        nh = 2;
-        for (int i = 0; i < 2; i++) {
-            HIPCHK(c, hipStreamWaitEvent(c->half_stream[i], c->ev_begin, 0));
-            hv[i].bufs = half_bufs(p, i); hv[i].B = p->half_B[i]; hv[i].st = c->half_stream[i];
-        }
-    } else {
-        hv[0].bufs = p->bufs; hv[0].B = p->B; hv[0].st = c->stream;
-    }
-
-    // Join on EVERY exit path: an early return between here and the end of the solve (a failed launch or event call on one half) must not
-    // leave work queued on a half stream that the context's stream never waits for -- the caller's next call would race with it.
-    struct SplitJoin {
-        ilqr_ctx* c; bool on;
-        ~SplitJoin() {
-            if (!on) return;
-            for (int i = 0; i < 2; i++)
-                if (hipEventRecord(c->ev_half_done[i], c->half_stream[i]) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_half_done[i], 0) != hipSuccess)
-                    (void)hipStreamSynchronize(c->half_stream[i]);  // last resort: drain it here
-        }
-    } split_join{c, pl.split};
-    FwdArgs f;
-    std::memset(&f, 0, sizeof(f));
-    f.line_search = line_search; f.early_stop = early_stop; f.nb_iter = nb_iter; f.penalty_roll = penalty0; f.n_alpha = pl.n_alpha; f.al = al ? 1 : 0; f.n_kp = p->hdesc.steps.n;
-    f.shared = has_shared_step(p->hdesc.steps) ? 1 : 0;
-    f.n_kp_all = p->desc.n_kp;
-    f.fused = pl.fused ? 1 : 0;
-    f.fwd_lds = pl.fwd_lds ? 1 : 0;
-    f.limits = p->desc.limits_set ? 1 : 0;
-    for (int k = 0; k < p->desc.n_kp; k++) f.kp_ext |= p->desc.kp_dist[k] | p->desc.kp_has_frame[k] | p->desc.kp_has_Ru[k] | p->desc.kp_joint[k];
+    if (split_begin(p, pl.split, hv, nh)) return 1;
+    SplitJoin split_join{c, pl.split};  // on every exit path
+    FwdArgs f = plan_fwd_args(p, pl);
+    f.line_search = line_search; f.early_stop = early_stop; f.nb_iter = nb_iter; f.penalty_roll = penalty0; f.al = al ? 1 : 0;
     for (int h = 0; h < nh; h++) {
         const Bufs& bf = hv[h].bufs;
         ProfScope ps(c, ILQR_PROF_ROLLOUT);
@@ -745,12 +770,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
             }
             {
                 ProfScope ps(c, ILQR_PROF_BACKWARD);
-                switch (pl.sweep) {
-                    case Sweep::SiDpp: sw.si_wg = pl.si_wg[h] ? 1 : 0; sw.si_io = pl.si_io[h] ? 1 : 0; launch_backward_si_dpp(al, pl.fused, pl.kd_sym == 1, pl.si_lanes[h], bf, B, st, sw); break;
-                    case Sweep::Rows: launch_backward_rows(kind, nd, al, bf, B, st); break;
-                    case Sweep::Mfma: launch_backward_mfma(kind, nd, al, bf, B, st); break;
-                    case Sweep::Generic: launch_backward_generic(kind, nd, al, bf, B, st); break;
-                }
+                launch_sweep(p, pl, h, al, bf, B, st, sw);
             }
             if (pl.split && it == 0 && h == 0) HIPCHK(c, hipEventRecord(c->ev_stagger, st));
             {
@@ -783,6 +803,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     // (the caller's stream continues when both halves are done: SplitJoin above, on every exit path)
     prof_mark(c, -1);
     p->has_gains = nb_iter >= 1;
+    p->has_plan = true;
     return 0;
 }
 
@@ -803,7 +824,7 @@ extern "C" int ilqr_solve_batch_cp(ilqr_problem* p, const double* psi, int Kw, i
     ilqr_ctx* c = p->ctx;
     if (has_shared_step(p->hdesc.steps)) return fail(c, BATCH_SHARED_STEP_TEXT);
     if (!p->has_state || !p->has_controls) return fail(c, "set_init_state and set_controls must be called before a solve");
-    p->has_gains = false;  // the batch solvers leave no gains
+    p->has_gains = p->has_plan = false;  // the batch solvers leave no gains (ilqr_problem_gains computes them about the plan)
     HIPCHK(c, hipSetDevice(c->device));
     std::string err;
     if (ensure_trace(p, nb_iter)) return 1;
@@ -821,12 +842,14 @@ extern "C" int ilqr_solve_batch_cp(ilqr_problem* p, const double* psi, int Kw, i
     if (psi && Kw > 16 && !(cp_time && Kw <= 32)) {  // wide basis: low-rank form of the normal equations (ilqr_batchwide.hip)
         if (batchwide_solve(p->cpw, p->hdesc, p->bufs, p->dims.n_x, p->dims.n_u, psi, Kw, nb_iter, early_stop, p->u0_zero, c->stream, err, prof_hook(c))) return fail(c, err);
         prof_mark(c, -1);
+        p->has_plan = true;
         return 0;
     }
     p->cp.xc_lane_solve = c->xc_cp_lane; p->cp.xc_general = c->xc_cp_general;
     if (batchcp_solve(p->cp, p->hdesc, p->bufs, p->dims.n_x, p->dims.n_u, p->dims.n_f, p->dims.n_Q, psi, Kw, nb_iter, early_stop, c->stream, err, prof_hook(c)))
         return fail(c, err);
     prof_mark(c, -1);
+    p->has_plan = true;
     return 0;
 }
 
@@ -835,13 +858,61 @@ extern "C" int ilqr_solve_batch(ilqr_problem* p, int nb_iter, int early_stop) {
     ilqr_ctx* c = p->ctx;
     if (has_shared_step(p->hdesc.steps)) return fail(c, BATCH_SHARED_STEP_TEXT);
     if (!p->has_state || !p->has_controls) return fail(c, "set_init_state and set_controls must be called before a solve");
-    p->has_gains = false;  // the batch solvers leave no gains
+    p->has_gains = p->has_plan = false;  // the batch solvers leave no gains (ilqr_problem_gains computes them about the plan)
     HIPCHK(c, hipSetDevice(c->device));
     std::string err;
     if (ensure_trace(p, nb_iter)) return 1;
     p->last_nb_iter = nb_iter;
     if (batchwide_solve(p->cpw, p->hdesc, p->bufs, p->dims.n_x, p->dims.n_u, nullptr, 0, nb_iter, early_stop, p->u0_zero, c->stream, err, prof_hook(c))) return fail(c, err);
     prof_mark(c, -1);
+    p->has_plan = true;
+    return 0;
+}
+
+// One backward pass (ILQRRecursive.cpp:68-97) about the plan the problem holds, whichever solver left it: k_gains_prepare, k_kp_derivs and the
+// sweep plan_riccati chooses for ilqr_solve_recursive(p, 1, 1, 0) -- no augmented-Lagrangian terms, no rollout, no line search.  Nothing is
+// pending when it starts: the fused path applies the last winner itself (Apply::WaveLast on the last iteration, and an instance that stopped
+// early before it is applied by the following sweep), every other path applies or flips inside the iteration that decided, and the batch
+// solvers clear `pend` in their rollout and never set it.  So X[cur], U[cur] are the plan of every instance, active or not.
+extern "C" int ilqr_problem_gains(ilqr_problem* p) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    if (!p->has_plan)
+        return fail(c, "ilqr_problem_gains needs a plan: run a solver since the problem's inputs last changed (ilqr_solve_recursive with nb_iter = 0 rolls out the controls as they are)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int kind = p->desc.kind, nd = p->desc.nb_deriv;
+    const RiccatiPlan pl = plan_riccati(plan_input(p, false, 1, 1));
+    p->has_gains = false;  // until the sweep is queued
+    p->bufs.kd_sym = pl.kd_sym;  // before half_bufs: it sizes the half's offset into KD
+    if (pl.needs_ws && !p->bufs.ws)
+        if (dalloc(p, &p->bufs.ws, (size_t)backward_ws_entries(kind, nd) * p->Bp, false)) return 1;
+    Half hv[2];
+    int nh = 1;
+    if (split_begin(p, pl.split, hv, nh)) return 1;
+    SplitJoin split_join{c, pl.split};  // on every exit path
+    const FwdArgs f = plan_fwd_args(p, pl);
+    SweepArgs sw;
+    sw.pen_in = 0.0; sw.pen_update_prev = 0.0; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0;
+    for (int h = 0; h < nh; h++) {
+        const Bufs& bf = hv[h].bufs;
+        const int B = hv[h].B;
+        hipStream_t st = hv[h].st;
+        {
+            ProfScope ps(c, ILQR_PROF_OTHER);
+            launch_gains_prepare(bf, B, st);
+        }
+        {
+            ProfScope ps(c, ILQR_PROF_OTHER);
+            launch_kp_derivs(kind, nd, bf, B, st, f);
+        }
+        {
+            ProfScope ps(c, ILQR_PROF_BACKWARD);
+            launch_sweep(p, pl, h, false, bf, B, st, sw);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    prof_mark(c, -1);
+    p->has_gains = true;
     return 0;
 }
 
@@ -908,7 +979,7 @@ extern "C" int ilqr_problem_warm_start(ilqr_problem* p, int shift) {
     ilqr_ctx* c = p->ctx;
     if (!p->has_state || !p->has_controls) return fail(c, "warm start needs a previous solve (set_init_state, set_controls, solve)");
     if (shift < 0 || shift >= p->T) return fail(c, "shift must be in [0, T)");
-    p->has_gains = false;  // U0 and the start state change
+    p->has_gains = p->has_plan = false;  // U0 and the start state change
     HIPCHK(c, hipSetDevice(c->device));
     launch_warm_start(p->bufs, const_cast<double*>(p->bufs.U0), const_cast<double*>(p->bufs.q0), const_cast<double*>(p->bufs.dq0), shift, p->B, p->T,
                       p->dims.n_x, p->dims.n_u, p->desc.nb_deriv, c->stream);
@@ -973,7 +1044,7 @@ struct ClRequest {
 static int cl_check(const ilqr_problem* p, const ClRequest& rq) {
     ilqr_ctx* c = p->ctx;
     if (!p->has_gains)
-        return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) since the problem's inputs last changed");
+        return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) or of ilqr_problem_gains since the problem's inputs last changed");
     if (rq.S < 1) return fail(c, "n_samples must be >= 1");
     const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u;
     if (rq.noisy) {
@@ -1176,7 +1247,7 @@ static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double*
     const size_t nn = (size_t)nxu * nxu, n_S = (size_t)B * T * nn, n_kS = (size_t)B * n_kp * nn;
     if (const char* why = cl_cov_size_refusal(B, T, n_kp, nxu, out->Sigma != nullptr, out->kp_Sigma != nullptr)) return fail(c, why);
     if (!p->has_gains)   // (behind the bounds on the call itself: those do not depend on the state of the problem)
-        return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) since the problem's inputs last changed");
+        return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) or of ilqr_problem_gains since the problem's inputs last changed");
     HIPCHK(c, hipSetDevice(c->device));
     const ClosedLoopCovPlan pl = plan_closed_loop_cov(p->desc.kind, p->desc.nb_deriv, B, c->n_simd, c->xc_generic || p->mapped);
     if (pl.rows && !launch_closed_loop_cov_rows) return fail(c, "closed loop cov: the row kernel is not part of this build (pin the generic kernels)");

@@ -68,6 +68,16 @@ __global__ __launch_bounds__(64) void k_init_rollout(Bufs a, double penalty) {
     a.status[b] = isfinite(cost) ? 0 : 1;
 }
 
+// ilqr_problem_gains: what a sweep about the held plan needs that a solve's rollout would have set up.  Every instance is swept (the sweeps skip
+// the instances an early stop made inactive; the next solve's rollout resets `active`), and the feed-forward it writes is unscaled: alpha = 1
+// (the getters' and the tracking law's rule is iters > 0 ? alpha : 1).  Nothing else of the plan is touched.
+__global__ __launch_bounds__(64) void k_gains_prepare(Bufs a) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.desc->B) return;
+    a.active[b] = 1;
+    a.alpha[b] = 1.0;
+}
+
 // l_x, l_xx of the keypoint steps (System::cost_x / cost_xx incl. the limit terms) for the current trajectory, one lane per
 // (instance, keypoint).  Keeps FK, the quaternion log map and J'QJ out of the sequential sweep: the sweep only loads
 // NX + NX*NX doubles at the (two) keypoint steps.
@@ -1089,6 +1099,8 @@ void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, co
         else hipLaunchKernelGGL((k_kp_derivs<S, false>), dim3((B + 63) / 64, f.n_kp), dim3(64), 0, st, a, f.fused);
     });
 }
+
+void launch_gains_prepare(const Bufs& a, int B, hipStream_t st) { hipLaunchKernelGGL(k_gains_prepare, dim3((B + 63) / 64), dim3(64), 0, st, a); }
 
 void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty) {
     SysAll::dispatch(kind, nd, [&](auto s) {

@@ -48,7 +48,7 @@ extern "C" {
 #define ILQR_STATUS_NONFINITE 1   /* accepted cost is NaN/Inf (the reference prints -nan and carries on) */
 #define ILQR_STATUS_ALPHA_FLOOR 2 /* last line search bottomed out at alpha <= alpha_floor (accept-anyway rule) */
 #define ILQR_STATUS_SWEEP_IO 4    /* a wave of the sweep's I/O-wave form gave up a bounded wait on its partner (a protocol error, never seen): the instance was \
-                                     made inactive, no later kernel touches it and its outputs are not a solution.  Sticky until the next solve. */
+                                     made inactive, no later kernel of the solve touches it and its outputs are not a solution.  Sticky until the next solve. */
 
 typedef struct ilqr_ctx ilqr_ctx;
 typedef struct ilqr_problem ilqr_problem;
@@ -235,9 +235,9 @@ int ilqr_problem_get_X(ilqr_problem* p, double* X);       /* [B][T][n_x]     ILQ
 int ilqr_problem_get_fX(ilqr_problem* p, double* fX);     /* [B][T][n_f]     tuple<1> (one batched FK pass) */
 int ilqr_problem_get_U(ilqr_problem* p, double* U);       /* [B][T-1][n_u]   tuple<2> */
 int ilqr_problem_get_K(ilqr_problem* p, double* K);       /* [B][T-1][n_u][n_x] tuple<3> */
-int ilqr_problem_get_d(ilqr_problem* p, double* d);       /* [B][T-1][n_u]   tuple<4> (scaled by accepted alpha) */
+int ilqr_problem_get_d(ilqr_problem* p, double* d);       /* [B][T-1][n_u]   tuple<4> (scaled by accepted alpha; after ilqr_problem_gains the sweep's d_k itself) */
 int ilqr_problem_get_cost(ilqr_problem* p, double* cost); /* [B]             tuple<5> */
-int ilqr_problem_get_alpha(ilqr_problem* p, double* alpha); /* [B] last accepted alpha */
+int ilqr_problem_get_alpha(ilqr_problem* p, double* alpha); /* [B] last accepted alpha (1.0 after ilqr_problem_gains) */
 int ilqr_problem_get_iters(ilqr_problem* p, int* iters);  /* [B] iterations run (early stop) */
 int ilqr_problem_get_status(ilqr_problem* p, int* status);/* [B] ILQR_STATUS_* */
 int ilqr_problem_get_lambda(ilqr_problem* p, double* lambda); /* [B][T-1][m] */
@@ -258,13 +258,33 @@ int ilqr_problem_warm_start(ilqr_problem* p, int shift);
  * x_meas[B][n_x] -> u_out[B][n_u]; K_k, d_k = the gains ilqr_problem_get_K / get_d return. */
 int ilqr_problem_track(ilqr_problem* p, int k, const double* x_meas, int with_feedforward, double* u_out);
 int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_meas, int with_feedforward, double* u_out);
-/* Closed loop of that law on the plan of the last Riccati solve: n_samples executions of every instance,
+/* Gains about the plan the problem holds: one backward pass of ILQRRecursive.cpp:68-97 about the X, U that ilqr_problem_get_X / ilqr_problem_get_U
+ * return, whichever of the four solvers left them and for any nb_iter, 0 included (ilqr_problem_set_controls, then ilqr_solve_recursive with
+ * nb_iter = 0, then this call: gains about an arbitrary control sequence).  The Riccati solvers' own K_k, d_k belong to the plan BEFORE the last
+ * step (ILQRRecursive.cpp:68-155 sweeps, then moves the trajectory), and the batch solvers leave none; this call makes K_k, d_k and the plan one.
+ *   cost      the system's stage cost: keypoint terms, the limit terms of both limit sets, the descriptor's reg.  No augmented-Lagrangian terms,
+ *             also after ilqr_solve_al or with constraints set: it is the sweep ilqr_solve_recursive would run at that trajectory.
+ *   writes    K_k, d_k into the problem's gain records, every instance (also those an early stop ended; an instance whose status carries
+ *             ILQR_STATUS_NONFINITE or ILQR_STATUS_SWEEP_IO gets unspecified gains, possibly NaN, and keeps its status).  The feed-forward is
+ *             unscaled: ilqr_problem_get_d returns the sweep's d_k itself, with_feedforward adds d_k, and ilqr_problem_get_alpha returns 1.0 for
+ *             every instance afterwards -- a caller who wants the solver's last step size reads it before this call.
+ *   keeps     X, U, fX, cost, iters, status, lambda and the cost / alpha trace, bit for bit.
+ *   runs      k_gains_prepare (every instance active, alpha = 1), k_kp_derivs and the sweep chosen for ilqr_solve_recursive(p, 1, 1, 0) on this
+ *             problem under the context's pins (batch size, two-stream split and the generic sweep's workspace included); no rollout, no
+ *             forward pass.  Under ilqr_profile_enable the call is charged to ILQR_PROF_OTHER and ILQR_PROF_BACKWARD only.
+ *   bits      under fixed pins, ilqr_problem_set_controls, a 0-iteration ilqr_solve_recursive and this call give the K of a fresh
+ *             ilqr_solve_recursive(p, 1, 1, 0) from the same controls byte for byte, and that solve's d is alpha times this call's, exactly.
+ * Afterwards ilqr_problem_track, the closed-loop entry points and their _dev forms accept the problem, until a solver, a setter or
+ * ilqr_problem_warm_start changes the plan or its inputs.  Fails unless one of the four solvers has run since the problem's inputs last changed.
+ * Asynchronous on the context's stream. */
+int ilqr_problem_gains(ilqr_problem* p);
+/* Closed loop of that law on the plan of the last Riccati solve (or the plan ilqr_problem_gains swept about): n_samples executions of every instance,
  *   x_0 = x0[b][s] (NULL: xbar_0);  u_k = ilqr_problem_track(k, x_k, with_feedforward);  x_{k+1} = f(x_k, u_k) + w[b][s][k] (NULL: none);
  *   cost[b][s] = sum_{k<T-1} cost(x_k, u_k, k) + cost(x_{T-1}, 0, T-1)     (the system's stage cost, no AL terms: what ilqr_solve_recursive reports),
  * with f the system's own step (dt = u_last^2 on the time systems).  Start states and disturbances are the caller's (ilqr_problem_closed_loop_noise draws them on the device).
  * x0[B][S][n_x] or NULL, w[B][S][T-1][n_x] or NULL; cost[B][S]; X[B][S][T][n_x] or NULL; U[B][S][T-1][n_u] or NULL.
- * Fails unless ilqr_solve_recursive / ilqr_solve_al with nb_iter >= 1 has run since the problem's inputs last changed (the batch solvers leave no
- * gains), for n_samples < 1, for a null cost, and when B * n_samples * T * n_x reaches 2^31 (the kernels' 32-bit offsets).
+ * Fails unless ilqr_solve_recursive / ilqr_solve_al with nb_iter >= 1 or ilqr_problem_gains has run since the problem's inputs last changed (the
+ * batch solvers and a 0-iteration solve leave no gains: ilqr_problem_gains computes them about their plan), for n_samples < 1, for a null cost, and when B * n_samples * T * n_x reaches 2^31 (the kernels' 32-bit offsets).
  * _dev: device pointers, asynchronous on the context's stream. */
 int ilqr_problem_closed_loop(ilqr_problem* p, int n_samples, const double* x0, const double* w, int with_feedforward, double* cost, double* X,
                              double* U);
