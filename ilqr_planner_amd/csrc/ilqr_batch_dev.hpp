@@ -64,6 +64,29 @@ __device__ __noinline__ void w_kp_derivs(const DevDesc* d, const Bufs* a, int b,
     }
 }
 
+// solver state of instance b at the start of a batch solve
+ILQR_DEV void batch_reset_instance(const Bufs& a, int b) {
+    a.cur[b] = 0;
+    a.active[b] = 1;
+    a.iters[b] = 0;
+    a.status[b] = 0;
+    a.alpha[b] = 1.0;
+    a.pend[b] = 0;
+    a.pred[b] = 0;
+}
+
+// what the winning lane of a batch line search records in iteration `it`: its step size and cost, the trace entry
+ILQR_DEV void batch_record_winner(const Bufs& a, int Bp, int b, int it, double alpha, double cost0, double cost) {
+    a.alpha[b] = alpha;
+    a.iters[b] = it + 1;
+    a.status[b] = (isfinite(cost) ? 0 : 1) | ((alpha < 1e-3) ? 2 : 0);
+    if (a.cost_trace) {
+        a.cost_trace[(size_t)it * Bp + b] = cost0;  // the reference prints the PRE-step cost (BatchILQRCP.cpp:160)
+        a.alpha_trace[(size_t)it * Bp + b] = alpha;
+    }
+    a.cost[b] = cost;
+}
+
 struct BTArgs { int it, early_stop; };
 
 // Backtracking with all step sizes at once: 16 lanes per instance, lane l rolls out u + 2^-l du (BatchILQR.cpp:138-158: the first
@@ -121,14 +144,7 @@ __global__ __launch_bounds__(64) void k_bt_linesearch(Bufs a, BTArgs c) {
     const double aw = ldexp(1.0, -win);
     for (int s = l; s < (T - 1) * NU; s += 16) AT(U, s, b) += aw * AT(DU, s, b);  // u = utmp of the winner, the 16 lanes share the copy
     if (l != win) return;
-    a.alpha[b] = alpha;
-    a.iters[b] = c.it + 1;
-    a.status[b] = (isfinite(cost) ? 0 : 1) | ((alpha < 1e-3) ? 2 : 0);
-    if (a.cost_trace) {
-        a.cost_trace[(size_t)c.it * Bp + b] = cost0;
-        a.alpha_trace[(size_t)c.it * Bp + b] = alpha;
-    }
-    a.cost[b] = cost;
+    batch_record_winner(a, Bp, b, c.it, alpha, cost0, cost);
     if (c.early_stop && alpha * sqrt(dun2) < 1e-3) a.active[b] = 0;  // :167
 }
 

@@ -11,10 +11,11 @@
 //   k_cp_linesearch backtracking on the true cost (:138-158): u + alpha PSI dw, accept if cost < cost0 or alpha < 1e-3.
 // The contraction is a 14x14 (Kw x Kw) matrix per instance at the BASELINE config: far too small for an MFMA tile to
 // pay; it is VALU work and the pass is bound by the rollout, like the recursive solver.
+//
+// This file holds the kernels and the host side: check, size the buffers (BatchSizes), tables, launch loop.  The shared tables (PSI padded,
+// PSI'R PSI and, for the coefficient-space path of the constant-dt systems, the sensitivities at the keypoint steps and PSI'PSI) are plain
+// host code in ilqr_batch_tables.hpp (narrow_tables; checked on a CPU by tests/cpp/batch_tables_main.cpp).
 #include "ilqr_batchcp.hpp"
-
-#include <cstdlib>
-#include <cstring>
 
 #include "ilqr_batch_dev.hpp"
 #include "ilqr_lanes.hpp"
@@ -312,13 +313,7 @@ __global__ void k_cp_init(Bufs a) {
     if (b >= d.B) return;
     const int Bp = d.Bp;
     for (int r = 0; r < (d.T - 1) * S::NU; r++) AT(a.U[0], r, b) = AT(a.U0, r, b);
-    a.cur[b] = 0;
-    a.active[b] = 1;
-    a.iters[b] = 0;
-    a.status[b] = 0;
-    a.alpha[b] = 1.0;
-    a.pend[b] = 0;
-    a.pred[b] = 0;
+    batch_reset_instance(a, b);
 }
 
 // final rollout of the solution so that X (and the cost of the returned u) can be read back
@@ -483,14 +478,7 @@ __global__ __launch_bounds__(64) void k_cpl_linesearch(Bufs a, CPArgs c) {
     const int win = L0 + __ffs(grp) - 1;
     if (!ok || !grp || l != win) return;
     UNR for (int q = 0; q < KWP; q++) AT(c.wv, q, b) = wn[q];
-    a.alpha[b] = alpha;
-    a.iters[b] = c.it + 1;
-    a.status[b] = (isfinite(cost) ? 0 : 1) | ((alpha < 1e-3) ? 2 : 0);
-    if (a.cost_trace) {
-        a.cost_trace[(size_t)c.it * Bp + b] = cost0;  // the reference prints the PRE-step cost (BatchILQRCP.cpp:160)
-        a.alpha_trace[(size_t)c.it * Bp + b] = alpha;
-    }
-    a.cost[b] = cost;
+    batch_record_winner(a, Bp, b, c.it, alpha, cost0, cost);
     if (c.early_stop) {
         double dun2 = 0;  // sum_k ||PSI_k dw||^2
         UNR for (int q = 0; q < KWP; q++) {
@@ -641,36 +629,48 @@ __global__ __launch_bounds__(256) void k_cpl_quad(Bufs a, CPArgs c) {
         double cs = sPart[0][4][l];
         UNR for (int w_ = 1; w_ < NW; w_++) cs += sPart[w_][4][l];
         c.c00[b] = cs;
-        a.cur[b] = 0;
-        a.active[b] = 1;
-        a.iters[b] = 0;
-        a.status[b] = 0;
-        a.alpha[b] = 1.0;
-        a.pend[b] = 0;
-        a.pred[b] = 0;
+        batch_reset_instance(a, b);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ host side
 
-template <class T>
-static bool cp_alloc(BatchCPState& st, T** p, size_t n, hipStream_t s) {
-    void* q = nullptr;
-    if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return false;
-    st.allocs.push_back(q);
-    (void)hipMemsetAsync(q, 0, (n ? n : 1) * sizeof(T), s);
-    *p = (T*)q;
-    return true;
-}
-
 void batchcp_free(BatchCPState& st) {
-    for (void* q : st.allocs) (void)hipFree(q);
+    st.arena.release();
     st = BatchCPState();
 }
 
+// buffers for `want`; a change of any sized quantity re-allocates everything (and with it forgets the tables)
+static bool cp_size(BatchCPState& st, const BatchSizes& want, hipStream_t s) {
+    if (st.sizes == want) return true;
+    batchcp_free(st);
+    DevArena& A = st.arena;
+    const size_t nx = want.n_x, nkp = want.n_kp, rows = want.rows, KWP = want.cols, Bp = want.Bp;
+    const bool ok = A.get(&st.psi, rows * KWP, s) && A.get(&st.H0, KWP * KWP, s) && A.get(&st.Wkp, nkp * nx * KWP * Bp, s) &&
+                    A.get(&st.Ckp, nkp * nx * nx * Bp, s) && A.get(&st.rkp, nkp * nx * Bp, s) && A.get(&st.gu, KWP * Bp, s) && A.get(&st.dw, KWP * Bp, s) &&
+                    A.get(&st.dun, Bp, s) && A.get(&st.wt, nkp * 2 * nx * KWP, s) && A.get(&st.pp, KWP * KWP, s) && A.get(&st.wref, nkp * nx * KWP, s) &&
+                    A.get(&st.wv, KWP * Bp, s) && A.get(&st.g0, KWP * Bp, s) && A.get(&st.c00, Bp, s) && A.get(&st.xbk, nkp * 2 * nx * Bp, s);
+    if (!ok) { batchcp_free(st); return false; }
+    st.sizes = want;
+    return true;
+}
+
+// The shared tables depend on PSI and on (horizon, dt, R, keypoint steps): rebuilt and uploaded only when one of them changes.
+static int cp_tables_to_device(BatchCPState& st, const BatchTableIn& in, hipStream_t stream, std::string& err) {
+    if (st.tab.same(in)) return 0;
+    st.tab.clear();
+    NarrowTables t;
+    narrow_tables(in, t);
+    bool up = dev_upload(st.psi, t.psip, stream) && dev_upload(st.H0, t.H0, stream);
+    if (up && in.sens) up = dev_upload(st.wt, t.wt, stream) && dev_upload(st.wref, t.wr, stream) && dev_upload(st.pp, t.pp, stream);
+    if (!up || hipStreamSynchronize(stream) != hipSuccess) { err = "ilqr_solve_batch_cp: table upload failed"; return 1; }
+    st.tab.set(in);
+    return 0;
+}
+
 template <class S, int KWP>
-static int run_cp(BatchCPState& st, const DevDesc& h, Bufs& bufs, int nb_iter, int early_stop, hipStream_t stream, std::string& err, const ProfHook& ph) {
-    constexpr int NX = S::NX;
+static int run_cp(BatchCPState& st, const DevDesc& h, Bufs& bufs, bool wave_solve, int nb_iter, int early_stop, hipStream_t stream, std::string& err,
+                  const ProfHook& ph) {
     const int B = h.B;
     const dim3 grid((B + LPB - 1) / LPB), block(LPB);
     const size_t lds_h = sizeof(double) * KWP * KWP * LPB;
@@ -682,7 +682,6 @@ static int run_cp(BatchCPState& st, const DevDesc& h, Bufs& bufs, int nb_iter, i
     c.psi = st.psi; c.H0 = st.H0; c.Wkp = st.Wkp; c.Ckp = st.Ckp; c.rkp = st.rkp; c.gu = st.gu; c.dw = st.dw; c.dun = st.dun;
     c.Kw = st.Kw; c.early_stop = early_stop; c.n_alpha = 11; c.it = 0;
     c.wref = nullptr;
-    const bool wave_solve = !st.xc_lane_solve;  // cross-check (ilqr_ctx_set_crosscheck): one lane per instance
     ph(ILQR_PROF_ROLLOUT);
     hipLaunchKernelGGL((k_cp_init<S>), dim3((B + 255) / 256), dim3(256), 0, stream, bufs);
     for (int it = 0; it < nb_iter; it++) {
@@ -703,52 +702,12 @@ static int run_cp(BatchCPState& st, const DevDesc& h, Bufs& bufs, int nb_iter, i
     return 0;
 }
 
-// PosOrn systems: iterate in coefficient space (see the kernels above).  psip = PSI padded to KWP columns (host copy).
+// PosOrn systems: iterate in coefficient space (see the kernels above) on the shared tables wt, wref, pp
 template <class S, int KWP>
-static int run_cpl(BatchCPState& st, const DevDesc& h, Bufs& bufs, const std::vector<double>& psip, int nb_iter, int early_stop, hipStream_t stream,
-                   std::string& err, const ProfHook& ph) {
-    constexpr int NX = S::NX, NU = S::NU, ND = S::ND;
-    const int B = h.B, T = h.T, nkp = h.n_kp;
-    const double dt = h.dt, hdt2 = dt * dt / 2;
-    // sensitivities by their recurrences (constant A, B): Wt_{i+1} = A Wt_i + B PSI_i from Wt_0 = 0 (true), and the reference's
-    // shifted one Wr_{i+1} = A Wr_i + B PSI_i from Wr_1 = 0, i >= 1 (BatchILQRCP.cpp:61-97, quirk D-1)
-    auto advance = [&](std::vector<double>& W, int i) {
-        for (int q = 0; q < KWP; q++) {
-            if (ND == 2) for (int r = 0; r < DOF; r++) W[r * KWP + q] += dt * W[(DOF + r) * KWP + q];
-            for (int r = 0; r < DOF; r++) {
-                const double ps = psip[((size_t)i * NU + r) * KWP + q];
-                if (ND == 1) W[r * KWP + q] += dt * ps;
-                else { W[r * KWP + q] += hdt2 * ps; W[(DOF + r) * KWP + q] += dt * ps; }
-            }
-        }
-    };
-    if (!st.cpl_tables) {
-    std::vector<std::vector<double>> Wt(T, std::vector<double>(NX * KWP, 0.0)), Wr(T, std::vector<double>(NX * KWP, 0.0));
-    for (int i = 0; i + 1 < T; i++) { Wt[i + 1] = Wt[i]; advance(Wt[i + 1], i); }
-    for (int i = 1; i + 1 < T; i++) { Wr[i + 1] = Wr[i]; advance(Wr[i + 1], i); }
-    std::vector<double> wt((size_t)(nkp > 0 ? nkp : 1) * 2 * NX * KWP, 0.0), wref((size_t)(nkp > 0 ? nkp : 1) * NX * KWP, 0.0), pp((size_t)KWP * KWP, 0.0);
-    for (int t = 0; t < nkp; t++) {
-        const int ts = h.kp_t[t];
-        std::copy(Wt[ts].begin(), Wt[ts].end(), wt.begin() + ((size_t)t * 2 + 0) * NX * KWP);
-        if (ts > 0) std::copy(Wt[ts - 1].begin(), Wt[ts - 1].end(), wt.begin() + ((size_t)t * 2 + 1) * NX * KWP);
-        std::copy(Wr[ts].begin(), Wr[ts].end(), wref.begin() + (size_t)t * NX * KWP);
-    }
-    const int rows = (T - 1) * NU;
-    for (int a_ = 0; a_ < KWP; a_++)
-        for (int b_ = 0; b_ < KWP; b_++) {
-            double s = 0;
-            for (int k = 0; k < rows; k++) s += psip[(size_t)k * KWP + a_] * psip[(size_t)k * KWP + b_];
-            pp[(size_t)a_ * KWP + b_] = s;
-        }
-    if (hipMemcpyAsync(st.wt, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(st.wref, wref.data(), wref.size() * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(st.pp, pp.data(), pp.size() * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess) {
-        err = "ilqr_solve_batch_cp: sensitivity upload failed";
-        return 1;
-    }
-    st.cpl_tables = true;
-    }  // tables
+static int run_cpl(BatchCPState& st, const DevDesc& h, Bufs& bufs, bool wave_solve, int nb_iter, int early_stop, hipStream_t stream, std::string& err,
+                   const ProfHook& ph) {
+    constexpr int NX = S::NX;
+    const int B = h.B, nkp = h.n_kp;
     const dim3 grid((B + LPB - 1) / LPB), block(LPB);
     const size_t lds_h = sizeof(double) * KWP * KWP * LPB;
     if (hipFuncSetAttribute((const void*)k_cp_solve<S, KWP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h) != hipSuccess) {
@@ -760,7 +719,6 @@ static int run_cpl(BatchCPState& st, const DevDesc& h, Bufs& bufs, const std::ve
     c.wt = st.wt; c.pp = st.pp; c.wv = st.wv; c.g0 = st.g0; c.c00 = st.c00; c.xbk = st.xbk;
     c.Kw = st.Kw; c.early_stop = early_stop; c.n_alpha = 11; c.it = 0;
     c.wref = st.wref;
-    const bool wave_solve = !st.xc_lane_solve;  // cross-check (ilqr_ctx_set_crosscheck): one lane per instance
     ph(ILQR_PROF_ROLLOUT);   // rollout of u0, its keypoint states and the quadratic forms of the control cost (walks the horizon)
     hipLaunchKernelGGL((k_cpl_states<S>), dim3((B + 255) / 256, DOF), dim3(256), 0, stream, bufs, c);
     hipLaunchKernelGGL((k_cpl_quad<S, KWP>), dim3((B + 15) / 16), dim3(256), 0, stream, bufs, c);
@@ -781,65 +739,37 @@ static int run_cpl(BatchCPState& st, const DevDesc& h, Bufs& bufs, const std::ve
     return 0;
 }
 
-int batchcp_solve(BatchCPState& st, const DevDesc& h, Bufs& bufs, int nx, int nu, int nf, int nq, const double* psi_host, int Kw,
-                  int nb_iter, int early_stop, hipStream_t stream, std::string& err, const ProfHook& ph) {
-    (void)nf; (void)nq;
+int batchcp_solve(BatchCPState& st, const DevDesc& h, Bufs& bufs, int nx, int nu, int, int, const double* psi_host, int Kw, int nb_iter, int early_stop,
+                  hipStream_t stream, std::string& err, const ProfHook& ph) {
+    // cross-check variants (ilqr_ctx_set_crosscheck), read here: a re-allocation below resets the whole state
+    const bool general = st.xc_general, wave_solve = !st.xc_lane_solve;  // the general path on the linear systems; one lane per instance in the solve
+    // check
     if (!psi_host || Kw <= 0) { err = "ilqr_solve_batch_cp: null PSI / Kw <= 0"; return 1; }
-    const bool time_sys = h.kind == 1 || h.kind == 3;
+    const bool time_sys = h.kind == 1 || h.kind == 3, lti_sys = h.kind == 0 || h.kind == 2;
     if (Kw > 32 || (Kw > 16 && !time_sys)) { err = "ilqr_solve_batch_cp: this path takes Kw <= 16 (Kw <= 32 on the time systems)"; return 1; }
     if (nb_iter < 0) { err = "nb_iter < 0"; return 1; }
-    const int KWP = Kw > 16 ? 32 : 16, T = h.T, Bp = h.Bp, nkp = h.n_kp > 0 ? h.n_kp : 1;
-    const int rows = (T - 1) * nu;
-    if (st.KWP != KWP || st.nkp != nkp || st.nx != nx || st.Bp != Bp || st.rows != rows) {
-        batchcp_free(st);
-        bool ok = cp_alloc(st, &st.psi, (size_t)rows * KWP, stream) && cp_alloc(st, &st.H0, (size_t)KWP * KWP, stream) &&
-                  cp_alloc(st, &st.Wkp, (size_t)nkp * nx * KWP * Bp, stream) && cp_alloc(st, &st.Ckp, (size_t)nkp * nx * nx * Bp, stream) &&
-                  cp_alloc(st, &st.rkp, (size_t)nkp * nx * Bp, stream) && cp_alloc(st, &st.gu, (size_t)KWP * Bp, stream) &&
-                  cp_alloc(st, &st.dw, (size_t)KWP * Bp, stream) && cp_alloc(st, &st.dun, (size_t)Bp, stream) &&
-                  cp_alloc(st, &st.wt, (size_t)nkp * 2 * nx * KWP, stream) && cp_alloc(st, &st.pp, (size_t)KWP * KWP, stream) && cp_alloc(st, &st.wref, (size_t)nkp * nx * KWP, stream) &&
-                  cp_alloc(st, &st.wv, (size_t)KWP * Bp, stream) && cp_alloc(st, &st.g0, (size_t)KWP * Bp, stream) &&
-                  cp_alloc(st, &st.c00, (size_t)Bp, stream) && cp_alloc(st, &st.xbk, (size_t)nkp * 2 * nx * Bp, stream);
-        if (!ok) { batchcp_free(st); err = "ilqr_solve_batch_cp: hipMalloc failed"; return 1; }
-        st.KWP = KWP; st.nkp = nkp; st.nx = nx; st.Bp = Bp; st.rows = rows;
-        st.sig.clear(); st.psi_host.clear(); st.cpl_tables = false;
-    }
+    // size
+    const int KWP = Kw > 16 ? 32 : 16;
+    BatchSizes want;
+    want.layout = BatchSizes::NARROW;
+    want.n_x = nx; want.n_kp = h.n_kp > 0 ? h.n_kp : 1; want.rows = (h.T - 1) * nu; want.cols = KWP; want.Bp = h.Bp;
+    if (!cp_size(st, want, stream)) { err = "ilqr_solve_batch_cp: hipMalloc failed"; return 1; }
     st.Kw = Kw;
-    // the shared tables depend on PSI and on (horizon, dt, R, keypoint steps): rebuilt only when one of them changes
-    std::vector<double> sig = {(double)T, (double)nu, (double)nx, (double)Kw, h.dt, (double)h.kind, (double)h.nd, (double)h.n_kp};
-    for (int i = 0; i < nu; i++) sig.push_back(h.R_diag[i]);
-    for (int i = 0; i < h.n_kp; i++) sig.push_back((double)h.kp_t[i]);
-    const bool same = st.sig == sig && st.psi_host.size() == (size_t)rows * Kw &&
-                      std::memcmp(st.psi_host.data(), psi_host, sizeof(double) * (size_t)rows * Kw) == 0;
-    if (!same) { st.cpl_tables = false; st.sig = sig; st.psi_host.assign(psi_host, psi_host + (size_t)rows * Kw); }
-    // PSI padded to KWP columns; H0 = PSI' R PSI with 1 on the padded diagonal (keeps H non-singular, dw_pad = 0)
-    std::vector<double> psip((size_t)rows * KWP, 0.0), H0((size_t)KWP * KWP, 0.0);
-    for (int k = 0; k < rows; k++)
-        for (int q = 0; q < Kw; q++) psip[(size_t)k * KWP + q] = psi_host[(size_t)k * Kw + q];
-    if (!same) {
-    for (int a_ = 0; a_ < Kw; a_++)
-        for (int b_ = 0; b_ < Kw; b_++) {
-            double s = 0;
-            for (int k = 0; k < rows; k++) s += psi_host[(size_t)k * Kw + a_] * h.R_diag[k % nu] * psi_host[(size_t)k * Kw + b_];
-            H0[(size_t)a_ * KWP + b_] = s;
-        }
-    for (int q = Kw; q < KWP; q++) H0[(size_t)q * KWP + q] = 1.0;
-    if (hipMemcpyAsync(st.psi, psip.data(), psip.size() * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(st.H0, H0.data(), H0.size() * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess) {
-        err = "ilqr_solve_batch_cp: PSI upload failed";
-        st.sig.clear();
-        return 1;
-    }
-    }  // !same
-    const bool general = st.xc_general;  // cross-check path (ilqr_ctx_set_crosscheck)
+    // tables.  The linear systems iterate on shared sensitivities (run_cpl) unless the general path is pinned (ilqr_ctx_set_crosscheck).
+    BatchTableIn in;
+    in.nd = h.nd; in.n_x = nx; in.n_u = nu; in.T = h.T; in.dt = h.dt; in.n_kp = h.n_kp; in.kp_t = h.kp_t; in.R_diag = h.R_diag;
+    in.psi = psi_host; in.Kw = Kw; in.ld = KWP;
+    in.sens = lti_sys && KWP == 16 && !general;
+    if (cp_tables_to_device(st, in, stream, err)) return 1;
+    // launch loop
     using TimeSys = SysList<Sys<3, 1>, Sys<1, 1>, Sys<1, 2>>;  // wider bases: the same kernels with 32 lanes per instance
-    using LtiSys = SysList<Sys<2, 1>, Sys<0, 1>, Sys<0, 2>>;   // the linear systems have shared tables (run_cpl) unless the general path is pinned
+    using LtiSys = SysList<Sys<2, 1>, Sys<0, 1>, Sys<0, 2>>;
     int rc = 1;
     if (KWP == 32) {
-        if (TimeSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cp<decltype(s), 32>(st, h, bufs, nb_iter, early_stop, stream, err, ph); })) return rc;
+        if (TimeSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cp<decltype(s), 32>(st, h, bufs, wave_solve, nb_iter, early_stop, stream, err, ph); })) return rc;
     } else {
-        if (!general && LtiSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cpl<decltype(s), 16>(st, h, bufs, psip, nb_iter, early_stop, stream, err, ph); })) return rc;
-        if (SysAll::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cp<decltype(s), 16>(st, h, bufs, nb_iter, early_stop, stream, err, ph); })) return rc;
+        if (in.sens && LtiSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cpl<decltype(s), 16>(st, h, bufs, wave_solve, nb_iter, early_stop, stream, err, ph); })) return rc;
+        if (SysAll::dispatch(h.kind, h.nd, [&](auto s) { rc = run_cp<decltype(s), 16>(st, h, bufs, wave_solve, nb_iter, early_stop, stream, err, ph); })) return rc;
     }
     err = "ilqr_solve_batch_cp: unknown system kind";
     return 1;

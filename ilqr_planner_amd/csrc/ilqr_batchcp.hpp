@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/ilqr_hip.h"  // ILQR_PROF_* categories
+#include "ilqr_batch_tables.hpp"
 #include "ilqr_kernels.hpp"
 
 namespace ilqr {
@@ -18,9 +19,37 @@ struct ProfHook {
     void operator()(int which) const { if (mark) mark(ctx, which); }
 };
 
+// The device allocations of a solver state: zero-filled typed buffers, released together.
+struct DevArena {
+    std::vector<void*> allocs;
+    template <class T>
+    bool get(T** p, size_t n, hipStream_t s) {
+        const size_t bytes = (n ? n : 1) * sizeof(T);
+        void* q = nullptr;
+        if (hipMalloc(&q, bytes) != hipSuccess) return false;
+        allocs.push_back(q);
+        if (hipMemsetAsync(q, 0, bytes, s) != hipSuccess) return false;
+        *p = (T*)q;
+        return true;
+    }
+    void release() {
+        for (void* q : allocs) (void)hipFree(q);
+        allocs.clear();
+    }
+};
+
+inline bool dev_upload(double* dst, const double* src, size_t n, hipStream_t s) {
+    return hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, s) == hipSuccess;
+}
+inline bool dev_upload(double* dst, const std::vector<double>& v, hipStream_t s) { return dev_upload(dst, v.data(), v.size(), s); }
+
 // Device buffers of the control-primitive solver; sized for one (problem, Kw) pair and reused across solves.
 struct BatchCPState {
-    int KWP = 0, Kw = 0, nkp = 0, nx = 0, Bp = 0, rows = 0;
+    DevArena arena;
+    BatchSizes sizes;   // what the buffers are sized for
+    BatchTableSig tab;  // what the shared tables on the device (psi, H0; wt, wref, pp) were built from: a solve with the same basis on the same system
+                        // skips the host-side table construction, the uploads and their stream synchronisations (0.25 ms of a 3.3 ms C5 solve)
+    int Kw = 0;
     bool xc_lane_solve = false, xc_general = false;  // cross-check variants, set from the context before every solve (ilqr_ctx_set_crosscheck)
     double* psi = nullptr;  // [(T-1) n_u][KWP]   PSI, columns zero-padded to KWP
     double* H0 = nullptr;   // [KWP][KWP]         PSI' R PSI (identity on the padded diagonal)
@@ -38,12 +67,6 @@ struct BatchCPState {
     double* g0 = nullptr;   // [KWP][Bp]          PSI' R u0
     double* c00 = nullptr;  // [Bp]               u0' R u0
     double* xbk = nullptr;  // [n_kp][2][NX][Bp]  x_t, x_{t-1} of the rollout of u0
-    std::vector<void*> allocs;
-    // what the shared tables on the device (psi, H0, wt, wref, pp) were built from: a solve with the same basis on the same system skips
-    // the host-side table construction, the uploads and their stream synchronisations (0.25 ms of a 3.3 ms C5 solve)
-    std::vector<double> psi_host;
-    std::vector<double> sig;
-    bool cpl_tables = false;  // wt / wref / pp of the coefficient-space path are valid for (psi_host, sig)
 };
 
 // Args shared by the three kernels
@@ -59,9 +82,9 @@ struct CPArgs {
 
 // Wide bases (Kw > 16) and BatchILQR's identity basis (psi_host == nullptr, Kw = (T-1) n_u): ilqr_batchwide.hip
 struct BatchWideState {
-    std::vector<void*> allocs;
-    long long key = -1;  // (m, N, Bp, kind) the buffers were sized for
-    std::vector<double> tab_sig, tab_psi;  // what the shared tables on the device were built from (rebuilt only when it changes)
+    DevArena arena;
+    BatchSizes sizes;   // what the buffers are sized for
+    BatchTableSig tab;  // what the shared tables on the device were built from (rebuilt only when it changes)
     // LTI systems: shared tables
     double *G = nullptr, *Et = nullptr, *ZPZ = nullptr, *PZ = nullptr;
     // per instance
@@ -72,9 +95,11 @@ struct BatchWideState {
 };
 int batchwide_solve(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nx, int nu, const double* psi_host, int Kw, int nb_iter, int early_stop,
                     bool u0_zero, hipStream_t stream, std::string& err, const ProfHook& ph = ProfHook());
-void batchwide_free(BatchWideState& st);
 
-int batchcp_solve(BatchCPState& st, const DevDesc& h, Bufs& bufs, int nx, int nu, int nf, int nq, const double* psi_host, int Kw,
+void batchwide_free(BatchWideState& st);  // releases the buffers and forgets sizes and tables
+
+// (n_f and n_Q are not needed; the signatures of these four are pinned by the host harness, tests/tools/hostsim/stubs.cpp)
+int batchcp_solve(BatchCPState& st, const DevDesc& h, Bufs& bufs, int nx, int nu, int /*nf*/, int /*nq*/, const double* psi_host, int Kw,
                   int nb_iter, int early_stop, hipStream_t stream, std::string& err, const ProfHook& ph = ProfHook());
 void batchcp_free(BatchCPState& st);
 

@@ -25,10 +25,13 @@
 //
 // Reference quirks kept: the shifted sensitivity (block j of Su meets B_j = dx_j/du_{j-1}, block 0 is zero),
 // limits on the pre-step state, acceptance of a step once alpha < 1e-3, the PRE-step cost in the message stream.
+//
+// This file holds the kernels for m <= 32 and the host side: check, size the buffers (BatchSizes), tables, launch loop.  What the tables
+// contain is plain host code in ilqr_batch_tables.hpp (wide_tables; checked on a CPU by tests/cpp/batch_tables_main.cpp); the pieces the
+// kernels share with ilqr_batchwide_big.hip (system assembly, elimination, the rows of the control-cost scalars) are in ilqr_batchwide.hpp.
 #include "ilqr_batchcp.hpp"
 
 #include <cmath>
-#include <cstring>
 
 #include "ilqr_batch_dev.hpp"
 #include "ilqr_batchwide.hpp"
@@ -93,13 +96,7 @@ __global__ __launch_bounds__(64) void k_wl_init(Bufs a, WArgs c) {
     AT(c.scal, 1, b) = gam;
     AT(c.scal, 2, b) = pi;
     c.beta[b] = 1.0;
-    a.cur[b] = 0;
-    a.active[b] = 1;
-    a.iters[b] = 0;
-    a.status[b] = 0;
-    a.alpha[b] = 1.0;
-    a.pend[b] = 0;
-    a.pred[b] = 0;
+    batch_reset_instance(a, b);
 }
 
 // states at keypoint kpi and the step before it for the family member (beta, cv + al dv)
@@ -184,7 +181,6 @@ __global__ __launch_bounds__(16) void k_wl_linearize(Bufs a, WArgs c) {
 //   sc = { v0.c, c'Gc, v0.d, c'Gd, d'Gd, ||PSI dw||^2 },  dw = Z d - beta y0
 template <class S, int MC>
 __global__ __launch_bounds__(64) void k_wl_solve(Bufs a, WArgs c) {
-    constexpr int NX = S::NX;
     __shared__ double Ms[MC][MC + 2], xs[MC], cs[MC], t1[MC], t2[MC], t3[MC];
     __shared__ int prS;
     const DevDesc& d = *a.desc;
@@ -192,60 +188,9 @@ __global__ __launch_bounds__(64) void k_wl_solve(Bufs a, WArgs c) {
     if (!a.active[b]) return;  // uniform
     const int Bp = d.Bp, m = c.m;
     const double beta = c.beta[b];
-    for (int e = lane; e < m * (m + 1); e += 64) {
-        const int row = e / (m + 1), col = e % (m + 1), kpi = row / NX, i = row % NX;
-        const double* Ck = c.Ckp + (size_t)kpi * NX * NX * Bp;
-        double s;
-        if (col == m) {
-            double cv0 = 0;
-            UNR for (int j = 0; j < NX; j++) cv0 += AT(Ck, i * NX + j, b) * AT(c.v0, kpi * NX + j, b);
-            s = (AT(c.rkp, row, b) - AT(c.cv, row, b)) + beta * cv0;
-        } else {
-            s = (row == col) ? 1.0 : 0.0;
-            UNR for (int j = 0; j < NX; j++) s += AT(Ck, i * NX + j, b) * c.G[(size_t)(kpi * NX + j) * m + col];
-        }
-        Ms[row][col] = s;
-    }
-    if (lane < m) cs[lane] = AT(c.cv, lane, b);
-    __syncthreads();
-    for (int k = 0; k < m; k++) {
-        if (lane == 0) {
-            int pr = k;
-            double pv = fabs(Ms[k][k]);
-            for (int i = k + 1; i < m; i++) {
-                const double v = fabs(Ms[i][k]);
-                if (v > pv) { pv = v; pr = i; }
-            }
-            prS = pr;
-        }
-        __syncthreads();
-        const int pr = prS;
-        if (lane <= m && lane >= k && pr != k) { const double t0 = Ms[k][lane]; Ms[k][lane] = Ms[pr][lane]; Ms[pr][lane] = t0; }
-        __syncthreads();
-        if (lane <= m && lane > k) {
-            const double piv = Ms[k][k], mk = Ms[k][lane];
-            for (int i = k + 1; i < m; i++) Ms[i][lane] -= (Ms[i][k] / piv) * mk;
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        for (int i = m - 1; i >= 0; i--) {
-            double s = Ms[i][m];
-            for (int q = i + 1; q < m; q++) s -= Ms[i][q] * xs[q];
-            xs[i] = s / Ms[i][i];
-        }
-    }
-    __syncthreads();
-    if (lane < m) {  // rows of ZPZ d, G d, G c
-        double sz = 0, sgd = 0, sgc = 0;
-        for (int j = 0; j < m; j++) {
-            sz += c.ZPZ[(size_t)lane * m + j] * xs[j];
-            sgd += c.G[(size_t)lane * m + j] * xs[j];
-            sgc += c.G[(size_t)lane * m + j] * cs[j];
-        }
-        t1[lane] = sz; t2[lane] = sgd; t3[lane] = sgc;
-        AT(c.dvb, lane, b) = xs[lane];
-    }
+    wl_assemble<S, MC, 64>(d, c, b, beta, lane, Ms, cs);
+    wl_lu_solve<MC>(Ms, m, xs, &prS);
+    wl_rows(c, Bp, b, lane, xs, cs, t1, t2, t3);
     __syncthreads();
     if (lane == 0) {
         double dZd = 0, dp0 = 0, v0d = 0, cGd = 0, dGd = 0, v0c = 0, cGc = 0;
@@ -286,14 +231,7 @@ __global__ __launch_bounds__(64) void k_wl_linesearch(Bufs a, WArgs c) {
     UNR for (int j = 0; j < MC; j++)
         if (j < m) AT(c.cv, j, b) = cv[j] + alpha * dv[j];
     c.beta[b] = bn;
-    a.alpha[b] = alpha;
-    a.iters[b] = c.it + 1;
-    a.status[b] = (isfinite(cost) ? 0 : 1) | ((alpha < 1e-3) ? 2 : 0);
-    if (a.cost_trace) {
-        a.cost_trace[(size_t)c.it * Bp + b] = cost0;  // the reference prints the PRE-step cost (BatchILQRCP.cpp:160)
-        a.alpha_trace[(size_t)c.it * Bp + b] = alpha;
-    }
-    a.cost[b] = cost;
+    batch_record_winner(a, Bp, b, c.it, alpha, cost0, cost);
     const double dun2 = AT(c.sc, 5, b);
     if (c.early_stop && alpha * sqrt(dun2 > 0 ? dun2 : 0.0) < 1e-3) a.active[b] = 0;  // :167
 }
@@ -461,34 +399,7 @@ __global__ __launch_bounds__(64) void k_wt_solve(Bufs a, WTArgs c) {
         Ms[row][col] = s;
     }
     __syncthreads();
-    for (int k = 0; k < m; k++) {  // LU with partial pivoting, lane q owns column q (column m = right-hand side)
-        if (lane == 0) {
-            int pr = k;
-            double pv = fabs(Ms[k][k]);
-            for (int i = k + 1; i < m; i++) {
-                const double v = fabs(Ms[i][k]);
-                if (v > pv) { pv = v; pr = i; }
-            }
-            prS = pr;
-        }
-        __syncthreads();
-        const int pr = prS;
-        if (lane <= m && lane >= k && pr != k) { const double t0 = Ms[k][lane]; Ms[k][lane] = Ms[pr][lane]; Ms[pr][lane] = t0; }
-        __syncthreads();
-        if (lane <= m && lane > k) {
-            const double piv = Ms[k][k], mk = Ms[k][lane];
-            for (int i = k + 1; i < m; i++) Ms[i][lane] -= (Ms[i][k] / piv) * mk;
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        for (int i = m - 1; i >= 0; i--) {
-            double s = Ms[i][m];
-            for (int q = i + 1; q < m; q++) s -= Ms[i][q] * kap[q];
-            kap[i] = s / Ms[i][i];
-        }
-    }
-    __syncthreads();
+    wl_lu_solve<MC>(Ms, m, kap, &prS);
     // du (a.U[1]) and ||du||^2; lane = column block
     double dn = 0;
     for (int j = lane; j <= T - 2; j += 64) {
@@ -528,206 +439,60 @@ __global__ void k_wt_init(Bufs a) {
     if (b >= d.B) return;
     const int Bp = d.Bp;
     for (int r = 0; r < (d.T - 1) * S::NU; r++) AT(a.U[0], r, b) = AT(a.U0, r, b);
-    a.cur[b] = 0;
-    a.active[b] = 1;
-    a.iters[b] = 0;
-    a.status[b] = 0;
-    a.alpha[b] = 1.0;
-    a.pend[b] = 0;
-    a.pred[b] = 0;
+    batch_reset_instance(a, b);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
 
-template <class T>
-static bool w_alloc(BatchWideState& st, T** p, size_t n, hipStream_t s) {
-    void* q = nullptr;
-    if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return false;
-    st.allocs.push_back(q);
-    (void)hipMemsetAsync(q, 0, (n ? n : 1) * sizeof(T), s);
-    *p = (T*)q;
-    return true;
-}
-
 void batchwide_free(BatchWideState& st) {
-    for (void* q : st.allocs) (void)hipFree(q);
+    st.arena.release();
     st = BatchWideState();
 }
 
-static bool upload(double* dst, const std::vector<double>& v, hipStream_t s) {
-    return hipMemcpyAsync(dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, s) == hipSuccess;
-}
-
-// Cholesky inverse of a symmetric positive matrix (row-major n x n); false if it is not positive
-static bool spd_inverse(std::vector<double>& A, int n) {
-    std::vector<double> L((size_t)n * n, 0.0);
-    for (int j = 0; j < n; j++) {
-        double s = A[(size_t)j * n + j];
-        for (int k = 0; k < j; k++) s -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
-        if (!(s > 0)) return false;
-        const double ljj = std::sqrt(s);
-        L[(size_t)j * n + j] = ljj;
-        for (int i = j + 1; i < n; i++) {
-            double t = A[(size_t)i * n + j];
-            for (int k = 0; k < j; k++) t -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
-            L[(size_t)i * n + j] = t / ljj;
-        }
+// buffers for `want`; a change of any sized quantity re-allocates everything (and with it forgets the tables)
+static bool wide_size(BatchWideState& st, const BatchSizes& want, hipStream_t s) {
+    if (st.sizes == want) return true;
+    batchwide_free(st);
+    DevArena& A = st.arena;
+    const size_t NX = want.n_x, nkp = want.n_kp, m = nkp * NX, N = want.rows, Kw = want.cols, Bp = want.Bp;
+    bool ok;
+    if (want.layout == BatchSizes::WIDE_TIME) {
+        ok = A.get(&st.Ckp, nkp * NX * NX * Bp, s) && A.get(&st.rkp, m * Bp, s) && A.get(&st.scal, Bp, s);
+    } else {
+        ok = A.get(&st.G, m * m, s) && A.get(&st.ZPZ, m * m, s) && A.get(&st.Et, nkp * 2 * NX * m, s) && A.get(&st.PZ, N * m, s) &&
+             A.get(&st.xbk, nkp * 2 * NX * Bp, s) && A.get(&st.av, nkp * 2 * NX * Bp, s) && A.get(&st.v0, m * Bp, s) && A.get(&st.p0, m * Bp, s) &&
+             A.get(&st.scal, 3 * Bp, s) && A.get(&st.cv, m * Bp, s) && A.get(&st.beta, Bp, s) && A.get(&st.Ckp, nkp * NX * NX * Bp, s) &&
+             A.get(&st.rkp, m * Bp, s) && A.get(&st.dvb, m * Bp, s) && A.get(&st.sc, 6 * Bp, s);
+        if (ok && m > 32)  // the kernels of ilqr_batchwide_big.hip
+            ok = A.get(&st.xs, nkp * 2 * NX * Bp, s) && A.get(&st.dxs, nkp * 2 * NX * Bp, s) && A.get(&st.kc, nkp * 2 * Bp, s);
+        if (ok && !want.ident)
+            ok = A.get(&st.u0hat, N * Bp, s) && A.get(&st.g0, Kw * Bp, s) && A.get(&st.y0, Kw * Bp, s) && A.get(&st.psi, N * Kw, s) &&
+                 A.get(&st.h0inv, Kw * Kw, s);
     }
-    std::vector<double> Li((size_t)n * n, 0.0);  // L^-1 (lower)
-    for (int c = 0; c < n; c++) {
-        Li[(size_t)c * n + c] = 1.0 / L[(size_t)c * n + c];
-        for (int i = c + 1; i < n; i++) {
-            double t = 0;
-            for (int k = c; k < i; k++) t -= L[(size_t)i * n + k] * Li[(size_t)k * n + c];
-            Li[(size_t)i * n + c] = t / L[(size_t)i * n + i];
-        }
-    }
-    for (int i = 0; i < n; i++)  // A^-1 = L^-T L^-1
-        for (int j = 0; j <= i; j++) {
-            double t = 0;
-            for (int k = i; k < n; k++) t += Li[(size_t)k * n + i] * Li[(size_t)k * n + j];
-            A[(size_t)i * n + j] = A[(size_t)j * n + i] = t;
-        }
+    if (!ok) { batchwide_free(st); return false; }
+    st.sizes = want;
     return true;
 }
 
-// LTI systems.  psi == nullptr: identity basis.  MC = 0: the kernels of ilqr_batchwide_big.hip (m > 32).
+// LTI systems: the shared tables depend on (system shape, dt, keypoint steps, R, PSI) only and stay on the device across solves
+static int wide_tables_to_device(BatchWideState& st, const BatchTableIn& in, hipStream_t stream, std::string& err) {
+    if (st.tab.same(in)) return 0;
+    st.tab.clear();
+    WideTables t;
+    if (!wide_tables(in, t)) { err = "wide-basis batch solve: PSI'R PSI is not positive definite (PSI must have full column rank)"; return 1; }
+    bool up = dev_upload(st.G, t.G, stream) && dev_upload(st.ZPZ, t.ZPZ, stream) && dev_upload(st.Et, t.Et, stream) && dev_upload(st.PZ, t.PZ, stream);
+    if (up && in.psi) up = dev_upload(st.psi, in.psi, (size_t)in.rows() * in.Kw, stream) && dev_upload(st.h0inv, t.h0inv, stream);
+    if (!up || hipStreamSynchronize(stream) != hipSuccess) { err = "wide-basis batch solve: table upload failed"; return 1; }
+    st.tab.set(in);
+    return 0;
+}
+
+// LTI systems.  ident: no PSI.  MC = 0: the kernels of ilqr_batchwide_big.hip (m > 32).
 template <class S, int MC>
-static int run_wl(BatchWideState& st, const DevDesc& h, Bufs& bufs, const double* psi, int Kw, int nb_iter, int early_stop, bool u0_zero,
-                  hipStream_t stream, std::string& err) {
+static int run_wl(BatchWideState& st, const DevDesc& h, Bufs& bufs, bool ident, int Kw, int nb_iter, int early_stop, bool u0_zero, hipStream_t stream,
+                  std::string& err) {
     constexpr int NX = S::NX, NU = S::NU, ND = S::ND;
     const int B = h.B, Bp = h.Bp, T = h.T, nkp = h.n_kp, m = nkp * NX, N = (T - 1) * NU;
-    const bool ident = psi == nullptr;
-    const double dt = h.dt, hdt2 = dt * dt / 2;
-    for (int i = 0; i < NU; i++)
-        if (!(h.R_diag[i] > 0)) { err = "wide-basis batch solve: the control penalty RtDiag must be positive"; return 1; }
-
-    // the shared tables depend on (system shape, dt, keypoint steps, R, PSI) only: keep them on the device across solves
-    std::vector<double> sig = {(double)h.kind, (double)ND, (double)T, dt, (double)nkp, (double)Kw, ident ? 1.0 : 0.0};
-    for (int t = 0; t < nkp; t++) sig.push_back(h.kp_t[t]);
-    for (int i = 0; i < NU; i++) sig.push_back(h.R_diag[i]);
-    const long long key = (((long long)m * 100003 + N) * 100003 + Bp) * 8 + h.kind * 2 + (ident ? 1 : 0) + (long long)Kw * 1000000007LL;
-    const bool fresh = st.key != key;
-    if (fresh) {
-        batchwide_free(st);
-        bool ok = w_alloc(st, &st.G, (size_t)m * m, stream) && w_alloc(st, &st.ZPZ, (size_t)m * m, stream) && w_alloc(st, &st.Et, (size_t)nkp * 2 * NX * m, stream) &&
-                  w_alloc(st, &st.PZ, (size_t)N * m, stream) && w_alloc(st, &st.xbk, (size_t)nkp * 2 * NX * Bp, stream) &&
-                  w_alloc(st, &st.av, (size_t)nkp * 2 * NX * Bp, stream) && w_alloc(st, &st.v0, (size_t)m * Bp, stream) && w_alloc(st, &st.p0, (size_t)m * Bp, stream) &&
-                  w_alloc(st, &st.scal, (size_t)3 * Bp, stream) && w_alloc(st, &st.cv, (size_t)m * Bp, stream) && w_alloc(st, &st.beta, (size_t)Bp, stream) &&
-                  w_alloc(st, &st.Ckp, (size_t)nkp * NX * NX * Bp, stream) && w_alloc(st, &st.rkp, (size_t)m * Bp, stream) &&
-                  w_alloc(st, &st.dvb, (size_t)m * Bp, stream) && w_alloc(st, &st.sc, (size_t)6 * Bp, stream);
-        if (ok && MC == 0)
-            ok = w_alloc(st, &st.xs, (size_t)nkp * 2 * NX * Bp, stream) && w_alloc(st, &st.dxs, (size_t)nkp * 2 * NX * Bp, stream) &&
-                 w_alloc(st, &st.kc, (size_t)nkp * 2 * Bp, stream);
-        if (ok && !ident)
-            ok = w_alloc(st, &st.u0hat, (size_t)N * Bp, stream) && w_alloc(st, &st.g0, (size_t)Kw * Bp, stream) && w_alloc(st, &st.y0, (size_t)Kw * Bp, stream) &&
-                 w_alloc(st, &st.psi, (size_t)N * Kw, stream) && w_alloc(st, &st.h0inv, (size_t)Kw * Kw, stream);
-        if (!ok) { batchwide_free(st); err = "wide-basis batch solve: hipMalloc failed"; return 1; }
-        st.key = key;
-    }
-    const bool same_tables = !fresh && st.tab_sig == sig && (ident || (st.tab_psi.size() == (size_t)N * Kw && !std::memcmp(st.tab_psi.data(), psi, sizeof(double) * N * Kw)));
-    if (!same_tables) {
-        // sensitivities at the keypoint steps by their recurrences: Wt_{i+1} = A Wt_i + B PSI_i from Wt_0 = 0 (true), and the
-        // reference's shifted Wr_{i+1} = A Wr_i + B PSI_i from Wr_1 = 0, i >= 1 (BatchILQRCP.cpp:61-97, quirk D-1).  NX x Kw, row-major.
-        auto advance = [&](std::vector<double>& W, int i) {
-            if (ND == 2)
-                for (int r = 0; r < DOF; r++)
-                    for (int q = 0; q < Kw; q++) W[(size_t)r * Kw + q] += dt * W[(size_t)(DOF + r) * Kw + q];
-            for (int r = 0; r < DOF; r++) {
-                if (ident) {
-                    const int q = i * NU + r;
-                    if (ND == 1) W[(size_t)r * Kw + q] += dt;
-                    else { W[(size_t)r * Kw + q] += hdt2; W[(size_t)(DOF + r) * Kw + q] += dt; }
-                } else {
-                    const double* pr = psi + (size_t)(i * NU + r) * Kw;
-                    for (int q = 0; q < Kw; q++) {
-                        if (ND == 1) W[(size_t)r * Kw + q] += dt * pr[q];
-                        else { W[(size_t)r * Kw + q] += hdt2 * pr[q]; W[(size_t)(DOF + r) * Kw + q] += dt * pr[q]; }
-                    }
-                }
-            }
-        };
-        std::vector<std::vector<double>> wt(2 * nkp, std::vector<double>((size_t)NX * Kw, 0.0));  // [kp][which]
-        std::vector<double> V((size_t)m * Kw, 0.0);
-        {
-            std::vector<double> Wt((size_t)NX * Kw, 0.0), Wr((size_t)NX * Kw, 0.0);
-            auto sample = [&](int i) {  // Wt = Wt_i, Wr = Wr_i
-                for (int t = 0; t < nkp; t++) {
-                    if (h.kp_t[t] == i) { wt[2 * t + 0] = Wt; std::copy(Wr.begin(), Wr.end(), V.begin() + (size_t)t * NX * Kw); }
-                    if (h.kp_t[t] - 1 == i) wt[2 * t + 1] = Wt;
-                }
-            };
-            sample(0);
-            for (int i = 0; i + 1 < T; i++) {
-                advance(Wt, i);
-                if (i >= 1) advance(Wr, i);
-                sample(i + 1);
-            }
-        }
-        // Z = H0^-1 V' (Kw x m)
-        std::vector<double> Z((size_t)Kw * m, 0.0), h0inv;
-        bool diag = ident;
-        if (ident) {
-            for (int q = 0; q < Kw; q++)
-                for (int j = 0; j < m; j++) Z[(size_t)q * m + j] = V[(size_t)j * Kw + q] / h.R_diag[q % NU];
-        } else {
-            h0inv.assign((size_t)Kw * Kw, 0.0);
-            for (int k = 0; k < N; k++) {
-                const double* pr = psi + (size_t)k * Kw;
-                const double rk = h.R_diag[k % NU];
-                for (int a_ = 0; a_ < Kw; a_++) {
-                    if (pr[a_] == 0.0) continue;
-                    const double pa = pr[a_] * rk;
-                    for (int b_ = 0; b_ < Kw; b_++) h0inv[(size_t)a_ * Kw + b_] += pa * pr[b_];
-                }
-            }
-            if (!spd_inverse(h0inv, Kw)) { err = "wide-basis batch solve: PSI'R PSI is not positive definite (PSI must have full column rank)"; return 1; }
-            for (int q = 0; q < Kw; q++)
-                for (int j = 0; j < m; j++) {
-                    double s = 0;
-                    for (int r = 0; r < Kw; r++) s += h0inv[(size_t)q * Kw + r] * V[(size_t)j * Kw + r];
-                    Z[(size_t)q * m + j] = s;
-                }
-        }
-        (void)diag;
-        std::vector<double> G((size_t)m * m, 0.0), Et((size_t)nkp * 2 * NX * m, 0.0), PZ((size_t)N * m, 0.0), ZPZ((size_t)m * m, 0.0);
-        for (int i = 0; i < m; i++)
-            for (int q = 0; q < Kw; q++) {
-                const double v = V[(size_t)i * Kw + q];
-                if (v == 0.0) continue;
-                for (int j = 0; j < m; j++) G[(size_t)i * m + j] += v * Z[(size_t)q * m + j];
-            }
-        for (int i = 0; i < m; i++)  // symmetric in exact arithmetic; the kernel relies on it
-            for (int j = 0; j < i; j++) G[(size_t)i * m + j] = G[(size_t)j * m + i] = 0.5 * (G[(size_t)i * m + j] + G[(size_t)j * m + i]);
-        for (int t = 0; t < 2 * nkp; t++)
-            for (int r = 0; r < NX; r++)
-                for (int q = 0; q < Kw; q++) {
-                    const double v = wt[t][(size_t)r * Kw + q];
-                    if (v == 0.0) continue;
-                    for (int j = 0; j < m; j++) Et[((size_t)t * NX + r) * m + j] += v * Z[(size_t)q * m + j];
-                }
-        if (ident) PZ = Z;
-        else
-            for (int k = 0; k < N; k++)
-                for (int q = 0; q < Kw; q++) {
-                    const double v = psi[(size_t)k * Kw + q];
-                    if (v == 0.0) continue;
-                    for (int j = 0; j < m; j++) PZ[(size_t)k * m + j] += v * Z[(size_t)q * m + j];
-                }
-        for (int k = 0; k < N; k++)
-            for (int i = 0; i < m; i++) {
-                const double v = PZ[(size_t)k * m + i];
-                if (v == 0.0) continue;
-                for (int j = 0; j < m; j++) ZPZ[(size_t)i * m + j] += v * PZ[(size_t)k * m + j];
-            }
-        bool up = upload(st.G, G, stream) && upload(st.ZPZ, ZPZ, stream) && upload(st.Et, Et, stream) && upload(st.PZ, PZ, stream);
-        if (up && !ident)
-            up = hipMemcpyAsync(st.psi, psi, (size_t)N * Kw * sizeof(double), hipMemcpyHostToDevice, stream) == hipSuccess && upload(st.h0inv, h0inv, stream);
-        if (!up || hipStreamSynchronize(stream) != hipSuccess) { err = "wide-basis batch solve: table upload failed"; return 1; }
-        st.tab_sig = sig;
-        if (!ident) st.tab_psi.assign(psi, psi + (size_t)N * Kw);
-    }
-
     WArgs c;
     c.G = st.G; c.Et = st.Et; c.ZPZ = st.ZPZ; c.PZ = st.PZ;
     c.xbk = st.xbk; c.av = st.av; c.v0 = st.v0; c.p0 = st.p0; c.scal = st.scal; c.cv = st.cv; c.beta = st.beta;
@@ -767,36 +532,12 @@ static int run_wl(BatchWideState& st, const DevDesc& h, Bufs& bufs, const double
     return 0;
 }
 
-template <class S>
-static int run_wl_m(BatchWideState& st, const DevDesc& h, Bufs& bufs, const double* psi, int Kw, int nb_iter, int early_stop, bool u0_zero,
-                    hipStream_t stream, std::string& err) {
-    const int m = h.n_kp * S::NX;
-    if (m <= 16) return run_wl<S, 16>(st, h, bufs, psi, Kw, nb_iter, early_stop, u0_zero, stream, err);
-    if (m <= 32) return run_wl<S, 32>(st, h, bufs, psi, Kw, nb_iter, early_stop, u0_zero, stream, err);
-    if (m <= ILQR_MAX_KP * S::NX) return run_wl<S, 0>(st, h, bufs, psi, Kw, nb_iter, early_stop, u0_zero, stream, err);
-    err = "wide-basis batch solve: n_keypoints * n_x must not exceed ILQR_MAX_KP * n_x";
-    return 1;
-}
-
 // time systems, identity basis.  MC = 0: the solve kernel of ilqr_batchwide_big.hip (m > 32).
 template <class S, int MC>
 static int run_wt(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nb_iter, int early_stop, hipStream_t stream, std::string& err) {
-    constexpr int NX = S::NX, NU = S::NU;
-    const int B = h.B, Bp = h.Bp, nkp = h.n_kp, m = nkp * NX;
-    for (int i = 0; i < NU; i++)
-        if (!(h.R_diag[i] > 0)) { err = "wide-basis batch solve: the control penalty RtDiag must be positive"; return 1; }
-    const long long key = -2 - ((((long long)m * 100003 + Bp) * 8) + h.kind * 2 + h.nd);
-    if (st.key != key) {
-        batchwide_free(st);
-        if (!(w_alloc(st, &st.Ckp, (size_t)nkp * NX * NX * Bp, stream) && w_alloc(st, &st.rkp, (size_t)m * Bp, stream) && w_alloc(st, &st.scal, (size_t)Bp, stream))) {
-            batchwide_free(st);
-            err = "wide-basis batch solve: hipMalloc failed";
-            return 1;
-        }
-        st.key = key;
-    }
+    const int B = h.B;
     WTArgs c;
-    c.Ckp = st.Ckp; c.rkp = st.rkp; c.dun2 = st.scal; c.m = m; c.it = 0; c.early_stop = early_stop;
+    c.Ckp = st.Ckp; c.rkp = st.rkp; c.dun2 = st.scal; c.m = h.n_kp * S::NX; c.it = 0; c.early_stop = early_stop;
     const dim3 grid((B + 63) / 64), block(64);
     hipLaunchKernelGGL((k_wt_init<S>), dim3((B + 255) / 256), dim3(256), 0, stream, bufs);
     for (int it = 0; it < nb_iter; it++) {
@@ -816,30 +557,56 @@ static int run_wt(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nb_iter,
     return 0;
 }
 
+// the kernels are compiled for m = n_kp n_x <= 16, <= 32 and above (batchwide_solve has checked n_kp <= ILQR_MAX_KP)
+template <class S>
+static int run_wl_m(BatchWideState& st, const DevDesc& h, Bufs& bufs, bool ident, int Kw, int nb_iter, int early_stop, bool u0_zero, hipStream_t stream,
+                    std::string& err) {
+    const int m = h.n_kp * S::NX;
+    if (m <= 16) return run_wl<S, 16>(st, h, bufs, ident, Kw, nb_iter, early_stop, u0_zero, stream, err);
+    if (m <= 32) return run_wl<S, 32>(st, h, bufs, ident, Kw, nb_iter, early_stop, u0_zero, stream, err);
+    return run_wl<S, 0>(st, h, bufs, ident, Kw, nb_iter, early_stop, u0_zero, stream, err);
+}
 template <class S>
 static int run_wt_m(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nb_iter, int early_stop, hipStream_t stream, std::string& err) {
     const int m = h.n_kp * S::NX;
     if (m <= 16) return run_wt<S, 16>(st, h, bufs, nb_iter, early_stop, stream, err);
     if (m <= 32) return run_wt<S, 32>(st, h, bufs, nb_iter, early_stop, stream, err);
-    if (m <= ILQR_MAX_KP * S::NX) return run_wt<S, 0>(st, h, bufs, nb_iter, early_stop, stream, err);
-    err = "wide-basis batch solve: n_keypoints * n_x must not exceed ILQR_MAX_KP * n_x";
-    return 1;
+    return run_wt<S, 0>(st, h, bufs, nb_iter, early_stop, stream, err);
 }
 
 int batchwide_solve(BatchWideState& st, const DevDesc& h, Bufs& bufs, int nx, int nu, const double* psi_host, int Kw, int nb_iter, int early_stop,
                     bool u0_zero, hipStream_t stream, std::string& err, const ProfHook& ph) {
-    (void)nx;
     ph(ILQR_PROF_BACKWARD);  // the whole wide-basis solve is charged to one category
+    // check
     const int N = (h.T - 1) * nu;
+    const bool lti = h.kind == 0 || h.kind == 2, ident = psi_host == nullptr;
     if (nb_iter < 0) { err = "nb_iter < 0"; return 1; }
+    if (!lti && h.kind != 1 && h.kind != 3) { err = "wide-basis batch solve: unknown system kind"; return 1; }
     if (h.n_kp <= 0) { err = "wide-basis batch solve: the system has no keypoint"; return 1; }
-    if (!psi_host) Kw = N;
+    if (ident) Kw = N;
     if (Kw <= 0 || Kw > N) { err = "wide-basis batch solve: Kw must be in 1 .. (T-1) n_u"; return 1; }
+    if (!lti && !ident) { err = "wide-basis batch solve: on time systems only the identity basis (ilqr_solve_batch) is supported for Kw > 32"; return 1; }
+    if (h.n_kp > ILQR_MAX_KP) { err = "wide-basis batch solve: n_keypoints * n_x must not exceed ILQR_MAX_KP * n_x"; return 1; }
+    for (int i = 0; i < nu; i++)
+        if (!(h.R_diag[i] > 0)) { err = "wide-basis batch solve: the control penalty RtDiag must be positive"; return 1; }
+    // size
+    BatchSizes want;
+    want.layout = lti ? BatchSizes::WIDE_LTI : BatchSizes::WIDE_TIME;
+    want.n_x = nx; want.n_kp = h.n_kp; want.Bp = h.Bp;
+    if (lti) { want.rows = N; want.cols = Kw; want.ident = ident; }
+    if (!wide_size(st, want, stream)) { err = "wide-basis batch solve: hipMalloc failed"; return 1; }
+    // tables
+    if (lti) {
+        BatchTableIn in;
+        in.nd = h.nd; in.n_x = nx; in.n_u = nu; in.T = h.T; in.dt = h.dt; in.n_kp = h.n_kp; in.kp_t = h.kp_t; in.R_diag = h.R_diag;
+        in.psi = psi_host; in.Kw = in.ld = Kw;
+        if (wide_tables_to_device(st, in, stream, err)) return 1;
+    }
+    // launch loop
     using LtiSys = SysList<Sys<0, 1>, Sys<0, 2>, Sys<2, 1>>;
     using TimeSys = SysList<Sys<1, 1>, Sys<1, 2>, Sys<3, 1>>;
     int rc = 1;
-    if (LtiSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_wl_m<decltype(s)>(st, h, bufs, psi_host, Kw, nb_iter, early_stop, u0_zero, stream, err); })) return rc;
-    if (psi_host) { err = "wide-basis batch solve: on time systems only the identity basis (ilqr_solve_batch) is supported for Kw > 32"; return 1; }
+    if (LtiSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_wl_m<decltype(s)>(st, h, bufs, ident, Kw, nb_iter, early_stop, u0_zero, stream, err); })) return rc;
     if (TimeSys::dispatch(h.kind, h.nd, [&](auto s) { rc = run_wt_m<decltype(s)>(st, h, bufs, nb_iter, early_stop, stream, err); })) return rc;
     err = "wide-basis batch solve: unknown system kind";
     return 1;

@@ -13,6 +13,7 @@
 // - Time systems: G = sum_j V_j R^-1 V_j' accumulates in registers (thread = one column and one row parity, MC / 2 entries), is stored
 //   into the LDS system, and M = I + C G is formed in place over it block row by block row (row block k of M needs row block k of G).
 // No kernel here carries a private segment; none is chosen by batch size.
+// The assembly of M = I + C G | rhs and the rows of ZPZ d, G d, G c are those of k_wl_solve (ilqr_batchwide.hpp: wl_assemble, wl_rows).
 #include "ilqr_batchcp.hpp"
 
 #include <cmath>
@@ -131,13 +132,7 @@ __global__ __launch_bounds__(64) void k_wb_init(Bufs a, WArgs c, WBig g) {
     AT(c.scal, 1, b) = gam;
     AT(c.scal, 2, b) = pi;
     c.beta[b] = 1.0;
-    a.cur[b] = 0;
-    a.active[b] = 1;
-    a.iters[b] = 0;
-    a.status[b] = 0;
-    a.alpha[b] = 1.0;
-    a.pend[b] = 0;
-    a.pred[b] = 0;
+    batch_reset_instance(a, b);
 }
 
 // One lane per (instance, keypoint): C_k = J'QJ + L, r_k = J'Q e + L ql at the iterate's keypoint states xs, row by row to memory as
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(64) void k_wb_linearize(Bufs a, WArgs c, WBig g) {
 // and dxs = Et d - beta ab; in the first iteration also cost0 from the keypoint terms of k_wb_linearize.
 template <class S, int MC>
 __global__ __launch_bounds__(2 * MC) void k_wb_solve(Bufs a, WArgs c, WBig g) {
-    constexpr int NX = S::NX, NT = 2 * MC;
+    constexpr int NT = 2 * MC;
     __shared__ double Ms[MC][MC + 2], xs[MC], cs[MC], t1[MC], t2[MC], t3[MC], pvS[2];
     __shared__ int prS[1];
     const DevDesc& d = *a.desc;
@@ -190,33 +185,9 @@ __global__ __launch_bounds__(2 * MC) void k_wb_solve(Bufs a, WArgs c, WBig g) {
         for (int k = 0; k < nkp; k++) { ce += AT(g.kc, 2 * k, b); cl += AT(g.kc, 2 * k + 1, b); }
         a.cost[b] = (ce + cl) + wl_uru(AT(c.scal, 0, b), AT(c.scal, 1, b), beta, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0);
     }
-    for (int e = tid; e < m * (m + 1); e += NT) {
-        const int row = e / (m + 1), col = e % (m + 1), kpi = row / NX, i = row % NX;
-        const double* Ck = c.Ckp + (size_t)kpi * NX * NX * Bp;
-        double s;
-        if (col == m) {
-            double cv0 = 0;
-            UNR for (int j = 0; j < NX; j++) cv0 += AT(Ck, i * NX + j, b) * AT(c.v0, kpi * NX + j, b);
-            s = (AT(c.rkp, row, b) - AT(c.cv, row, b)) + beta * cv0;
-        } else {
-            s = (row == col) ? 1.0 : 0.0;
-            UNR for (int j = 0; j < NX; j++) s += AT(Ck, i * NX + j, b) * c.G[(size_t)(kpi * NX + j) * m + col];
-        }
-        Ms[row][col] = s;
-    }
-    if (tid < m) cs[tid] = AT(c.cv, tid, b);
-    __syncthreads();
+    wl_assemble<S, MC, NT>(d, c, b, beta, tid, Ms, cs);
     wb_lu_solve<MC>(Ms, m, xs, prS, pvS);
-    if (tid < m) {  // rows of ZPZ d, G d, G c
-        double sz = 0, sgd = 0, sgc = 0;
-        for (int j = 0; j < m; j++) {
-            sz += c.ZPZ[(size_t)tid * m + j] * xs[j];
-            sgd += c.G[(size_t)tid * m + j] * xs[j];
-            sgc += c.G[(size_t)tid * m + j] * cs[j];
-        }
-        t1[tid] = sz; t2[tid] = sgd; t3[tid] = sgc;
-        AT(c.dvb, tid, b) = xs[tid];
-    }
+    wl_rows(c, Bp, b, tid, xs, cs, t1, t2, t3);
     if (tid < 2 * m) {  // state row tid of the keypoint records: dxs = Et d - beta ab
         const double* et = c.Et + (size_t)tid * m;
         double s = 0;
@@ -284,14 +255,7 @@ __global__ __launch_bounds__(64) void k_wb_linesearch(Bufs a, WArgs c, WBig g) {
     for (int r = l; r < 2 * m; r += 16) AT(g.xs, r, b) = fma(aw, AT(g.dxs, r, b), AT(g.xs, r, b));  // the winner's trial states, same bits
     if (l != win) return;
     c.beta[b] = bn;
-    a.alpha[b] = alpha;
-    a.iters[b] = c.it + 1;
-    a.status[b] = (isfinite(cost) ? 0 : 1) | ((alpha < 1e-3) ? 2 : 0);
-    if (a.cost_trace) {
-        a.cost_trace[(size_t)c.it * Bp + b] = cost0;  // the reference prints the PRE-step cost (BatchILQRCP.cpp:160)
-        a.alpha_trace[(size_t)c.it * Bp + b] = alpha;
-    }
-    a.cost[b] = cost;
+    batch_record_winner(a, Bp, b, c.it, alpha, cost0, cost);
     const double dun2 = AT(c.sc, 5, b);
     if (c.early_stop && alpha * sqrt(dun2 > 0 ? dun2 : 0.0) < 1e-3) a.active[b] = 0;  // :167
 }

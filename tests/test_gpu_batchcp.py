@@ -143,6 +143,20 @@ def test_cp_time_system_basis_up_to_32_columns(ctx, cfg_name, T, K):
     p.close()
 
 
+@pytest.mark.parametrize("cfg_name", ["C2", "C2nd"])
+def test_narrow_tables_follow_the_basis(ctx, cfg_name):
+    """Narrow basis A (RBF, K = 2), B (Bernstein), A again, the identity (the wide solver's state), A again on one problem object, on the
+    coefficient-space path: each solve gives the bits of a fresh problem object (tests/test_gpu_batchwide.py: check_table_cache)."""
+    from tests.test_gpu_batchwide import check_table_cache
+    from tests.test_gpu_batchwide_keypoints import _cfg
+
+    T, K = 12, 2
+    kp_t = [T // 2 - 1, T - 1]
+    bases = dict(A=np.kron(orc.psi("rbf", T - 1, K), np.eye(7)), B=np.kron(orc.psi("bernstein", T - 1, K), np.eye(7)), I=None)
+    assert bases["A"].shape[1] == 14
+    check_table_cache(ctx, _cfg(cfg_name, T, kp_t), kp_t, bases, ["A", "B", "A", "I", "A"])
+
+
 def test_cp_errors(ctx):
     from ilqr_planner_amd import workloads
 

@@ -158,6 +158,57 @@ def test_batch_ilqr_edge_shapes(ctx, cfg_name, T, B):
         np.testing.assert_allclose(U[i].reshape(-1), r["u"], rtol=0, atol=tol * max(1.0, np.abs(r["u"]).max()))
 
 
+def check_table_cache(ctx, cfg, kp_t, bases, order, B=5, nb_iter=4):
+    """One problem object solves the cases of `order` (keys of `bases`; a basis of None is solve_batch) one after the other, its controls
+    re-set before each solve, so that the device buffers are re-sized and the shared tables rebuilt or kept between them.  Every solve
+    gives the bits of a fresh problem object that solves only that case, and the repeats of a case give the bits of its first solve:
+    cost, X, U, iters, status and both traces."""
+    from ilqr_planner_amd import workloads
+
+    desc, inp = workloads.make_batch(ctx, cfg, B=B, limits="urdf", kp_t=kp_t)
+    inp["U0"] = inp["U0"] + 0.2 * np.random.default_rng(5).standard_normal(inp["U0"].shape)
+
+    def solve(p, psi):
+        p.set_controls(inp["U0"])
+        if psi is None:
+            p.solve_batch(nb_iter, False)
+        else:
+            p.solve_batch_cp(psi, nb_iter, False)
+        ct, at = p.trace(nb_iter)
+        return dict(cost=p.cost(), X=p.X(), U=p.U(), iters=p.iters(), status=p.status(), cost_trace=ct, alpha_trace=at)
+
+    p = workloads.load_batch(ctx, desc, inp, B)
+    runs = [(name, solve(p, bases[name])) for name in order]
+    p.close()
+    first = {}
+    for i, (name, out) in enumerate(runs):
+        if name not in first:
+            q = workloads.load_batch(ctx, desc, inp, B)
+            fresh = solve(q, bases[name])
+            q.close()
+            first[name] = out
+            assert np.all(np.isfinite(fresh["cost"])) and np.all(fresh["iters"] == nb_iter)
+            for k in out:
+                assert np.array_equal(out[k], fresh[k]), f"solve {i} ({name}): {k} differs from a fresh problem's"
+        for k in out:
+            assert np.array_equal(out[k], first[name][k]), f"solve {i} ({name}): {k} differs from the first solve of {name}"
+    names = list(first)
+    assert not np.array_equal(first[names[0]]["U"], first[names[1]]["U"])  # the cases are different problems
+
+
+@pytest.mark.parametrize("cfg_name,n_kp", [("C2", 2), ("C2nd", 2), ("C2", 6)], ids=["C2", "C2nd", "C2-kp6-m42"])
+def test_wide_tables_follow_the_basis(ctx, cfg_name, n_kp):
+    """Wide basis A (RBF), B (Bernstein), A again, the identity (other buffer sizes), A again on one problem object; with six keypoints
+    the same through the m > 32 kernels."""
+    from tests.test_gpu_batchwide_keypoints import _cfg, _spread
+
+    T, K = 12, 3
+    kp_t = [T // 2 - 1, T - 1] if n_kp == 2 else _spread(T, n_kp)
+    bases = dict(A=np.kron(orc.psi("rbf", T - 1, K), np.eye(7)), B=np.kron(orc.psi("bernstein", T - 1, K), np.eye(7)), I=None)
+    assert bases["A"].shape[1] == 21
+    check_table_cache(ctx, _cfg(cfg_name, T, kp_t), kp_t, bases, ["A", "B", "A", "I", "A"])
+
+
 def test_wide_errors(ctx):
     from ilqr_planner_amd import workloads
 
