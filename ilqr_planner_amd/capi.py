@@ -20,6 +20,7 @@ STATUS_OK, STATUS_NONFINITE, STATUS_ALPHA_FLOOR, STATUS_SWEEP_IO = 0, 1, 2, 4  #
 LQT_MAX_NX, LQT_MAX_NU = 16, 8
 CL_STATS = 5  # mean, variance, min, max, n_bad (ILQR_CL_STATS)
 KP_ERR, KP_STATS, CL_OUTCOME = 5, 12, 4  # ILQR_KP_ERR (pos, orn, vel, angvel, time), ILQR_KP_STATS (mean[5], max[5], n_miss, n_bad), ILQR_CL_OUTCOME
+CL_CON_STATS, CL_OUTCOME_CON = 6, 5  # ILQR_CL_CON_STATS (mean/max con_max, mean/max con_steps, n_con, n_bad), ILQR_CL_OUTCOME_CON (n_ok, n_miss, n_lim, n_con, n_bad)
 KP_ERR_POS, KP_ERR_ORN, KP_ERR_VEL, KP_ERR_ANGVEL, KP_ERR_TIME = range(5)
 PROF_ROLLOUT, PROF_BACKWARD, PROF_FORWARD, PROF_OTHER, PROF_APPLY = 0, 1, 2, 3, 4
 
@@ -37,6 +38,8 @@ EXPORTS = [
     "ilqr_problem_reset_multipliers", "ilqr_problem_warm_start", "ilqr_problem_track", "ilqr_problem_track_dev",
     "ilqr_problem_closed_loop", "ilqr_problem_closed_loop_dev", "ilqr_problem_closed_loop_noise", "ilqr_problem_closed_loop_noise_dev",
     "ilqr_problem_closed_loop_report", "ilqr_problem_closed_loop_report_dev", "ilqr_problem_closed_loop_cov", "ilqr_problem_closed_loop_cov_dev",
+    "ilqr_problem_closed_loop_report_con", "ilqr_problem_closed_loop_report_con_dev", "ilqr_problem_closed_loop_cov_con",
+    "ilqr_problem_closed_loop_cov_con_dev",
     "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck", "ilqr_problem_gains",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
@@ -119,7 +122,21 @@ class Cov(C.Structure):
     _fields_ = [("Sigma", C.c_void_p), ("kp_Sigma", C.c_void_p), ("kp_var", C.c_void_p), ("u_var", C.c_void_p), ("lim_z", C.c_void_p)]
 
 
+class Con(C.Structure):
+    """Mirror of ilqr_cl_con: four pointers (host or device), 0 / None where the output is not asked for."""
+
+    _fields_ = [("con_max", C.c_void_p), ("con_steps", C.c_void_p), ("con_stats", C.c_void_p), ("outcome_con", C.c_void_p)]
+
+
+class CovCon(C.Structure):
+    """Mirror of ilqr_cl_cov_con: two pointers (host or device), 0 / None where the output is not asked for."""
+
+    _fields_ = [("con_var", C.c_void_p), ("con_z", C.c_void_p)]
+
+
 ClosedLoopCov = collections.namedtuple("ClosedLoopCov", "Sigma kp_Sigma kp_var u_var lim_z")
+ClosedLoopReportCon = collections.namedtuple("ClosedLoopReportCon", "cost stats kp_err kp_stats lim_cost outcome con_max con_steps con_stats outcome_con")
+ClosedLoopCovCon = collections.namedtuple("ClosedLoopCovCon", "Sigma kp_Sigma kp_var u_var lim_z con_var con_z")
 ClosedLoopNoise = collections.namedtuple("ClosedLoopNoise", "cost stats X U w")
 ClosedLoopReport = collections.namedtuple("ClosedLoopReport", "cost stats kp_err kp_stats lim_cost outcome X U w")
 
@@ -172,6 +189,12 @@ def load():
     L.ilqr_problem_closed_loop_report_dev.argtypes = [vp, C.c_int, C.POINTER(Noise), vp, vp, C.c_int, C.POINTER(Tol), vp, vp, C.POINTER(Report)]
     L.ilqr_problem_closed_loop_cov.argtypes = [vp, dp, dp, C.POINTER(Cov)]
     L.ilqr_problem_closed_loop_cov_dev.argtypes = [vp, dp, dp, C.POINTER(Cov)]
+    L.ilqr_problem_closed_loop_report_con.argtypes = [vp, C.c_int, C.POINTER(Noise), dp, dp, C.c_int, C.POINTER(Tol), dp, dp, C.POINTER(Report),
+                                                      C.c_double, C.POINTER(Con)]
+    L.ilqr_problem_closed_loop_report_con_dev.argtypes = [vp, C.c_int, C.POINTER(Noise), vp, vp, C.c_int, C.POINTER(Tol), vp, vp, C.POINTER(Report),
+                                                          C.c_double, C.POINTER(Con)]
+    L.ilqr_problem_closed_loop_cov_con.argtypes = [vp, dp, dp, C.POINTER(Cov), C.POINTER(CovCon)]
+    L.ilqr_problem_closed_loop_cov_con_dev.argtypes = [vp, dp, dp, C.POINTER(Cov), C.POINTER(CovCon)]
     L.ilqr_solve_recursive.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.ilqr_solve_al.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]
     L.ilqr_solve_batch_cp.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
@@ -627,6 +650,44 @@ class BatchProblem:
                                                                   C.byref(tol) if tol is not None else None, cost_ptr or None, stats_ptr or None,
                                                                   C.byref(rp)))
 
+    def closed_loop_report_con(self, con_tol, samples=None, seed=None, sigma_w=None, sigma_x0=None, x0=None, w=None, with_feedforward: bool = False,
+                               kp_tol=None, lim_tol=None, instance_offset=0, sample_offset=0, want_cost: bool = True, want_stats: bool = True,
+                               want_kp_err: bool = True, want_kp_stats: bool = True, want_lim_cost: bool = True, want_outcome: bool = True,
+                               want_con_max: bool = True, want_con_steps: bool = True, want_con_stats: bool = True, want_outcome_con: bool = True):
+        """closed_loop_report with the executions judged against the rows of set_constraints as well (ilqr_problem_closed_loop_report_con;
+        definitions in include/ilqr_hip.h): con_max [B][S], con_steps [B][S], con_stats [B][6] (mean con_max, max con_max, mean con_steps, max
+        con_steps, n_con, n_bad) and, with kp_tol or lim_tol, outcome_con [B][5] (n_ok, n_miss, n_lim, n_con, n_bad).  One rollout; the other
+        arguments and outputs are closed_loop_report's.  Returns a ClosedLoopReportCon; what was not asked for is None."""
+        S, n, x0, w = self._cl_inputs(samples, x0, w)
+        nz = self.noise(seed, sigma_w, sigma_x0, instance_offset, sample_offset) if seed is not None else None
+        judged = kp_tol is not None or lim_tol is not None
+        tol = self.tol(kp_tol, 0.0 if lim_tol is None else lim_tol) if judged else None
+        cost, stats = _out(want_cost, self.B, n), _out(want_stats, self.B, CL_STATS)
+        kp_err, kp_stats = _out(want_kp_err, self.B, n, self.n_kp, KP_ERR), _out(want_kp_stats and judged, self.B, self.n_kp, KP_STATS)
+        lim_cost, outcome = _out(want_lim_cost, self.B, n), _out(want_outcome and judged, self.B, CL_OUTCOME)
+        con_max, con_steps = _out(want_con_max, self.B, n), _out(want_con_steps, self.B, n)
+        con_stats, outcome_con = _out(want_con_stats, self.B, CL_CON_STATS), _out(want_outcome_con and judged, self.B, CL_OUTCOME_CON)
+        rp = Report(*(a.ctypes.data if a is not None else None for a in (kp_err, kp_stats, lim_cost, outcome)))
+        co = Con(*(a.ctypes.data if a is not None else None for a in (con_max, con_steps, con_stats, outcome_con)))
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_report_con(self.h, S, C.byref(nz) if nz is not None else None, _dp(x0), _dp(w),
+                                                                  int(bool(with_feedforward)), C.byref(tol) if tol is not None else None, _dp(cost),
+                                                                  _dp(stats), C.byref(rp), float(con_tol), C.byref(co)))
+        return ClosedLoopReportCon(cost, stats, kp_err, kp_stats, lim_cost, outcome, con_max, con_steps, con_stats, outcome_con)
+
+    def closed_loop_report_con_dev(self, samples: int, noise, x0_ptr, w_ptr, with_feedforward: bool, tol, con_tol, cost_ptr=None, stats_ptr=None,
+                                   kp_err_ptr=None, kp_stats_ptr=None, lim_cost_ptr=None, outcome_ptr=None, con_max_ptr=None, con_steps_ptr=None,
+                                   con_stats_ptr=None, outcome_con_ptr=None):
+        """Device pointers (0 / None where ilqr_problem_closed_loop_report_con takes NULL), asynchronous on the context's stream; noise:
+        self.noise(..) or None, tol: self.tol(..) or None."""
+        rp = Report(kp_err_ptr or None, kp_stats_ptr or None, lim_cost_ptr or None, outcome_ptr or None)
+        co = Con(con_max_ptr or None, con_steps_ptr or None, con_stats_ptr or None, outcome_con_ptr or None)
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_report_con_dev(self.h, int(samples), C.byref(noise) if noise is not None else None,
+                                                                      x0_ptr or None, w_ptr or None, int(bool(with_feedforward)),
+                                                                      C.byref(tol) if tol is not None else None, cost_ptr or None, stats_ptr or None,
+                                                                      C.byref(rp), float(con_tol), C.byref(co)))
+
     def _sigma(self, sig):
         """A sigma of a covariance call: None (zeros, passed as NULL), a scalar (every entry) or n_x values in the user's state layout."""
         return None if sig is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sig, dtype=np.float64), (self.dims.n_x,)))
@@ -650,6 +711,30 @@ class BatchProblem:
         cv = Cov(Sigma_ptr or None, kp_Sigma_ptr or None, kp_var_ptr or None, u_var_ptr or None, lim_z_ptr or None)
         self.ctx.crosscheck_from_env()
         self.ctx.check(self.L.ilqr_problem_closed_loop_cov_dev(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)), C.byref(cv)))
+
+    def closed_loop_cov_con(self, sigma_w=None, sigma_x0=None, want_Sigma: bool = False, want_kp_Sigma: bool = False, want_kp_var: bool = False,
+                            want_u_var: bool = False, want_lim_z: bool = False, want_con_var: bool = True, want_con_z: bool = True):
+        """closed_loop_cov with the rows of set_constraints read off the same recursion (ilqr_problem_closed_loop_cov_con; definitions in
+        include/ilqr_hip.h): con_var [B][T-1][m], the first-order variance of every row at every control step, and con_z [B], how many standard
+        deviations the plan keeps from its constraints.  Returns a ClosedLoopCovCon; what was not asked for is None."""
+        nx = self.dims.n_x
+        Sigma, kp_Sigma = _out(want_Sigma, self.B, self.T, nx, nx), _out(want_kp_Sigma, self.B, self.n_kp, nx, nx)
+        kp_var, u_var = _out(want_kp_var, self.B, self.n_kp, KP_ERR), _out(want_u_var, self.B, self.T - 1, self.dims.n_u)
+        lim_z = _out(want_lim_z, self.B)
+        con_var, con_z = _out(want_con_var, self.B, self.T - 1, max(self.m, 0)), _out(want_con_z, self.B)
+        cv = Cov(*(a.ctypes.data if a is not None else None for a in (Sigma, kp_Sigma, kp_var, u_var, lim_z)))
+        co = CovCon(*(a.ctypes.data if a is not None else None for a in (con_var, con_z)))
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_cov_con(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)), C.byref(cv), C.byref(co)))
+        return ClosedLoopCovCon(Sigma, kp_Sigma, kp_var, u_var, lim_z, con_var, con_z)
+
+    def closed_loop_cov_con_dev(self, sigma_w=None, sigma_x0=None, Sigma_ptr=None, kp_Sigma_ptr=None, kp_var_ptr=None, u_var_ptr=None, lim_z_ptr=None,
+                                con_var_ptr=None, con_z_ptr=None):
+        """Device pointers (0 / None where the output is not asked for), asynchronous on the context's stream; the sigmas are host values."""
+        cv = Cov(Sigma_ptr or None, kp_Sigma_ptr or None, kp_var_ptr or None, u_var_ptr or None, lim_z_ptr or None)
+        co = CovCon(con_var_ptr or None, con_z_ptr or None)
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_cov_con_dev(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)), C.byref(cv), C.byref(co)))
 
     def close(self):
         if self.h:

@@ -1515,6 +1515,28 @@ static void closed_loop_report_of(ilqr_problem* p, sys::System& s, int B, const 
                                           &tol, nullptr, nullptr, &rp));
 }
 
+// the tolerances of a ClosedLoopInputs as the C struct (kp_tol already checked by closed_loop_report_of)
+static ilqr_cl_tol closed_loop_tol(const ClosedLoopInputs& cl, size_t nk) {
+    ilqr_cl_tol tol{};
+    const size_t nt = cl.kp_tol.size();
+    for (size_t k = 0; k < ILQR_MAX_KP; k++)
+        for (size_t g = 0; g < ILQR_KP_ERR; g++)
+            tol.kp_tol[k][g] = (k >= nk || nt == 0) ? -1.0 : (nt == 1 ? cl.kp_tol[0] : (nt == ILQR_KP_ERR ? cl.kp_tol[g] : cl.kp_tol[k * ILQR_KP_ERR + g]));
+    tol.lim_tol = cl.lim_tol;
+    return tol;
+}
+
+// ilqr_problem_closed_loop_report_con for the same executions, a rollout of its own for the reason above; `out` is not asked for
+static void closed_loop_con_of(ilqr_problem* p, sys::System& s, int B, const ClosedLoopInputs& cl, const ilqr_noise* nz, ClosedLoopResult& o) {
+    const size_t n = (size_t)B * cl.S;
+    o.con_max.resize(n); o.con_steps.resize(n); o.con_stats.resize((size_t)B * ILQR_CL_CON_STATS);
+    if (cl.has_tol) o.outcome_con.resize((size_t)B * ILQR_CL_OUTCOME_CON);
+    const ilqr_cl_tol tol = closed_loop_tol(cl, s.deviceKeypoints().size());
+    ilqr_cl_con co{o.con_max.data(), o.con_steps.data(), o.con_stats.data(), cl.has_tol ? o.outcome_con.data() : nullptr};
+    check(ilqr_problem_closed_loop_report_con(p, cl.S, nz, cl.x0.empty() ? nullptr : cl.x0.data(), cl.w.empty() ? nullptr : cl.w.data(),
+                                              cl.with_feedforward ? 1 : 0, cl.has_tol ? &tol : nullptr, nullptr, nullptr, nullptr, cl.con_tol, &co));
+}
+
 // ilqr_problem_closed_loop on the problem a batched solve has just finished with
 static void closed_loop_of(ilqr_problem* p, sys::System& s, int B, const ClosedLoopInputs& cl, ClosedLoopResult& o) {
     o.B = B; o.S = cl.S; o.T = s.getHorizon(); o.n_x = s.getNbStateVar(); o.n_u = s.getNbCtrlVar();
@@ -1554,6 +1576,7 @@ static void closed_loop_of(ilqr_problem* p, sys::System& s, int B, const ClosedL
         }
     }
     if (cl.has_tol) closed_loop_report_of(p, s, B, cl, cl.has_seed ? &nz : nullptr, o);
+    if (cl.has_con_tol) closed_loop_con_of(p, s, B, cl, cl.has_seed ? &nz : nullptr, o);
 }
 
 void closed_loop_cov_sigma_error() { throw std::runtime_error("[closed_loop_batch] sigma_w and sigma_x0 must be a scalar or have nb_state_var entries"); }
@@ -1573,6 +1596,11 @@ static void closed_loop_cov_of(ilqr_problem* p, sys::System& s, int B, const Clo
     o.u_var.resize((size_t)B * (o.T - 1) * o.n_u); o.lim_z.resize((size_t)B);
     ilqr_cl_cov out{cv.want_Sigma ? o.Sigma.data() : nullptr, o.kp_Sigma.data(), o.kp_var.data(), o.u_var.data(), o.lim_z.data()};
     check(ilqr_problem_closed_loop_cov(p, sg[0].empty() ? nullptr : sg[0].data(), sg[1].empty() ? nullptr : sg[1].data(), &out));
+    if (cv.want_con) {  // a call of its own: what the call above returned stays exactly what it was
+        o.con_var.resize((size_t)B * (o.T - 1) * o.m); o.con_z.resize((size_t)B);
+        ilqr_cl_cov_con co{o.con_var.data(), o.con_z.data()};
+        check(ilqr_problem_closed_loop_cov_con(p, sg[0].empty() ? nullptr : sg[0].data(), sg[1].empty() ? nullptr : sg[1].data(), nullptr, &co));
+    }
 }
 
 std::pair<BatchResult, ClosedLoopCovResult> ILQRRecursive::closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool line_search,
@@ -1631,7 +1659,10 @@ std::pair<BatchResult, ClosedLoopResult> AL_ILQR::closedLoopBatch(const BatchInp
 std::pair<BatchResult, ClosedLoopCovResult> AL_ILQR::closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, int lag, double penalty,
                                                                         double scaling, bool line_search, bool early_stop) {
     ClosedLoopCovResult o;
-    BatchResult r = solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, [&](ilqr_problem* p) { closed_loop_cov_of(p, *s, in.B, cv, o); });
+    BatchResult r = solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, [&](ilqr_problem* p) {
+        o.m = lowered_m;
+        closed_loop_cov_of(p, *s, in.B, cv, o);
+    });
     return {std::move(r), std::move(o)};
 }
 
@@ -1656,6 +1687,7 @@ BatchResult AL_ILQR::solveBatchThen(const BatchInputs& in, int nb_iter, int lag,
     }
     const int m = (int)keep.size();
     if (m == 0) throw std::runtime_error("[AL_ILQR] all constraint rows are zero");
+    lowered_m = m;
     bool per_step = false;
     for (int k = 1; k < T - 1 && !per_step; k++)
         for (int r_ : keep) {

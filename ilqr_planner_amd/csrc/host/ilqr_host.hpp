@@ -490,6 +490,9 @@ struct ClosedLoopInputs {
     std::vector<double> kp_tol;   // one value (every keypoint and group), ILQR_KP_ERR values (every keypoint) or n_kp x ILQR_KP_ERR; negative: not
                                   // judged; empty: nothing is judged
     double lim_tol = 0;
+    // con_tol given (AL_ILQR): the executions are also judged against the constraint rows the class lowers (ilqr_problem_closed_loop_report_con)
+    bool has_con_tol = false;
+    double con_tol = 0;
 };
 struct ClosedLoopResult {
     int B = 0, S = 0, T = 0, n_x = 0, n_u = 0;
@@ -498,12 +501,15 @@ struct ClosedLoopResult {
     // with tolerances (ClosedLoopInputs::has_tol), else empty: [B][S][n_kp][5], [B][n_kp][12], [B][S], [B][4]
     int n_kp = 0;
     std::vector<double> kp_err, kp_stats, lim_cost, outcome;
+    // with con_tol (ClosedLoopInputs::has_con_tol), else empty: [B][S], [B][S], [B][6]; outcome_con [B][5] with tolerances as well
+    std::vector<double> con_max, con_steps, con_stats, outcome_con;
 };
 
 // The covariance of that closed loop under the noise model of ClosedLoopInputs::seed, propagated analytically (ilqr_problem_closed_loop_cov)
 struct ClosedLoopCovInputs {
     std::vector<double> sigma_w, sigma_x0;   // one value (every entry) or n_x values; empty: 0
     bool want_Sigma = false;                 // the covariance at every step (B T n_x^2 doubles)
+    bool want_con = false;                   // AL_ILQR: the variance of the constraint rows the class lowers (ilqr_problem_closed_loop_cov_con)
 };
 // the one place of closed_loop_cov_batch's rule for a sigma (a scalar or nb_state_var entries) and of its error text, which is closed_loop_batch's
 [[noreturn]] void closed_loop_cov_sigma_error();
@@ -511,6 +517,8 @@ struct ClosedLoopCovResult {
     int B = 0, T = 0, n_x = 0, n_u = 0, n_kp = 0;
     std::vector<double> Sigma;                           // [B][T][n_x][n_x], empty unless asked for
     std::vector<double> kp_Sigma, kp_var, u_var, lim_z;  // [B][n_kp][n_x][n_x], [B][n_kp][5], [B][T-1][n_u], [B]
+    int m = 0;                                           // the rows the class lowered
+    std::vector<double> con_var, con_z;                  // [B][T-1][m], [B]; empty unless want_con
 };
 
 struct Constraint {  // AL-ILQR.h:20-23
@@ -566,6 +574,7 @@ private:
     std::shared_ptr<sys::System> s;
     std::vector<Constraint> inequality;
     std::vector<Vec> multipliers;  // persists across solve() calls like the reference's member
+    int lowered_m = 0;             // rows of the last solveBatchThen on the device (the all-zero ones are dropped)
 };
 
 class BatchILQR {  // BatchILQR.h:21-53: the batch solver on the full control sequence (= BatchILQRCP with the identity basis)

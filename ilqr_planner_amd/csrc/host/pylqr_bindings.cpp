@@ -104,9 +104,13 @@ static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& 
 static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const py::object& w, const py::object& samples, bool with_ff,
                                                    const py::object& seed = py::none(), const py::object& sigma_w = py::none(),
                                                    const py::object& sigma_x0 = py::none(), const py::object& kp_tol = py::none(),
-                                                   const py::object& lim_tol = py::none()) {
+                                                   const py::object& lim_tol = py::none(), const py::object& con_tol = py::none()) {
     solver::ClosedLoopInputs cl;
     cl.with_feedforward = with_ff;
+    if (!con_tol.is_none()) {
+        cl.has_con_tol = true;
+        cl.con_tol = con_tol.cast<double>();
+    }
     if (!kp_tol.is_none() || !lim_tol.is_none()) {  // either one asks for the report
         cl.has_tol = true;
         if (!kp_tol.is_none()) {
@@ -145,9 +149,10 @@ static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const p
 }
 
 // numpy -> ClosedLoopCovInputs: a sigma is None, a scalar or nb_state_var entries
-static solver::ClosedLoopCovInputs closed_loop_cov_inputs(const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
+static solver::ClosedLoopCovInputs closed_loop_cov_inputs(const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool want_con = false) {
     solver::ClosedLoopCovInputs cv;
     cv.want_Sigma = want_Sigma;
+    cv.want_con = want_con;
     for (int which = 0; which < 2; which++) {
         const py::object& sg = which ? sigma_x0 : sigma_w;
         if (sg.is_none()) continue;
@@ -348,14 +353,28 @@ PYBIND11_MODULE(PyLQR, m) {
         .def_property_readonly("lim_cost", [](const solver::ClosedLoopResult& r) -> py::object {
             return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.lim_cost, {r.B, r.S})); })
         .def_property_readonly("outcome", [](const solver::ClosedLoopResult& r) -> py::object {
-            return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.outcome, {r.B, ILQR_CL_OUTCOME})); });
+            return r.outcome.empty() ? py::object(py::none()) : py::object(shaped(r.outcome, {r.B, ILQR_CL_OUTCOME})); })
+        // filled when AL_ILQR.closed_loop_batch is given con_tol, else None; outcome_con needs kp_tol or lim_tol as well
+        .def_property_readonly("con_max", [](const solver::ClosedLoopResult& r) -> py::object {
+            return r.con_stats.empty() ? py::object(py::none()) : py::object(shaped(r.con_max, {r.B, r.S})); })
+        .def_property_readonly("con_steps", [](const solver::ClosedLoopResult& r) -> py::object {
+            return r.con_stats.empty() ? py::object(py::none()) : py::object(shaped(r.con_steps, {r.B, r.S})); })
+        .def_property_readonly("con_stats", [](const solver::ClosedLoopResult& r) -> py::object {
+            return r.con_stats.empty() ? py::object(py::none()) : py::object(shaped(r.con_stats, {r.B, ILQR_CL_CON_STATS})); })
+        .def_property_readonly("outcome_con", [](const solver::ClosedLoopResult& r) -> py::object {
+            return r.outcome_con.empty() ? py::object(py::none()) : py::object(shaped(r.outcome_con, {r.B, ILQR_CL_OUTCOME_CON})); });
     py::class_<solver::ClosedLoopCovResult>(m_sol, "ClosedLoopCovResult")
         .def_property_readonly("Sigma", [](const solver::ClosedLoopCovResult& r) -> py::object {   // None unless want_Sigma
             return r.Sigma.empty() ? py::object(py::none()) : py::object(shaped(r.Sigma, {r.B, r.T, r.n_x, r.n_x})); })
         .def_property_readonly("kp_Sigma", [](const solver::ClosedLoopCovResult& r) { return shaped(r.kp_Sigma, {r.B, r.n_kp, r.n_x, r.n_x}); })
         .def_property_readonly("kp_var", [](const solver::ClosedLoopCovResult& r) { return shaped(r.kp_var, {r.B, r.n_kp, ILQR_CL_COV_KP}); })
         .def_property_readonly("u_var", [](const solver::ClosedLoopCovResult& r) { return shaped(r.u_var, {r.B, r.T - 1, r.n_u}); })
-        .def_property_readonly("lim_z", [](const solver::ClosedLoopCovResult& r) { return shaped(r.lim_z, {r.B}); });
+        .def_property_readonly("lim_z", [](const solver::ClosedLoopCovResult& r) { return shaped(r.lim_z, {r.B}); })
+        // filled when AL_ILQR.closed_loop_cov_batch is given want_con, else None
+        .def_property_readonly("con_var", [](const solver::ClosedLoopCovResult& r) -> py::object {
+            return r.con_z.empty() ? py::object(py::none()) : py::object(shaped(r.con_var, {r.B, r.T - 1, r.m})); })
+        .def_property_readonly("con_z", [](const solver::ClosedLoopCovResult& r) -> py::object {
+            return r.con_z.empty() ? py::object(py::none()) : py::object(shaped(r.con_z, {r.B})); });
     py::class_<solver::Constraint>(m_sol, "Constraint").def(py::init<>()).def_readwrite("A", &solver::Constraint::A).def_readwrite("b", &solver::Constraint::b);
     py::class_<solver::ILQRRecursive>(m_sol, "ILQRRecursive")
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
@@ -396,22 +415,24 @@ PYBIND11_MODULE(PyLQR, m) {
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
                 const py::object& kp, const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed,
-                const py::object& sigma_w, const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol, bool pg) {
-                 return self.closedLoopBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol), nb_iter,
-                                             lag, pen, sc, ls, es);
+                const py::object& sigma_w, const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol, bool pg, const py::object& con_tol) {
+                 return self.closedLoopBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg),
+                                             closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol, con_tol), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(),
              py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none(), py::arg("seed") = py::none(),
-             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none(), py::arg("plan_gains") = false)
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none(), py::arg("plan_gains") = false,
+             py::arg("con_tol") = py::none())
         .def("closed_loop_cov_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
-                const py::object& kp, const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg) {
-                 return self.closedLoopCovBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, lag, pen, sc, ls, es);
+                const py::object& kp, const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg, bool want_con) {
+                 return self.closedLoopCovBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma, want_con), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
-             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("plan_gains") = false);
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("plan_gains") = false,
+             py::arg("want_con") = false);
     // bindings.cpp:778-782
     py::class_<solver::BatchILQR>(m_sol, "BatchILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("Q"))

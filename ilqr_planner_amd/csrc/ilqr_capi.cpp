@@ -66,6 +66,7 @@ struct ilqr_problem {
     DevScratch cl_cost;  // closed_loop_noise without a cost array: the per-sample costs k_closed_loop_stats reduces
     DevScratch cl_kpx;   // closed_loop: state | control of every sample at the step-table entries (k_closed_loop_coop -> k_closed_loop_kp)
     DevScratch cl_rep;   // closed_loop_report through device pointers: kp_err | lim_cost where the caller asks only for their reductions
+    DevScratch cl_con_ws;   // closed_loop_report_con through device pointers: con_max | con_steps where the caller asks only for their reductions
     DevScratch cl_cov_ws;   // closed_loop_cov: the per-lane matrices of the generic kernel k_cl_cov
     DevScratch cl_cov_kps;  // closed_loop_cov through device pointers: kp_Sigma where the caller asks only for kp_var
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
@@ -463,7 +464,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
     for (void* q : p->allocs) (void)hipFree(q);
-    for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_cost, &p->cl_cov_ws, &p->cl_cov_kps}) b->release();
+    for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_con_ws, &p->cl_cost, &p->cl_cov_ws, &p->cl_cov_kps}) b->release();
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
     delete p;
@@ -1038,6 +1039,13 @@ struct ClRequest {
     bool report = false;
     const ilqr_cl_tol* tol = nullptr;
     const ilqr_cl_report* out = nullptr;
+    // ilqr_problem_closed_loop_report_con: a report (out may be null) with the constraint rows judged in the rollout (ClArgs::con_max,
+    // con_steps), then the two reductions
+    bool con = false;
+    double con_tol = 0;
+    const ilqr_cl_con* co = nullptr;
+    ilqr_cl_report rep() const { return (report && out) ? *out : ilqr_cl_report{}; }
+    ilqr_cl_con cons() const { return (con && co) ? *co : ilqr_cl_con{}; }
 };
 
 // Every refusal, before anything is allocated or launched; the caller sees the first condition that fails.
@@ -1060,10 +1068,11 @@ static int cl_check(const ilqr_problem* p, const ClRequest& rq) {
     } else if (!rq.report && !rq.cost) return fail(c, "cost is a null pointer");
     if (rq.report) {
         const ilqr_cl_tol* tol = rq.tol;
-        const ilqr_cl_report* out = rq.out;
+        const ilqr_cl_report rpv = rq.rep();
+        const ilqr_cl_report* out = &rpv;
+        const bool no_out = !out->kp_err && !out->kp_stats && !out->lim_cost && !out->outcome;
         if (rq.noisy && rq.w) return fail(c, "closed loop report: noise and w are both given (the draw or the caller's disturbances, not both)");
-        if (!out || (!out->kp_err && !out->kp_stats && !out->lim_cost && !out->outcome))
-            return fail(c, "closed loop report: every report output is a null pointer");
+        if (!rq.con && no_out) return fail(c, "closed loop report: every report output is a null pointer");
         if (tol) {
             bool nan = std::isnan(tol->lim_tol);
             for (int k = 0; k < p->hdesc.steps.kp[p->hdesc.steps.n]; k++)
@@ -1072,6 +1081,14 @@ static int cl_check(const ilqr_problem* p, const ClRequest& rq) {
             if (tol->lim_tol < 0) return fail(c, "closed loop report: lim_tol must be >= 0");
         } else if (out->kp_stats || out->outcome)
             return fail(c, "closed loop report: tol is a null pointer while kp_stats or outcome is asked for");
+        if (rq.con) {
+            const ilqr_cl_con oc = rq.cons();
+            if (p->bufs.m <= 0) return fail(c, "closed loop report con: no constraints set");
+            if (std::isnan(rq.con_tol)) return fail(c, "closed loop report con: con_tol is NaN");
+            if (oc.outcome_con && !tol) return fail(c, "closed loop report con: tol is a null pointer while outcome_con is asked for");
+            if (no_out && !oc.con_max && !oc.con_steps && !oc.con_stats && !oc.outcome_con)
+                return fail(c, "closed loop report con: con and out both ask for nothing");
+        }
     }
     // the kernels address the caller's arrays with 32-bit element offsets
     const size_t n = (size_t)p->B * rq.S;
@@ -1090,7 +1107,7 @@ struct ClStaging {
     double* base;
     size_t used = 0;
     bool failed = false;  // a copy in has failed: the context holds the error
-    struct Back { double* host; const double* dev; size_t n; } back[9];  // at most cost, stats, w_out, X, U and the four report outputs
+    struct Back { double* host; const double* dev; size_t n; } back[13];  // at most cost, stats, w_out, X, U, the four report outputs and the four of the constraints
     int n_back = 0;
     int copy(void* dst, const void* src, size_t n, hipMemcpyKind kind) { HIPCHK(c, hipMemcpyAsync(dst, src, n * sizeof(double), kind, c->stream)); return 0; }
     double* take(size_t n) { used += n; return base ? base + (used - n) : nullptr; }
@@ -1116,6 +1133,7 @@ struct ClBound {  // what the kernels see
     ClArgs a;
     double* stats = nullptr;  // the device side of stats
     ilqr_cl_report dr = {};   // ... and of the four report outputs
+    ilqr_cl_con dc = {};      // ... and of the four outputs of the constraints
 };
 
 // Per array: the caller's device pointer, a slice of staging (host pointers), or a workspace of the problem (what the caller does not ask for
@@ -1124,10 +1142,15 @@ static int cl_bind(ilqr_problem* p, const ClRequest& rq, const ClosedLoopPlan& p
     ilqr_ctx* c = p->ctx;
     const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u;
     const size_t n = (size_t)p->B * rq.S;
-    const ilqr_cl_report rp = rq.report ? *rq.out : ilqr_cl_report{};
+    const ilqr_cl_report rp = rq.rep();
+    const ilqr_cl_con oc = rq.cons();
     const int n_kp = p->hdesc.steps.kp[p->hdesc.steps.n];
-    const bool want_ke = rp.kp_err || rp.kp_stats || rp.outcome, want_lc = rp.lim_cost || rp.outcome;  // kp_err feeds both reductions, lim_cost the outcome
+    // kp_err feeds both reductions, lim_cost the outcome; outcome_con reads what outcome reads
+    const bool want_ke = rp.kp_err || rp.kp_stats || rp.outcome || oc.outcome_con, want_lc = rp.lim_cost || rp.outcome || oc.outcome_con;
     const size_t n_ke = want_ke ? n * n_kp * ILQR_KP_ERR : 0, n_lc = want_lc ? n : 0;
+    // con_max switches the kernels' constraint code on, so it exists for any of the four; con_steps feeds con_stats
+    const bool want_cm = oc.con_max || oc.con_steps || oc.con_stats || oc.outcome_con, want_cs = oc.con_steps || oc.con_stats;
+    const size_t n_cm = want_cm ? n : 0, n_cs = want_cs ? n : 0;
     if (pl.coop || rq.report)  // the report reads the states of the step-table entries from either kernel
         if (p->cl_kpx.reserve(c, (size_t)(p->hdesc.steps.n > 0 ? p->hdesc.steps.n : 1) * (p->dims.n_x + p->dims.n_u) * n)) return 1;
     ClArgs& a = b.a;
@@ -1138,6 +1161,7 @@ static int cl_bind(ilqr_problem* p, const ClRequest& rq, const ClosedLoopPlan& p
     }
     b.stats = rq.stats;
     b.dr = rp;
+    b.dc = oc;
     if (rq.dev) {
         if (!rq.cost) {  // the per-sample costs live in a workspace: stats and outcome read them there
             if (p->cl_cost.reserve(c, n)) return 1;
@@ -1148,6 +1172,12 @@ static int cl_bind(ilqr_problem* p, const ClRequest& rq, const ClosedLoopPlan& p
             if (p->cl_rep.reserve(c, ws_ke + ws_lc)) return 1;
             if (!rp.kp_err) b.dr.kp_err = p->cl_rep.ptr;
             if (!rp.lim_cost) b.dr.lim_cost = p->cl_rep.ptr + ws_ke;
+        }
+        if (rq.con) {  // con_max | con_steps likewise
+            const size_t ws_cm = oc.con_max ? 0 : n_cm, ws_cs = oc.con_steps ? 0 : n_cs;
+            if (p->cl_con_ws.reserve(c, ws_cm + ws_cs)) return 1;
+            if (!oc.con_max) b.dc.con_max = p->cl_con_ws.ptr;
+            if (!oc.con_steps) b.dc.con_steps = p->cl_con_ws.ptr + ws_cm;
         }
     } else {
         if (rq.x0) a.x0 = stg.take_in(rq.x0, n * nxu);
@@ -1163,9 +1193,16 @@ static int cl_bind(ilqr_problem* p, const ClRequest& rq, const ClosedLoopPlan& p
             b.dr.kp_stats = stg.take_out(rp.kp_stats, rp.kp_stats ? (size_t)p->B * n_kp * ILQR_KP_STATS : 0);
             b.dr.outcome = stg.take_out(rp.outcome, rp.outcome ? (size_t)p->B * ILQR_CL_OUTCOME : 0);
         }
+        if (rq.con) {
+            b.dc.con_max = stg.take_out(oc.con_max, n_cm);
+            b.dc.con_steps = stg.take_out(oc.con_steps, n_cs);
+            b.dc.con_stats = stg.take_out(oc.con_stats, oc.con_stats ? (size_t)p->B * ILQR_CL_CON_STATS : 0);
+            b.dc.outcome_con = stg.take_out(oc.outcome_con, oc.outcome_con ? (size_t)p->B * ILQR_CL_OUTCOME_CON : 0);
+        }
         if (stg.failed) return 1;
     }
     if (rq.report) { a.kpx = pl.coop ? nullptr : p->cl_kpx.ptr; a.lim_cost = want_lc ? b.dr.lim_cost : nullptr; }
+    if (rq.con) { a.con_tol = rq.con_tol; a.con_max = want_cm ? b.dc.con_max : nullptr; a.con_steps = want_cs ? b.dc.con_steps : nullptr; }
     return 0;
 }
 
@@ -1176,10 +1213,14 @@ static void cl_launch(ilqr_problem* p, const ClRequest& rq, const ClosedLoopPlan
     else launch_closed_loop(kind, nd, p->bufs, b.a, B, p->mapped ? &p->map : nullptr, st);
     if (rq.stats) launch_closed_loop_stats(b.a.cost, B, S, b.stats, st);
     if (!rq.report) return;
-    const ilqr_cl_report& rp = *rq.out;
-    if (rp.kp_err || rp.kp_stats || rp.outcome) launch_closed_loop_kp_err(kind, nd, p->bufs, B, S, n_kp, p->cl_kpx.ptr, b.dr.kp_err, st);
+    const ilqr_cl_report rp = rq.rep();
+    const ilqr_cl_con oc = rq.cons();
+    if (rp.kp_err || rp.kp_stats || rp.outcome || oc.outcome_con) launch_closed_loop_kp_err(kind, nd, p->bufs, B, S, n_kp, p->cl_kpx.ptr, b.dr.kp_err, st);
     if (rp.kp_stats) launch_closed_loop_kp_stats(b.dr.kp_err, *rq.tol, B, S, n_kp, b.dr.kp_stats, st);
     if (rp.outcome) launch_closed_loop_outcome(b.a.cost, b.dr.kp_err, b.dr.lim_cost, *rq.tol, B, S, n_kp, b.dr.outcome, st);
+    if (oc.con_stats) launch_closed_loop_con_stats(b.dc.con_max, b.dc.con_steps, rq.con_tol, B, S, b.dc.con_stats, st);
+    if (oc.outcome_con)
+        launch_closed_loop_outcome_con(b.a.cost, b.dr.kp_err, b.dr.lim_cost, b.dc.con_max, *rq.tol, rq.con_tol, B, S, n_kp, b.dc.outcome_con, st);
 }
 
 static int closed_loop(ilqr_problem* p, const ClRequest& rq) {
@@ -1232,22 +1273,45 @@ extern "C" int ilqr_problem_closed_loop_report_dev(ilqr_problem* p, int n_sample
                            .noise = noise, .stats = stats, .report = true, .tol = tol, .out = out});
 }
 
+extern "C" int ilqr_problem_closed_loop_report_con(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
+                                                   int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats,
+                                                   const ilqr_cl_report* out, double con_tol, const ilqr_cl_con* con) {
+    return closed_loop(p, {.S = n_samples, .x0 = x0, .w = w, .with_ff = with_feedforward, .cost = cost, .noisy = noise != nullptr, .noise = noise,
+                           .stats = stats, .report = true, .tol = tol, .out = out, .con = true, .con_tol = con_tol, .co = con});
+}
+extern "C" int ilqr_problem_closed_loop_report_con_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
+                                                       int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats,
+                                                       const ilqr_cl_report* out, double con_tol, const ilqr_cl_con* con) {
+    return closed_loop(p, {.S = n_samples, .x0 = x0, .w = w, .with_ff = with_feedforward, .cost = cost, .dev = true, .noisy = noise != nullptr,
+                           .noise = noise, .stats = stats, .report = true, .tol = tol, .out = out, .con = true, .con_tol = con_tol, .co = con});
+}
+
 // The covariance of that closed loop, propagated analytically (ilqr_closed_loop_cov.hpp).  Which kernel runs is decided by plan_closed_loop_cov.
 // kp_var is formed from kp_Sigma by a kernel of its own, so kp_Sigma always exists where kp_var is asked for: the caller's array, a slice of
 // staging, or the problem's workspace.
-static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out, bool dev) {
+// with_con: ilqr_problem_closed_loop_cov_con -- `out_` may be null, and the kernels also read the constraint rows off Sigma_k (con).
+static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out_, bool dev, bool with_con = false,
+                           const ilqr_cl_cov_con* con = nullptr) {
     if (!p) return 1;
+    const ilqr_cl_cov none = {};
+    const ilqr_cl_cov* out = (with_con && !out_) ? &none : out_;
+    const ilqr_cl_cov_con oc = (with_con && con) ? *con : ilqr_cl_cov_con{};
     ilqr_ctx* c = p->ctx;
     const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u, B = p->B, n_kp = p->hdesc.steps.kp[p->hdesc.steps.n];
     for (int i = 0; i < nxu; i++)
         for (const double* sg : {sigma_w, sigma_x0})
             if (sg && (!(sg[i] >= 0) || !std::isfinite(sg[i]))) return fail(c, "closed loop: every sigma_w and sigma_x0 must be finite and >= 0");
-    if (!out || (!out->Sigma && !out->kp_Sigma && !out->kp_var && !out->u_var && !out->lim_z))
-        return fail(c, "closed loop cov: every output is a null pointer");
+    const bool no_out = !out || (!out->Sigma && !out->kp_Sigma && !out->kp_var && !out->u_var && !out->lim_z);
+    if (!with_con && no_out) return fail(c, "closed loop cov: every output is a null pointer");
     const size_t nn = (size_t)nxu * nxu, n_S = (size_t)B * T * nn, n_kS = (size_t)B * n_kp * nn;
     if (const char* why = cl_cov_size_refusal(B, T, n_kp, nxu, out->Sigma != nullptr, out->kp_Sigma != nullptr)) return fail(c, why);
     if (!p->has_gains)   // (behind the bounds on the call itself: those do not depend on the state of the problem)
         return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) or of ilqr_problem_gains since the problem's inputs last changed");
+    if (with_con) {
+        if (p->bufs.m <= 0) return fail(c, "closed loop cov con: no constraints set");
+        if (no_out && !oc.con_var && !oc.con_z) return fail(c, "closed loop cov con: con and out both ask for nothing");
+    }
+    const size_t n_cv = (size_t)B * (T - 1) * (with_con ? p->bufs.m : 0);
     HIPCHK(c, hipSetDevice(c->device));
     const ClosedLoopCovPlan pl = plan_closed_loop_cov(p->desc.kind, p->desc.nb_deriv, B, c->n_simd, c->xc_generic || p->mapped);
     if (pl.rows && !launch_closed_loop_cov_rows) return fail(c, "closed loop cov: the row kernel is not part of this build (pin the generic kernels)");
@@ -1263,12 +1327,15 @@ static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double*
     const size_t n_kv = (size_t)B * n_kp * ILQR_CL_COV_KP, n_uv = (size_t)B * (T - 1) * nuu;
     double* kp_var = out->kp_var;
     a.Sigma = out->Sigma; a.kp_Sigma = out->kp_Sigma; a.u_var = out->u_var; a.lim_z = out->lim_z;
+    a.con_var = oc.con_var; a.con_z = oc.con_z;
     auto bind = [&](ClStaging& stg) {  // the staging slices of a host-pointer call (ClStaging: first the sizing walk, then the real one)
         if (out->Sigma) a.Sigma = stg.take_out(out->Sigma, n_S);
         a.kp_Sigma = want_kS ? stg.take_out(out->kp_Sigma, n_kS) : nullptr;
         if (out->kp_var) kp_var = stg.take_out(out->kp_var, n_kv);
         if (out->u_var) a.u_var = stg.take_out(out->u_var, n_uv);
         if (out->lim_z) a.lim_z = stg.take_out(out->lim_z, (size_t)B);
+        if (oc.con_var) a.con_var = stg.take_out(oc.con_var, n_cv);
+        if (oc.con_z) a.con_z = stg.take_out(oc.con_z, (size_t)B);
     };
     if (!dev) {
         ClStaging size{c, nullptr};
@@ -1297,6 +1364,15 @@ extern "C" int ilqr_problem_closed_loop_cov(ilqr_problem* p, const double* sigma
 }
 extern "C" int ilqr_problem_closed_loop_cov_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out) {
     return closed_loop_cov(p, sigma_w, sigma_x0, out, true);
+}
+
+extern "C" int ilqr_problem_closed_loop_cov_con(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
+                                                const ilqr_cl_cov_con* con) {
+    return closed_loop_cov(p, sigma_w, sigma_x0, out, false, true, con);
+}
+extern "C" int ilqr_problem_closed_loop_cov_con_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
+                                                    const ilqr_cl_cov_con* con) {
+    return closed_loop_cov(p, sigma_w, sigma_x0, out, true, true, con);
 }
 
 extern "C" int ilqr_problem_get_K(ilqr_problem* p, double* K) { return get_gains(p, K, nullptr); }

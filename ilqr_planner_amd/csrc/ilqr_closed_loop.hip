@@ -16,13 +16,17 @@
 // for bit (a lane per entry would need a second pass for the ordered sum).
 // Both kernels take every case of the descriptor (second limit set, shared steps, dead zones, object frames, joint keypoints): they call the
 // functions of ilqr_closed_loop.hpp.  Layouts of 7-joint problems only; narrower chains take the generic kernel's mapped variant.
+#include <type_traits>
+
 #include "ilqr_closed_loop.hpp"
 
 namespace ilqr {
 
 #define NOUNR _Pragma("unroll 1")
 
-template <class S, bool SYM, int NS, bool FF>
+// CON: judge the constraint rows (ilqr_problem_closed_loop_report_con; c.con_max is given).  A template argument like FF: as a run-time branch
+// on c.con_max it cost the calls that do not ask 0.4 to 2.8 %.
+template <class S, bool SYM, int NS, bool FF, bool CON>
 __global__ __launch_bounds__(64) void k_closed_loop_coop(Bufs a, ClArgs c, int depth, double* __restrict__ kpx) {
     constexpr int NX = S::NX, NU = S::NU, NI = 64 / NS;
     constexpr int RS = SYM ? KD_SYM_RS : NU * kd_rowp(NX);   // doubles of a gain record in memory
@@ -55,6 +59,7 @@ __global__ __launch_bounds__(64) void k_closed_loop_coop(Bufs a, ClArgs c, int d
         UNR for (int i = 0; i < NX; i++) if ((on >> i) & 1u) x[i] += nz[i];
     }
     double lim = 0;
+    ClCon con;
     int st = 0;
     NOUNR for (int k0 = 0; k0 < T - 1; k0 += depth) {
         const int nk = (T - 1 - k0 < depth) ? T - 1 - k0 : depth;
@@ -83,6 +88,7 @@ __global__ __launch_bounds__(64) void k_closed_loop_coop(Bufs a, ClArgs c, int d
             if (c.X && valid) { UNR for (int i = 0; i < NX; i++) c.X[(g * T + k) * NX + i] = x[i]; }
             cl_control<S>(r, SYM, FF, r + RS, r + RS + NX, 1, sc, x, u);
             if (c.U && valid) { UNR for (int i = 0; i < NU; i++) c.U[(g * (T - 1) + k) * NU + i] = u[i]; }
+            if constexpr (CON) cl_con<S>(a, c.con_tol, k, x, u, con);
             lim += cl_limits<S>(d, x);
             if (st < d.steps.n && d.steps.t[st] == k) {  // uniform: state | control of the step-table entry for k_closed_loop_kp
                 if (valid) {
@@ -107,6 +113,7 @@ __global__ __launch_bounds__(64) void k_closed_loop_coop(Bufs a, ClArgs c, int d
         UNR for (int i = 0; i < NU; i++) o[(size_t)(NX + i) * BS] = 0.0;
     }
     if (c.lim_cost) c.lim_cost[g] = lim;  // uniform: only the report asks
+    if constexpr (CON) cl_con_store(c, g, con);
     c.cost[g] = lim;
 }
 
@@ -133,8 +140,11 @@ __global__ __launch_bounds__(64) void k_closed_loop_kp(Bufs a, int n_samples, co
 template <class S, bool SYM, int NS>
 static void launch_ns(const Bufs& a, const ClArgs& c, int B, const ClosedLoopPlan& pl, double* kpx, hipStream_t st) {
     const dim3 grid((B + 64 / NS - 1) / (64 / NS), (c.S + NS - 1) / NS), block(64);
-    if (c.with_ff) hipLaunchKernelGGL((k_closed_loop_coop<S, SYM, NS, true>), grid, block, pl.lds_bytes, st, a, c, pl.depth, kpx);
-    else hipLaunchKernelGGL((k_closed_loop_coop<S, SYM, NS, false>), grid, block, pl.lds_bytes, st, a, c, pl.depth, kpx);
+    auto go = [&](auto ff, auto con) {
+        hipLaunchKernelGGL((k_closed_loop_coop<S, SYM, NS, decltype(ff)::value, decltype(con)::value>), grid, block, pl.lds_bytes, st, a, c, pl.depth, kpx);
+    };
+    if (c.with_ff) c.con_max ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+    else c.con_max ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
 }
 template <class S, bool SYM>
 static void launch_sys(const Bufs& a, const ClArgs& c, int B, const ClosedLoopPlan& pl, double* kpx, hipStream_t st) {

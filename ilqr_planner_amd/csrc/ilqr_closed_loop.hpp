@@ -32,6 +32,10 @@ struct ClArgs {
     double* kpx = nullptr;                  // generic kernel: the state at every step-table entry, in the cooperative kernel's layout
                                             // [steps.n][n_x + n_u][B * S] (the x rows only); the cooperative kernel has its own argument
     double* lim_cost = nullptr;             // [B][S]: the limit terms of the execution, summed over the steps
+    // ilqr_problem_closed_loop_report_con: con_max null in every other call, and the kernels then do not look at the constraint rows
+    double con_tol = 0;
+    double* con_max = nullptr;              // [B][S]: the maximum of g over the steps and rows, NaN if a g was not finite
+    double* con_steps = nullptr;            // [B][S] or null: the steps with a row above con_tol
 };
 
 // x_{k+1} += w_k: the caller's w, the draw (nz, on: noise_draw), or both; w_out gets what was added (0 where nothing was).  An entry without
@@ -74,6 +78,35 @@ ILQR_DEV double cl_limits(const DevDesc& d, const double* x) {
     return c;
 }
 
+// What an execution carries across its steps for ilqr_problem_closed_loop_report_con: the running maximum of g, the number of steps with a row
+// above con_tol, and whether a g was not finite.
+struct ClCon {
+    double hi = -INFINITY, steps = 0;
+    bool bad = false;
+};
+
+// The constraint rows of step k at the execution's (x_k, u_k), device layout: g[r] = A_k[r] [x; u] - b_k[r] in con_g's order (state columns
+// ascending, control columns ascending, then - b).  A rolled loop over the rows, each row unrolled; the addresses are wave-uniform.  One
+// function for both kernels, like the rest of the step.
+template <class S>
+ILQR_DEV void cl_con(const Bufs& a, double con_tol, int k, const double* x, const double* u, ClCon& cc) {
+    double hk = -INFINITY;
+    bool bad = false;
+    _Pragma("unroll 1") for (int r = 0; r < a.m; r++) {
+        const double g = con_g<S>(a, k, r, x, u);
+        bad = bad || !isfinite(g);
+        hk = (g > hk || g != g) ? g : hk;   // a NaN stays: the step then counts for nothing
+    }
+    cc.bad = cc.bad || bad;
+    cc.hi = hk > cc.hi ? hk : cc.hi;
+    if (hk > con_tol) cc.steps += 1.0;
+}
+// con_max and con_steps of pair g
+ILQR_DEV void cl_con_store(const ClArgs& c, int g, const ClCon& cc) {
+    c.con_max[g] = cc.bad ? NAN : cc.hi;
+    if (c.con_steps) c.con_steps[g] = cc.steps;
+}
+
 // acc + the task terms of step-table entry st: every keypoint on the step adds its own, in keypoint order (stage_cost)
 template <class S>
 ILQR_DEV double cl_kp_terms(const DevDesc& d, const Bufs& a, int b, int st, const double* x, const double* u, double acc) {
@@ -109,5 +142,12 @@ void launch_closed_loop_kp_stats(const double* kp_err, const ilqr_cl_tol& tol, i
 // k_closed_loop_outcome: outcome[B][ILQR_CL_OUTCOME] of cost, kp_err and lim_cost
 void launch_closed_loop_outcome(const double* cost, const double* kp_err, const double* lim_cost, const ilqr_cl_tol& tol, int B, int S, int n_kp,
                                 double* outcome, hipStream_t st);
+
+// ilqr_problem_closed_loop_report_con (ilqr_kernels.hip), after either rollout
+// k_closed_loop_con_stats: con_stats[B][ILQR_CL_CON_STATS] of con_max and con_steps
+void launch_closed_loop_con_stats(const double* con_max, const double* con_steps, double con_tol, int B, int S, double* con_stats, hipStream_t st);
+// k_closed_loop_outcome_con: outcome_con[B][ILQR_CL_OUTCOME_CON] of cost, kp_err, lim_cost and con_max
+void launch_closed_loop_outcome_con(const double* cost, const double* kp_err, const double* lim_cost, const double* con_max, const ilqr_cl_tol& tol,
+                                    double con_tol, int B, int S, int n_kp, double* outcome_con, hipStream_t st);
 
 }  // namespace ilqr

@@ -46,6 +46,15 @@ __device__ __forceinline__ double cv_row_min(double v) {
     return v;
 }
 
+// sum over the 16 lanes of the DPP row, result in all sixteen: cv_row_min's four moves
+__device__ __forceinline__ double cv_row_sum(double v) {
+    v += dppz_f64<0xB1>(v);
+    v += dppz_f64<0x4E>(v);
+    v += dppz_f64<0x141>(v);
+    v += dppz_f64<0x140>(v);
+    return v;
+}
+
 #define CV_ALL_ " row_mask:0xf bank_mask:0xf"
 // acc[c] += bcast_L(src[c]) * mul for N consecutive columns (N = 8 or 7): the row_newbcast FMA form of k_backward_rows (rw_fmac,
 // ilqr_kernels_rowsweep.hip) -- one statement, first the two wait states a DPP read needs after a VALU write of any of its operands; inside
@@ -69,7 +78,9 @@ __device__ __forceinline__ void cv_fmac(double* acc, const double* src, double m
 
 }  // namespace
 
-template <class S, bool SYM>
+// CON: the constraint rows are read off Sigma_k as well (ilqr_problem_closed_loop_cov_con).  A template argument: the vector c costs the kernel
+// 24 to 66 registers, which the plain covariance call does not pay.
+template <class S, bool SYM, bool CON>
 __global__ __launch_bounds__(64) void k_cl_cov_rows(Bufs a, ClCovArgs c) {
     constexpr int NX = S::NX, NU = S::NU, ND = S::ND, TM = S::TM, IPW = 4;
     constexpr int ROWP = kd_rowp(NX), RS = SYM ? KD_SYM_RS : NU * ROWP;
@@ -148,7 +159,7 @@ __global__ __launch_bounds__(64) void k_cl_cov_rows(Bufs a, ClCovArgs c) {
     UNR for (int j = 0; j < NX; j++) kr[j] = 0.0;
     UNR for (int cc = 0; cc < NX; cc++) Sg[cc] = (isX && cc == l) ? c.sx02[vx] : 0.0;
     if (T >= 2) load(0, kr, ub, vb);
-    double zmin = INFINITY;
+    double zmin = INFINITY, zcon = INFINITY;
     int st = 0;  // step table walk
     const int n_kp = d.steps.kp[d.steps.n];
     for (int k = 0; k < T; k++) {
@@ -183,6 +194,29 @@ __global__ __launch_bounds__(64) void k_cl_cov_rows(Bufs a, ClCovArgs c) {
         const double br = isQ ? b1 : (isV ? dt : 0.0);
         const double cr = TM ? cov_time_col<ND>(isQ, isV, isT, dts, ui, vb) : 0.0;
         const double dtq = (ND == 2 && isQ) ? dt : 0.0;
+        if constexpr (CON) {  // the constraint rows of the step
+            _Pragma("unroll 1") for (int r = 0; r < a.m; r++) {
+                const size_t row = (size_t)(a.per_step ? k : 0) * a.m + r;
+                const double* Ar = a.conA + row * (NX + NU);
+                // every lane forms c = a_x + K' a_u: K[i][j] from the lane of control i, as in the H block
+                double cv[NX];
+                UNR for (int j = 0; j < NX; j++) cv[j] = Ar[j];
+                cv_for<0, NU>([&](auto ic) {
+                    constexpr int I = decltype(ic)::value, L = (I < DOF) ? I : TL;
+                    const double au = Ar[NX + I];
+                    UNR for (int j = 0; j < NX; j++) cv[j] = fma(dppz_bcast<L>(K_[j]), au, cv[j]);
+                });
+                // lane l: c[l] (Sigma[l] . c); the idle lanes hold a zero row.  The plan's share of the row: a_x[l] xbar[l] + a_u[i] ubar[i]
+                double sc = 0, cl = 0;
+                UNR for (int j = 0; j < NX; j++) { sc = fma(Sg[j], cv[j], sc); cl = (j == l) ? cv[j] : cl; }
+                const double var = cv_row_sum(cl * sc);
+                double mu = isX ? Ar[vx] * xb : 0.0;
+                if (isC) mu = fma(Ar[NX + ci], ub, mu);
+                mu = cv_row_sum(mu);
+                if (c.con_var && ok && l == 0) c.con_var[((size_t)b * (T - 1) + k) * a.m + r] = var;
+                if (var > 0) zcon = fmin(zcon, (a.conb[row] - mu) / sqrt(var));
+            }
+        }
         double G[NX], M[NX], H[NU];
         UNR for (int cc = 0; cc < NX; cc++) G[cc] = 0;
         cv_for<0, NX>([&](auto jc) {
@@ -224,11 +258,13 @@ __global__ __launch_bounds__(64) void k_cl_cov_rows(Bufs a, ClCovArgs c) {
     }
     zmin = cv_row_min(zmin);
     if (c.lim_z && ok && l == 0) c.lim_z[b] = zmin;
+    if (CON && c.con_z && ok && l == 0) c.con_z[b] = zcon;   // every lane of the row holds the same zcon: the sums above are row sums
 }
 
 template <class S, bool SYM>
 static void launch_rows(const Bufs& a, const ClCovArgs& c, int B, hipStream_t st) {
-    hipLaunchKernelGGL((k_cl_cov_rows<S, SYM>), dim3((B + 3) / 4), dim3(64), 0, st, a, c);
+    if (c.con_var || c.con_z) hipLaunchKernelGGL((k_cl_cov_rows<S, SYM, true>), dim3((B + 3) / 4), dim3(64), 0, st, a, c);
+    else hipLaunchKernelGGL((k_cl_cov_rows<S, SYM, false>), dim3((B + 3) / 4), dim3(64), 0, st, a, c);
 }
 
 void launch_closed_loop_cov_rows(int kind, int nd, const Bufs& a, const ClCovArgs& c, int B, hipStream_t st) {

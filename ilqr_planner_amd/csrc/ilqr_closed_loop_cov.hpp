@@ -27,6 +27,9 @@ struct ClCovArgs {
     double* kp_Sigma = nullptr;  // [B][n_kp][n_x][n_x]
     double* u_var = nullptr;     // [B][T-1][n_u]
     double* lim_z = nullptr;     // [B]
+    // ilqr_problem_closed_loop_cov_con: both null in every other call, and the kernels then do not look at the constraint rows (a.conA, a.conb)
+    double* con_var = nullptr;   // [B][T-1][m]: c' Sigma_k c, c = A_k[r][0:n_x]' + K_k' A_k[r][n_x:]'
+    double* con_z = nullptr;     // [B]
     double* ws = nullptr;        // generic kernel: [cl_cov_ws_entries][Bp] matrices of a step (entry e of instance b at ws[e Bp + b])
 };
 

@@ -678,8 +678,10 @@ __global__ void k_track_map(Bufs a, const double* __restrict__ x_meas, int k, in
 // Closed loop of the tracking law (ilqr_closed_loop.hpp): S executions per instance from the caller's start states under the caller's
 // disturbances, one lane per (instance, sample), k_init_rollout's loop with the control of k_track in place of U0.  Natural layouts on the
 // user's dimensions (ClArgs), addressed with 32-bit element offsets (checked by the host).  MAP: a chain of fewer than 7 joints -- device
-// entry i is the user's mx.usr[i]; padded entries start on the plan (0), get no disturbance and keep the plan's control.
-template <class S, bool MAP>
+// entry i is the user's mx.usr[i]; padded entries start on the plan (0), get no disturbance and keep the plan's control.  CON: judge the
+// constraint rows (ilqr_problem_closed_loop_report_con; c.con_max is given).  A template argument like the cooperative kernel's FF: as a
+// run-time branch it pushed the 2nd-order instantiations, which sit at the register ceiling, into scratch.
+template <class S, bool MAP, bool CON>
 __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap mx, IndexMap mu) {
     constexpr int NX = S::NX, NU = S::NU;
     const DevDesc& d = *a.desc;
@@ -704,6 +706,7 @@ __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap m
         UNR for (int i = 0; i < NX; i++) if ((on >> i) & 1u) x[i] += nz[i];
     }
     double lim = 0, kpc = 0;
+    ClCon con;
     int st = 0;  // step table walk, as in k_init_rollout
     for (int k = 0; k < T - 1; k++) {
         if (c.X) {
@@ -714,6 +717,7 @@ __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap m
         if (c.U) {
             UNR for (int i = 0; i < NU; i++) { const int iu = MAP ? mu.usr[i] : i; if (iu >= 0) c.U[(g * (T - 1) + k) * nuu + iu] = u[i]; }
         }
+        if constexpr (CON) cl_con<S>(a, c.con_tol, k, x, u, con);  // before FK: x and u are live here anyway
         lim += cl_limits<S>(d, x);
         if (st < d.steps.n && d.steps.t[st] == k) {
             if (c.kpx) cl_store_kpx<NX, NU>(c, d, st, g, x);  // uniform: only the report asks
@@ -742,6 +746,7 @@ __global__ __launch_bounds__(64) void k_closed_loop(Bufs a, ClArgs c, IndexMap m
         kpc = cl_kp_terms<S>(d, a, b, st, x, zu, kpc);
     }
     if (c.lim_cost) c.lim_cost[g] = lim;
+    if constexpr (CON) cl_con_store(c, g, con);
     c.cost[g] = lim + kpc;
 }
 
@@ -854,6 +859,62 @@ __global__ __launch_bounds__(64) void k_closed_loop_outcome(const double* __rest
     o[0] = (double)n_ok; o[1] = (double)n_miss; o[2] = (double)n_lim; o[3] = (double)n_bad;
 }
 
+// con_stats[b] = { mean con_max, max con_max, mean con_steps, max con_steps, n_con, n_bad } of con_max / con_steps[b][0 .. S-1]: one lane per
+// instance over the samples in sample order, like k_closed_loop_stats and for its reason.  A sample is bad if its con_max is not finite.
+__global__ __launch_bounds__(64) void k_closed_loop_con_stats(const double* __restrict__ con_max, const double* __restrict__ con_steps,
+                                                             double con_tol, int B, int S, double* __restrict__ con_stats) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    int n = 0, n_con = 0;
+    double sm = 0, hm = -INFINITY, ss = 0, hs = -INFINITY;
+    for (int s = 0; s < S; s++) {
+        const size_t g = (size_t)b * S + s;
+        const double v = con_max[g], q = con_steps[g];
+        if (!isfinite(v)) continue;
+        n++;
+        sm += v; hm = v > hm ? v : hm;
+        ss += q; hs = q > hs ? q : hs;
+        if (v > con_tol) n_con++;
+    }
+    double* o = con_stats + (size_t)b * ILQR_CL_CON_STATS;
+    o[0] = n ? sm / n : NAN;
+    o[1] = n ? hm : NAN;
+    o[2] = n ? ss / n : NAN;
+    o[3] = n ? hs : NAN;
+    o[4] = (double)n_con;
+    o[5] = (double)(S - n);
+}
+
+// outcome_con[b] = { n_ok, n_miss, n_lim, n_con, n_bad }: k_closed_loop_outcome with the constraint rows as a third way to fail
+__global__ __launch_bounds__(64) void k_closed_loop_outcome_con(const double* __restrict__ cost, const double* __restrict__ kp_err,
+                                                               const double* __restrict__ lim_cost, const double* __restrict__ con_max,
+                                                               ilqr_cl_tol tol, double con_tol, int B, int S, int n_kp,
+                                                               double* __restrict__ outcome_con) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    int n_ok = 0, n_miss = 0, n_lim = 0, n_con = 0, n_bad = 0;
+    for (int s = 0; s < S; s++) {
+        const size_t g = (size_t)b * S + s;
+        if (!isfinite(cost[g])) { n_bad++; continue; }
+        bool miss = false;
+        for (int k = 0; k < n_kp; k++) {
+            const double* e = kp_err + (g * n_kp + k) * ILQR_KP_ERR;
+            double v[ILQR_KP_ERR];
+            UNR for (int j = 0; j < ILQR_KP_ERR; j++) v[j] = e[j];
+            miss = miss || cl_kp_miss(v, tol.kp_tol[k]);
+        }
+        const bool lim = lim_cost[g] > tol.lim_tol;
+        const double cm = con_max[g];
+        const bool con = cm > con_tol || !isfinite(cm);
+        n_miss += miss ? 1 : 0;
+        n_lim += lim ? 1 : 0;
+        n_con += con ? 1 : 0;
+        n_ok += (!miss && !lim && !con) ? 1 : 0;
+    }
+    double* o = outcome_con + (size_t)b * ILQR_CL_OUTCOME_CON;
+    o[0] = (double)n_ok; o[1] = (double)n_miss; o[2] = (double)n_lim; o[3] = (double)n_con; o[4] = (double)n_bad;
+}
+
 // Per-instance statistics of the closed-loop costs: one lane per instance over cost[b][0 .. S-1] in sample order, in two passes, so the sums do
 // not depend on the batch size or on which kernel made the costs.  stats[b] = { mean, unbiased variance, min, max, n_bad }: n_bad counts the
 // samples whose cost is not finite, the other four are over the finite ones (variance 0 for a single one, all four NaN for none).
@@ -888,7 +949,7 @@ __global__ __launch_bounds__(64) void k_closed_loop_stats(const double* __restri
 // triangle of Sigma' is computed and mirrored, so the workspace -- and every Sigma_k stored from it -- is exactly symmetric.  MAP: a chain of
 // fewer than 7 joints; the gain entries of padded rows and columns are read as 0, so the padding takes no part (its Sigma stays 0).
 template <class S>
-constexpr int cl_cov_ws_doubles() { return 2 * S::NX * S::NX + S::NU * S::NX + S::NU + S::NX; }
+constexpr int cl_cov_ws_doubles() { return 2 * S::NX * S::NX + S::NU * S::NX + S::NU + 2 * S::NX; }
 int cl_cov_ws_entries(int kind, int nd) {
     int n = 0;
     SysAll::dispatch(kind, nd, [&](auto s) { n = cl_cov_ws_doubles<decltype(s)>(); });
@@ -907,7 +968,7 @@ __global__ __launch_bounds__(64) void k_cl_cov(Bufs a, ClCovArgs c, IndexMap mx,
     const double* Xb = a.X[cur] + b;  // entry `row` of the plan: Xb[row * Bp]
     const double* Ub = a.U[cur] + b;
     double* const w = c.ws + b;
-    constexpr int oS = 0, oM = oS + NX * NX, oG = oM + NX * NX, oH = oG + NU * NX, oC = oH + NU, oEnd = oC + NX;
+    constexpr int oS = 0, oM = oS + NX * NX, oG = oM + NX * NX, oH = oG + NU * NX, oC = oH + NU, oV = oC + NX, oEnd = oV + NX;
     static_assert(oEnd == cl_cov_ws_doubles<S>(), "workspace layout");
 #define WS(o, i, j, C) w[(size_t)((o) + (i) * (C) + (j)) * Bp]
 #define WV(o, i) w[(size_t)((o) + (i)) * Bp]
@@ -916,7 +977,7 @@ __global__ __launch_bounds__(64) void k_cl_cov(Bufs a, ClCovArgs c, IndexMap mx,
     auto ctl = [](int r) { return r < DOF ? r : ((ND == 2 && r < 2 * DOF) ? r - DOF : NU - 1); };   // the control of row r (the time row: the time control)
     NOUNR for (int i = 0; i < NX; i++)
         NOUNR for (int j = 0; j < NX; j++) WS(oS, i, j, NX) = (i == j) ? c.sx02[i] : 0.0;
-    double zmin = INFINITY;
+    double zmin = INFINITY, zcon = INFINITY;
     int st = 0;  // step table walk
     for (int k = 0; k < T; k++) {
         // ---- what is read off Sigma_k: the outputs, the margin to the bounds
@@ -950,6 +1011,28 @@ __global__ __launch_bounds__(64) void k_cl_cov(Bufs a, ClCovArgs c, IndexMap mx,
         const double* rec = KD_REC(a.KD, Bp, rs, k, b);
         auto K = [&](int i, int j) { return (MAP && (mu.usr[i] < 0 || mx.usr[j] < 0)) ? 0.0 : rec[kd_off(sym, rowp, i, j)]; };
         const double* u = Ub + (size_t)k * NU * Bp;  // u_i = u[i Bp]
+        if (c.con_var || c.con_z) {  // uniform: the constraint rows of the step, c' Sigma_k c with c = a_x + K' a_u (ilqr_problem_closed_loop_cov_con)
+            NOUNR for (int r = 0; r < a.m; r++) {
+                const size_t row = (size_t)(a.per_step ? k : 0) * a.m + r;
+                const double* Ar = a.conA + row * (NX + NU);
+                double mu = 0;   // A_k[r] [xbar_k; ubar_k], in con_g's order
+                NOUNR for (int j = 0; j < NX; j++) {
+                    double cj = Ar[j];
+                    NOUNR for (int i = 0; i < NU; i++) cj += K(i, j) * Ar[NX + i];
+                    WV(oV, j) = cj;
+                    mu += Ar[j] * Xb[((size_t)k * NX + j) * Bp];
+                }
+                NOUNR for (int i = 0; i < NU; i++) mu += Ar[NX + i] * u[(size_t)i * Bp];
+                double var = 0;
+                NOUNR for (int i = 0; i < NX; i++) {
+                    double si = 0;
+                    NOUNR for (int j = 0; j < NX; j++) si += WS(oS, i, j, NX) * WV(oV, j);
+                    var += WV(oV, i) * si;
+                }
+                if (c.con_var) c.con_var[((size_t)b * (T - 1) + k) * a.m + r] = var;
+                if (var > 0) zcon = fmin(zcon, (a.conb[row] - mu) / sqrt(var));
+            }
+        }
         const double dts = TM ? u[(size_t)(NU - 1) * Bp] : 0.0;
         const double dt = TM ? dts * dts : d.dt;
         const double b1 = (ND == 1) ? dt : dt * dt / 2;   // B on the position rows; dt on the velocity rows
@@ -1005,6 +1088,7 @@ __global__ __launch_bounds__(64) void k_cl_cov(Bufs a, ClCovArgs c, IndexMap mx,
 #undef WS
 #undef WV
     if (c.lim_z) c.lim_z[b] = zmin;
+    if (c.con_z) c.con_z[b] = zcon;
 }
 
 // kp_var[b][kpi][g]: the trace of group g's 3 x 3 block of Jf Sigma_t Jf' (include/ilqr_hip.h), one lane per (instance, keypoint), from
@@ -1161,8 +1245,10 @@ void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B,
     const dim3 grid(((unsigned)B * c.S + 63) / 64), block(64);
     SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
-        if (m) hipLaunchKernelGGL((k_closed_loop<S, true>), grid, block, 0, st, a, c, m->x, m->u);
-        else hipLaunchKernelGGL((k_closed_loop<S, false>), grid, block, 0, st, a, c, IndexMap{}, IndexMap{});
+        if (m && c.con_max) hipLaunchKernelGGL((k_closed_loop<S, true, true>), grid, block, 0, st, a, c, m->x, m->u);
+        else if (m) hipLaunchKernelGGL((k_closed_loop<S, true, false>), grid, block, 0, st, a, c, m->x, m->u);
+        else if (c.con_max) hipLaunchKernelGGL((k_closed_loop<S, false, true>), grid, block, 0, st, a, c, IndexMap{}, IndexMap{});
+        else hipLaunchKernelGGL((k_closed_loop<S, false, false>), grid, block, 0, st, a, c, IndexMap{}, IndexMap{});
     });
 }
 void launch_closed_loop_cov(int kind, int nd, const Bufs& a, const ClCovArgs& c, int B, const DofMap* m, hipStream_t st) {
@@ -1189,6 +1275,14 @@ void launch_closed_loop_kp_err(int kind, int nd, const Bufs& a, int B, int S, in
 void launch_closed_loop_kp_stats(const double* kp_err, const ilqr_cl_tol& tol, int B, int S, int n_kp, double* kp_stats, hipStream_t st) {
     if (n_kp <= 0) return;
     hipLaunchKernelGGL(k_closed_loop_kp_stats, dim3((B + 63) / 64, n_kp), dim3(64), 0, st, kp_err, tol, B, S, n_kp, kp_stats);
+}
+void launch_closed_loop_con_stats(const double* con_max, const double* con_steps, double con_tol, int B, int S, double* con_stats, hipStream_t st) {
+    hipLaunchKernelGGL(k_closed_loop_con_stats, dim3((B + 63) / 64), dim3(64), 0, st, con_max, con_steps, con_tol, B, S, con_stats);
+}
+void launch_closed_loop_outcome_con(const double* cost, const double* kp_err, const double* lim_cost, const double* con_max, const ilqr_cl_tol& tol,
+                                    double con_tol, int B, int S, int n_kp, double* outcome_con, hipStream_t st) {
+    hipLaunchKernelGGL(k_closed_loop_outcome_con, dim3((B + 63) / 64), dim3(64), 0, st, cost, kp_err, lim_cost, con_max, tol, con_tol, B, S, n_kp,
+                       outcome_con);
 }
 void launch_closed_loop_outcome(const double* cost, const double* kp_err, const double* lim_cost, const ilqr_cl_tol& tol, int B, int S, int n_kp,
                                 double* outcome, hipStream_t st) {

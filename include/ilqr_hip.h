@@ -420,6 +420,61 @@ typedef struct {
 int ilqr_problem_closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out);
 int ilqr_problem_closed_loop_cov_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out);
 
+/* The two answers above, judged against the inequality rows of ilqr_problem_set_constraints: the only hard constraints of the library, which
+ * neither cost, kp_err nor lim_cost look at.  Rows are (A_k, b_k) exactly as ilqr_problem_set_constraints received them: m rows on the user's
+ * [x; u] layout, the same rows for every k with per_step = 0.  For execution (b, s) and control step k = 0 .. T-2
+ *   g[k][r] = sum_j A_k[r][j] x_k[j] + sum_i A_k[r][n_x + i] u_k[i] - b_k[r]
+ * with x_k the execution's state and u_k the commanded control (what the U output of the rollout holds): AL_ILQR::constraints
+ * (AL-ILQR.cpp:21-44) on the executed trajectory.  g <= 0 is feasible; x_{T-1} has no control and is not judged, as in the reference.  The
+ * summation order is fixed -- state columns ascending, then control columns ascending, then - b_k[r] -- and is the same in both rollout kernels.
+ *
+ * Sampled: ilqr_problem_closed_loop_report_con.  The arguments of ilqr_problem_closed_loop_report, then con_tol and the outputs (ilqr_cl_con);
+ * `out` may be NULL here.  One rollout; cost, stats and the four outputs of `out` are bit for bit those of ilqr_problem_closed_loop_report.
+ *   con_max[B][S]                    the maximum of g[k][r] over k and r: <= 0 means feasible throughout; NaN if any g of the execution is not finite
+ *   con_steps[B][S]                  the number of steps k with max_r g[k][r] > con_tol (strict), stored as a double
+ *   con_stats[B][ILQR_CL_CON_STATS]  { mean con_max, max con_max, mean con_steps, max con_steps, n_con, n_bad } over the samples of instance b in
+ *                                    sample order: a sample is bad if its con_max is not finite; means and maxima are over the good samples (NaN
+ *                                    for none); n_con counts the good samples with con_max > con_tol
+ *   outcome_con[B][ILQR_CL_OUTCOME_CON]  { n_ok, n_miss, n_lim, n_con, n_bad }: n_bad, n_miss and n_lim exactly as in `outcome`; n_con counts the
+ *                                    finite-cost samples whose con_max exceeds con_tol or is not finite; n_ok those with none of the three.
+ *                                    Needs tol.
+ * Each may be NULL; not all four unless `out` asks for something.  No per-step output exists: the 32-bit bounds are those of the report call.
+ * Refused: everything ilqr_problem_closed_loop_report refuses (a NULL `out` is not), no constraints set, a NaN con_tol, outcome_con without
+ * tol, con and out both asking for nothing.
+ *
+ * Analytic: ilqr_problem_closed_loop_cov_con.  In the closed loop u - ubar = K_k (x - xbar), so to first order row r at step k has variance
+ *   con_var[k][r] = c' Sigma_k c,   c = A_k[r][0:n_x]' + K_k' A_k[r][n_x:]'
+ * with Sigma_k and K_k those of ilqr_problem_closed_loop_cov (exact on the constant-dt systems, where the loop is linear).
+ *   con_var[B][T-1][m]   the variance above
+ *   con_z[B]             how many standard deviations the plan keeps from its constraints: the minimum over k <= T-2 and the rows with
+ *                        con_var > 0 of (b_k[r] - A_k[r] [xbar_k; ubar_k]) / sqrt(con_var[k][r]); +inf if there is no such (k, r), negative where
+ *                        the plan itself violates a row
+ * `out` may be NULL; what it asks for is what ilqr_problem_closed_loop_cov returns, bit for bit per kernel.  Refused: what that call refuses
+ * (a NULL `out` is not), no constraints set, con and out both asking for nothing.
+ * _dev forms: as above. */
+#define ILQR_CL_CON_STATS 6     /* mean con_max, max con_max, mean con_steps, max con_steps, n_con, n_bad */
+#define ILQR_CL_OUTCOME_CON 5   /* n_ok, n_miss, n_lim, n_con, n_bad */
+typedef struct {
+    double* con_max;      /* [B][S] or NULL */
+    double* con_steps;    /* [B][S] or NULL */
+    double* con_stats;    /* [B][ILQR_CL_CON_STATS] or NULL */
+    double* outcome_con;  /* [B][ILQR_CL_OUTCOME_CON] or NULL */
+} ilqr_cl_con;
+int ilqr_problem_closed_loop_report_con(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
+                                        int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out,
+                                        double con_tol, const ilqr_cl_con* con);
+int ilqr_problem_closed_loop_report_con_dev(ilqr_problem* p, int n_samples, const ilqr_noise* noise, const double* x0, const double* w,
+                                            int with_feedforward, const ilqr_cl_tol* tol, double* cost, double* stats, const ilqr_cl_report* out,
+                                            double con_tol, const ilqr_cl_con* con);
+typedef struct {
+    double* con_var;  /* [B][T-1][m] or NULL */
+    double* con_z;    /* [B] or NULL */
+} ilqr_cl_cov_con;
+int ilqr_problem_closed_loop_cov_con(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
+                                     const ilqr_cl_cov_con* con);
+int ilqr_problem_closed_loop_cov_con_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
+                                         const ilqr_cl_cov_con* con);
+
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];
  * any output may be NULL.  Host pointers. */
