@@ -158,13 +158,13 @@ extern "C" int ilqr_ctx_set_split(ilqr_ctx* c, int on) {
 }
 
 static_assert((int)SweepPin::Mfma == ILQR_XC_SWEEP_MFMA && (int)SweepPin::Rows == ILQR_XC_SWEEP_ROWS && (int)SweepPin::SiWave == ILQR_XC_SWEEP_SI_WAVE &&
-              (int)SweepPin::SiWg == ILQR_XC_SWEEP_SI_WG && (int)SweepPin::SiWgIo == ILQR_XC_SWEEP_SI_WG_IO && (int)FwdPin::Wg == ILQR_XC_FWD_WG &&
+              (int)SweepPin::SiWg == ILQR_XC_SWEEP_SI_WG && (int)SweepPin::SiWgIo == ILQR_XC_SWEEP_SI_WG_IO && (int)SweepPin::SiWgPrep == ILQR_XC_SWEEP_SI_WG_PREP && (int)FwdPin::Wg == ILQR_XC_FWD_WG &&
               (int)FwdPin::Dpp == ILQR_XC_FWD_DPP && (int)FwdPin::WgLds == ILQR_XC_FWD_WG_LDS && (int)RerollPin::Rows == ILQR_XC_REROLL_ROWS && (int)RerollPin::Dpp == ILQR_XC_REROLL_DPP,
               "variant pins of ilqr_plan.hpp and include/ilqr_hip.h");
 
 extern "C" int ilqr_ctx_set_crosscheck(ilqr_ctx* c, int generic_kernels, int cp_lane_solve, int cp_general, int sweep, int forward, int reroll) {
     if (!c) return 1;
-    if (sweep < 0 || sweep > 6 || sweep == 3) return fail(c, "ilqr_ctx_set_crosscheck: sweep must be ILQR_XC_AUTO, ILQR_XC_SWEEP_MFMA, ILQR_XC_SWEEP_ROWS, ILQR_XC_SWEEP_SI_WAVE, ILQR_XC_SWEEP_SI_WG or ILQR_XC_SWEEP_SI_WG_IO");
+    if (sweep < 0 || sweep > 7 || sweep == 3) return fail(c, "ilqr_ctx_set_crosscheck: sweep must be ILQR_XC_AUTO, ILQR_XC_SWEEP_MFMA, ILQR_XC_SWEEP_ROWS, ILQR_XC_SWEEP_SI_WAVE, ILQR_XC_SWEEP_SI_WG, ILQR_XC_SWEEP_SI_WG_IO or ILQR_XC_SWEEP_SI_WG_PREP");
     if (forward < 0 || forward > 3) return fail(c, "ilqr_ctx_set_crosscheck: forward must be ILQR_XC_AUTO, ILQR_XC_FWD_WG, ILQR_XC_FWD_DPP or ILQR_XC_FWD_WG_LDS");
     if (reroll < 0 || reroll > 2) return fail(c, "ilqr_ctx_set_crosscheck: reroll must be ILQR_XC_AUTO, ILQR_XC_REROLL_ROWS or ILQR_XC_REROLL_DPP");
     c->xc_sweep = (SweepPin)sweep;
@@ -710,7 +710,7 @@ static FwdArgs plan_fwd_args(const ilqr_problem* p, const RiccatiPlan& pl) {
 static void launch_sweep(const ilqr_problem* p, const RiccatiPlan& pl, int h, bool al, const Bufs& bf, int B, hipStream_t st, SweepArgs& sw) {
     const int kind = p->desc.kind, nd = p->desc.nb_deriv;
     switch (pl.sweep) {
-        case Sweep::SiDpp: sw.si_wg = pl.si_wg[h] ? 1 : 0; sw.si_io = pl.si_io[h] ? 1 : 0; launch_backward_si_dpp(al, pl.fused, pl.kd_sym == 1, pl.si_lanes[h], bf, B, st, sw); break;
+        case Sweep::SiDpp: sw.si_wg = pl.si_wg[h] ? 1 : 0; sw.si_io = pl.si_io[h] ? 1 : 0; sw.si_prep = pl.si_prep[h] ? 1 : 0; launch_backward_si_dpp(al, pl.fused, pl.kd_sym == 1, pl.si_lanes[h], bf, B, st, sw); break;
         case Sweep::Rows: launch_backward_rows(kind, nd, al, bf, B, st); break;
         case Sweep::Mfma: launch_backward_mfma(kind, nd, al, bf, B, st); break;
         case Sweep::Generic: launch_backward_generic(kind, nd, al, bf, B, st); break;
@@ -752,7 +752,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     HIPCHK(c, hipGetLastError());
     double penalty = penalty0;
     SweepArgs sw;
-    sw.pen_in = penalty; sw.pen_update_prev = penalty; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0;
+    sw.pen_in = penalty; sw.pen_update_prev = penalty; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0; sw.si_prep = 0;
     for (int it = 0; it < nb_iter; it++) {
         FwdArgs fi = f;
         fi.it = it;
@@ -893,7 +893,7 @@ extern "C" int ilqr_problem_gains(ilqr_problem* p) {
     SplitJoin split_join{c, pl.split};  // on every exit path
     const FwdArgs f = plan_fwd_args(p, pl);
     SweepArgs sw;
-    sw.pen_in = 0.0; sw.pen_update_prev = 0.0; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0;
+    sw.pen_in = 0.0; sw.pen_update_prev = 0.0; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0; sw.si_prep = 0;
     for (int h = 0; h < nh; h++) {
         const Bufs& bf = hv[h].bufs;
         const int B = hv[h].B;

@@ -80,6 +80,7 @@ struct SweepArgs {
     int do_update_prev;      // the previous iteration was an update iteration
     int si_wg;               // k_backward_si_dpp in its workgroup form (RiccatiPlan::si_wg of the launched half): same bits
     int si_io;               // ... with the I/O wave (RiccatiPlan::si_io of the launched half): same bits
+    int si_prep;             // ... and the two preparing waves (RiccatiPlan::si_prep of the launched half): same bits
 };
 
 // Launchers of one Riccati iteration; which of them run is decided by plan_riccati (ilqr_plan.hpp).

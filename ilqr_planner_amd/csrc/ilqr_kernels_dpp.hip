@@ -190,6 +190,21 @@ constexpr int SW_WAVES = 4;
 constexpr int SW_RING = 8;             // slots per ring: two groups of PF steps, which lets the chain waves run 4 steps ahead of the I/O wave (with 4 slots: none)
 constexpr int SW_POLL_CHAIN = 1 << 20; // polls of s_sleep 1 (64 clocks) + an LDS round trip: 28 ms at 2.4 GHz from the sleeps alone
 constexpr int SW_POLL_IO = 1 << 18;    // polls of s_sleep 4 (256 clocks) + an LDS round trip: 28 ms at 2.4 GHz from the sleeps alone
+// PREP (IO bit 2, with bits 0 and 1): two more waves that execute no Riccati arithmetic either and take everything of a step that depends only on
+// what is loaded off the chain waves.  Preparing wave q serves chain waves 2 q and 2 q + 1 in the chain's own layout (lane j: row j mod 8 of instance
+// 8 q + j / 8 of the workgroup, so the 8-lane butterfly of g = a . x - b is the chain's): it loads xbar, ubar, x(1), u(1) and the multiplier PF steps
+// ahead, blends, drops x | u into the workgroup's x | u ring for the I/O wave, forms the limit terms and the AL bookkeeping (I_k, the multiplier
+// update and its store) with the chain's expressions, writes {u, lim, l_x of the limits, I_k, lam + I_k g, beyond} of its (instance, row) into slot
+// (n - 1) mod SW_PRING of the prepared ring and then stores n into its word of sFl ("prepared").  Before it writes step n it needs consumed >= n -
+// SW_PRING: the I/O wave consumes a step only after every live chain wave has produced it, i.e. has read its prepared entry, so that one word frees
+// both the prepared slot and the x | u slot.  A chain wave needs prepared >= the last step of a group of PF steps, checked once per group behind the
+// pivots of the group's first step (which need nothing that is loaded); it loads nothing in the loop but the keypoint derivatives, does not blend
+// and writes no x | u.  No cycle of waits: preparing step n waits for "consumed n - SW_PRING", that for "produced n - SW_PRING" of the chain waves,
+// that for "prepared n - SW_PRING + PF - 1" at most -- always an earlier step.  Same bits (tests/test_gpu_sweep_prep.py).  Measured on C3
+// at B = 4096 (profiles/sweep_prep_ab_bench.txt): 5.57 against 5.99 ms per solve; the chain wave's four-step loop went from 1768 to 1569 instructions.
+constexpr int SW_PREP = 2;             // preparing waves: 8 instances each
+constexpr int SW_PRING = 8;            // slots of the prepared ring = how far a preparing wave runs ahead of the I/O wave
+constexpr int SW_PENT = 6;             // doubles per (instance, row) and slot: three 16-byte reads for the chain wave
 namespace {
 __device__ __forceinline__ int wait_consumed(int seen, unsigned addr, int need) {
     int v = seen, cons, cnt;
@@ -214,11 +229,13 @@ __device__ __forceinline__ int wait_consumed(int seen, unsigned addr, int need) 
 }
 }  // namespace
 template <int LPI, int MR, bool FUSED, bool UNIF, bool WG = false, int IO = 0>
-__global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
+__global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP : 0)) * 64 : 64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
     constexpr int N = 7, IPW = 64 / LPI;
     constexpr int NWV = WG ? SW_WAVES : 1;
     constexpr bool IOK = (IO & 1) != 0, IOX = (IO & 2) != 0;  // the I/O wave sends the gain records / stores the accepted x, u
+    constexpr bool PRP = (IO & 4) != 0;                       // two preparing waves hand the chain waves what a step needs of x, u and the multipliers
     constexpr int NIMG = IOK ? SW_RING : 2, XRING = SW_RING, XROW = 18;
+    static_assert(!PRP || (IOK && IOX && FUSED && SW_PRING == XRING && SW_WAVES * (64 / LPI) == 8 * SW_PREP), "the preparing waves: on top of the full I/O wave, one x | u slot per prepared slot");
     static_assert(!WG || (LPI == 16 && FUSED), "the workgroup form: 4 instances per wave, 16 per workgroup = one 128-byte line per row segment");
     static_assert(!IO || (WG && MR <= 1), "the I/O wave: workgroup form, at most one constraint row (256 VGPRs at two waves on a SIMD)");
     constexpr int MRR = MR > 0 ? MR : 1;
@@ -230,7 +247,9 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_ba
     __shared__ __attribute__((aligned(16))) double sKw[NWV][NIMG][IMG + 64];
     // IOX: the accepted x | u of a step, [row 0 .. 6 x, 7 .. 13 u, 14 dump][instance of the workgroup], row stride XROW (banks)
     __shared__ double sXU[IOX ? XRING : 1][IOX ? 2 * N + 1 : 1][IOX ? XROW : 1];
-    __shared__ int sFl[IO ? NWV + 1 : 1];  // produced (per chain wave), consumed
+    // PRP: what the chain waves consume of a step, [slot][instance of the workgroup x 8 + row][u, lim, lx of the limits, I_k, lam + I_k g, beyond]
+    __shared__ __attribute__((aligned(16))) double sPr[PRP ? SW_PRING : 1][PRP ? 8 * SW_WAVES * (64 / LPI) : 1][PRP ? SW_PENT : 2];
+    __shared__ int sFl[IO ? NWV + 1 + (PRP ? SW_PREP : 0) : 1];  // produced (per chain wave), consumed, prepared (per preparing wave)
     const DevDesc& d = *a.desc;
     const int wv = WG ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0;
     double (*const sK)[IMG + 64] = sKw[wv < NWV ? wv : 0];
@@ -321,7 +340,95 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_ba
             }
             return;
         }
-        if (lane == 0) { sFl[wv] = 0; if (wv == 0) sFl[NWV] = 0; }
+        if (PRP && wv > NWV) {  // ---- a preparing wave: lane j owns row j mod 8 of instance 8 pw + j / 8 of the workgroup
+            const int pw = wv - NWV - 1, iw = pw * 8 + (lane >> 3), rp = lane & 7;
+            const int bi = xcd_tile() * (NWV * IPW) + iw;
+            const bool in = bi < d.B;
+            const int bbi = in ? bi : 0;
+            const bool oki = in && a.active[bbi];
+            const int pwi = in ? a.pend[bbi] : 0;
+            const int curi = a.cur[bbi];
+            __syncthreads();  // every wave has read active, pend and cur of the 16 instances; the flags are zero
+            if (__ballot((oki || pwi > 0) ? 1 : 0) == 0ull) return;  // neither of its chain waves runs
+            const bool acci = pwi > 0, blendi = pwi > 1;
+            const double aacc = acci ? ldexp(1.0, -(pwi - 1)) : 1.0;
+            int rd = curi, r1 = blendi ? 1 - curi : curi;
+            if (acci && !blendi) rd = r1 = 1 - curi;
+            const bool updi = acci && sw.do_update_prev;
+            const bool isVp = rp < N;
+            const int vp = isVp ? rp : 0;
+            const int Bpp = d.Bp, Tp = d.T;
+            const int lim_on = d.limits_set;
+            const double pen = d.penalty, pen_xx = d.pen_xx;
+            const int lw_v = isVp ? d.lw[vp] : 0;
+            const double smax_v = lw_v != 0 ? d.smax[vp] : __builtin_inf(), smin_v = lw_v != 0 ? d.smin[vp] : -__builtin_inf();
+            const double Avp = (MR == 1 && isVp) ? a.conA[vp] : 0.0, bp = (MR == 1) ? a.conb[0] : 0.0;
+            double* const Xb = a.X[0];
+            double* const Ub = a.U[0];
+            const unsigned bufo = (unsigned)((a.X[1] - a.X[0]) * (ptrdiff_t)sizeof(double));
+            const unsigned Vstep = (unsigned)N * Bpp * 8u, Lstep = (unsigned)MR * Bpp * 8u;
+            unsigned oA = (unsigned)rd * bufo + ((unsigned)((Tp - 2) * N + vp) * Bpp + bbi) * 8u;  // xbar, ubar
+            unsigned oB = (unsigned)r1 * bufo + ((unsigned)((Tp - 2) * N + vp) * Bpp + bbi) * 8u;  // x(1), u(1)
+            unsigned oL = ((unsigned)(Tp - 2) * MR * Bpp + bbi) * 8u, oLw = oL;                   // the multiplier: loads, store
+            constexpr int PF = 4;
+            double xr[PF], ur[PF], x1r[PF], u1r[PF], lr[PF];
+            auto fetch = [&](int slot, int kk) {  // as the chain waves' fetch: every load unconditional
+                xr[slot] = ldg(Xb, oA);
+                ur[slot] = ldg(Ub, oA);
+                x1r[slot] = ldg(Xb, oB);
+                u1r[slot] = ldg(Ub, oB);
+                lr[slot] = 0;
+                if (MR > 0) lr[slot] = ldg(a.lambda, oL);
+                if (kk > 0) { oA -= Vstep; oB -= Vstep; oL -= Lstep; }
+            };
+            UNR for (int q = 0; q < PF; q++) { fetch(q, Tp - 2 - q); __builtin_amdgcn_sched_barrier(0); }
+            const unsigned fl_c = lds_addr(&sFl[NWV]);
+            int gave = 0;  // uniform
+            for (int k0 = Tp - 2; k0 >= 0; k0 -= PF) {
+              const int s0 = (Tp - 2 - k0) % SW_PRING;  // uniform: the slot of the group's first step
+              UNR for (int jj = 0; jj < PF; jj++) {
+                const int k = k0 - jj;
+                double xv = ring_take(xr[jj]), uv = ring_take(ur[jj]);
+                const double x1v = ring_take(x1r[jj]), u1v = ring_take(u1r[jj]);
+                xv = fma(aacc, x1v - xv, xv);  // accepted trajectory (k_apply's expression)
+                uv = fma(aacc, u1v - uv, uv);
+                double lam = (MR > 0) ? ring_take(lr[jj]) : 0.0;
+                __builtin_amdgcn_sched_barrier(0);
+                fetch(jj, k - PF);
+                if (k < 0) continue;  // uniform: dummy step of the last group
+                // step n = T - 1 - k goes into the slots of step n - SW_PRING: free once the I/O wave has consumed that step (one asm statement, as in the chain waves)
+                const int need = __builtin_amdgcn_readfirstlane(Tp - 1 - k - SW_PRING);
+                gave |= wait_consumed(flag_read(&sFl[NWV]), fl_c, need);
+                sXU[s0 + jj][isVp ? vp : 2 * N][iw] = xv;  // the I/O wave stores them as lines, under the instance's own blend
+                sXU[s0 + jj][isVp ? N + vp : 2 * N][iw] = uv;
+                double beyond = 0, lim = 0, lxl = 0, Isk = 0, lt = 0;
+                if (lim_on) {  // uniform.  The chain waves' expressions
+                    beyond = fmax(xv - smax_v, 0.0) + fmax(smin_v - xv, 0.0);
+                    lim = (beyond > 0.0) ? pen_xx : 0.0;
+                    lxl = pen * fmax(xv - smax_v, 0.0) - pen * fmax(smin_v - xv, 0.0);
+                }
+                if (MR == 1) {
+                    const double gr = oct_row_g(Avp, xv, bp);
+                    Isk = sw.pen_in * ((gr < 0 && lam == 0) ? 0.0 : 1.0);
+                    const double nv = fma(sw.pen_update_prev, gr, lam);
+                    const double nl = nv > 0 ? nv : 0;
+                    lam = updi ? nl : lam;
+                    if (updi && rp == 0) stg(a.lambda, oLw, lam);
+                    lt = lam + Isk * gr;
+                    oLw -= Lstep;
+                }
+                double2* e = reinterpret_cast<double2*>(sPr[s0 + jj][iw * 8 + rp]);
+                e[0] = make_double2(uv, lim);
+                e[1] = make_double2(lxl, Isk);
+                e[2] = make_double2(lt, beyond);
+                flag_write(&sFl[NWV + 1 + pw], Tp - 1 - k);  // prepared: after the data it announces
+              }
+              k0 = gave ? 0 : k0;  // (a select on the loop counter, no branch: the loop ends here)
+            }
+            if (gave && rp == 0 && in) { a.active[bbi] = 0; atomicOr(&a.status[bbi], ILQR_STATUS_SWEEP_IO); }  // the I/O wave is gone
+            return;
+        }
+        if (lane == 0) { sFl[wv] = 0; if (wv == 0) { sFl[NWV] = 0; if (PRP) { UNR for (int q = 0; q < SW_PREP; q++) sFl[NWV + 1 + q] = 0; } } }
         __syncthreads();
     }
     if (__ballot((ok || acc) ? 1 : 0) == 0ull) return;  // wave-uniform (the waves of a workgroup never meet in the loop)
@@ -445,32 +552,39 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_ba
         }
         if (kk > 0) { oA -= Vstep; oB -= Vstep; oL -= Lstep; }  // uniform; no load inside the branch
     };
-    UNR for (int q = 0; q < PF; q++) { fetch(q, T - 2 - q); __builtin_amdgcn_sched_barrier(0); }
+    if (!PRP) { UNR for (int q = 0; q < PF; q++) { fetch(q, T - 2 - q); __builtin_amdgcn_sched_barrier(0); } }
     // store side of the fused acceptance: the accepted x, u of step k go where x(1), u(1) were read (PF steps behind the loads)
     unsigned oW = (unsigned)r1 * bufo + ((unsigned)((T - 2) * N + v) * Bp + bb) * 8u;
     unsigned oLw = ((unsigned)(T - 2) * m * Bp + bb) * 8u;
 
     static_assert(SW_RING % PF == 0, "a step's slot is the group's first slot + its place in the group");
     const unsigned fl_cons = lds_addr(&sFl[IO ? NWV : 0]);
+    const int fl_pi = PRP ? NWV + 1 + wv / (SW_WAVES / SW_PREP) : 0;  // PRP: the wave's preparing wave
+    const unsigned fl_prep = lds_addr(&sFl[fl_pi]);
+    const int pent = (wv * IPW + g) * 8 + r;                             // PRP: the lane's entry of a prepared slot (both halves of an instance read the same)
     int gave_up = 0;  // uniform
     const int xcol = wv * IPW + g, xrow = isV ? (low ? v : N + v) : 2 * N;  // IOX: where this lane drops its x (low half) or u (the copy)
     for (int k0 = T - 2; k0 >= 0; k0 -= PF) {
       const int sl0 = IOK ? (T - 2 - k0) % SW_RING : 0, xs0 = IOX ? (T - 2 - k0) % XRING : 0;  // uniform: the slots of the group's first step
       UNR for (int jj = 0; jj < PF; jj++) {
         const int k = k0 - jj;
-        double xv = ring_take(xr[jj]), uv = ring_take(ur[jj]);
-        if (FUSED) {  // accepted trajectory (k_apply's expression)
+        double xv = 0, uv = 0;
+        if (!PRP) { xv = ring_take(xr[jj]); uv = ring_take(ur[jj]); }
+        if (FUSED && !PRP) {  // accepted trajectory (k_apply's expression)
             const double x1v = ring_take(x1r[jj]), u1v = ring_take(u1r[jj]);
             xv = fma(aacc, x1v - xv, xv);
             uv = fma(aacc, u1v - uv, uv);
         }
         double lam[MRR], Isk[MRR];
         UNR for (int rr = 0; rr < MRR; rr++) {
-            lam[rr] = (MR > 0) ? ring_take(lr[jj][rr]) : 0.0;
-            Isk[rr] = (MR > 0 && !FUSED) ? ring_take(ir[jj][rr]) : ir[jj][rr];
+            lam[rr] = (MR > 0 && !PRP) ? ring_take(lr[jj][rr]) : 0.0;
+            Isk[rr] = PRP ? 0.0 : (MR > 0 && !FUSED) ? ring_take(ir[jj][rr]) : ir[jj][rr];
         }
-        __builtin_amdgcn_sched_barrier(0);  // the slots are free: only now their next loads
-        fetch(jj, k - PF);
+        if (!PRP) {
+            __builtin_amdgcn_sched_barrier(0);  // the slots are free: only now their next loads
+            fetch(jj, k - PF);
+        }
+        const int prepared = (PRP && jj == 0) ? flag_read(&sFl[fl_pi]) : 0;       // read here, needed behind the pivots
         const int consumed = (IO && jj == 0) ? flag_read(&sFl[IO ? NWV : 0]) : 0;  // read here, needed at the step's end
         // the image of the step before this one (in time) leaves now: LDS -> registers here, registers -> memory after the pivots
         const bool kprev = k < T - 2;
@@ -495,18 +609,32 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_ba
             if (!IOK && k == -1) SEND_()
             continue;
         }
-        if (FUSED) {
+        // PRP: the step's prepared entry {u, lim | lx of the limits, I_k | lam + I_k g, beyond}; the group's check stands behind the first step's pivots
+        double2 pe0 = make_double2(0, 0), pe1 = pe0, pe2 = pe0;
+#define PREP_READ_()                                                                          \
+        {                                                                                     \
+            const double2* e = reinterpret_cast<const double2*>(sPr[PRP ? sl0 + jj : 0][PRP ? pent : 0]); \
+            pe0 = e[0]; pe1 = e[1]; pe2 = e[2];                                               \
+        }
+        if (PRP && jj > 0) PREP_READ_()
+        if (FUSED && !PRP) {
             if (IOX) sXU[xs0 + jj][xrow][xcol] = low ? xv : uv;  // the I/O wave stores them as lines, under the instance's own blend
             else if (wr) { stg(Xb, oW, xv); stg(Ub, oW, uv); }
             oW -= Vstep;
         }
-        const double Qu = Rv * uv + dt * p;  // Qu = R u + B'p
+        const double Qu0 = PRP ? 0.0 : Rv * uv + dt * p;  // Qu = R u + B'p
         // ---- S = D + dt^2 P (row r), then the seven pivots: afterwards myrc * s = row r of -S^-1
         double s[N];
         UNR for (int j = 0; j < N; j++) s[j] = fma(dt2, P[j], Dd[j]);
         double myrc = 0.0;
         pivots<LPI>(s, nm1, myrc);
         if (!IOK && kprev) SEND_()
+        if (PRP && jj == 0) {  // once per group: its last step (of the sweep: T - 1) is prepared.  The bounded poll falls through at once in the common case
+            const int last = T - 1 - k + PF - 1;
+            gave_up |= wait_consumed(prepared, fl_prep, __builtin_amdgcn_readfirstlane(last < T - 1 ? last : T - 1));
+            PREP_READ_()
+        }
+        const double Qu = PRP ? Rv * pe0.x + dt * p : Qu0;
         const double nrc = -myrc;
         // row r of S^-1 is M = nrc s.  With uniform control weights M is never formed: N = M D - I = (nrc D) s - I, and the two
         // products with M run on s and are scaled afterwards.
@@ -570,6 +698,10 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_ba
             asm volatile("" : "+v"(lx));
             kpi--;
             kp_next = (kpi >= 0) ? __builtin_amdgcn_readfirstlane(d.kp_t[kpi]) : -1;
+        } else if (PRP && lim_on) {  // uniform.  The preparing wave's beyond, lim and l_x
+            const double lim = pe0.y;
+            if (__ballot(pe2.y > 0.0 ? 1 : 0) != 0ull) { UNR for (int j = 0; j < N; j++) Pn[j] = fma(-nm1[j], lim, Pn[j]); }  // uniform; adds exact zeros otherwise
+            lx = pe1.x;
         } else if (lim_on) {  // uniform.  inspectJointLimit (System.cpp:121-142) branch-free; l_xx of the limits is diagonal
             const double beyond = fmax(xv - smax_v, 0.0) + fmax(smin_v - xv, 0.0);
             const double lim = (beyond > 0.0) ? pen_xx : 0.0;
@@ -579,7 +711,12 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_ba
         }
         if (MR > 0) {
             UNR for (int rr = 0; rr < MRR; rr++) {
-                if (MR == 1 || rr < m) {
+                if (PRP) {  // I_k and lam + I_k g of the preparing wave (which also updated and stored the multiplier)
+                    Isk[rr] = pe1.y;
+                    const double wI = Av[rr] * Isk[rr];
+                    UNR for (int j = 0; j < N; j++) Pn[j] = fma(wI, Arow[rr][j], Pn[j]);
+                    lx += Av[rr] * pe2.x;
+                } else if (MR == 1 || rr < m) {
                     // g = A_r . x - b: every lane multiplies its own component, 8-lane butterfly (lane 7 adds 0); all lanes of the instance hold it
                     const double gr = oct_row_g(Av[rr], xv, bbr[rr]);
                     if (FUSED) {  // AL-ILQR.cpp:190 (mask with the multipliers before the update), :202-208 (update)
@@ -618,17 +755,20 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64) void k_ba
 }
 
 constexpr int SW_IO = 3;  // what the I/O wave carries: the gain records and the accepted x, u (the stages that were measured: profiles/sweep_io_variations.txt)
+constexpr int SW_IO_PREP = SW_IO | 4;  // ... with the two preparing waves
 template <int LPI, bool FUSED, bool UNIF, bool WG = false, int IO = 0>
 static void launch_dpp2(bool al, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
     constexpr int IWG = (WG ? SW_WAVES : 1) * (64 / LPI);  // instances per workgroup
-    const dim3 grid(grid_x8((B + IWG - 1) / IWG)), block(WG ? (SW_WAVES + (IO ? 1 : 0)) * 64 : 64);
+    const dim3 grid(grid_x8((B + IWG - 1) / IWG)), block(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP : 0)) * 64 : 64);
     if (!al || a.m == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 0, FUSED, UNIF, WG, IO>), grid, block, 0, st, a, sw);
     else if (a.m <= 1) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 1, FUSED, UNIF, WG, IO>), grid, block, 0, st, a, sw);
     else if constexpr (IO == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 4, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
 }
 
 void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
-    if (lpi == 16 && fused && sw.si_wg && sw.si_io && (!al || a.m <= 1)) {  // ... with the I/O wave (RiccatiPlan::si_io): at most one constraint row
+    if (lpi == 16 && fused && sw.si_wg && sw.si_io && sw.si_prep && (!al || a.m <= 1)) {  // ... with the I/O wave and the preparing waves (RiccatiPlan::si_prep)
+        if (uniform_R) launch_dpp2<16, true, true, true, SW_IO_PREP>(al, a, B, st, sw); else launch_dpp2<16, true, false, true, SW_IO_PREP>(al, a, B, st, sw);
+    } else if (lpi == 16 && fused && sw.si_wg && sw.si_io && (!al || a.m <= 1)) {  // ... with the I/O wave (RiccatiPlan::si_io): at most one constraint row
         if (uniform_R) launch_dpp2<16, true, true, true, SW_IO>(al, a, B, st, sw); else launch_dpp2<16, true, false, true, SW_IO>(al, a, B, st, sw);
     } else if (lpi == 16 && fused && sw.si_wg) {  // the workgroup form (RiccatiPlan::si_wg): instantiated for the fused acceptance only
         if (uniform_R) launch_dpp2<16, true, true, true>(al, a, B, st, sw); else launch_dpp2<16, true, false, true>(al, a, B, st, sw);

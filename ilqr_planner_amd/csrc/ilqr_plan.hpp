@@ -56,11 +56,20 @@ constexpr int SI_WG_MIN_BATCH = 256;
 // slower at a measured size; smaller batches were not measured and stay on lone waves, as for SI_WG_MIN_BATCH.  The halves of a split solve
 // (ilqr_ctx_set_split(2)) were not measured either and keep the four-wave form under AUTO: the form's 99 KB of LDS allow one workgroup per CU, so
 // two halves of 4096 instances on two streams could no longer share the CUs as the 20 KB workgroups of the four-wave form do.  The pin forces it there too.
+// Since SI_PREP_MIN_BATCH (below) equals this threshold, AUTO never takes the I/O wave without the preparing waves; the pin SiWgIo still does.
 constexpr int SI_IO_MIN_BATCH = 256;
 constexpr bool si_io_supported(bool al, int m) { return !al || m <= 1; }
+// The I/O-wave form with two preparing waves (they load xbar, ubar, x(1), u(1) and the multiplier, blend, form the limit terms and the AL
+// bookkeeping and hand the chain waves what a step consumes through a ring in LDS: the chain waves load nothing in the loop but keypoint
+// derivatives), wherever the I/O wave is taken and the LAUNCHED batch has this many instances.  Same bits (tests/test_gpu_sweep_prep.py), so the
+// threshold is a pure speed choice.  Measured on C3 (profiles/sweep_prep_batch_scan.txt, ms per solve, the I/O-wave form against the same with the
+// preparing waves): B = 256 5.08 / 4.63, 1024 5.27 / 4.81, 2048 5.40 / 4.96, 3072 6.07 / 5.65, 4096 5.96 / 5.56 -- faster at every measured size, so from
+// the smallest one; smaller batches do not get the I/O wave.  148 KB of LDS: one workgroup per CU, as for the I/O-wave form; split halves keep the
+// four-wave form under AUTO as there.  The pin forces it wherever the I/O wave is supported.
+constexpr int SI_PREP_MIN_BATCH = 256;
 
 // Variant pins of ilqr_ctx_set_crosscheck: AUTO (0) = by batch size; the values are the ILQR_XC_* constants of include/ilqr_hip.h
-enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2, SiWave = 4, SiWg = 5, SiWgIo = 6 };  // SiWave / SiWg / SiWgIo: the form of k_backward_si_dpp (same bits); AUTO elsewhere.  (3 is no pin: ilqr_ctx_set_crosscheck refuses it)
+enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2, SiWave = 4, SiWg = 5, SiWgIo = 6, SiWgPrep = 7 };  // SiWave / SiWg / SiWgIo / SiWgPrep: the form of k_backward_si_dpp (same bits); AUTO elsewhere.  (3 is no pin: ilqr_ctx_set_crosscheck refuses it)
 enum class FwdPin { Auto = 0, Wg = 1, Dpp = 2, WgLds = 3 };  // WgLds: Wg with k_forward_wg, the predecessor of k_forward_reg (same bits)
 enum class RerollPin { Auto = 0, Rows = 1, Dpp = 2 };
 
@@ -106,6 +115,7 @@ struct RiccatiPlan {
     Sweep sweep = Sweep::Generic;
     int si_lanes[2] = {16, 16};   // Sweep::SiDpp: lanes per instance of the whole batch or of each half (split)
     bool si_wg[2] = {false, false};  // Sweep::SiDpp with 16 lanes: the workgroup form (SI_WG_MIN_BATCH, or the pins SiWave / SiWg), per launched half
+    bool si_prep[2] = {false, false};  // ... and the two preparing waves (SI_PREP_MIN_BATCH where AUTO takes the I/O wave, or the pin SiWgPrep; never under SiWave / SiWg / SiWgIo): only where si_io
     bool si_io[2] = {false, false};  // ... with the I/O wave (SI_IO_MIN_BATCH on an unsplit solve, or the pin SiWgIo; never under SiWave / SiWg): only where si_wg, at most one AL row
     Forward forward = Forward::Generic;
     bool fwd_lds = false;         // Forward::WaveWg under the pin FwdPin::WgLds: k_forward_wg instead of k_forward_reg
@@ -130,7 +140,7 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     // waves (measured: B = 2048 600 against 548 us, B = 4096 597 against 1040)
     if (cooperative && in.off32 && backward_si_supported(kind, nd, in.al, in.m, in.per_step, in.con_state_only)) p.sweep = Sweep::SiDpp;
     else if (cooperative && backward_mfma_supported(kind, nd, in.al, in.m)) {
-        const bool pinned = in.sweep == SweepPin::Mfma || in.sweep == SweepPin::Rows;  // (SiWave / SiWg / SiWgIo pin nothing here)
+        const bool pinned = in.sweep == SweepPin::Mfma || in.sweep == SweepPin::Rows;  // (SiWave / SiWg / SiWgIo / SiWgPrep pin nothing here)
         const bool rows = in.sweep == SweepPin::Rows || (!pinned && in.B > 2 * in.n_simd);
         p.sweep = rows && backward_rows_supported(kind, nd, in.al, in.m) ? Sweep::Rows : Sweep::Mfma;
     }
@@ -180,10 +190,12 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     // the 8-lane grouping (B > 4 n_simd) stays on the one-wave form, whatever the pin says
     const int launched[2] = {b0, in.B - b0};
     for (int h = 0; h < 2; h++) {
-        const bool wg_pin = in.sweep == SweepPin::SiWg || in.sweep == SweepPin::SiWgIo;  // (SiWgIo acts as SiWg where the I/O wave is not supported)
+        const bool io_pin = in.sweep == SweepPin::SiWgIo || in.sweep == SweepPin::SiWgPrep;  // (SiWgPrep acts as SiWgIo where the preparing waves are not supported)
+        const bool wg_pin = in.sweep == SweepPin::SiWg || io_pin;  // (SiWgIo acts as SiWg where the I/O wave is not supported)
         p.si_wg[h] = p.sweep == Sweep::SiDpp && p.si_lanes[h] == 16 && (wg_pin || (in.sweep != SweepPin::SiWave && launched[h] >= SI_WG_MIN_BATCH));
         p.si_io[h] = p.si_wg[h] && si_io_supported(in.al, in.m) &&
-                     (in.sweep == SweepPin::SiWgIo || (in.sweep != SweepPin::SiWg && !p.split && launched[h] >= SI_IO_MIN_BATCH));
+                     (io_pin || (in.sweep != SweepPin::SiWg && !p.split && launched[h] >= SI_IO_MIN_BATCH));
+        p.si_prep[h] = p.si_io[h] && (in.sweep == SweepPin::SiWgPrep || (in.sweep != SweepPin::SiWgIo && launched[h] >= SI_PREP_MIN_BATCH));
     }
     return p;
 }

@@ -170,7 +170,10 @@ int ilqr_ctx_set_split(ilqr_ctx* ctx, int on);
 #define ILQR_XC_SWEEP_SI_WAVE 4 /* sweep of the single-integrator systems: k_backward_si_dpp on lone waves at any batch size: the same bits as AUTO (3 is no sweep pin: refused) */
 #define ILQR_XC_SWEEP_SI_WG 5   /*   ... in its four-wave workgroup form without the I/O wave (16 lanes per instance only): the same bits as AUTO */
 #define ILQR_XC_SWEEP_SI_WG_IO 6 /*  ... in its workgroup form with the I/O wave, a fifth wave that stores the chain waves' gain records and their accepted x, u, the \
-                                     latter as whole 128-byte lines (16 lanes per instance, at most one constraint row; ILQR_XC_SWEEP_SI_WG elsewhere; AUTO: from \
+                                     latter as whole 128-byte lines (16 lanes per instance, at most one constraint row; ILQR_XC_SWEEP_SI_WG elsewhere; AUTO takes \
+                                     it only together with the preparing waves of the next pin): the same bits as AUTO */
+#define ILQR_XC_SWEEP_SI_WG_PREP 7 /* ... with the I/O wave and two preparing waves, which load x, u and the multipliers, blend, and form the limit and AL terms \
+                                     of every step for the chain waves (where the I/O wave is supported; ILQR_XC_SWEEP_SI_WG_IO's choice elsewhere; AUTO: from \
                                      256 launched instances of an unsplit solve): the same bits as AUTO */
 #define ILQR_XC_FWD_WG 1       /* forward pass of the single-integrator systems: the large-batch k_forward_reg (AUTO: beyond 3 n_simd instances) */
 #define ILQR_XC_FWD_DPP 2      /*   ... the latency-built k_forward_dpp (AUTO: up to 3 n_simd); agrees with the others to rounding */
