@@ -40,7 +40,7 @@ EXPORTS = [
     "ilqr_problem_closed_loop_report", "ilqr_problem_closed_loop_report_dev", "ilqr_problem_closed_loop_cov", "ilqr_problem_closed_loop_cov_dev",
     "ilqr_problem_closed_loop_report_con", "ilqr_problem_closed_loop_report_con_dev", "ilqr_problem_closed_loop_cov_con",
     "ilqr_problem_closed_loop_cov_con_dev",
-    "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck", "ilqr_problem_gains",
+    "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck", "ilqr_problem_gains", "ilqr_problem_gains_al",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
     "ilqr_lqt_get_d",
@@ -179,6 +179,7 @@ def load():
     L.ilqr_problem_reset_multipliers.argtypes = [vp]
     L.ilqr_problem_warm_start.argtypes = [vp, C.c_int]
     L.ilqr_problem_gains.argtypes = [vp]
+    L.ilqr_problem_gains_al.argtypes = [vp, C.c_double]
     L.ilqr_problem_track.argtypes = [vp, C.c_int, dp, C.c_int, dp]
     L.ilqr_problem_track_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.ilqr_problem_closed_loop.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp]
@@ -523,6 +524,13 @@ class BatchProblem:
         closed-loop calls run on them; X, U, cost, iters, status, lam and the trace are untouched.  Asynchronous on the context's stream."""
         self.ctx.crosscheck_from_env()
         self.ctx.check(self.L.ilqr_problem_gains(self.h))
+
+    def gains_al(self, penalty: float):
+        """gains() with the augmented-Lagrangian terms of the constraint rows (ilqr_problem_gains_al): the AL sweep about X(), U() with the active-set
+        weights penalty * I of that plan and the multipliers lam() as they are; no multiplier moves.  `penalty`: the one the plan's solve ended
+        with, or any other finite value >= 0."""
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_gains_al(self.h, float(penalty)))
 
     def track(self, k: int, x_meas, with_feedforward: bool = False):
         x = _f64(x_meas, (self.B, self.dims.n_x))

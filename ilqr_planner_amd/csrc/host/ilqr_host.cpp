@@ -1444,14 +1444,16 @@ static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter,
     r.U.resize((size_t)B * nU);
     r.cost.resize(B); r.alpha.resize(B); r.iters.resize(B); r.status.resize(B);
     check(ilqr_problem_get_alpha(g.p, r.alpha.data()));  // the solver's last step size: ilqr_problem_gains puts 1 there
-    if (in.plan_gains) check(ilqr_problem_gains(g.p));   // K, d about the plan the solve leaves, before any of them is read
+    // K, d about the plan the solve leaves, before any of them is read: with the AL terms of the lowered rows where AL_ILQR asks for them
+    if (in.al_gains_penalty > 0) check(ilqr_problem_gains_al(g.p, in.al_gains_penalty));
+    else if (in.plan_gains) check(ilqr_problem_gains(g.p));
     check(ilqr_problem_get_X(g.p, r.X.data()));
     check(ilqr_problem_get_U(g.p, r.U.data()));
     check(ilqr_problem_get_cost(g.p, r.cost.data()));
     check(ilqr_problem_get_iters(g.p, r.iters.data()));
     check(ilqr_problem_get_status(g.p, r.status.data()));
     if (in.want_fX) { r.fX.resize((size_t)B * T * dm.n_f); check(ilqr_problem_get_fX(g.p, r.fX.data())); }
-    if ((gains && in.want_gains && nb_iter > 0) || in.plan_gains) {
+    if ((gains && in.want_gains && nb_iter > 0) || in.plan_gains || in.al_gains_penalty > 0) {
         r.K.resize((size_t)B * nU * dm.n_x);
         r.d.resize((size_t)B * nU);
         check(ilqr_problem_get_K(g.p, r.K.data()));
@@ -1464,6 +1466,12 @@ static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter,
     }
     if (post_solve) post_solve(g.p);
     return r;
+}
+
+// BatchInputs::al_gains_penalty is AL_ILQR's: the other classes lower no constraint rows
+static void refuse_al_gains(const BatchInputs& in, const char* cls) {
+    if (in.al_gains_penalty != 0)
+        throw std::runtime_error(std::string("[") + cls + "] al_gains_penalty is honoured by AL_ILQR only (this solver lowers no constraint rows): leave it 0 and use plan_gains");
 }
 
 // the per-iteration stream of the reference ("Iteration i, Cost: c, alpha= a[, time= t]") for instance 0
@@ -1493,6 +1501,7 @@ static std::vector<Vec> rows_of(const std::vector<double>& v, int n, int w) {
 }
 
 BatchResult ILQRRecursive::solveBatch(const BatchInputs& in, int nb_iter, bool line_search, bool early_stop) {
+    refuse_al_gains(in, "ILQRRecursive");
     return run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) { check(ilqr_solve_recursive(p, nb_iter, line_search, early_stop)); }, nullptr);
 }
 
@@ -1605,6 +1614,7 @@ static void closed_loop_cov_of(ilqr_problem* p, sys::System& s, int B, const Clo
 
 std::pair<BatchResult, ClosedLoopCovResult> ILQRRecursive::closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool line_search,
                                                                               bool early_stop) {
+    refuse_al_gains(in, "ILQRRecursive");
     ClosedLoopCovResult o;
     BatchResult r = run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) { check(ilqr_solve_recursive(p, nb_iter, line_search, early_stop)); },
                               [&](ilqr_problem* p) { closed_loop_cov_of(p, *s, in.B, cv, o); });
@@ -1613,6 +1623,7 @@ std::pair<BatchResult, ClosedLoopCovResult> ILQRRecursive::closedLoopCovBatch(co
 
 std::pair<BatchResult, ClosedLoopResult> ILQRRecursive::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool line_search,
                                                                         bool early_stop) {
+    refuse_al_gains(in, "ILQRRecursive");
     ClosedLoopResult o;
     BatchResult r = run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) { check(ilqr_solve_recursive(p, nb_iter, line_search, early_stop)); },
                               [&](ilqr_problem* p) { closed_loop_of(p, *s, in.B, cl, o); });
@@ -1645,6 +1656,13 @@ std::tuple<std::vector<Vec>, std::vector<Vec>, std::vector<Vec>, std::vector<Mat
 AL_ILQR::AL_ILQR(const std::shared_ptr<sys::System>& s_, const std::vector<Constraint>& ineq, const std::vector<Vec>& initLambda)
     : s(s_), inequality(ineq), multipliers(initLambda) {}
 
+double AL_ILQR::finalPenalty(int nb_iter, int lag_update_step, double penalty, double scaling_factor) {
+    if (lag_update_step <= 0) throw std::runtime_error("[AL_ILQR] lag_update_step must be positive");
+    for (int it = 0; it < nb_iter; it++)
+        if ((it + 1) % lag_update_step == 0) penalty *= scaling_factor;  // ilqr_solve_al's own sequence of products: the same double
+    return penalty;
+}
+
 BatchResult AL_ILQR::solveBatch(const BatchInputs& in, int nb_iter, int lag, double penalty, double scaling, bool line_search, bool early_stop) {
     return solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, nullptr);
 }
@@ -1670,6 +1688,8 @@ std::pair<BatchResult, ClosedLoopCovResult> AL_ILQR::closedLoopCovBatch(const Ba
 BatchResult AL_ILQR::solveBatchThen(const BatchInputs& in, int nb_iter, int lag, double penalty, double scaling, bool line_search, bool early_stop,
                                     const std::function<void(ilqr_problem*)>& then) {
     const int T = s->getHorizon(), ns = s->getNbStateVar() + s->getNbCtrlVar();
+    if (!(std::isfinite(in.al_gains_penalty) && in.al_gains_penalty >= 0))
+        throw std::runtime_error("[AL_ILQR] al_gains_penalty must be finite and >= 0 (0: off; AL_ILQR::finalPenalty gives the one the solve ends with)");
     if ((int)inequality.size() != T - 1 || (int)multipliers.size() != T - 1)
         throw std::runtime_error("[AL_ILQR] need one Constraint and one multiplier vector per timestep (horizon-1)");
     const int m_full = inequality[0].A.rows;
@@ -1750,6 +1770,7 @@ BatchILQRCP::BatchILQRCP(const std::shared_ptr<sys::System>& s_, const Mat& psi)
 static BatchResult batch_gauss_newton(sys::System& s, const Mat* psi, const Mat* Q, const BatchInputs& in, int nb_iter, bool early_stop,
                                       const std::function<void(ilqr_problem*)>& then = nullptr) {
     const int T = s.getHorizon(), nu = s.getNbCtrlVar();
+    refuse_al_gains(in, psi ? "BatchILQRCP" : "BatchILQR");
     if (psi && psi->rows != (T - 1) * nu) throw std::runtime_error("[BatchILQRCP] psi must have (horizon-1)*nb_ctrl_var rows");
     // the sparse form of the reference stacks a target block per keypoint of the concatenated list, every sub-system's target into each of a
     // shared step's blocks (SequentialSystem.cpp:186-260); a plain System evaluates its last keypoint in the blocks of all: not reproduced

@@ -472,6 +472,11 @@ struct BatchInputs {
     // K, d of the result are the gains about the plan the solve leaves (ilqr_problem_gains: one sweep about the returned X, U, feed-forward
     // unscaled), for any solver -- the batch solvers, which leave none of their own, included; the closed loops then run on them
     bool plan_gains = false;
+    // AL_ILQR only (the other classes throw if it is set): positive = K, d of the result are the gains about the plan WITH the augmented-
+    // Lagrangian terms of the lowered rows at this penalty (ilqr_problem_gains_al: active-set weights of the plan, the multipliers the solve
+    // leaves); it implies plan_gains, and closedLoopBatch / closedLoopCovBatch run on them.  0 = off.  AL_ILQR::finalPenalty gives the
+    // penalty a solve ends with.
+    double al_gains_penalty = 0;
 };
 
 // Closed loop of the tracking law on the plan a batched Riccati solve leaves (ilqr_problem_closed_loop): S executions per instance.
@@ -567,6 +572,9 @@ public:
                                                              double scaling_factor, bool line_search = true, bool early_stop = false);
     std::pair<BatchResult, ClosedLoopCovResult> closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, int lag_update_step,
                                                                    double penalty, double scaling_factor, bool line_search = true, bool early_stop = false);
+    // the penalty a solve of nb_iter iterations ends with: penalty *= scaling_factor once per update iteration ((it + 1) % lag_update_step == 0),
+    // formed as the solver forms it (the same double) -- what BatchInputs::al_gains_penalty wants for the gains about that solve's plan
+    static double finalPenalty(int nb_iter, int lag_update_step, double penalty, double scaling_factor);
 
 private:
     BatchResult solveBatchThen(const BatchInputs& in, int nb_iter, int lag_update_step, double penalty, double scaling_factor, bool line_search, bool early_stop,

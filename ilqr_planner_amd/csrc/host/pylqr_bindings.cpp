@@ -70,6 +70,12 @@ static solver::BatchInputs plan_gains(solver::BatchInputs in, bool on) {
     return in;
 }
 
+// AL_ILQR: al_gains_penalty = p: K, d are the gains about that plan with the AL terms of the lowered rows at penalty p (ilqr_problem_gains_al)
+static solver::BatchInputs al_gains(solver::BatchInputs in, const py::object& penalty) {
+    if (!penalty.is_none()) in.al_gains_penalty = penalty.cast<double>();
+    return in;
+}
+
 // numpy -> BatchInputs: U0 [B][T-1][n_u] or [T-1][n_u]; q0/dq0 [B][dof] or None; kp_targets list of [B][n_f] or None
 static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& q0, const py::object& dq0, const py::object& kp_targets, bool flat_u = false) {
     solver::BatchInputs in;
@@ -409,30 +415,36 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("line_search"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
-                const py::object& kp, bool pg) { return self.solveBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), nb_iter, lag, pen, sc, ls, es); },
+                const py::object& kp, bool pg, const py::object& agp) {
+                 return self.solveBatch(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), nb_iter, lag, pen, sc, ls, es);
+             },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
-             py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
+             py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
+             py::arg("al_gains_penalty") = py::none())
+        .def_static("final_penalty", &solver::AL_ILQR::finalPenalty, py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"))
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
                 const py::object& kp, const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed,
-                const py::object& sigma_w, const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol, bool pg, const py::object& con_tol) {
-                 return self.closedLoopBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg),
+                const py::object& sigma_w, const py::object& sigma_x0, const py::object& kp_tol, const py::object& lim_tol, bool pg, const py::object& con_tol,
+                const py::object& agp) {
+                 return self.closedLoopBatch(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp),
                                              closed_loop_inputs(x0, w, samples, ff, seed, sigma_w, sigma_x0, kp_tol, lim_tol, con_tol), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("x0") = py::none(),
              py::arg("w") = py::none(), py::arg("with_feedforward") = false, py::arg("samples") = py::none(), py::arg("seed") = py::none(),
              py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none(), py::arg("plan_gains") = false,
-             py::arg("con_tol") = py::none())
+             py::arg("con_tol") = py::none(), py::arg("al_gains_penalty") = py::none())
         .def("closed_loop_cov_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
-                const py::object& kp, const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg, bool want_con) {
-                 return self.closedLoopCovBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma, want_con), nb_iter, lag, pen, sc, ls, es);
+                const py::object& kp, const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg, bool want_con,
+                const py::object& agp) {
+                 return self.closedLoopCovBatch(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma, want_con), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
              py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("plan_gains") = false,
-             py::arg("want_con") = false);
+             py::arg("want_con") = false, py::arg("al_gains_penalty") = py::none());
     // bindings.cpp:778-782
     py::class_<solver::BatchILQR>(m_sol, "BatchILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("Q"))

@@ -875,14 +875,16 @@ extern "C" int ilqr_solve_batch(ilqr_problem* p, int nb_iter, int early_stop) {
 // pending when it starts: the fused path applies the last winner itself (Apply::WaveLast on the last iteration, and an instance that stopped
 // early before it is applied by the following sweep), every other path applies or flips inside the iteration that decided, and the batch
 // solvers clear `pend` in their rollout and never set it.  So X[cur], U[cur] are the plan of every instance, active or not.
-extern "C" int ilqr_problem_gains(ilqr_problem* p) {
-    if (!p) return 1;
+//
+// With al (ilqr_problem_gains_al): the backward pass of AL-ILQR.cpp:94-145, i.e. the sweep chosen for ilqr_solve_al(p, 1, ..) with the active-set
+// weights of the held plan and the multipliers as they are -- k_gains_al_weights forms Is for the sweeps that read it; the fused sweep forms its
+// weights itself from SweepArgs::pen_in.  Is is scratch: every AL solve re-forms it before a sweep reads it (k_init_rollout<.., AL> on the generic
+// path, k_al_post at it = -1 behind the LTI rollout, and the fused sweep never reads it), and nothing else reads it.
+static int gains_about_plan(ilqr_problem* p, bool al, double penalty) {
     ilqr_ctx* c = p->ctx;
-    if (!p->has_plan)
-        return fail(c, "ilqr_problem_gains needs a plan: run a solver since the problem's inputs last changed (ilqr_solve_recursive with nb_iter = 0 rolls out the controls as they are)");
     HIPCHK(c, hipSetDevice(c->device));
     const int kind = p->desc.kind, nd = p->desc.nb_deriv;
-    const RiccatiPlan pl = plan_riccati(plan_input(p, false, 1, 1));
+    const RiccatiPlan pl = plan_riccati(plan_input(p, al, 1, 1));
     p->has_gains = false;  // until the sweep is queued
     p->bufs.kd_sym = pl.kd_sym;  // before half_bufs: it sizes the half's offset into KD
     if (pl.needs_ws && !p->bufs.ws)
@@ -893,7 +895,7 @@ extern "C" int ilqr_problem_gains(ilqr_problem* p) {
     SplitJoin split_join{c, pl.split};  // on every exit path
     const FwdArgs f = plan_fwd_args(p, pl);
     SweepArgs sw;
-    sw.pen_in = 0.0; sw.pen_update_prev = 0.0; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0; sw.si_prep = 0;
+    sw.pen_in = penalty; sw.pen_update_prev = penalty; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0; sw.si_prep = 0;
     for (int h = 0; h < nh; h++) {
         const Bufs& bf = hv[h].bufs;
         const int B = hv[h].B;
@@ -902,19 +904,42 @@ extern "C" int ilqr_problem_gains(ilqr_problem* p) {
             ProfScope ps(c, ILQR_PROF_OTHER);
             launch_gains_prepare(bf, B, st);
         }
+        if (al && !pl.fused) {  // the sweeps that read Is
+            ProfScope ps(c, ILQR_PROF_OTHER);
+            launch_gains_al_weights(kind, nd, bf, B, p->T, penalty, st);
+        }
         {
             ProfScope ps(c, ILQR_PROF_OTHER);
             launch_kp_derivs(kind, nd, bf, B, st, f);
         }
         {
             ProfScope ps(c, ILQR_PROF_BACKWARD);
-            launch_sweep(p, pl, h, false, bf, B, st, sw);
+            launch_sweep(p, pl, h, al, bf, B, st, sw);
         }
     }
     HIPCHK(c, hipGetLastError());
     prof_mark(c, -1);
     p->has_gains = true;
     return 0;
+}
+
+extern "C" int ilqr_problem_gains(ilqr_problem* p) {
+    if (!p) return 1;
+    if (!p->has_plan)
+        return fail(p->ctx, "ilqr_problem_gains needs a plan: run a solver since the problem's inputs last changed (ilqr_solve_recursive with nb_iter = 0 rolls out the controls as they are)");
+    return gains_about_plan(p, false, 0.0);
+}
+
+extern "C" int ilqr_problem_gains_al(ilqr_problem* p, double penalty) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    if (p->bufs.m <= 0)
+        return fail(c, "ilqr_problem_gains_al needs constraint rows: call ilqr_problem_set_constraints, then a solver (ilqr_problem_gains sweeps without them)");
+    if (!p->has_plan)
+        return fail(c, "ilqr_problem_gains_al needs a plan: run a solver since the problem's inputs and constraints last changed (ilqr_solve_al with nb_iter = 0 rolls out the controls as they are)");
+    if (!(std::isfinite(penalty) && penalty >= 0.0))
+        return fail(c, "ilqr_problem_gains_al: the penalty must be finite and >= 0 (got " + std::to_string(penalty) + "): pass the penalty the plan's solve ended with, or its initial one");
+    return gains_about_plan(p, true, penalty);
 }
 
 // ------------------------------------------------------------------------------------------------ results

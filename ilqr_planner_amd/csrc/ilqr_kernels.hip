@@ -78,6 +78,28 @@ __global__ __launch_bounds__(64) void k_gains_prepare(Bufs a) {
     a.alpha[b] = 1.0;
 }
 
+// ilqr_problem_gains_al: the active-set weights penalty * I_k of the held plan for the sweeps that read Is (AL-ILQR.cpp:21-44,190), one lane per
+// (instance, step): g by con_g on X[cur], U[cur] -- the expression k_init_rollout and k_al_post evaluate on the same bytes, so the weights are the
+// ones a fresh solve about this plan would form -- with the multipliers as they are.  Unlike k_al_post it looks at no iteration count and updates
+// no multiplier: every instance gets its weights, and only Is is written.
+template <class S>
+__global__ __launch_bounds__(256) void k_gains_al_weights(Bufs a, double penalty) {
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    const int k = blockIdx.y;
+    if (b >= d.B) return;
+    const int Bp = d.Bp;
+    const int cur = a.cur[b];
+    double x[S::NX], u[S::NU];
+    UNR for (int i = 0; i < S::NX; i++) x[i] = AT(a.X[cur], k * S::NX + i, b);
+    UNR for (int i = 0; i < S::NU; i++) u[i] = AT(a.U[cur], k * S::NU + i, b);
+    for (int r = 0; r < a.m; r++) {
+        const double g = con_g<S>(a, k, r, x, u);
+        const double lam = AT(a.lambda, k * a.m + r, b);
+        AT(a.Is, k * a.m + r, b) = penalty * ((g < 0 && lam == 0) ? 0.0 : 1.0);
+    }
+}
+
 // l_x, l_xx of the keypoint steps (System::cost_x / cost_xx incl. the limit terms) for the current trajectory, one lane per
 // (instance, keypoint).  Keeps FK, the quaternion log map and J'QJ out of the sequential sweep: the sweep only loads
 // NX + NX*NX doubles at the (two) keypoint steps.
@@ -1185,6 +1207,12 @@ void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, co
 }
 
 void launch_gains_prepare(const Bufs& a, int B, hipStream_t st) { hipLaunchKernelGGL(k_gains_prepare, dim3((B + 63) / 64), dim3(64), 0, st, a); }
+
+void launch_gains_al_weights(int kind, int nd, const Bufs& a, int B, int T, double penalty, hipStream_t st) {
+    SysAll::dispatch(kind, nd, [&](auto s) {
+        hipLaunchKernelGGL((k_gains_al_weights<decltype(s)>), dim3((B + 255) / 256, T - 1), dim3(256), 0, st, a, penalty);
+    });
+}
 
 void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty) {
     SysAll::dispatch(kind, nd, [&](auto s) {

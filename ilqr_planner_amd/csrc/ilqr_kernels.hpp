@@ -87,6 +87,7 @@ struct SweepArgs {
 // generic lane-per-instance kernels (ilqr_kernels.hip)
 void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty);  // k_init_rollout
 void launch_gains_prepare(const Bufs& a, int B, hipStream_t st);  // k_gains_prepare: every instance active, alpha = 1 (ilqr_problem_gains)
+void launch_gains_al_weights(int kind, int nd, const Bufs& a, int B, int T, double penalty, hipStream_t st);  // k_gains_al_weights: Is of the held plan (ilqr_problem_gains_al, the sweeps that read Is)
 void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // l_x, l_xx at the keypoint steps (FK + Jacobian), feeding every sweep
 void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // k_backward, needs Bufs::ws
 int backward_ws_entries(int kind, int nd);  // doubles per instance of k_backward's workspace

@@ -281,6 +281,23 @@ int ilqr_problem_track_dev(ilqr_problem* p, int k, const double* x_meas, int wit
  * ilqr_problem_warm_start changes the plan or its inputs.  Fails unless one of the four solvers has run since the problem's inputs last changed.
  * Asynchronous on the context's stream. */
 int ilqr_problem_gains(ilqr_problem* p);
+/* The same about the plan of a constrained problem, with the augmented-Lagrangian terms of the rows of ilqr_problem_set_constraints: one backward
+ * pass of AL-ILQR.cpp:94-145 about the X, U the problem holds, whichever solver left them (nb_iter = 0 included).  The gains of ilqr_problem_gains
+ * pull an execution back to the plan but not to the feasible side; the leftovers of an ilqr_solve_al belong to the trajectory before its last step.
+ *   cost      what ilqr_problem_gains sweeps, plus c_u' I c_u, c_u' I c_x, c_x' I c_x on Quu, Qux, Qxx and c' (lambda + I g) on Qu, Qx.
+ *   weights   I_k[r] = penalty * ((g_k[r] < 0 && lambda_k[r] == 0) ? 0 : 1) (AL-ILQR.cpp:21-44,190) with g on the held plan and lambda the
+ *             multipliers the problem holds now (ilqr_problem_get_lambda).  No multiplier is updated.  `penalty` is the caller's: the one a solve
+ *             ended with is penalty0 * scaling^(nb_iter / lag_update_step), formed by repeated multiplication.
+ *   writes    K_k, d_k as ilqr_problem_gains does (unscaled feed-forward, ilqr_problem_get_alpha 1.0; instances with ILQR_STATUS_NONFINITE or
+ *             ILQR_STATUS_SWEEP_IO get unspecified gains and keep their status), and the internal active-set weights, which every AL solve forms anew.
+ *   keeps     X, U, fX, cost, iters, status, lambda and the cost / alpha trace, bit for bit.
+ *   runs      k_gains_prepare, k_gains_al_weights where the sweep reads stored weights, k_kp_derivs and the sweep chosen for ilqr_solve_al(p, 1, ..)
+ *             on this problem under the context's pins; no rollout, no forward pass, no multiplier update.  ILQR_PROF_OTHER and ILQR_PROF_BACKWARD.
+ *   bits      under fixed pins, ilqr_problem_set_constraints(.., lambda), ilqr_problem_set_controls, a 0-iteration ilqr_solve_al and this call give
+ *             the K of a fresh ilqr_solve_al(p, 1, 2, penalty, 1.0, 1, 0) from the same inputs byte for byte, and that solve's d is alpha times this call's.
+ * Fails without constraint rows, unless a solver has run since the problem's inputs and constraints last changed, and for a penalty that is
+ * negative or not finite.  Afterwards as ilqr_problem_gains; a later ilqr_problem_gains overwrites the records with the plain gains. */
+int ilqr_problem_gains_al(ilqr_problem* p, double penalty);
 /* Closed loop of that law on the plan of the last Riccati solve (or the plan ilqr_problem_gains swept about): n_samples executions of every instance,
  *   x_0 = x0[b][s] (NULL: xbar_0);  u_k = ilqr_problem_track(k, x_k, with_feedforward);  x_{k+1} = f(x_k, u_k) + w[b][s][k] (NULL: none);
  *   cost[b][s] = sum_{k<T-1} cost(x_k, u_k, k) + cost(x_{T-1}, 0, T-1)     (the system's stage cost, no AL terms: what ilqr_solve_recursive reports),
