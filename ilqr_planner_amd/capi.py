@@ -23,6 +23,7 @@ KP_ERR, KP_STATS, CL_OUTCOME = 5, 12, 4  # ILQR_KP_ERR (pos, orn, vel, angvel, t
 CL_CON_STATS, CL_OUTCOME_CON = 6, 5  # ILQR_CL_CON_STATS (mean/max con_max, mean/max con_steps, n_con, n_bad), ILQR_CL_OUTCOME_CON (n_ok, n_miss, n_lim, n_con, n_bad)
 KP_ERR_POS, KP_ERR_ORN, KP_ERR_VEL, KP_ERR_ANGVEL, KP_ERR_TIME = range(5)
 PROF_ROLLOUT, PROF_BACKWARD, PROF_FORWARD, PROF_OTHER, PROF_APPLY = 0, 1, 2, 3, 4
+ADOPT_STATE, ADOPT_TARGETS, ADOPT_CONTROLS0, ADOPT_CONTROLS, ADOPT_MULTIPLIERS = 1, 2, 4, 8, 16  # ILQR_ADOPT_* (bits of ilqr_problem_adopt's `what`)
 
 # every symbol include/ilqr_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
@@ -41,6 +42,8 @@ EXPORTS = [
     "ilqr_problem_closed_loop_report_con", "ilqr_problem_closed_loop_report_con_dev", "ilqr_problem_closed_loop_cov_con",
     "ilqr_problem_closed_loop_cov_con_dev",
     "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck", "ilqr_problem_gains", "ilqr_problem_gains_al",
+    "ilqr_problem_adopt", "ilqr_problem_adopt_dev", "ilqr_problem_spread_controls", "ilqr_problem_spread_controls_dev",
+    "ilqr_problem_select", "ilqr_problem_select_dev", "ilqr_problem_get_at", "ilqr_problem_get_at_dev",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
     "ilqr_lqt_get_d",
@@ -104,6 +107,12 @@ class Noise(C.Structure):
                 ("sigma_x0", C.c_double * MAX_NX)]
 
 
+class Seeds(C.Structure):
+    """Mirror of ilqr_seeds."""
+
+    _fields_ = [("seed", C.c_ulonglong), ("group_offset", C.c_uint), ("member_offset", C.c_uint), ("sigma_u", C.c_double * MAX_NU)]
+
+
 class Tol(C.Structure):
     """Mirror of ilqr_cl_tol."""
 
@@ -139,6 +148,8 @@ ClosedLoopReportCon = collections.namedtuple("ClosedLoopReportCon", "cost stats 
 ClosedLoopCovCon = collections.namedtuple("ClosedLoopCovCon", "Sigma kp_Sigma kp_var u_var lim_z con_var con_z")
 ClosedLoopNoise = collections.namedtuple("ClosedLoopNoise", "cost stats X U w")
 ClosedLoopReport = collections.namedtuple("ClosedLoopReport", "cost stats kp_err kp_stats lim_cost outcome X U w")
+Selection = collections.namedtuple("Selection", "winner best n_candidates")
+Rows = collections.namedtuple("Rows", "X U cost iters status")
 
 _lib = None
 
@@ -180,6 +191,14 @@ def load():
     L.ilqr_problem_warm_start.argtypes = [vp, C.c_int]
     L.ilqr_problem_gains.argtypes = [vp]
     L.ilqr_problem_gains_al.argtypes = [vp, C.c_double]
+    for n in ("ilqr_problem_adopt", "ilqr_problem_adopt_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, C.c_int]
+    for n in ("ilqr_problem_spread_controls", "ilqr_problem_spread_controls_dev"):
+        getattr(L, n).argtypes = [vp, C.c_int, C.POINTER(Seeds)]
+    for n in ("ilqr_problem_select", "ilqr_problem_select_dev"):
+        getattr(L, n).argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    for n in ("ilqr_problem_get_at", "ilqr_problem_get_at_dev"):
+        getattr(L, n).argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.ilqr_problem_track.argtypes = [vp, C.c_int, dp, C.c_int, dp]
     L.ilqr_problem_track_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.ilqr_problem_closed_loop.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp]
@@ -743,6 +762,70 @@ class BatchProblem:
         co = CovCon(con_var_ptr or None, con_z_ptr or None)
         self.ctx.crosscheck_from_env()
         self.ctx.check(self.L.ilqr_problem_closed_loop_cov_con_dev(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)), C.byref(cv), C.byref(co)))
+
+    # ---- multi-start: the calls that join instances (include/ilqr_hip.h "multi-start")
+    @staticmethod
+    def _i32(a, n=None):
+        a = np.ascontiguousarray(np.asarray(a), dtype=np.int32)
+        if a.ndim != 1 or (n is not None and a.shape[0] != n):
+            raise ValueError(f"expected {n if n is not None else 'a vector of'} ints, got shape {a.shape}")
+        return a
+
+    def adopt(self, src: "BatchProblem", index, what: int):
+        """Instance i of this problem takes from instance index[i] of `src` what the ADOPT_* bits of `what` name (ilqr_problem_adopt): device to
+        device.  index: B ints in 0 .. src.B-1 (index[b] = b // S replicates G tasks over G * S instances)."""
+        idx = self._i32(index, self.B)
+        self.ctx.check(self.L.ilqr_problem_adopt(self.h, src.h, idx.ctypes.data, int(what)))
+
+    def adopt_dev(self, src: "BatchProblem", index_ptr, what: int):
+        """index_ptr: B ints in device memory (clamped into src's batch by the kernel); asynchronous on the context's stream."""
+        self.ctx.check(self.L.ilqr_problem_adopt_dev(self.h, src.h, index_ptr, int(what)))
+
+    def _seeds(self, seed, sigma_u, group_offset, member_offset):
+        sd = Seeds(int(seed), int(group_offset), int(member_offset))
+        for i, v in enumerate(np.broadcast_to(np.asarray(sigma_u, dtype=np.float64), (self.dims.n_u,))):
+            sd.sigma_u[i] = float(v)
+        return sd
+
+    def spread_controls(self, group_size: int, seed: int, sigma_u, group_offset: int = 0, member_offset: int = 0):
+        """The starts of every group of `group_size` instances (ilqr_problem_spread_controls): member 0 keeps its U0, every other member gets
+        U0 += sigma_u * z; sigma_u: a scalar or n_u values in the user's control layout.  Asynchronous on the context's stream."""
+        self.ctx.check(self.L.ilqr_problem_spread_controls(self.h, int(group_size), C.byref(self._seeds(seed, sigma_u, group_offset, member_offset))))
+
+    def spread_controls_dev(self, group_size: int, seed: int, sigma_u, group_offset: int = 0, member_offset: int = 0):
+        self.ctx.check(self.L.ilqr_problem_spread_controls_dev(self.h, int(group_size), C.byref(self._seeds(seed, sigma_u, group_offset, member_offset))))
+
+    def select(self, group_size: int, score=None, eligible=None, want_winner: bool = True, want_best: bool = True, want_n_candidates: bool = True):
+        """The best member of every group (ilqr_problem_select): score [B] or None (the cost), eligible [B] ints or None (all).  Returns a Selection
+        (winner [G] int32, best [G], n_candidates [G] int32); what was not asked for is None."""
+        G = self.B // int(group_size) if int(group_size) >= 1 else 0
+        sc = _f64(score, (self.B,)) if score is not None else None
+        el = self._i32(eligible, self.B) if eligible is not None else None
+        win = np.empty(G, dtype=np.int32) if want_winner else None
+        best = np.empty(G) if want_best else None
+        nc = np.empty(G, dtype=np.int32) if want_n_candidates else None
+        self.ctx.check(self.L.ilqr_problem_select(self.h, int(group_size), *(a.ctypes.data if a is not None else None for a in (sc, el, win, best, nc))))
+        return Selection(win, best, nc)
+
+    def select_dev(self, group_size: int, score_ptr=None, eligible_ptr=None, winner_ptr=None, best_ptr=None, n_candidates_ptr=None):
+        """Device pointers (0 / None: the cost, all eligible, output not asked for); asynchronous on the context's stream."""
+        self.ctx.check(self.L.ilqr_problem_select_dev(self.h, int(group_size), score_ptr or None, eligible_ptr or None, winner_ptr or None,
+                                                      best_ptr or None, n_candidates_ptr or None))
+
+    def get_at(self, index, want_X: bool = True, want_U: bool = True, want_cost: bool = True, want_iters: bool = True, want_status: bool = True):
+        """Rows index[0 .. n-1] of X(), U(), cost(), iters(), status() (ilqr_problem_get_at).  Returns a Rows; what was not asked for is None."""
+        idx = self._i32(index)
+        n = idx.shape[0]
+        X, U, cost = _out(want_X, n, self.T, self.dims.n_x), _out(want_U, n, self.T - 1, self.dims.n_u), _out(want_cost, n)
+        it = np.empty(n, dtype=np.int32) if want_iters else None
+        st = np.empty(n, dtype=np.int32) if want_status else None
+        self.ctx.check(self.L.ilqr_problem_get_at(self.h, n, idx.ctypes.data, *(a.ctypes.data if a is not None else None for a in (X, U, cost, it, st))))
+        return Rows(X, U, cost, it, st)
+
+    def get_at_dev(self, n: int, index_ptr, X_ptr=None, U_ptr=None, cost_ptr=None, iters_ptr=None, status_ptr=None):
+        """Device pointers (0 / None where the output is not asked for; indices clamped by the kernel); asynchronous on the context's stream."""
+        self.ctx.check(self.L.ilqr_problem_get_at_dev(self.h, int(n), index_ptr, X_ptr or None, U_ptr or None, cost_ptr or None, iters_ptr or None,
+                                                      status_ptr or None))
 
     def close(self):
         if self.h:

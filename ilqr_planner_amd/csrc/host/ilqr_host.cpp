@@ -1505,6 +1505,74 @@ BatchResult ILQRRecursive::solveBatch(const BatchInputs& in, int nb_iter, bool l
     return run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) { check(ilqr_solve_recursive(p, nb_iter, line_search, early_stop)); }, nullptr);
 }
 
+// ---- multi-start (include/ilqr_hip.h "multi-start")
+struct MultiStartOut {
+    std::vector<int> winner, n_candidates, coarse_iters;   // [G]; coarse_iters: the iterations the winner's coarse solve ran
+    std::vector<double> coarse_best, coarse_first;         // [G]
+};
+
+// Steps 2 to 7 of solveMultiStart on the task problem pg, which run_batch has loaded from the caller's inputs: a problem of G * S starts adopts
+// the tasks (index b / S), its controls are spread, every start runs the coarse solve, the best of each group is selected by cost, pg adopts the
+// winners' controls (and multipliers: al) and runs the caller's solve.  rows(q, B): the constraint rows of a problem of B instances (al) or null;
+// solve(q, stage): stage 0 the coarse iterations, stage 1 the caller's.  The plans, controls and multipliers never leave the device; the index
+// of the replication (G * S ints) goes up once, and what the selection returns is part of the result.
+static void multi_start(sys::System& s, ilqr_problem* pg, int G, const MultiStartInputs& ms, bool al, const std::function<void(ilqr_problem*, int)>& rows,
+                        const std::function<void(ilqr_problem*, int)>& solve, MultiStartOut& o) {
+    const int nu = s.getNbCtrlVar();
+    if (ms.S < 1) throw std::runtime_error("[solveMultiStart] S must be >= 1");
+    if (ms.coarse_iter < 0) throw std::runtime_error("[solveMultiStart] coarse_iter must be >= 0");
+    if ((long long)G * ms.S > 0x7fffffffLL) throw std::runtime_error("[solveMultiStart] G * S exceeds the largest batch");
+    if (!ms.sigma_u.empty() && ms.sigma_u.size() != 1 && (int)ms.sigma_u.size() != nu)
+        throw std::runtime_error("[solveMultiStart] sigma_u must be empty, one value or nb_ctrl_var values");
+    const int S = ms.S, B = G * S;
+    ilqr_problem_desc d;
+    s.lower(&d);
+    ProblemGuard starts;
+    check(ilqr_problem_create(device_context(), &d, B, &starts.p));
+    if (rows) rows(starts.p, B);
+    std::vector<int> rep(B), first(G);
+    for (int b = 0; b < B; b++) rep[b] = b / S;
+    for (int g = 0; g < G; g++) first[g] = g * S;
+    check(ilqr_problem_adopt(starts.p, pg, rep.data(), ILQR_ADOPT_STATE | ILQR_ADOPT_TARGETS | ILQR_ADOPT_CONTROLS0));
+    ilqr_seeds sd;
+    std::memset(&sd, 0, sizeof(sd));
+    sd.seed = ms.seed;
+    for (int i = 0; i < nu && !ms.sigma_u.empty(); i++) sd.sigma_u[i] = ms.sigma_u.size() == 1 ? ms.sigma_u[0] : ms.sigma_u[i];
+    check(ilqr_problem_spread_controls(starts.p, S, &sd));
+    solve(starts.p, 0);
+    o.winner.resize(G); o.n_candidates.resize(G); o.coarse_iters.resize(G); o.coarse_best.resize(G); o.coarse_first.resize(G);
+    check(ilqr_problem_select(starts.p, S, nullptr, nullptr, o.winner.data(), o.coarse_best.data(), o.n_candidates.data()));
+    {   // member 0's coarse cost and the iterations the winner's coarse solve ran, in one call: rows first[0 .. G-1], winner[0 .. G-1]
+        std::vector<int> at(first), it(2 * (size_t)G);
+        at.insert(at.end(), o.winner.begin(), o.winner.end());
+        std::vector<double> cost(2 * (size_t)G);
+        check(ilqr_problem_get_at(starts.p, 2 * G, at.data(), nullptr, nullptr, cost.data(), it.data(), nullptr));
+        std::copy(cost.begin(), cost.begin() + G, o.coarse_first.begin());
+        std::copy(it.begin() + G, it.end(), o.coarse_iters.begin());
+    }
+    check(ilqr_problem_adopt(pg, starts.p, o.winner.data(), ILQR_ADOPT_CONTROLS | (al ? ILQR_ADOPT_MULTIPLIERS : 0)));
+    solve(pg, 1);
+}
+
+static MultiStartResult multi_start_result(BatchResult&& r, const MultiStartInputs& ms, MultiStartOut&& o) {
+    MultiStartResult m;
+    static_cast<BatchResult&>(m) = std::move(r);
+    m.S = ms.S;
+    m.winner = std::move(o.winner); m.n_candidates = std::move(o.n_candidates);
+    m.coarse_best = std::move(o.coarse_best); m.coarse_first = std::move(o.coarse_first);
+    return m;
+}
+
+MultiStartResult ILQRRecursive::solveMultiStart(const BatchInputs& in, const MultiStartInputs& ms, int nb_iter, bool line_search, bool early_stop) {
+    refuse_al_gains(in, "ILQRRecursive");
+    MultiStartOut o;
+    BatchResult r = run_batch(*s, in, nb_iter, true, nullptr, nullptr, [&](ilqr_problem* p) {
+        multi_start(*s, p, in.B, ms, false, nullptr,
+                    [&](ilqr_problem* q, int stage) { check(ilqr_solve_recursive(q, stage == 0 ? ms.coarse_iter : nb_iter, line_search, early_stop)); }, o);
+    }, nullptr);
+    return multi_start_result(std::move(r), ms, std::move(o));
+}
+
 // ilqr_problem_closed_loop_report for the same executions: the rollout is repeated (same inputs, same bits), so that what closed_loop_of
 // returns without tolerances stays exactly what it was
 static void closed_loop_report_of(ilqr_problem* p, sys::System& s, int B, const ClosedLoopInputs& cl, const ilqr_noise* nz, ClosedLoopResult& o) {
@@ -1667,6 +1735,13 @@ BatchResult AL_ILQR::solveBatch(const BatchInputs& in, int nb_iter, int lag, dou
     return solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, nullptr);
 }
 
+MultiStartResult AL_ILQR::solveMultiStart(const BatchInputs& in, const MultiStartInputs& ms, int nb_iter, int lag, double penalty, double scaling, bool line_search,
+                                          bool early_stop) {
+    MultiStartOut o;
+    BatchResult r = solveBatchThen(in, nb_iter, lag, penalty, scaling, line_search, early_stop, nullptr, &ms, &o);
+    return multi_start_result(std::move(r), ms, std::move(o));
+}
+
 std::pair<BatchResult, ClosedLoopResult> AL_ILQR::closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, int lag, double penalty,
                                                                   double scaling, bool line_search, bool early_stop) {
     ClosedLoopResult o;
@@ -1686,7 +1761,7 @@ std::pair<BatchResult, ClosedLoopCovResult> AL_ILQR::closedLoopCovBatch(const Ba
 
 // the batched solve; `then` (or null) runs on the solved problem before it is released
 BatchResult AL_ILQR::solveBatchThen(const BatchInputs& in, int nb_iter, int lag, double penalty, double scaling, bool line_search, bool early_stop,
-                                    const std::function<void(ilqr_problem*)>& then) {
+                                    const std::function<void(ilqr_problem*)>& then, const MultiStartInputs* ms, MultiStartOut* mo) {
     const int T = s->getHorizon(), ns = s->getNbStateVar() + s->getNbCtrlVar();
     if (!(std::isfinite(in.al_gains_penalty) && in.al_gains_penalty >= 0))
         throw std::runtime_error("[AL_ILQR] al_gains_penalty must be finite and >= 0 (0: off; AL_ILQR::finalPenalty gives the one the solve ends with)");
@@ -1727,7 +1802,21 @@ BatchResult AL_ILQR::solveBatchThen(const BatchInputs& in, int nb_iter, int lag,
     std::vector<double> lam_out;
     BatchResult r = run_batch(
         *s, in, nb_iter, false, nullptr, [&](ilqr_problem* p) { check(ilqr_problem_set_constraints(p, m, per_step ? 1 : 0, A.data(), b.data(), lam.data())); },
-        [&](ilqr_problem* p) { check(ilqr_solve_al(p, nb_iter, lag, penalty, scaling, line_search, early_stop)); },
+        [&](ilqr_problem* p) {
+            if (!ms) { check(ilqr_solve_al(p, nb_iter, lag, penalty, scaling, line_search, early_stop)); return; }
+            // multi-start: the starts carry the same rows and initial multipliers; the polishing solve continues the coarse one's penalty
+            multi_start(*s, p, in.B, *ms, true,
+                        [&](ilqr_problem* q, int Bq) {
+                            std::vector<double> lq((size_t)Bq * (T - 1) * m);
+                            for (size_t e = 0; e < lq.size(); e++) lq[e] = lam[e % ((size_t)(T - 1) * m)];
+                            check(ilqr_problem_set_constraints(q, m, per_step ? 1 : 0, A.data(), b.data(), lq.data()));
+                        },
+                        [&](ilqr_problem* q, int stage) {
+                            if (stage == 0) check(ilqr_solve_al(q, ms->coarse_iter, lag, penalty, scaling, line_search, early_stop));
+                            else check(ilqr_solve_al(q, nb_iter, lag, finalPenalty(ms->coarse_iter, lag, penalty, scaling), scaling, line_search, early_stop));
+                        },
+                        *mo);
+        },
         [&](ilqr_problem* p) {
             lam_out.resize(lam.size());
             check(ilqr_problem_get_lambda(p, lam_out.data()));
@@ -1735,6 +1824,19 @@ BatchResult AL_ILQR::solveBatchThen(const BatchInputs& in, int nb_iter, int lag,
         });
     // persist instance 0's multipliers (the reference's `multipliers` member)
     double pen = penalty;
+    if (ms) {   // the dropped rows of task 0 through the coarse iterations of its winner, then through the polishing solve from that solve's penalty
+        const int it_coarse = mo->coarse_iters.empty() ? 0 : mo->coarse_iters[0];
+        for (int it = 0; it < it_coarse; it++) {
+            if ((it + 1) % lag == 0) {
+                pen *= scaling;
+                for (int k = 0; k < T - 1; k++)
+                    for (int r_ = 0; r_ < m_full; r_++)
+                        if (std::find(keep.begin(), keep.end(), r_) == keep.end())
+                            multipliers[k][r_] = std::max(0.0, multipliers[k][r_] + pen * (0.0 - inequality[k].b[r_]));
+            }
+        }
+        pen = finalPenalty(ms->coarse_iter, lag, penalty, scaling);
+    }
     const int it_run = r.iters.empty() ? 0 : r.iters[0];
     for (int it = 0; it < it_run; it++) {
         if ((it + 1) % lag == 0) {

@@ -479,6 +479,23 @@ struct BatchInputs {
     double al_gains_penalty = 0;
 };
 
+// Multi-start (include/ilqr_hip.h "multi-start"): every task of a BatchInputs (in.B = G tasks) is solved from S starts on G * S instances --
+// member 0 from the task's own U0, the others from U0 + sigma_u z (ilqr_problem_spread_controls) -- for coarse_iter iterations; the start with
+// the lowest cost wins its group (ilqr_problem_select), and its plan is polished by the caller's nb_iter iterations on the G problem.
+struct MultiStartInputs {
+    int S = 1;                      // starts per task
+    unsigned long long seed = 0;
+    std::vector<double> sigma_u;    // one value (every control entry) or n_u values in the user's layout; empty: 0
+    int coarse_iter = 1;            // iterations every start runs before the selection
+};
+// The usual result of the G tasks (the polished plans; cost_trace / alpha_trace are the polishing solve's) and what the selection saw
+struct MultiStartResult : BatchResult {
+    int S = 0;
+    std::vector<int> winner, n_candidates;           // [G]: the winning instance g * S + s, the number of candidates of the group
+    std::vector<double> coarse_best, coarse_first;   // [G]: the winner's cost after the coarse iterations, member 0's
+};
+struct MultiStartOut;   // ilqr_host.cpp
+
 // Closed loop of the tracking law on the plan a batched Riccati solve leaves (ilqr_problem_closed_loop): S executions per instance.
 struct ClosedLoopInputs {
     int S = 1;
@@ -549,6 +566,8 @@ public:
     std::tuple<std::vector<Vec>, std::vector<Vec>, std::vector<Vec>, std::vector<Mat>, std::vector<Vec>, double> solve(
         const std::vector<Vec>& U0, int nb_iter, bool line_search = true, bool early_stop = true, CallBackMessage* cb = nullptr);
     BatchResult solveBatch(const BatchInputs& in, int nb_iter, bool line_search = true, bool early_stop = true);
+    // every task from ms.S starts: adopt, spread_controls, ms.coarse_iter iterations, select by cost, adopt the winners' controls, nb_iter iterations
+    MultiStartResult solveMultiStart(const BatchInputs& in, const MultiStartInputs& ms, int nb_iter, bool line_search = true, bool early_stop = true);
     // solveBatch, then the closed loop on its plan, in one stateless call
     std::pair<BatchResult, ClosedLoopResult> closedLoopBatch(const BatchInputs& in, const ClosedLoopInputs& cl, int nb_iter, bool line_search = true,
                                                              bool early_stop = true);
@@ -572,13 +591,17 @@ public:
                                                              double scaling_factor, bool line_search = true, bool early_stop = false);
     std::pair<BatchResult, ClosedLoopCovResult> closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, int lag_update_step,
                                                                    double penalty, double scaling_factor, bool line_search = true, bool early_stop = false);
+    // as ILQRRecursive::solveMultiStart; the winners' multipliers are adopted with their controls, and the nb_iter iterations start from
+    // finalPenalty(ms.coarse_iter, ..)
+    MultiStartResult solveMultiStart(const BatchInputs& in, const MultiStartInputs& ms, int nb_iter, int lag_update_step, double penalty, double scaling_factor,
+                                     bool line_search = true, bool early_stop = false);
     // the penalty a solve of nb_iter iterations ends with: penalty *= scaling_factor once per update iteration ((it + 1) % lag_update_step == 0),
     // formed as the solver forms it (the same double) -- what BatchInputs::al_gains_penalty wants for the gains about that solve's plan
     static double finalPenalty(int nb_iter, int lag_update_step, double penalty, double scaling_factor);
 
 private:
     BatchResult solveBatchThen(const BatchInputs& in, int nb_iter, int lag_update_step, double penalty, double scaling_factor, bool line_search, bool early_stop,
-                               const std::function<void(ilqr_problem*)>& then);
+                               const std::function<void(ilqr_problem*)>& then, const MultiStartInputs* ms = nullptr, MultiStartOut* mo = nullptr);
     std::shared_ptr<sys::System> s;
     std::vector<Constraint> inequality;
     std::vector<Vec> multipliers;  // persists across solve() calls like the reference's member

@@ -106,6 +106,20 @@ static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& 
     return in;
 }
 
+// solve_multistart(..., S, seed, sigma_u, coarse_iter): sigma_u None (0), a scalar or nb_ctrl_var values
+static solver::MultiStartInputs multistart_inputs(int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter) {
+    solver::MultiStartInputs ms;
+    ms.S = S;
+    ms.seed = seed;
+    ms.coarse_iter = coarse_iter;
+    if (!sigma_u.is_none()) {
+        arr_t a = arr_t::ensure(sigma_u);
+        if (!a || a.ndim() > 1) throw std::runtime_error("[solve_multistart] sigma_u must be a scalar or have nb_ctrl_var entries");
+        ms.sigma_u.assign(a.data(), a.data() + a.size());
+    }
+    return ms;
+}
+
 // numpy -> ClosedLoopInputs: x0 [B][S][n_x] or None, w [B][S][T-1][n_x] or None; samples: S where neither array gives it
 static solver::ClosedLoopInputs closed_loop_inputs(const py::object& x0, const py::object& w, const py::object& samples, bool with_ff,
                                                    const py::object& seed = py::none(), const py::object& sigma_w = py::none(),
@@ -346,6 +360,12 @@ PYBIND11_MODULE(PyLQR, m) {
         .def_property_readonly("cost_trace", [](const solver::BatchResult& r) { return shaped(r.cost_trace, {r.cost_trace.empty() ? 0 : r.B, r.nb_iter}); })
         .def_property_readonly("alpha_trace", [](const solver::BatchResult& r) { return shaped(r.alpha_trace, {r.alpha_trace.empty() ? 0 : r.B, r.nb_iter}); })
         .def_readonly("seconds", &solver::BatchResult::seconds);
+    py::class_<solver::MultiStartResult, solver::BatchResult>(m_sol, "MultiStartResult")
+        .def_readonly("S", &solver::MultiStartResult::S)
+        .def_property_readonly("winner", [](const solver::MultiStartResult& r) { return py::array_t<int>(r.winner.size(), r.winner.data()); })
+        .def_property_readonly("n_candidates", [](const solver::MultiStartResult& r) { return py::array_t<int>(r.n_candidates.size(), r.n_candidates.data()); })
+        .def_property_readonly("coarse_best", [](const solver::MultiStartResult& r) { return shaped(r.coarse_best, {r.B}); })
+        .def_property_readonly("coarse_first", [](const solver::MultiStartResult& r) { return shaped(r.coarse_first, {r.B}); });
     py::class_<solver::ClosedLoopResult>(m_sol, "ClosedLoopResult")
         .def_property_readonly("cost", [](const solver::ClosedLoopResult& r) { return shaped(r.cost, {r.B, r.S}); })
         .def_property_readonly("X", [](const solver::ClosedLoopResult& r) { return shaped(r.X, {r.B, r.S, r.T, r.n_x}); })
@@ -391,6 +411,14 @@ PYBIND11_MODULE(PyLQR, m) {
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
              py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
+        // every task (the batch of U0 / q0 / kp_targets) from S starts: solve_batch's arguments, then the starts
+        .def("solve_multistart",
+             [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter,
+                const py::object& q0, const py::object& dq0, const py::object& kp, bool pg) {
+                 return self.solveMultiStart(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), multistart_inputs(S, seed, sigma_u, coarse_iter), nb_iter, ls, es);
+             },
+             py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(),
+             py::arg("coarse_iter") = 1, py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
         .def("closed_loop_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
                 const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
@@ -421,6 +449,15 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
              py::arg("al_gains_penalty") = py::none())
+        .def("solve_multistart",
+             [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, int S, unsigned long long seed,
+                const py::object& sigma_u, int coarse_iter, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& agp) {
+                 return self.solveMultiStart(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), multistart_inputs(S, seed, sigma_u, coarse_iter), nb_iter, lag,
+                                             pen, sc, ls, es);
+             },
+             py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
+             py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(), py::arg("coarse_iter") = 1, py::arg("q0") = py::none(),
+             py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("al_gains_penalty") = py::none())
         .def_static("final_penalty", &solver::AL_ILQR::finalPenalty, py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"))
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,

@@ -5,6 +5,8 @@
 //   init rollout -> nb_iter x { backward sweep, forward line search }
 // which mirrors ILQRRecursive::solve / AL_ILQR::solve (reference src/solver/ILQRRecursive.cpp:21-181,
 // src/solver/AL-ILQR.cpp:50-232).  No CPU fallback exists: every entry point fails loudly if HIP does.
+// The one exception to "host-side only": the small kernels that join instances (ilqr_multistart_kernels.hpp, included at the end) are compiled
+// with this file, for the reason given there.
 #include "../../include/ilqr_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -21,6 +23,7 @@
 #include "ilqr_closed_loop_cov.hpp"
 #include "ilqr_ctx.hpp"
 #include "ilqr_kernels.hpp"
+#include "ilqr_multistart.hpp"
 #include "ilqr_plan.hpp"
 
 using namespace ilqr;
@@ -69,6 +72,8 @@ struct ilqr_problem {
     DevScratch cl_con_ws;   // closed_loop_report_con through device pointers: con_max | con_steps where the caller asks only for their reductions
     DevScratch cl_cov_ws;   // closed_loop_cov: the per-lane matrices of the generic kernel k_cl_cov
     DevScratch cl_cov_kps;  // closed_loop_cov through device pointers: kp_Sigma where the caller asks only for kp_var
+    DevScratch ms_idx;   // adopt / get_at / select through host pointers: the index (or the eligibility flags) as ints
+    DevScratch ms_out;   // select / get_at through host pointers: best | winner, n_candidates and iters | status as ints
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
     BatchCPState cp;
     BatchWideState cpw;
@@ -464,7 +469,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
     for (void* q : p->allocs) (void)hipFree(q);
-    for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_con_ws, &p->cl_cost, &p->cl_cov_ws, &p->cl_cov_kps}) b->release();
+    for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_con_ws, &p->cl_cost, &p->cl_cov_ws, &p->cl_cov_kps, &p->ms_idx, &p->ms_out}) b->release();
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
     delete p;
@@ -1453,6 +1458,223 @@ extern "C" int ilqr_problem_get_fX(ilqr_problem* p, double* fX) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ multi-start
+// The calls that join instances (include/ilqr_hip.h "multi-start"): every refusal first, then the launches of ilqr_multistart.hpp on the context's
+// stream, charged to ILQR_PROF_OTHER.  Host forms stage their int arrays in ms_idx / ms_out and their doubles in `staging`, and synchronise.
+
+static int ms_groups(ilqr_ctx* c, const char* fn, int B, int S) {
+    if (S < 1) return fail(c, std::string(fn) + ": group_size must be >= 1 (got " + std::to_string(S) + ")");
+    if (B % S != 0) return fail(c, std::string(fn) + ": the batch (" + std::to_string(B) + ") is not a multiple of group_size (" + std::to_string(S) + ")");
+    return 0;
+}
+// n ints at the front of a scratch of doubles
+static int ms_ints(ilqr_ctx* c, DevScratch& s, size_t n, int** out) {
+    if (s.reserve(c, (n + 1) / 2 + 1)) return 1;
+    *out = (int*)s.ptr;
+    return 0;
+}
+// the index of a call as the kernels read it: the caller's device pointer, or the host array checked against 0 .. B_src-1 and uploaded
+static int ms_index(ilqr_problem* owner, const char* fn, const int* index, int n, int B_src, bool dev, const int** out) {
+    ilqr_ctx* c = owner->ctx;
+    if (dev) { *out = index; return 0; }
+    for (int i = 0; i < n; i++)
+        if (index[i] < 0 || index[i] >= B_src)
+            return fail(c, std::string(fn) + ": index[" + std::to_string(i) + "] = " + std::to_string(index[i]) + " is outside 0 .. " + std::to_string(B_src - 1));
+    int* d = nullptr;
+    if (ms_ints(c, owner->ms_idx, (size_t)n, &d)) return 1;
+    HIPCHK(c, hipMemcpyAsync(d, index, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    *out = d;
+    return 0;
+}
+
+static int adopt(ilqr_problem* dst, ilqr_problem* src, const int* index, int what, bool dev) {
+    if (!dst) return 1;
+    ilqr_ctx* c = dst->ctx;
+    const char* fn = "ilqr_problem_adopt";
+    if (!src) return fail(c, "ilqr_problem_adopt: src is a null pointer");
+    if (!index) return fail(c, "ilqr_problem_adopt: index is a null pointer");
+    if (src->ctx != c) return fail(c, "ilqr_problem_adopt: both problems must belong to one context");
+    if (dst == src) return fail(c, "ilqr_problem_adopt: dst and src are the same problem");
+    const ilqr_problem_desc &dd = dst->desc, &sd = src->desc;
+    if (dd.kind != sd.kind) return fail(c, "ilqr_problem_adopt: the problems differ in kind (" + std::to_string(dd.kind) + " and " + std::to_string(sd.kind) + ")");
+    if (dd.nb_deriv != sd.nb_deriv) return fail(c, "ilqr_problem_adopt: the problems differ in nb_deriv (" + std::to_string(dd.nb_deriv) + " and " + std::to_string(sd.nb_deriv) + ")");
+    if (dd.dof != sd.dof) return fail(c, "ilqr_problem_adopt: the problems differ in dof (" + std::to_string(dd.dof) + " and " + std::to_string(sd.dof) + ")");
+    if (dd.horizon != sd.horizon) return fail(c, "ilqr_problem_adopt: the problems differ in horizon (" + std::to_string(dd.horizon) + " and " + std::to_string(sd.horizon) + ")");
+    if (dd.n_kp != sd.n_kp) return fail(c, "ilqr_problem_adopt: the problems differ in n_kp (" + std::to_string(dd.n_kp) + " and " + std::to_string(sd.n_kp) + ")");
+    if (what & ILQR_ADOPT_TARGETS)   // a joint-space keypoint's target rows are laid out as a state, a pose keypoint's as f(x): the rows are copied as they are
+        for (int k = 0; k < dd.n_kp; k++)
+            if ((dd.kp_joint[k] != 0) != (sd.kp_joint[k] != 0))
+                return fail(c, "ilqr_problem_adopt: ILQR_ADOPT_TARGETS needs equal kp_joint flags (keypoint " + std::to_string(k) + " is a joint-space keypoint in one problem only)");
+    const int all = ILQR_ADOPT_STATE | ILQR_ADOPT_TARGETS | ILQR_ADOPT_CONTROLS0 | ILQR_ADOPT_CONTROLS | ILQR_ADOPT_MULTIPLIERS;
+    if (what == 0 || (what & ~all)) return fail(c, "ilqr_problem_adopt: `what` must be a combination of the ILQR_ADOPT_* bits (got " + std::to_string(what) + ")");
+    if ((what & ILQR_ADOPT_CONTROLS0) && (what & ILQR_ADOPT_CONTROLS))
+        return fail(c, "ilqr_problem_adopt: ILQR_ADOPT_CONTROLS0 and ILQR_ADOPT_CONTROLS both name dst's U0: give one of them");
+    if ((what & ILQR_ADOPT_STATE) && !src->has_state) return fail(c, "ilqr_problem_adopt: ILQR_ADOPT_STATE needs a start state in src (ilqr_problem_set_init_state)");
+    if ((what & ILQR_ADOPT_CONTROLS0) && !src->has_controls) return fail(c, "ilqr_problem_adopt: ILQR_ADOPT_CONTROLS0 needs controls in src (ilqr_problem_set_controls)");
+    if ((what & ILQR_ADOPT_CONTROLS) && !src->has_plan)
+        return fail(c, "ilqr_problem_adopt: ILQR_ADOPT_CONTROLS needs a plan in src: run a solver since its inputs last changed");
+    if (what & ILQR_ADOPT_MULTIPLIERS) {
+        if (src->bufs.m <= 0 || dst->bufs.m <= 0) return fail(c, "ilqr_problem_adopt: ILQR_ADOPT_MULTIPLIERS needs constraint rows in both problems (ilqr_problem_set_constraints)");
+        if (src->bufs.m != dst->bufs.m || src->bufs.per_step != dst->bufs.per_step)
+            return fail(c, "ilqr_problem_adopt: ILQR_ADOPT_MULTIPLIERS needs rows of equal m and per_step (dst " + std::to_string(dst->bufs.m) + ", " + std::to_string(dst->bufs.per_step) +
+                               "; src " + std::to_string(src->bufs.m) + ", " + std::to_string(src->bufs.per_step) + ")");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int* idx = nullptr;
+    if (ms_index(dst, fn, index, dst->B, src->B, dev, &idx)) return 1;
+    dst->has_gains = dst->has_plan = false;
+    const int T = dst->T, NU = dst->dims.n_u, NF = dst->dims.n_f;
+    const Bufs &sb = src->bufs, &db = dst->bufs;
+    hipStream_t st = c->stream;
+    auto rows = [&](const double* s0, const double* s1, const int* cur, const double* to, int n) {
+        ProfScope ps(c, ILQR_PROF_OTHER);
+        launch_adopt_rows(s0, s1, cur, idx, const_cast<double*>(to), n, dst->B, dst->Bp, src->B, src->Bp, st);
+    };
+    if (what & ILQR_ADOPT_STATE) {
+        rows(sb.q0, nullptr, nullptr, db.q0, DOF);
+        rows(sb.dq0, nullptr, nullptr, db.dq0, DOF);
+    }
+    if (what & ILQR_ADOPT_TARGETS) rows(sb.kp_tg, nullptr, nullptr, db.kp_tg, dd.n_kp * NF);
+    if (what & ILQR_ADOPT_CONTROLS0) rows(sb.U0, nullptr, nullptr, db.U0, (T - 1) * NU);
+    if (what & ILQR_ADOPT_CONTROLS) rows(sb.U[0], sb.U[1], sb.cur, db.U0, (T - 1) * NU);
+    if (what & ILQR_ADOPT_MULTIPLIERS) rows(sb.lambda, nullptr, nullptr, db.lambda, (T - 1) * db.m);
+    HIPCHK(c, hipGetLastError());
+    prof_mark(c, -1);
+    if (what & ILQR_ADOPT_STATE) dst->has_state = true;
+    if (what & (ILQR_ADOPT_CONTROLS0 | ILQR_ADOPT_CONTROLS)) { dst->has_controls = true; dst->u0_zero = false; }
+    if (!dev) HIPCHK(c, hipStreamSynchronize(c->stream));  // the index array is the caller's
+    return 0;
+}
+extern "C" int ilqr_problem_adopt(ilqr_problem* dst, ilqr_problem* src, const int* index, int what) { return adopt(dst, src, index, what, false); }
+extern "C" int ilqr_problem_adopt_dev(ilqr_problem* dst, ilqr_problem* src, const int* index, int what) { return adopt(dst, src, index, what, true); }
+
+extern "C" int ilqr_problem_spread_controls(ilqr_problem* p, int group_size, const ilqr_seeds* seeds) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    const char* fn = "ilqr_problem_spread_controls";
+    if (ms_groups(c, fn, p->B, group_size)) return 1;
+    if (!seeds) return fail(c, "ilqr_problem_spread_controls: seeds is a null pointer");
+    if (!p->has_controls) return fail(c, "ilqr_problem_spread_controls needs controls: call ilqr_problem_set_controls (or ilqr_problem_adopt) first");
+    for (int i = 0; i < p->udims.n_u; i++)
+        if (!(seeds->sigma_u[i] >= 0) || !std::isfinite(seeds->sigma_u[i]))
+            return fail(c, "ilqr_problem_spread_controls: every sigma_u must be finite and >= 0 (sigma_u[" + std::to_string(i) + "] = " + std::to_string(seeds->sigma_u[i]) + ")");
+    const int G = p->B / group_size;
+    if ((unsigned long long)seeds->group_offset + (unsigned long long)G > (1ull << 32) ||
+        (unsigned long long)seeds->member_offset + (unsigned long long)group_size > (1ull << 32))
+        return fail(c, "ilqr_problem_spread_controls: group_offset + G or member_offset + group_size exceeds 2^32 (the generator's counter)");
+    HIPCHK(c, hipSetDevice(c->device));
+    p->has_gains = p->has_plan = false;
+    p->u0_zero = false;
+    {
+        ProfScope ps(c, ILQR_PROF_OTHER);
+        launch_spread_controls(const_cast<double*>(p->bufs.U0), p->B, p->Bp, p->T - 1, group_size, *seeds, p->map.u, c->stream);
+    }
+    HIPCHK(c, hipGetLastError());
+    prof_mark(c, -1);
+    return 0;
+}
+extern "C" int ilqr_problem_spread_controls_dev(ilqr_problem* p, int group_size, const ilqr_seeds* seeds) {
+    return ilqr_problem_spread_controls(p, group_size, seeds);
+}
+
+static int select_groups(ilqr_problem* p, int S, const double* score, const int* eligible, int* winner, double* best, int* n_cand, bool dev) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    const char* fn = "ilqr_problem_select";
+    if (ms_groups(c, fn, p->B, S)) return 1;
+    if (!winner && !best && !n_cand) return fail(c, "ilqr_problem_select: winner, best and n_candidates are all null pointers");
+    if (!p->has_plan) return fail(c, "ilqr_problem_select needs a plan: run a solver since the problem's inputs last changed");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int B = p->B, G = B / S;
+    const double* dscore = score ? score : p->bufs.cost;
+    const int* delig = eligible;
+    int *dwin = winner, *dn = n_cand;
+    double* dbest = best;
+    if (!dev) {
+        if (score) {
+            if (p->staging.reserve(c, (size_t)B)) return 1;
+            HIPCHK(c, hipMemcpyAsync(p->staging.ptr, score, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+            dscore = p->staging.ptr;
+        }
+        if (eligible) {
+            int* e = nullptr;
+            if (ms_ints(c, p->ms_idx, (size_t)B, &e)) return 1;
+            HIPCHK(c, hipMemcpyAsync(e, eligible, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+            delig = e;
+        }
+        if (p->ms_out.reserve(c, (size_t)2 * G + 2)) return 1;   // best[G] | winner[G] | n_candidates[G] (ints)
+        dbest = p->ms_out.ptr;
+        dwin = (int*)(p->ms_out.ptr + G);
+        dn = dwin + G;
+    }
+    {
+        ProfScope ps(c, ILQR_PROF_OTHER);
+        launch_select_group(dscore, delig, p->bufs.status, G, S, dwin, dbest, dn, c->stream);
+    }
+    HIPCHK(c, hipGetLastError());
+    prof_mark(c, -1);
+    if (!dev) {
+        if (winner) HIPCHK(c, hipMemcpyAsync(winner, dwin, sizeof(int) * (size_t)G, hipMemcpyDeviceToHost, c->stream));
+        if (best) HIPCHK(c, hipMemcpyAsync(best, dbest, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, c->stream));
+        if (n_cand) HIPCHK(c, hipMemcpyAsync(n_cand, dn, sizeof(int) * (size_t)G, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+extern "C" int ilqr_problem_select(ilqr_problem* p, int group_size, const double* score, const int* eligible, int* winner, double* best, int* n_candidates) {
+    return select_groups(p, group_size, score, eligible, winner, best, n_candidates, false);
+}
+extern "C" int ilqr_problem_select_dev(ilqr_problem* p, int group_size, const double* score, const int* eligible, int* winner, double* best, int* n_candidates) {
+    return select_groups(p, group_size, score, eligible, winner, best, n_candidates, true);
+}
+
+static int get_at(ilqr_problem* p, int n, const int* index, double* X, double* U, double* cost, int* iters, int* status, bool dev) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    const char* fn = "ilqr_problem_get_at";
+    if (n < 1) return fail(c, "ilqr_problem_get_at: n must be >= 1 (got " + std::to_string(n) + ")");
+    if (!index) return fail(c, "ilqr_problem_get_at: index is a null pointer");
+    if (!X && !U && !cost && !iters && !status) return fail(c, "ilqr_problem_get_at: every output is a null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int* idx = nullptr;
+    if (ms_index(p, fn, index, n, p->B, dev, &idx)) return 1;
+    const int rx = p->T * p->udims.n_x, ru = (p->T - 1) * p->udims.n_u;
+    double *dX = X, *dU = U, *dcost = cost;
+    int *dit = iters, *dst = status;
+    if (!dev) {
+        if (p->staging.reserve(c, (size_t)n * ((size_t)rx + ru + 1))) return 1;
+        dX = p->staging.ptr;
+        dU = dX + (size_t)n * rx;
+        dcost = dU + (size_t)n * ru;
+        if (ms_ints(c, p->ms_out, (size_t)2 * n, &dit)) return 1;
+        dst = dit + n;
+    }
+    const Bufs& b = p->bufs;
+    // one mark per launch that happens
+    if (X) { ProfScope ps(c, ILQR_PROF_OTHER); launch_get_at(b.X[0], b.X[1], b.cur, idx, dX, n, p->B, p->Bp, rx, p->mapped ? &p->map.x : nullptr, c->stream); }
+    if (U) { ProfScope ps(c, ILQR_PROF_OTHER); launch_get_at(b.U[0], b.U[1], b.cur, idx, dU, n, p->B, p->Bp, ru, p->mapped ? &p->map.u : nullptr, c->stream); }
+    if (cost) { ProfScope ps(c, ILQR_PROF_OTHER); launch_get_at(b.cost, nullptr, nullptr, idx, dcost, n, p->B, p->Bp, 1, nullptr, c->stream); }
+    if (iters) { ProfScope ps(c, ILQR_PROF_OTHER); launch_get_at_int(b.iters, idx, dit, n, p->B, c->stream); }
+    if (status) { ProfScope ps(c, ILQR_PROF_OTHER); launch_get_at_int(b.status, idx, dst, n, p->B, c->stream); }
+    HIPCHK(c, hipGetLastError());
+    prof_mark(c, -1);
+    if (!dev) {
+        if (X) HIPCHK(c, hipMemcpyAsync(X, dX, sizeof(double) * (size_t)n * rx, hipMemcpyDeviceToHost, c->stream));
+        if (U) HIPCHK(c, hipMemcpyAsync(U, dU, sizeof(double) * (size_t)n * ru, hipMemcpyDeviceToHost, c->stream));
+        if (cost) HIPCHK(c, hipMemcpyAsync(cost, dcost, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (iters) HIPCHK(c, hipMemcpyAsync(iters, dit, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (status) HIPCHK(c, hipMemcpyAsync(status, dst, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+extern "C" int ilqr_problem_get_at(ilqr_problem* p, int n, const int* index, double* X, double* U, double* cost, int* iters, int* status) {
+    return get_at(p, n, index, X, U, cost, iters, status, false);
+}
+extern "C" int ilqr_problem_get_at_dev(ilqr_problem* p, int n, const int* index, double* X, double* U, double* cost, int* iters, int* status) {
+    return get_at(p, n, index, X, U, cost, iters, status, true);
+}
+
 // ------------------------------------------------------------------------------------------------ stand-alone FK
 
 extern "C" int ilqr_fk_batch(ilqr_ctx* c, const ilqr_problem_desc* d, int n, const double* q, double* pos, double* quat, double* jac) {
@@ -1496,3 +1718,7 @@ extern "C" int ilqr_fk_batch(ilqr_ctx* c, const ilqr_problem_desc* d, int n, con
         for (size_t r = 0; r < (size_t)n * 6; r++) std::memcpy(jac_out + r * dof, &jw[r * DOF], sizeof(double) * dof);
     return rc;
 }
+
+// the kernels that join instances (adopt, spread, select, get_at) and their launchers: this is the one translation unit that defines them
+#define ILQR_MULTISTART_KERNELS_TU
+#include "ilqr_multistart_kernels.hpp"

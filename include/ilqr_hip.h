@@ -495,6 +495,78 @@ int ilqr_problem_closed_loop_cov_con(ilqr_problem* p, const double* sigma_w, con
 int ilqr_problem_closed_loop_cov_con_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
                                          const ilqr_cl_cov_con* con);
 
+/* ---- multi-start: the calls that join instances (no reference function: the reference solves one problem from one U0) -------------------
+ * iLQR is a local method; a caller with one task runs it from S starts on the idle lanes, keeps the best plan and polishes it.  Everything above
+ * stays inside one instance; these four calls move data between instances, and between two problems, without leaving HBM.
+ * Groups.  B = G * group_size; instance b = g * group_size + s is member s of group g.  Every call that takes a group_size fails with an error
+ * text for group_size < 1 or B % group_size != 0.
+ * _dev forms: every array is a device pointer and the call is asynchronous on the context's stream; structs are host memory, read before return.
+ * Offsets: instance indices are ints; every offset into a device buffer or a natural-layout array is 64-bit (B T n may pass 2^31).
+ * Under ilqr_profile_enable all of it is charged to ILQR_PROF_OTHER.
+ *
+ * ilqr_problem_adopt(dst, src, index, what): instance i of dst takes from instance index[i] of src (index[B_dst]) what the bits of `what` name:
+ *   ILQR_ADOPT_STATE        q0, dq0
+ *   ILQR_ADOPT_TARGETS      every keypoint's target
+ *   ILQR_ADOPT_CONTROLS0    the controls src was given with ilqr_problem_set_controls (or adopted, spread or warm-started since): dst's U0
+ *   ILQR_ADOPT_CONTROLS     the accepted plan's controls become dst's U0: the bytes ilqr_problem_get_U(src) returns.  src must hold a plan, as for
+ *                           ilqr_problem_gains
+ *   ILQR_ADOPT_MULTIPLIERS  src's current multipliers (ilqr_problem_get_lambda) become dst's current ones, not its lambda0
+ *                           (ilqr_problem_reset_multipliers still restores what ilqr_problem_set_constraints gave dst); both problems must have
+ *                           constraint rows of equal m and per_step
+ * Both problems belong to one context, dst != src, and kind, nb_deriv, dof, horizon and n_kp are equal; every other descriptor field and the batch
+ * sizes may differ, except that ILQR_ADOPT_TARGETS needs equal kp_joint flags (a joint-space keypoint's target is laid out as a state, a pose
+ * keypoint's as f(x), and the rows are copied as they are).  Refused, each with its own text: a null problem or index, problems of two contexts, dst == src, a descriptor field of the five
+ * that differs, TARGETS between keypoints whose kp_joint flags differ, `what` 0 or with an unknown bit, CONTROLS0 together with CONTROLS, STATE or CONTROLS0 from a src that was never given them, CONTROLS
+ * without a plan, MULTIPLIERS without rows or with rows of another shape.  The host form refuses an index outside 0 .. B_src-1 and names the
+ * first bad one; the _dev form cannot look: its kernel clamps every index into 0 .. B_src-1.  No out-of-range read is possible.
+ * Copies are device to device between the private layouts (k_adopt_rows); a chain of fewer than 7 joints copies its padded rows as they are.
+ * Afterwards dst is in the state the host setters would have left: start state / controls count as given, no plan and no gains (ilqr_problem_gains and
+ * the closed-loop calls are refused until a solve).  src is untouched.  With index[b] = b / S the call replicates: a problem of G * S instances is
+ * fed from a problem of G tasks.
+ *
+ * ilqr_problem_spread_controls(p, group_size, seeds): the starts of a group.  The member with global index member_offset + s = 0 keeps its U0;
+ * every other member gets U0[b][k][i] += sigma_u[i] * z for k = 0 .. T-2 and the control entries i of the user's layout.
+ *   z: the generator of ilqr_problem_closed_loop_noise above (Philox4x32-10, the same two normals per call); key = the seed, counter =
+ *   (group_offset + g, member_offset + s, k, j); pair j serves control entries 2j and 2j + 1 (for an odd n_u the last z1 is dropped).
+ *   The product is rounded on its own, then one rounded add.  An entry with sigma 0 is not touched, a pair with both sigmas 0 is not generated,
+ *   the padded entries of a chain of fewer than 7 joints get nothing.  The draw of (seed, global group, global member, step, entry) depends on
+ *   nothing else: a cut-out of groups or members, run with its offsets, reproduces the large call bit for bit.
+ *   This is the stream of ilqr_problem_closed_loop_noise (there the counter is (instance, sample, step, pair)): a caller who draws both uses two seeds.
+ * Needs controls set; afterwards the problem holds no plan and no gains.  Refused: a null seeds, a negative or non-finite sigma,
+ * group_offset + G or member_offset + group_size beyond 2^32.  The two forms are one: the call takes no array and is asynchronous in both.
+ *
+ * ilqr_problem_select(p, group_size, score, eligible, winner, best, n_candidates): the best member of every group.
+ *   score[B] or NULL (the cost ilqr_problem_get_cost returns); eligible[B] ints or NULL (all): e.g. formed from the `outcome` of a zero-noise,
+ *   one-sample ilqr_problem_closed_loop_report(_con).
+ *   Instance b is a candidate if eligible[b] != 0, its status carries neither ILQR_STATUS_NONFINITE nor ILQR_STATUS_SWEEP_IO and its score is finite.
+ *   winner[G] (ints): the candidate of the group with the smallest score; scores compare as doubles (-0 ties with +0), ties go to the lowest b.
+ *   best[G]: that score.  n_candidates[G] (ints): the number of candidates.
+ *   A group without a candidate gets winner = g * group_size, best = NaN, n_candidates = 0: a winner is always a valid index for ilqr_problem_adopt.
+ * Needs a plan (as ilqr_problem_gains).  Each output may be NULL, not all three.  The key (score, b) is totally ordered, so the result does not
+ * depend on how the kernel maps groups to lanes (k_select_group: 1, 4, 16 or 64 lanes per group by group_size; any group_size).
+ *
+ * ilqr_problem_get_at(p, n, index, X, U, cost, iters, status): rows index[0 .. n-1] of what ilqr_problem_get_X, _get_U, _get_cost, _get_iters and
+ * _get_status return, byte for byte: X[n][T][n_x], U[n][T-1][n_u], cost[n], iters[n], status[n].  Each output may be NULL, not all five; indices may
+ * repeat and come in any order and are handled as in ilqr_problem_adopt (host form: refused outside 0 .. B-1; _dev: clamped).  n >= 1. */
+#define ILQR_ADOPT_STATE 1
+#define ILQR_ADOPT_TARGETS 2
+#define ILQR_ADOPT_CONTROLS0 4
+#define ILQR_ADOPT_CONTROLS 8
+#define ILQR_ADOPT_MULTIPLIERS 16
+typedef struct {
+    unsigned long long seed;
+    unsigned int group_offset, member_offset;   /* this call's first global group / member */
+    double sigma_u[ILQR_MAX_NU];                /* user's control layout; 0 = none */
+} ilqr_seeds;
+int ilqr_problem_adopt(ilqr_problem* dst, ilqr_problem* src, const int* index, int what);
+int ilqr_problem_adopt_dev(ilqr_problem* dst, ilqr_problem* src, const int* index, int what);
+int ilqr_problem_spread_controls(ilqr_problem* p, int group_size, const ilqr_seeds* seeds);
+int ilqr_problem_spread_controls_dev(ilqr_problem* p, int group_size, const ilqr_seeds* seeds);
+int ilqr_problem_select(ilqr_problem* p, int group_size, const double* score, const int* eligible, int* winner, double* best, int* n_candidates);
+int ilqr_problem_select_dev(ilqr_problem* p, int group_size, const double* score, const int* eligible, int* winner, double* best, int* n_candidates);
+int ilqr_problem_get_at(ilqr_problem* p, int n, const int* index, double* X, double* U, double* cost, int* iters, int* status);
+int ilqr_problem_get_at_dev(ilqr_problem* p, int n, const int* index, double* X, double* U, double* cost, int* iters, int* status);
+
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];
  * any output may be NULL.  Host pointers. */
