@@ -412,6 +412,7 @@ static void fx_jac_frame(const orc_system* s, const orc_keypoint* kp, const doub
     }
 }
 void orc_get_fx_jac(const orc_system* s, const double* x, double* fx, double* J) { fx_jac_frame(s, NULL, x, fx, J); }
+void orc_get_fx_jac_kp(const orc_system* s, const orc_keypoint* kp, const double* x, double* fx, double* J) { fx_jac_frame(s, kp, x, fx, J); }
 
 /* PosOrnKeypoint::diff (PosOrnKeypoint.cpp:24-45), SpacetimeKeypoint::diff (SpacetimeKeypoint.cpp:19-25) */
 void orc_kp_diff(const orc_system* s, const orc_keypoint* kp, const double* fx, double* e) {

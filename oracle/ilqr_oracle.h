@@ -111,6 +111,8 @@ void orc_sd_transport(const double v[4], const double b1[4], const double b2[4],
 
 /* System virtuals */
 void orc_get_fx_jac(const orc_system* s, const double* x, double* fx, double* J /* n_Q x n_x, may be NULL */);
+/* ... as keypoint kp's own sub-system sees it: through kp's object frame when it has one (test aid; fx, J may be NULL) */
+void orc_get_fx_jac_kp(const orc_system* s, const orc_keypoint* kp, const double* x, double* fx, double* J);
 void orc_kp_diff(const orc_system* s, const orc_keypoint* kp, const double* fx, double* e);
 double orc_cost(const orc_system* s, const double* x, const double* u, int k);
 void orc_cost_x(const orc_system* s, const double* x, int k, double* lx);

@@ -125,6 +125,7 @@ def lib():
         L.orc_system_finalize.argtypes = [C.POINTER(System)]
         L.orc_fk.argtypes = [C.POINTER(Chain), dp, dp, dp, dp, dp, dp, dp]
         L.orc_get_fx_jac.argtypes = [C.POINTER(System), dp, dp, dp]
+        L.orc_get_fx_jac_kp.argtypes = [C.POINTER(System), C.POINTER(Keypoint), dp, dp, dp]
         L.orc_kp_diff.argtypes = [C.POINTER(System), C.POINTER(Keypoint), dp, dp]
         L.orc_cost.argtypes = [C.POINTER(System), dp, dp, C.c_int]
         L.orc_cost.restype = C.c_double
@@ -355,10 +356,14 @@ def fk(chain: Chain, q, dq=None):
     return p, quat, J[: 6 * dof].reshape(6, dof), dx, w
 
 
-def get_fx_jac(s: System, x):
+def get_fx_jac(s: System, x, kp=None):
+    """kp: index of a keypoint of s -- f(x) and its Jacobian as that keypoint's own sub-system sees them (through its object frame)."""
     x = _arr(x, s.n_x)
     fx, J = np.zeros(s.n_f), np.zeros(s.n_Q * s.n_x)
-    lib().orc_get_fx_jac(C.byref(s), _dp(x), _dp(fx), _dp(J))
+    if kp is None:
+        lib().orc_get_fx_jac(C.byref(s), _dp(x), _dp(fx), _dp(J))
+    else:
+        lib().orc_get_fx_jac_kp(C.byref(s), C.byref(s.kp[kp]), _dp(x), _dp(fx), _dp(J))
     return fx, J.reshape(s.n_Q, s.n_x)
 
 

@@ -40,6 +40,46 @@ def panda_segs(tool_rpy=(0, 0, 0), tool_xyz=(0, 0, 0)):
     return orc.chain_from_urdf(urdf_text(), "panda_link0", "panda_tip", tool_rpy, tool_xyz)
 
 
+# Hand-written chains that are not the Panda (tests/golden/chains/): name -> (file, base link, tip link).  "gen4cut3" is gen4 cut at the
+# link behind its third moving joint.
+GENERAL_CHAINS = {"gen7": ("gen7.urdf", "g7_base", "g7_tip"), "gen4": ("gen4.urdf", "g4_base", "g4_tip"), "gen4cut3": ("gen4.urdf", "g4_base", "g4_l3")}
+TOOL_FRAMES = {"identity": (None, None), "rotated": ([2.8, -0.4, 1.3], [0.02, -0.03, 0.07])}  # tool_rpy (its first entry is the Z angle), tool_xyz
+
+
+def general_chain_text(name):
+    return open(os.path.join(GOLDEN, "chains", GENERAL_CHAINS[name][0])).read()
+
+
+def chain_pair(urdf_text_, base, tip, tool_rpy=None, tool_xyz=None):
+    """(chain, segs) of one URDF chain with one tool frame: the `chain` dict of workloads.make_batch / capi.make_desc from the library's
+    own reader, and the oracle's `segs` from the oracle's reader."""
+    from ilqr_planner_amd import capi
+
+    zero = (0.0, 0.0, 0.0)
+    return (capi.chain_from_urdf(urdf_text_, base, tip, tool_rpy, tool_xyz),
+            orc.chain_from_urdf(urdf_text_, base, tip, tool_rpy if tool_rpy is not None else zero, tool_xyz if tool_xyz is not None else zero))
+
+
+def general_chain(name, tool="identity"):
+    """chain_pair of one of GENERAL_CHAINS with one of TOOL_FRAMES"""
+    _, base, tip = GENERAL_CHAINS[name]
+    return chain_pair(general_chain_text(name), base, tip, *TOOL_FRAMES[tool])
+
+
+def object_frames():
+    """Two object frames (4 x 4 poses) for keypoints seen through a frame: a general rotation, and one 0.15 rad short of a half turn about
+    the oblique axis (1, 2, -2) / 3, so that a tool near the base orientation is seen with a negative trace."""
+    out = []
+    for axis, th, t in (([2.0, -1.0, 3.0], 0.9, [0.3, -0.2, 0.25]), ([1.0, 2.0, -2.0], np.pi - 0.15, [0.1, 0.35, 0.2])):
+        a = np.asarray(axis) / np.linalg.norm(axis)
+        K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+        T = np.eye(4)
+        T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+        T[:3, 3] = t
+        out.append(T)
+    return out
+
+
 def oracle_system(prob, segs=None):
     segs = segs or panda_segs()
     kind = orc.SYS_POS_ORN if prob["kind"] == "POS_ORN" else orc.SYS_POS_ORN_TIME
@@ -117,6 +157,8 @@ def oracle_system_of_instance(cfg, inp, i, segs=None):
             d["ctime"] = tg[-1]
         if cfg.get("kp_dist") and cfg["kp_dist"][k] is not None:
             d["dist"] = cfg["kp_dist"][k]  # PosOrnKeypointDistFunct
+        if cfg.get("kp_frames") and cfg["kp_frames"][k] is not None:
+            d["frame"] = cfg["kp_frames"][k]  # 4 x 4 pose of the object frame the keypoint's sub-system works in
         if cfg.get("hybrid"):  # workloads "C2h"/"C4h": joint-space via point of a JointSpace(Time)PlannerSys sub-system, then a pose goal
             nu_ = 7 + (1 if tm else 0)
             if k == 0:
@@ -155,10 +197,14 @@ def oracle_solve_instance(cfg, inp, i, nb_iter, early_stop, segs=None):
 
 
 class OracleFK:
-    """Stand-in for capi.Context in CPU-only experiments/tests: workloads.make_batch only needs fk_batch()."""
+    """Stand-in for capi.Context in CPU-only experiments/tests: workloads.make_batch only needs fk_batch().  segs: the oracle's chain
+    (default: the Panda)."""
+
+    def __init__(self, segs=None):
+        self.segs = segs
 
     def fk_batch(self, desc, q):
-        ch = orc.make_chain(panda_segs())
+        ch = orc.make_chain(self.segs or panda_segs())
         q = np.asarray(q, float)
         pos, quat = np.zeros((len(q), 3)), np.zeros((len(q), 4))
         for i in range(len(q)):

@@ -266,16 +266,18 @@ def prove_instance(cfg, inp, i, states, ct, at, iters, segs=None, nb_iter=None, 
     return dict(verdict=verdict, steps=steps, n_ties=n_ties, n_ill=n_ill, worst_ill_ratio=worst_ratio)
 
 
-def check_batch(p, cfg, inp, nb_iter, early_stop, run_solver, oracle_solve, always=(0, 1, 2, 3), rtol=1e-4, indices=None, states_out=None):
+def check_batch(p, cfg, inp, nb_iter, early_stop, run_solver, oracle_solve, always=(0, 1, 2, 3), rtol=1e-4, indices=None, states_out=None,
+                segs=None):
     """The parity gate of a solved batch `p` (already solved with nb_iter / early_stop): every instance is within `rtol` of the oracle's
     own end-to-end run, or is PROVEN (see the module header).  The instances in `always` are proven whatever their distance.  Returns
     (summary, rel, failures) -- failures lists the unexplained instances with their failing steps; the caller asserts it is empty.
     indices: check only these instances (a sample of a big batch); rel is then indexed like the batch, zero elsewhere.
-    states_out: a list that receives the states of the re-runs (gpu_states), for a caller that needs them too."""
+    states_out: a list that receives the states of the re-runs (gpu_states), for a caller that needs them too.
+    segs: the oracle's chain the batch was made on (default: the Panda)."""
     cost, iters = p.cost(), p.iters()
     ct, at = p.trace(nb_iter)
     B = len(cost)
-    segs = panda_segs()
+    segs = segs or panda_segs()
     rel, flagged = np.zeros(B), []
     todo = list(range(B)) if indices is None else [int(i) for i in indices]
     for i in todo:
@@ -507,15 +509,15 @@ def prove_instance_batch(cfg, inp, i, psi, states, ct_ext, at_ext, n, early_stop
     return dict(verdict=verdict, steps=steps, n_ties=n_ties, n_ill=n_ill, worst_ill_ratio=worst_ratio)
 
 
-def check_batch_solver(p, cfg, inp, psi, nb_iter, early_stop, solve, always=(0, 1), rtol=1e-4, indices=None):
+def check_batch_solver(p, cfg, inp, psi, nb_iter, early_stop, solve, always=(0, 1), rtol=1e-4, indices=None, segs=None):
     """The parity gate of the batch solvers: `p` has been solved with solve(p, nb_iter, early_stop).  Every instance (of `indices`) has
     the oracle's step-size sequence and a cost trace within `rtol` of the oracle's own end-to-end run, or is PROVEN iteration by
     iteration; the instances in `always` are proven whatever their distance.  No share of a batch is excused.  Returns
-    (summary, rel, failures, oracle_runs)."""
+    (summary, rel, failures, oracle_runs).  segs: the oracle's chain the batch was made on (default: the Panda)."""
     iters = p.iters()
     ct, at = p.trace(nb_iter)
     B = len(iters)
-    segs = panda_segs()
+    segs = segs or panda_segs()
     rel, flagged, runs = np.zeros(B), [], {}
     todo = list(range(B)) if indices is None else [int(i) for i in indices]
     for i in todo:

@@ -132,21 +132,6 @@ def test_exact_embedding_batch_ilqr(ctx, name):
 # ---- parity against the oracle at the native dof
 
 
-def _prove(cfg, inp, i, states, ct, at, iters, sysm):
-    """Every iteration of instance i reproduced by one oracle iteration from the GPU's state (parity_proof's steps (b) and (c)), on the
-    native chain's oracle System."""
-    for it in range(int(iters[i])):
-        r = pp.one_step(cfg, inp, i, it, states, sysm=sysm)
-        pr = r["probe"][0]
-        ok, _, why = pp.decisions_follow(pr, float(at[i, it]))
-        if not ok:
-            return f"iteration {it}: {why}"
-        co = pp._cost_at(pr, float(at[i, it]))
-        if co is None or pp._rel(float(ct[i, it]), co) > pp.STEP_RTOL:
-            return f"iteration {it}: cost {ct[i, it]} vs {co}"
-    return None
-
-
 @pytest.mark.parametrize("name", ["C2", "C4"])
 def test_parity_riccati(ctx, name):
     B, nb_iter = 48, 8
@@ -164,7 +149,7 @@ def test_parity_riccati(ctx, name):
             continue
         if states is None:
             states = pp.gpu_states(p, cfg, nb_iter, False, workloads.run_solver)
-        why = _prove(cfg, inp, i, states, ct, at, iters, nc.oracle_system(cfg, inp, i, segs))
+        why = nc.prove(cfg, inp, i, states, ct, at, iters, nc.oracle_system(cfg, inp, i, segs))
         if why:
             unexplained.append((i, why))
     p.close()

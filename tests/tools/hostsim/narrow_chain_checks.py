@@ -2,6 +2,10 @@
 library and runs this script in a child process of its own: its library never meets the product library).
 
     python tests/tools/hostsim/narrow_chain_checks.py <libilqr_hostsim.so>
+    python tests/tools/hostsim/narrow_chain_checks.py <libilqr_hostsim.so> general
+
+"general": instead, FK and the Jacobian of the hand-written chains of tests/golden/chains/ (fixed segments folded before, between and behind
+the joints; four joints padded to seven behind axes that are not z) with both tool frames, against tests/kinematics_reference.py.
 """
 import os
 import sys
@@ -23,7 +27,11 @@ B, NIT = 3, 6
 SHAPES = (("C2", "C3"), ("C2nd", "C2ndal"), ("C4t1", "C4t1al"), ("C4", "C4al"))  # (recursive, AL) of POS_ORN 1, 2 and POS_ORN_TIME 1, 2
 
 
-def check_fk(ctx, dof):
+def check_fk(ctx, dof, chain=None):
+    """chain = (name, tool) of tests.helpers.GENERAL_CHAINS / TOOL_FRAMES: that chain against the high-precision reference; None: the cut
+    Panda chain of dof joints against the oracle."""
+    if chain is not None:
+        return check_fk_general(ctx, dof, *chain)
     ch = nc.capi_chain(dof)
     assert ch["dof"] == dof
     desc = capi.make_desc(kind=capi.SYS_POS_ORN, nb_deriv=1, horizon=2, dt=0.1, R_diag=[1e-5] * dof, chain=ch, kp_timesteps=[], kp_Q=[])
@@ -35,6 +43,25 @@ def check_fk(ctx, dof):
         assert np.allclose(pos[i], p, atol=1e-12, rtol=0) and np.allclose(quat[i], qt, atol=1e-12, rtol=0), (dof, i)
         assert jac[i].shape == (6, dof) and np.allclose(jac[i], J, atol=1e-12, rtol=0), (dof, i)
     print(f"fk {dof} joints: pose and Jacobian match the oracle", flush=True)
+
+
+def check_fk_general(ctx, dof, name, tool, n=40):
+    from tests import kinematics_reference as kr
+    from tests.helpers import GENERAL_CHAINS, TOOL_FRAMES, general_chain, general_chain_text
+
+    ch, _ = general_chain(name, tool)
+    assert ch["dof"] == dof
+    desc = capi.make_desc(kind=capi.SYS_POS_ORN, nb_deriv=1, horizon=2, dt=0.1, R_diag=[1e-5] * dof, chain=ch, kp_timesteps=[], kp_Q=[])
+    q = np.random.default_rng(100 + dof).uniform(-3.1, 3.1, (n, dof))
+    pos, quat, jac = ctx.fk_batch(desc, q)
+    ref = kr.read_chain(general_chain_text(name), *GENERAL_CHAINS[name][1:])
+    rpy, xyz = TOOL_FRAMES[tool]
+    near = 0
+    for i in range(n):
+        r = kr.fk(ref, q[i], rpy or (0, 0, 0), xyz or (0, 0, 0))
+        near += kr.assert_pose(r, pos[i], quat[i], jac[i], atol=1e-12, what=(name, tool, i))
+    assert near <= 0.02 * n, (name, tool, near)
+    print(f"fk {name} ({dof} joints, {tool} tool): pose and Jacobian match the high-precision reference; {near} of {n} at a branch boundary", flush=True)
 
 
 def check_solves(ctx, dof):
@@ -101,6 +128,13 @@ def check_errors(ctx):
 def main():
     ctx = capi.Context(0)
     ctx.set_crosscheck(generic_kernels=True)
+    if sys.argv[2:] == ["general"]:
+        for name, dof in (("gen7", 7), ("gen4", 4), ("gen4cut3", 3)):
+            for tool in ("identity", "rotated"):
+                check_fk(ctx, dof, chain=(name, tool))
+        ctx.close()
+        print("general chains: ok")
+        return
     check_errors(ctx)
     for dof in (6, 3):
         check_fk(ctx, dof)
