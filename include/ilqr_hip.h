@@ -131,9 +131,17 @@ typedef struct {
     double state_min2[ILQR_MAX_NX + 1];
     int limit_weight2[ILQR_MAX_NX + 1];
     int limit_multiplicity2;
-    double reg;          /* 1e-6 */
-    double alpha_floor;  /* 1e-3 */
-    double stop_tol;     /* 1e-3 */
+    /* The three constants below are read by the Riccati solvers (ilqr_solve_recursive, ilqr_solve_al) and by ilqr_problem_gains /
+     * ilqr_problem_gains_al, which launch the same sweeps.  The batch solvers (ilqr_solve_batch_cp, ilqr_solve_batch), LQT and the host loop
+     * keep the reference's literals whatever is set here.  Away from the defaults: tests/test_gpu_solver_constants.py. */
+    double reg;          /* 1e-6.  Added to the diagonal of Quu inside its inverse only, never in the value update (ILQRRecursive.cpp:89); >= 0 */
+    double alpha_floor;  /* 1e-3.  The line search halves alpha while alpha > alpha_floor and accepts the first step size at or below it whatever its
+                            cost (ILQRRecursive.cpp:155): 1 + ceil(log2(1 / alpha_floor)) step sizes, at most 64.  Up to 16 step sizes
+                            (alpha_floor >= 2^-15) are rolled out at once by the cooperative forward passes; below that the plan changes: the
+                            generic forward pass tries them one after the other under the same sweeps, and the single-integrator sweep no longer
+                            applies the previous winner itself (csrc/ilqr_plan.hpp).  Same results, slower.  > 0 and finite */
+    double stop_tol;     /* 1e-3.  Early stop when alpha * sqrt(sum_k |du_k|) < stop_tol (ILQRRecursive.cpp:174, AL-ILQR.cpp:225); the second
+                            condition of the non-AL rule, cost < 1e-3, is a literal */
 } ilqr_problem_desc;
 
 /* dimensions derived from (kind, nb_deriv, dof): n_x, n_u, n_f (target space), n_Q (residual space) */

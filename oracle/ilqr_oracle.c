@@ -71,6 +71,13 @@ void orc_set_probe_all(int on) { g_probe_all = on; }
 void orc_set_resume_x(const double* X) { g_resume_x = X; g_resume_x_dev = 0; }
 double orc_get_resume_x_dev(void) { return g_resume_x_dev; }
 void orc_set_resume(int it0, double init_penalty, const double* lambda_mask) { g_it0 = it0; g_init_penalty = init_penalty; g_lambda_mask = lambda_mask; }
+/* Test aid: the three solver constants of the Riccati solvers (ilqr_problem_desc's reg, alpha_floor, stop_tol on the device).  The
+   defaults are the reference's literals, so a solve that never calls this computes what it always did.  The batch solvers below keep
+   their literals: the device's batch solvers ignore the three fields too. */
+static __thread double g_reg = 1e-6;         /* added to Quu's diagonal inside the inverse only (quirk D-3) */
+static __thread double g_alpha_floor = 1e-3; /* the line search halves while alpha > alpha_floor */
+static __thread double g_stop_tol = 1e-3;    /* early stop: alpha * sqrt(dun) < stop_tol */
+void orc_set_constants(double reg, double alpha_floor, double stop_tol) { g_reg = reg; g_alpha_floor = alpha_floor; g_stop_tol = stop_tol; }
 
 /* Test aid (variant bit 1): the inverse of a symmetric positive definite matrix by the symmetric sweep operator without pivoting --
    another backward-stable algorithm for the same quantity.  Used only to measure how far an iteration's result depends on HOW Quu is
@@ -784,10 +791,10 @@ static int solve_riccati(const orc_system* s, const orc_constraints* c, double* 
                     }
                 }
             }
-            /* Quu_inv = -(Quu + 1e-6 I)^-1 ; regularisation only inside the inverse (quirk D-3) */
+            /* Quu_inv = -(Quu + reg I)^-1, reg = 1e-6 in the reference ; regularisation only inside the inverse (quirk D-3) */
             double Qr[ORC_MAX_NU * ORC_MAX_NU], Qi[ORC_MAX_NU * ORC_MAX_NU];
             memcpy(Qr, Quu, sizeof(double) * nu * nu);
-            for (int i = 0; i < nu; i++) Qr[i * nu + i] += 1e-6;
+            for (int i = 0; i < nu; i++) Qr[i * nu + i] += g_reg;
             orc_inverse(nu, Qr, Qi);
             for (int i = 0; i < nu * nu; i++) Qi[i] = -1 * Qi[i];
             double* Kk = Ks + (size_t)k * nu * nx;
@@ -846,10 +853,10 @@ static int solve_riccati(const orc_system* s, const orc_constraints* c, double* 
             }
             newCost += orc_cost(s, nX + (size_t)(T - 1) * nx, zero_u, T - 1);
             if (pr && pr->n_trials < ORC_MAX_TRIALS) { pr->trial_alpha[pr->n_trials] = alpha; pr->trial_cost[pr->n_trials] = newCost; pr->n_trials++; }
-            if (!accepted && !(((newCost >= cost0) || isnan(newCost)) && alpha > 1e-3 && line_search)) {
+            if (!accepted && !(((newCost >= cost0) || isnan(newCost)) && alpha > g_alpha_floor && line_search)) {
                 accepted = 1;
                 acc_alpha = alpha; acc_cost = newCost; acc_dun = dun; acc_mask = mask_margin;
-                if (pr && g_probe_all && alpha > 1e-3 && line_search) { /* put the accepted rollout aside */
+                if (pr && g_probe_all && alpha > g_alpha_floor && line_search) { /* put the accepted rollout aside */
 #define SAVE_(dst, src, n) do { dst = (double*)malloc(sizeof(double) * (n)); memcpy(dst, src, sizeof(double) * (n)); } while (0)
                     SAVE_(sv_X, nX, (size_t)T * nx); SAVE_(sv_fX, nfX, (size_t)T * nf); SAVE_(sv_U, nU, (size_t)(T - 1) * nu);
                     SAVE_(sv_A, As, (size_t)(T - 1) * nx * nx); SAVE_(sv_B, Bs, (size_t)(T - 1) * nx * nu);
@@ -857,7 +864,7 @@ static int solve_riccati(const orc_system* s, const orc_constraints* c, double* 
 #undef SAVE_
                 }
             }
-        } while (!accepted || (sv_X && alpha_t > 1e-3));
+        } while (!accepted || (sv_X && alpha_t > g_alpha_floor));
         alpha = acc_alpha;
         if (sv_X) { /* back to the accepted rollout; alpha_t ran on */
             memcpy(nX, sv_X, sizeof(double) * T * nx); memcpy(nfX, sv_fX, sizeof(double) * T * nf); memcpy(nU, sv_U, sizeof(double) * (T - 1) * nu);
@@ -891,9 +898,9 @@ static int solve_riccati(const orc_system* s, const orc_constraints* c, double* 
         if (trace_alpha) trace_alpha[it] = alpha;
         it_done = it + 1;
         if (c) {
-            if (early_stop && alpha * sqrt(dun) < 1e-3) break; /* AL-ILQR.cpp:225 */
+            if (early_stop && alpha * sqrt(dun) < g_stop_tol) break; /* AL-ILQR.cpp:225 */
         } else {
-            if (early_stop && alpha * sqrt(dun) < 1e-3 && cost0 < 1e-3) break; /* ILQRRecursive.cpp:174 */
+            if (early_stop && alpha * sqrt(dun) < g_stop_tol && cost0 < 1e-3) break; /* ILQRRecursive.cpp:174 */
         }
     }
 #undef CONSTRAINTS

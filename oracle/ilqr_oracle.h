@@ -162,7 +162,7 @@ void orc_set_variant(int v);  /* test aid, algebraically neutral variants: bit 0
 /* ---- test aids for the per-instance parity proof (tests/parity_proof.py).  Not part of the restated algorithm: they only RECORD the
  * quantities the reference's discontinuous decisions are taken on, and let a solve resume from a state handed in from outside.
  * Thread-local: set and solve on the same thread. */
-#define ORC_MAX_TRIALS 16
+#define ORC_MAX_TRIALS 64 /* the device caps its step-size count at 64 (n_alpha_of) */
 typedef struct {
     double cost0;                        /* cost of the trajectory the iteration starts from (ILQRRecursive.cpp:155 compares against it) */
     int n_trials;                        /* line-search trials recorded (the last one is the accepted one unless orc_set_probe_all is on) */
@@ -189,6 +189,12 @@ void orc_set_probe_all(int on);
  * its active-set / limit tests are taken on the very numbers the caller's were.  NULL switches it off. */
 void orc_set_resume_x(const double* X);
 double orc_get_resume_x_dev(void);
+/* Test aid: the three constants a caller of the device's Riccati solvers may set (ilqr_problem_desc: reg, alpha_floor, stop_tol).  In
+ * orc_solve_recursive / orc_solve_al[_gains] ONLY, reg replaces the 1e-6 added to Quu inside its inverse, alpha_floor the 1e-3 every
+ * `alpha > 1e-3` of the line search compares with (the continuation of orc_set_probe_all included), stop_tol the 1e-3 that
+ * alpha * sqrt(dun) is compared with in the two early-stop tests; the `cost0 < 1e-3` of ILQRRecursive.cpp:174 stays a literal, as on
+ * the device.  The batch solvers keep the reference's literals.  Defaults (1e-6, 1e-3, 1e-3) = the reference; thread-local. */
+void orc_set_constants(double reg, double alpha_floor, double stop_tol);
 
 #ifdef __cplusplus
 }

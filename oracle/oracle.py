@@ -89,7 +89,7 @@ class System(C.Structure):
     ]
 
 
-MAX_TRIALS = 16
+MAX_TRIALS = 64
 
 
 class ProbeRec(C.Structure):
@@ -158,6 +158,8 @@ def lib():
         L.orc_set_resume_x.restype = None
         L.orc_get_resume_x_dev.argtypes = []
         L.orc_get_resume_x_dev.restype = C.c_double
+        L.orc_set_constants.argtypes = [C.c_double, C.c_double, C.c_double]
+        L.orc_set_constants.restype = None
         for n in ("orc_sd_logmap", "orc_sd_expmap"):
             getattr(L, n).argtypes = [dp, dp, dp]
         L.orc_sd_transport.argtypes = [dp, dp, dp, dp]
@@ -394,6 +396,49 @@ def step(s: System, x, u):
     return xn, fx, A.reshape(s.n_x, s.n_x), B.reshape(s.n_x, s.n_u), J.reshape(s.n_Q, s.n_x)
 
 
+DEFAULT_CONSTANTS = dict(reg=1e-6, alpha_floor=1e-3, stop_tol=1e-3)  # the reference's literals = ilqr_problem_desc's defaults
+
+
+def full_constants(constants=None):
+    """The three solver constants as a complete dict: the defaults, overridden by whatever `constants` names."""
+    out = dict(DEFAULT_CONSTANTS)
+    if constants:
+        unknown = set(constants) - set(out)
+        assert not unknown, f"unknown solver constants {sorted(unknown)}"
+        out.update({k: float(v) for k, v in constants.items()})
+    return out
+
+
+class constants:
+    """Context manager: the Riccati solvers (solve_recursive, solve_al) run with these solver constants inside the block and with the
+    reference's literals after it, whatever happens in between.  Test aid, see orc_set_constants in ilqr_oracle.h; the batch solvers
+    ignore it.  Thread-local like the other aids; do not nest."""
+
+    def __init__(self, reg=None, alpha_floor=None, stop_tol=None):
+        self.c = full_constants({k: v for k, v in dict(reg=reg, alpha_floor=alpha_floor, stop_tol=stop_tol).items() if v is not None})
+
+    def __enter__(self):
+        lib().orc_set_constants(self.c["reg"], self.c["alpha_floor"], self.c["stop_tol"])
+        return self
+
+    def __exit__(self, *exc):
+        d = DEFAULT_CONSTANTS
+        lib().orc_set_constants(d["reg"], d["alpha_floor"], d["stop_tol"])
+
+
+class _NoConstants:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        pass
+
+
+def _constants_ctx(c):
+    """constants=None leaves the oracle exactly as it is (the default path is not touched at all)."""
+    return constants(**full_constants(c)) if c is not None else _NoConstants()
+
+
 class _Aids:
     """Arms the oracle's test aids around one solve: the decision-margin probe and / or a resume state (see ilqr_oracle.h)."""
 
@@ -440,23 +485,25 @@ class _Aids:
         return out
 
 
-def solve_recursive(s: System, U0, nb_iter, line_search=True, early_stop=True, probe=False, resume=None):
+def solve_recursive(s: System, U0, nb_iter, line_search=True, early_stop=True, probe=False, resume=None, constants=None):
+    """constants: dict with any of reg, alpha_floor, stop_tol -- set for this solve only (test aid, ilqr_oracle.h); None = the reference's."""
     T, nx, nu, nf = s.T, s.n_x, s.n_u, s.n_f
     U0 = _arr(U0, (T - 1) * nu)
     X, fX, U = np.zeros((T, nx)), np.zeros((T, nf)), np.zeros((T - 1, nu))
     K, d = np.zeros((T - 1, nu, nx)), np.zeros((T - 1, nu))
     cost_ = np.zeros(1)
     tc, ta = np.full(max(nb_iter, 1), np.nan), np.full(max(nb_iter, 1), np.nan)
-    with _Aids(nb_iter, probe, resume) as aids:
+    with _constants_ctx(constants), _Aids(nb_iter, probe, resume) as aids:
         n = lib().orc_solve_recursive(C.byref(s), _dp(U0), nb_iter, int(line_search), int(early_stop), _dp(X), _dp(fX), _dp(U),
                                       _dp(K), _dp(d), _dp(cost_), _dp(tc), _dp(ta))
     return dict(X=X, fX=fX, U=U, K=K, d=d, cost=float(cost_[0]), iters=n, trace_cost=tc[:n], trace_alpha=ta[:n], probe=aids.records(n), x_dev=aids.x_dev)
 
 
-def solve_al(s: System, A, b, lambda0, U0, nb_iter, lag_update_step, penalty, scaling, line_search=True, early_stop=True, probe=False, resume=None):
+def solve_al(s: System, A, b, lambda0, U0, nb_iter, lag_update_step, penalty, scaling, line_search=True, early_stop=True, probe=False, resume=None,
+             constants=None):
     """A: (m, n_x+n_u) or (T-1, m, n_x+n_u); b likewise; lambda0: (T-1, m) (copied; returned updated).
     probe: also return the per-iteration decision margins; resume: dict(it0, init_penalty, lambda_mask) (test aids, ilqr_oracle.h).
-    Returns the gains K, d of the last sweep as solve_recursive does."""
+    constants: as in solve_recursive.  Returns the gains K, d of the last sweep as solve_recursive does."""
     T, nx, nu, nf = s.T, s.n_x, s.n_u, s.n_f
     A, b = _arr(A), _arr(b)
     per_step = 1 if A.ndim == 3 else 0
@@ -468,7 +515,7 @@ def solve_al(s: System, A, b, lambda0, U0, nb_iter, lag_update_step, penalty, sc
     K, d = np.zeros((T - 1, nu, nx)), np.zeros((T - 1, nu))
     cost_ = np.zeros(1)
     tc, ta = np.full(max(nb_iter, 1), np.nan), np.full(max(nb_iter, 1), np.nan)
-    with _Aids(nb_iter, probe, resume) as aids:
+    with _constants_ctx(constants), _Aids(nb_iter, probe, resume) as aids:
         n = lib().orc_solve_al_gains(C.byref(s), C.byref(c), _dp(lam), _dp(U0), nb_iter, lag_update_step, penalty, scaling,
                                      int(line_search), int(early_stop), _dp(X), _dp(fX), _dp(U), _dp(K), _dp(d), _dp(cost_), _dp(tc), _dp(ta))
     return dict(X=X, fX=fX, U=U, K=K, d=d, cost=float(cost_[0]), iters=n, trace_cost=tc[:n], trace_alpha=ta[:n], lam=lam, probe=aids.records(n),

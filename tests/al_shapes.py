@@ -6,8 +6,8 @@ registers of k_backward_si_dpp, up to 16 rows in the LDS of k_backward_mfma or o
 else in the generic sweep with its workspace.  The workloads carry one row (q_6 <= bound), so the constraint sets here are made for the tests:
 m rows that BIND for some instances of a batch and not for others, on positions, velocities, the time state and the controls.
 
-Not reached from here: the non-fused instantiations of k_backward_si_dpp (FUSED = false) run only with alpha_floor < 2^-15 (more than 16
-step sizes: the generic forward pass).  The oracle carries the reference's hard-wired floor of 1e-3, so there is nothing to compare them with."""
+The non-fused instantiations of k_backward_si_dpp (FUSED = false) run only with alpha_floor < 2^-15 (more than 16 step sizes: the generic
+forward pass); tests/solver_constants.py runs them, the 4-row state-only set made here included, against the oracle with the same floor."""
 from __future__ import annotations
 
 import numpy as np

@@ -228,6 +228,49 @@ int main() {
         CHECK(p.sweep == Sweep::SiDpp); CHECK(p.forward == Forward::Generic); CHECK(p.apply == Apply::None);
         CHECK(!p.fused); CHECK(p.kd_sym == 0); CHECK(!p.al_update); CHECK(!p.split);
     }
+    {
+        where = "n_alpha_of at its edges";
+        CHECK(n_alpha_of(true, 0.125) == 4);   // the floor is a step size: 1, 1/2, 1/4, 1/8
+        CHECK(n_alpha_of(true, 0.1) == 5);     // 1/8 > 0.1 goes on to 1/16
+        CHECK(n_alpha_of(true, 1e-3) == 11);
+        CHECK(n_alpha_of(true, 4e-5) == 16);   // 2^-15 = 3.05e-5: the last count the cooperative forward passes hold
+        CHECK(n_alpha_of(true, 2e-5) == 17);   // the first one past them
+        CHECK(n_alpha_of(true, 1e-6) == 21);
+        CHECK(n_alpha_of(true, 0.0) == 64);    // capped
+        CHECK(n_alpha_of(false, 1e-3) == 1); CHECK(n_alpha_of(false, 1e-6) == 1);  // no line search
+    }
+    for (int B : {256, 2048, 4096}) {
+        // more than 16 step sizes: the cooperative sweeps stay, the forward pass is the generic one, which applies its own winner and (AL) does the
+        // multiplier update itself; nothing is split
+        for (double floor : {2e-5, 1e-6}) {
+            for (int al = 0; al < 2; al++) {
+                where = "C2nd, alpha_floor < 2^-15";
+                PlanIn in = base(0, 2, al != 0, B);
+                if (al) { in.m = 2; in.con_state_only = true; }
+                in.alpha_floor = floor;
+                RiccatiPlan p = plan_riccati(in);
+                CHECK(p.n_alpha == (floor == 2e-5 ? 17 : 21));
+                CHECK(p.sweep == (B == 4096 ? Sweep::Rows : Sweep::Mfma)); CHECK(p.forward == Forward::Generic); CHECK(p.apply == Apply::None);
+                CHECK(!p.al_update); CHECK(!p.split); CHECK(!p.fused); CHECK(p.kd_sym == 0); CHECK(!p.needs_ws);
+                CHECK(p.init == Init::Lti); CHECK(p.init_al_update == (al != 0));
+                where = "C4, alpha_floor < 2^-15";
+                in = base(1, 2, al != 0, B);
+                if (al) { in.m = 2; in.con_state_only = true; }
+                in.alpha_floor = floor;
+                p = plan_riccati(in);
+                CHECK(p.sweep == (B == 4096 ? Sweep::Rows : Sweep::Mfma)); CHECK(p.forward == Forward::Generic); CHECK(p.apply == Apply::None);
+                CHECK(!p.al_update); CHECK(!p.split); CHECK(!p.fused); CHECK(p.kd_sym == 0); CHECK(!p.needs_ws);
+                in.sweep = SweepPin::Mfma; in.reroll = RerollPin::Dpp;
+                p = plan_riccati(in);
+                CHECK(p.sweep == Sweep::Mfma); CHECK(p.forward == Forward::Generic); CHECK(p.apply == Apply::None); CHECK(!p.split);
+            }
+        }
+        where = "C4, alpha_floor 4e-5";  // sixteen step sizes are still cooperative
+        PlanIn in = c4(B);
+        in.alpha_floor = 4e-5;
+        const RiccatiPlan p = plan_riccati(in);
+        CHECK(p.n_alpha == 16); CHECK(p.forward == Forward::Mfma); CHECK(p.apply != Apply::None);
+    }
     for (int B : {2048, 4096}) {
         where = "C3, off32 false";
         PlanIn in = c3(B);

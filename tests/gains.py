@@ -36,6 +36,9 @@ AL = dict(row=5, bound=2.0, penalty=0.25, scaling=1.1, lag=3)   # one state row 
 # STOP_CASE's iters are asserted to hold instances that stopped early
 STOP_CASE = ("C1j", 9, 6)
 REFUSAL = "ilqr_problem_gains needs a plan"
+# The sweeps of ilqr_problem_gains read the descriptor's reg (inside the inverse of Quu only): one case away from its default of 1e-6, where a sweep
+# that put reg into the value update or dropped a reg term of a closed form is off by far more than the tolerances -- (shape, T, constants)
+REG_CASE = ("C3", 25, dict(reg=1e-2))
 
 
 def make_case(ctx, name, T, Bn=B):
@@ -91,14 +94,15 @@ def make_plan(p, cfg, source, psi=None):
     return n
 
 
-def oracle_gains(s, U, variant=0, perturb=None):
-    """K, d of the oracle's backward pass about rollout(U): its one-iteration solve with the line search off (alpha = 1: d unscaled)."""
+def oracle_gains(s, U, variant=0, perturb=None, constants=None):
+    """K, d of the oracle's backward pass about rollout(U): its one-iteration solve with the line search off (alpha = 1: d unscaled).
+    constants: the solver constants of the case's descriptor (tests/solver_constants.py), None = the defaults."""
     u = np.asarray(U, float).reshape(-1)
     if perturb is not None:
         u = u * (1.0 + np.where(np.arange(u.size) % 2 == 0, perturb[0], perturb[1]) * 2.0 ** -52)
     orc.set_variant(variant)
     try:
-        r = orc.solve_recursive(s, u, 1, False, False)
+        r = orc.solve_recursive(s, u, 1, False, False, constants=constants)
     finally:
         orc.set_variant(0)
     return r["K"], r["d"]
@@ -108,14 +112,14 @@ def new_stats():
     return dict(n=0, ill=0, worst_K=0.0, worst_d=0.0, worst_ratio=0.0)
 
 
-def check_against_oracle(systems, U, K, d, status, tag, stats, instances=None):
+def check_against_oracle(systems, U, K, d, status, tag, stats, instances=None, constants=None):
     """(a) for every instance (or `instances`) whose status is not NONFINITE."""
     idx = list(range(len(systems))) if instances is None else list(instances)
     n_ill = 0
     for i in idx:
         if status[i] & 1:
             continue
-        Kr, dr = oracle_gains(systems[i], U[i])
+        Kr, dr = oracle_gains(systems[i], U[i], constants=constants)
         assert np.all(np.isfinite(K[i])) and np.all(np.isfinite(d[i])), f"{tag}: gains of instance {i} are not finite"
         okK = np.abs(K[i] - Kr) <= K_TOL["atol"] + K_TOL["rtol"] * np.abs(Kr)
         okd = np.abs(d[i] - dr) <= D_TOL["atol"] + D_TOL["rtol"] * np.abs(dr)
@@ -126,7 +130,7 @@ def check_against_oracle(systems, U, K, d, status, tag, stats, instances=None):
             continue
         sK, sd = np.zeros_like(Kr), np.zeros_like(dr)   # the oracle's own sensitivity, per entry
         for kw in [dict(variant=v) for v in pp.VARIANTS] + [dict(perturb=pt) for pt in pp.PERTURB]:
-            Kv, dv = oracle_gains(systems[i], U[i], **kw)
+            Kv, dv = oracle_gains(systems[i], U[i], constants=constants, **kw)
             sK, sd = np.maximum(sK, np.abs(Kv - Kr)), np.maximum(sd, np.abs(dv - dr))
         for name, got, ref, ok, sens in (("K", K[i], Kr, okK, sK), ("d", d[i], dr, okd, sd)):
             bad = ~ok & ~(np.abs(got - ref) <= pp.ILL_FACTOR * sens)
@@ -158,7 +162,7 @@ def check_unmoved(before, after, alpha, tag):
     assert np.array_equal(alpha, np.ones_like(alpha)), f"{tag}: alpha is not all ones after gains()"
 
 
-def check_plan_gains(p, cfg, systems, source, tag, stats, psi=None, instances=None, want_stopped=False):
+def check_plan_gains(p, cfg, systems, source, tag, stats, psi=None, instances=None, want_stopped=False, constants=None):
     """A plan of `source`, gains() about it: (a) and (c).  Returns the plan dict for the execution checks."""
     n = make_plan(p, cfg, source, psi)
     before = snapshot(p, n)
@@ -169,8 +173,41 @@ def check_plan_gains(p, cfg, systems, source, tag, stats, psi=None, instances=No
     K, d = p.K(), p.d()
     after = snapshot(p, n)
     check_unmoved(before, after, p.alpha(), tag)
-    check_against_oracle(systems, before["U"], K, d, before["status"], tag, stats, instances)
+    check_against_oracle(systems, before["U"], K, d, before["status"], tag, stats, instances, constants)
     return dict(X=before["X"], U=before["U"], K=K, d=d, cost=before["cost"])
+
+
+def with_constants(desc, constants):
+    """A copy of the descriptor with the solver constants set (the made cases are shared: theirs stay as they are)."""
+    out = type(desc).from_buffer_copy(desc)
+    for k, v in constants.items():
+        setattr(out, k, float(v))
+    return out
+
+
+def reg_moves_the_gains(Kd_at, Kd_default):
+    """The condition that keeps a reg case from being vacuous, on the oracle alone: K about the same controls moves by more than 100 x its
+    tolerance somewhere when reg does."""
+    (K1, _), (K0, _) = Kd_at, Kd_default
+    return bool(np.max(np.abs(K1 - K0) / (K_TOL["atol"] + K_TOL["rtol"] * np.abs(K0))) > 100)
+
+
+def check_reg_case(ctx, stats):
+    """REG_CASE: a zero plan and a recursive plan made with reg = 1e-2, gains() about them: (a) against the oracle with the same reg, (b), (c)."""
+    name, T, constants = REG_CASE
+    cfg, desc, inp, systems = make_case(ctx, name, T)
+    desc = with_constants(desc, constants)
+    p = workloads.load_batch(ctx, desc, inp, B)
+    try:
+        for source in ("zero", "rec"):
+            plan = check_plan_gains(p, cfg, systems, source, f"{name} T={T} {source} {constants}", stats, constants=constants)
+            for i in (0, 1):
+                assert reg_moves_the_gains(oracle_gains(systems[i], plan["U"][i], constants=constants), oracle_gains(systems[i], plan["U"][i])), \
+                    f"{name} T={T} {source}: reg does not move the gains of instance {i}"
+            p.set_controls(inp["U0"])
+        check_bits(p, inp, bits_controls(inp), f"{name} T={T} {constants} bits")
+    finally:
+        p.close()
 
 
 def check_bits(p, inp, U, tag):

@@ -48,6 +48,7 @@ K_TOL, D_TOL = gn.K_TOL, gn.D_TOL
 NO_ROWS = "ilqr_problem_gains_al needs constraint rows"
 NO_PLAN = "ilqr_problem_gains_al needs a plan"
 BAD_PENALTY = "the penalty must be finite and >= 0"
+REG_CASE = ("C3-m1", 25, dict(reg=1e-2))   # as gains.REG_CASE, for the sweeps of ilqr_problem_gains_al
 
 # (e): tests/closed_loop_con.py picked its sigmas for T <= 10.  At T = 25 the executions of PosOrnTime-2 about a plan of six AL iterations leave
 # every bound under them (non-finite on the host build, in closed_loop_noise alone: no property of the gains under test); a hundredth keeps them finite
@@ -121,14 +122,15 @@ def restore(p, inp):
 
 # ----------------------------------------------------------------------------------------------------------- (a)
 
-def oracle_gains(s, A, b, lam, U, pen, variant=0, perturb=None):
-    """(K, d, mask_margin_in) of the oracle's AL sweep about rollout(U) with the multipliers lam and the penalty pen."""
+def oracle_gains(s, A, b, lam, U, pen, variant=0, perturb=None, constants=None):
+    """(K, d, mask_margin_in) of the oracle's AL sweep about rollout(U) with the multipliers lam and the penalty pen.
+    constants: the solver constants of the case's descriptor (tests/solver_constants.py), None = the defaults."""
     u = np.asarray(U, float).reshape(-1)
     if perturb is not None:
         u = u * (1.0 + np.where(np.arange(u.size) % 2 == 0, perturb[0], perturb[1]) * 2.0 ** -52)
     orc.set_variant(variant)
     try:
-        r = orc.solve_al(s, A, b, lam, u, 1, 2, pen, 1.0, line_search=False, early_stop=False, probe=True)
+        r = orc.solve_al(s, A, b, lam, u, 1, 2, pen, 1.0, line_search=False, early_stop=False, probe=True, constants=constants)
     finally:
         orc.set_variant(0)
     return r["K"], r["d"], r["probe"][0]["mask_margin_in"]
@@ -138,7 +140,7 @@ def new_stats():
     return dict(gn.new_stats(), skipped=0)
 
 
-def check_against_oracle(systems, inp, U, lam, pen, K, d, status, tag, stats, instances=None):
+def check_against_oracle(systems, inp, U, lam, pen, K, d, status, tag, stats, instances=None, constants=None):
     """(a) for every instance (or `instances`) whose status is not NONFINITE."""
     idx = list(range(len(systems))) if instances is None else list(instances)
     A, b = inp["A"], inp["b"]
@@ -146,7 +148,7 @@ def check_against_oracle(systems, inp, U, lam, pen, K, d, status, tag, stats, in
     for i in idx:
         if status[i] & 1:
             continue
-        Kr, dr, margin = oracle_gains(systems[i], A, b, lam[i], U[i], pen)
+        Kr, dr, margin = oracle_gains(systems[i], A, b, lam[i], U[i], pen, constants=constants)
         assert np.all(np.isfinite(K[i])) and np.all(np.isfinite(d[i])), f"{tag}: gains of instance {i} are not finite"
         tK, td = K_TOL["atol"] + K_TOL["rtol"] * np.abs(Kr), D_TOL["atol"] + D_TOL["rtol"] * np.abs(dr)
         okK, okd = np.abs(K[i] - Kr) <= tK, np.abs(d[i] - dr) <= td
@@ -160,7 +162,7 @@ def check_against_oracle(systems, inp, U, lam, pen, K, d, status, tag, stats, in
             continue
         sK, sd = np.zeros_like(Kr), np.zeros_like(dr)   # the oracle's own sensitivity, per entry
         for kw in [dict(variant=v) for v in pp.VARIANTS] + [dict(perturb=pt) for pt in pp.PERTURB]:
-            Kv, dv, _ = oracle_gains(systems[i], A, b, lam[i], U[i], pen, **kw)
+            Kv, dv, _ = oracle_gains(systems[i], A, b, lam[i], U[i], pen, constants=constants, **kw)
             sK, sd = np.maximum(sK, np.abs(Kv - Kr)), np.maximum(sd, np.abs(dv - dr))
         for name, got, ref, ok, sens in (("K", K[i], Kr, okK, sK), ("d", d[i], dr, okd, sd)):
             bad = ~ok & ~(np.abs(got - ref) <= pp.ILL_FACTOR * sens)
@@ -177,7 +179,7 @@ def check_against_oracle(systems, inp, U, lam, pen, K, d, status, tag, stats, in
     assert 10 * n_skip <= len(idx), f"{tag}: {n_skip} of {len(idx)} instances have a row at rounding distance from its bound (at most one in ten may be skipped)"
 
 
-def check_plan_gains(p, cfg, inp, systems, source, pens, tag, stats, psi=None, instances=None):
+def check_plan_gains(p, cfg, inp, systems, source, pens, tag, stats, psi=None, instances=None, constants=None):
     """A plan of `source`, gains_al(pen) about it for every pen of `pens`: (a) and (c).  Returns the plan dict (gains of the last pen)."""
     n = make_plan(p, cfg, inp, source, psi)
     before = gn.snapshot(p, n)
@@ -186,8 +188,30 @@ def check_plan_gains(p, cfg, inp, systems, source, pens, tag, stats, psi=None, i
         K, d = p.K(), p.d()
         gn.check_unmoved(before, gn.snapshot(p, n), p.alpha(), f"{tag} pen={pen:.6g}")
         if systems is not None:
-            check_against_oracle(systems, inp, before["U"], before["lam"], pen, K, d, before["status"], f"{tag} pen={pen:.6g}", stats, instances)
+            check_against_oracle(systems, inp, before["U"], before["lam"], pen, K, d, before["status"], f"{tag} pen={pen:.6g}", stats, instances,
+                                 constants)
     return dict(X=before["X"], U=before["U"], K=K, d=d, cost=before["cost"], lam=before["lam"], status=before["status"])
+
+
+def check_reg_case(ctx, stats):
+    """REG_CASE: a zero plan and an AL plan made with reg = 1e-2, gains_al about them at both penalties: (a) against the oracle with the same reg, (c);
+    then (b) on the multipliers and controls of that solve."""
+    case, T, constants = REG_CASE
+    cfg, desc, inp, systems = make_case(ctx, case, T)
+    p = workloads.load_batch(ctx, gn.with_constants(desc, constants), inp, B)
+    try:
+        for source in ("zero", "al"):
+            restore(p, inp)
+            plan = check_plan_gains(p, cfg, inp, systems, source, penalties(cfg), f"{case} T={T} {source} {constants}", stats, constants=constants)
+            pen = penalties(cfg)[1]
+            for i in (0, 1):
+                at = oracle_gains(systems[i], inp["A"], inp["b"], plan["lam"][i], plan["U"][i], pen, constants=constants)
+                assert gn.reg_moves_the_gains(at[:2], oracle_gains(systems[i], inp["A"], inp["b"], plan["lam"][i], plan["U"][i], pen)[:2]), \
+                    f"{case} T={T} {source}: reg does not move the gains of instance {i}"
+        lam, U = multipliers_and_controls(p, cfg, inp)
+        check_bits(p, inp, lam, U, penalties(cfg)[1], f"{case} T={T} {constants} bits")
+    finally:
+        p.close()
 
 
 # ----------------------------------------------------------------------------------------------------------- (b), (d)

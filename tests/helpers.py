@@ -182,6 +182,8 @@ def oracle_system_of_instance(cfg, inp, i, segs=None):
 
 
 def oracle_solve_instance(cfg, inp, i, nb_iter, early_stop, segs=None):
+    """The oracle's own run of instance i, with the solver constants of the case (cfg["constants"], absent = the reference's)."""
+    consts = cfg.get("constants")
     s = oracle_system_of_instance(cfg, inp, i, segs)
     U0 = inp["U0"][i]
     if cfg["kind"] in (2, 3) and inp.get("dof", 7) < 7:  # joint-space batches are padded to 7 joints on the device only
@@ -189,10 +191,11 @@ def oracle_solve_instance(cfg, inp, i, nb_iter, early_stop, segs=None):
         U0 = np.hstack([U0[:, :n], U0[:, 7:]])
     U0 = U0.reshape(-1)
     if cfg["solver"] == "recursive":
-        return orc.solve_recursive(s, U0, nb_iter, True, early_stop)
+        return orc.solve_recursive(s, U0, nb_iter, True, early_stop, constants=consts)
     if cfg["solver"] == "al":
         al = cfg["al"]
-        return orc.solve_al(s, inp["A"], inp["b"], inp["lambda0"][i], U0, nb_iter, al["lag"], al["penalty"], al["scaling"], True, early_stop)
+        return orc.solve_al(s, inp["A"], inp["b"], inp["lambda0"][i], U0, nb_iter, al["lag"], al["penalty"], al["scaling"], True, early_stop,
+                            constants=consts)
     raise KeyError(cfg["solver"])
 
 

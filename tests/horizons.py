@@ -83,7 +83,7 @@ def check_case(ctx, cfg, desc, inp, tag, nb_iter=NIT, always=(0, 1), out=None):
     the device's own state before its last iteration (the iteration that wrote them: a gain image left from an earlier iteration shows
     there, while the drift of an ill-conditioned instance over several iterations does not); the trajectories where the path is the
     oracle's.  Returns a one-line summary; out: a dict that receives the longer solve's cost, iters, step sizes, multipliers (AL), its
-    distance to the oracle's runs and those runs."""
+    distance to the oracle's runs, those runs and the status words."""
     Bn = len(inp["q0"])
     segs = panda_segs()
     p = workloads.load_batch(ctx, desc, inp, Bn)
@@ -99,6 +99,7 @@ def check_case(ctx, cfg, desc, inp, tag, nb_iter=NIT, always=(0, 1), out=None):
         K, d, X, U, cost, iters = p.K(), p.d(), p.X(), p.U(), p.cost(), p.iters()
         at = p.trace(nb_iter)[1]
         lam = p.lam() if cfg["solver"] == "al" else None
+        status = p.status()
         runs = {}
 
         def oracle_solve(i):
@@ -136,11 +137,11 @@ def check_case(ctx, cfg, desc, inp, tag, nb_iter=NIT, always=(0, 1), out=None):
             np.testing.assert_allclose(U[i][:, :nuo], r["U"], rtol=0, atol=2e-3, err_msg=f"{tag}: U of instance {i}")
             nxu += 1
     if out is not None:
-        out.update(cost=cost, iters=iters, alpha=at, lam=lam, rel=rel, runs=runs)
+        out.update(cost=cost, iters=iters, alpha=at, lam=lam, rel=rel, runs=runs, status=status)
     mult = ""
     if "n_multiplier_checked" in summ:  # AL: every multiplier update recomputed (parity_proof.check_multipliers)
         mult = (f", multipliers of {summ['n_multiplier_checked']} ({summ['n_multiplier_updates']} updates, {summ['n_multiplier_skipped']} skipped, "
                 f"{summ['n_clamp_ties']} clamp ties, worst {summ['worst_multiplier_ratio']:.2f} of the bound)")
     return (f"{tag}: gains of {n1} / {n4} instances (1 / {nb_iter} iterations; {ill1} / {ill4} ill-conditioned), trajectories of {nxu}, within 1e-4 "
             f"{summ['frac_within_1e4']:.2f}, proofs {summ['n_proofs']} ({summ['n_steps_checked']} steps, {summ['n_tie_decisions']} ties, "
-            f"{summ['n_steps_ill_conditioned']} ill-conditioned)" + mult)
+            f"{summ['n_steps_ill_conditioned']} ill-conditioned, worst step {summ['worst_step_rel']:.1e})" + mult)

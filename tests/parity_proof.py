@@ -67,6 +67,13 @@ TIE_RTOL = 1e-9     # a line-search comparison newCost < cost0 is a tie when |ne
 MASK_ATOL = 1e-12   # AL rows with several non-zero coefficients only (see the header)
 STOP_RTOL = 1e-9    # early-stop tests alpha sqrt(sum ||du||) < 1e-3 and cost < 1e-3: relative distance to the threshold
 ALPHA_FLOOR = 1e-3  # ILQRRecursive.cpp:155 / BatchILQRCP.cpp:152
+STOP_TOL = 1e-3     # ILQRRecursive.cpp:174 / AL-ILQR.cpp:225
+
+
+def constants_of(cfg):
+    """The solver constants a case runs its Riccati solver with: cfg["constants"] = dict(reg, alpha_floor, stop_tol) (any subset; the
+    loader writes the same values into the problem descriptor), the reference's literals where the key or an entry is absent."""
+    return orc.full_constants(cfg.get("constants"))
 
 
 def _unpad(cfg, inp, a):
@@ -106,12 +113,13 @@ def one_step(cfg, inp, i, it, states, segs=None, sysm=None, probe="all", perturb
         U = U * (1.0 + sg * 2.0 ** -52)
         X = None
     if cfg["solver"] == "recursive":
-        return orc.solve_recursive(s, U, 1, True, False, probe=probe, resume=dict(it0=it, X=X))
+        return orc.solve_recursive(s, U, 1, True, False, probe=probe, resume=dict(it0=it, X=X), constants=cfg.get("constants"))
     al = cfg["al"]
     pen = al["penalty"] * al["scaling"] ** (it // al["lag"])          # penalty in force during iteration `it`
     pen_in = al["penalty"] * al["scaling"] ** ((it - 1) // al["lag"]) if it else pen  # ... when the incoming trajectory was rolled out
     res = dict(it0=it, init_penalty=pen_in, lambda_mask=states[it - 1]["lam"][i] if it else None, X=X)
-    return orc.solve_al(s, inp["A"], inp["b"], states[it]["lam"][i], U, 1, al["lag"], pen, al["scaling"], True, False, probe=probe, resume=res)
+    return orc.solve_al(s, inp["A"], inp["b"], states[it]["lam"][i], U, 1, al["lag"], pen, al["scaling"], True, False, probe=probe, resume=res,
+                        constants=cfg.get("constants"))
 
 
 def _rel(a, b):
@@ -123,10 +131,11 @@ def _rel(a, b):
     return abs(a - b) / max(abs(b), 1e-300)
 
 
-def decisions_follow(pr, ag, line_search=True, floor_strict=False):
+def decisions_follow(pr, ag, line_search=True, floor_strict=False, alpha_floor=ALPHA_FLOOR):
     """(b) of the header.  pr: oracle probe record with ALL trials; ag: the step size the GPU accepted.  Returns (ok, ties, detail):
     ties = number of comparisons that go the other way within TIE_RTOL.  floor_strict: the batch solvers stop at alpha < 1e-3
-    (BatchILQRCP.cpp:152), the recursive ones go on while alpha > 1e-3 (ILQRRecursive.cpp:155) -- the same last step size 2^-10."""
+    (BatchILQRCP.cpp:152), the recursive ones go on while alpha > 1e-3 (ILQRRecursive.cpp:155) -- the same last step size 2^-10.
+    alpha_floor: the floor the Riccati solve ran with (constants_of); the batch solvers (floor_strict) always have 1e-3."""
     c0 = pr["cost0"]
     ties = 0
     for a, c in zip(pr["alpha"], pr["cost"]):
@@ -134,7 +143,7 @@ def decisions_follow(pr, ag, line_search=True, floor_strict=False):
         if floor_strict:  # BatchILQRCP.cpp:152: if ((cost < cost0) || (alpha < 1e-3)) accept
             at_floor, improves = a < ALPHA_FLOOR, bool(c < c0)
         else:             # ILQRRecursive.cpp:155: while (((newCost >= cost0) || isNaN(newCost)) && alpha > 1e-3 && line_search)
-            at_floor, improves = not (a > ALPHA_FLOOR), not (bool(c >= c0) or np.isnan(c))
+            at_floor, improves = not (a > alpha_floor), not (bool(c >= c0) or np.isnan(c))
         if a > ag:  # the GPU rejected this step size
             if at_floor or not line_search:
                 return False, ties, dict(alpha=a, why="went below the floor")
@@ -196,6 +205,8 @@ def prove_instance(cfg, inp, i, states, ct, at, iters, segs=None, nb_iter=None, 
     n_ties = n_ill = 0
     worst_ratio = 0.0
     multi = _multi_nonzero_rows(cfg, inp)
+    consts = constants_of(cfg)
+    stop_tol = consts["stop_tol"]
     for it in range(n):
         r = one_step(cfg, inp, i, it, states, segs, s)
         pr = r["probe"][0]
@@ -214,7 +225,7 @@ def prove_instance(cfg, inp, i, states, ct, at, iters, segs=None, nb_iter=None, 
             if st["cost0_rel"] > COST0_RTOL:
                 fails.append("cost0")
         # (b) decisions from the oracle's own trial costs
-        ok, ties, why = decisions_follow(pr, ag)
+        ok, ties, why = decisions_follow(pr, ag, alpha_floor=consts["alpha_floor"])
         if not ok:
             if multi and pr["mask_margin_in"] <= MASK_ATOL:  # g of a multi-coefficient row is a sum in another order on the GPU
                 ties += 1
@@ -253,10 +264,10 @@ def prove_instance(cfg, inp, i, states, ct, at, iters, segs=None, nb_iter=None, 
             # the stop decision taken on this iteration's result (ILQRRecursive.cpp:174-176, AL-ILQR.cpp:225)
             crit = ao * np.sqrt(pr["dun"])
             co = float(r["trace_cost"][0])
-            stop_o = crit < 1e-3 and (cfg["solver"] == "al" or co < 1e-3)
+            stop_o = crit < stop_tol and (cfg["solver"] == "al" or co < 1e-3)  # (the cost threshold is a literal on both sides)
             stop_g = (it == n - 1) and (n < nb_iter)
             if stop_o != stop_g:
-                near = abs(crit - 1e-3) <= STOP_RTOL * 1e-3 or (cfg["solver"] != "al" and abs(co - 1e-3) <= STOP_RTOL * 1e-3)
+                near = abs(crit - stop_tol) <= STOP_RTOL * stop_tol or (cfg["solver"] != "al" and abs(co - 1e-3) <= STOP_RTOL * 1e-3)
                 st["stop"] = "tie:early-stop" if near else "FAIL"
                 st["stop_crit"] = float(crit)
                 if near:
@@ -416,14 +427,16 @@ def check_multipliers(cfg, inp, states, final, iters, indices=None):
 def summarize(results):
     """Fractions over a list of (within_1e4: bool, proof or None) pairs, plus what the proofs leaned on: the number of decisions
     taken inside the rounding of the oracle's own comparison (ties) and of steps accepted as ill-conditioned, with the worst ratio of
-    the GPU's deviation to the oracle's own variant sensitivity (<= ILL_FACTOR by construction)."""
+    the GPU's deviation to the oracle's own variant sensitivity (<= ILL_FACTOR by construction); worst_step_rel: the largest relative
+    distance of a checked step's cost to the oracle's at the same step size (a measured value, reported only)."""
     n = len(results)
     within = sum(1 for w, _ in results if w)
     tie = sum(1 for w, pf in results if not w and pf and pf["verdict"] == "tie")
     stepwise = sum(1 for w, pf in results if not w and pf and pf["verdict"] == "stepwise")
     unexpl = n - within - tie - stepwise
     proofs = [pf for _, pf in results if pf]
-    return dict(n=n, frac_within_1e4=within / n, frac_proven_tie=tie / n, frac_proven_stepwise=stepwise / n, frac_unexplained=unexpl / n,
+    rels = [st["rel"] for pf in proofs for st in pf["steps"] if "rel" in st and np.isfinite(st["rel"]) and not st["how"].startswith("FAIL")]
+    return dict(worst_step_rel=max(rels, default=0.0), n=n, frac_within_1e4=within / n, frac_proven_tie=tie / n, frac_proven_stepwise=stepwise / n, frac_unexplained=unexpl / n,
                 n_proofs=len(proofs), n_steps_checked=sum(len(pf["steps"]) for pf in proofs), n_tie_decisions=sum(pf["n_ties"] for pf in proofs),
                 n_steps_ill_conditioned=sum(pf["n_ill"] for pf in proofs), worst_ill_ratio=max([pf["worst_ill_ratio"] for pf in proofs], default=0.0))
 

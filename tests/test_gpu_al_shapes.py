@@ -26,8 +26,8 @@ every multiplier update from the device's own trajectory in extended precision a
 (parity_proof.check_multipliers), gains at every step after 1 and 6 iterations, trajectories where the path is the oracle's; and the multipliers
 after the solve against the oracle's on those instances.
 
-Not reached: k_backward_si_dpp<FUSED = false> runs only with alpha_floor < 2^-15 (the generic forward pass), and the oracle carries the reference's
-hard-wired floor of 1e-3: nothing to compare it with.  The same sets on the host build of the generic kernels: tests/test_al_shapes_cpu.py."""
+k_backward_si_dpp<FUSED = false> runs only with alpha_floor < 2^-15 (the generic forward pass): tests/test_gpu_solver_constants.py, with MR = 1 and
+with the 4-row state-only set of this table.  The same sets on the host build of the generic kernels: tests/test_al_shapes_cpu.py."""
 import pytest
 
 from tests import al_shapes as al

@@ -226,14 +226,17 @@ def test_rerolls_of_the_winner_agree(ctx, cfg_name, B, monkeypatch):
     np.testing.assert_allclose(b["X"][fin], a["X"][fin], rtol=0, atol=1e-8)
 
 
-@pytest.mark.parametrize("cfg_name,solver,m", [("C3", "al", 0), ("C2", "recursive", 0), ("C3", "al", 4)], ids=["C3-al", "C2-recursive", "C3-al-m4"])
-def test_sweep_lane_groupings_agree(ctx, cfg_name, solver, m, monkeypatch):
+@pytest.mark.parametrize("cfg_name,solver,m,alpha_floor", [("C3", "al", 0, None), ("C2", "recursive", 0, None), ("C3", "al", 4, None), ("C3", "al", 0, 2e-5)],
+                         ids=["C3-al", "C2-recursive", "C3-al-m4", "C3-al-floor2e-5"])
+def test_sweep_lane_groupings_agree(ctx, cfg_name, solver, m, alpha_floor, monkeypatch):
     """The register-resident sweep of the single-integrator systems runs with 16 lanes per instance while that gives every SIMD at most one
     wave and with 8 lanes per instance (two instances per DPP row, every broadcast issued once per half with a bank mask) beyond: a batch
     just over 4 x 1024 instances takes the second form, a 61-instance cut-out of it the first.  Same operations on the same operands in the
     same order in both: bit-identical results, whichever half of a DPP row an instance sits in; the cut-out then goes through the
     per-instance proof.  C3 with m = 4: the binding 4-row set of tests/al_shapes.py, all four register rows in use; the multipliers are
-    bit-identical too."""
+    bit-identical too.  C3 with alpha_floor = 2e-5: 17 step sizes, one more than the cooperative forward passes hold -- the sweep no longer applies
+    the previous winner itself (k_backward_si_dpp<FUSED = false>, plain gain records) under the generic forward pass, in both lane groupings; the
+    oracle and the proof run with the same floor (tests/solver_constants.py)."""
     from ilqr_planner_amd import workloads
     from tests import parity_proof as pp
 
@@ -244,10 +247,15 @@ def test_sweep_lane_groupings_agree(ctx, cfg_name, solver, m, monkeypatch):
     if m:
         cfg_s, inp = _with_rows(ctx, cfg_name, 40, m, "state", inp)
         cfg = dict(cfg, al=cfg_s["al"])
+    if alpha_floor is not None:
+        cfg["constants"] = dict(alpha_floor=alpha_floor)  # what the oracle and the proof take their floor from
+        desc.alpha_floor = alpha_floor
     big = _solve(ctx, cfg, desc, inp, B, nb_iter, solver)
     rng = np.random.default_rng(11)
     idx = np.sort(rng.choice(B, 61, replace=False))
     desc_s, _ = workloads.make_batch(ctx, cfg, B=len(idx))
+    if alpha_floor is not None:
+        desc_s.alpha_floor = alpha_floor
     inp_s = _take(inp, idx)
     small = _solve(ctx, cfg, desc_s, inp_s, len(idx), nb_iter, solver, keep=True)
     np.testing.assert_array_equal(small["cost"], big["cost"][idx])

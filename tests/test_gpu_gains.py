@@ -66,6 +66,14 @@ def test_oracle_sweep_about_riccati_plans(ctx, name):
           f"tolerance: K {stats['worst_K']:.3f}, d {stats['worst_d']:.3f}")
 
 
+def test_oracle_sweep_and_bits_at_reg_1e_2(ctx):
+    """gains.REG_CASE: the descriptor's reg away from its default, the oracle with the same reg (orc_set_constants)."""
+    stats = gn.new_stats()
+    gn.check_reg_case(ctx, stats)
+    print(f"reg case: {stats}")
+    assert stats["n"] >= gn.B
+
+
 @pytest.mark.parametrize("name", gn.SHAPES)
 def test_oracle_sweep_on_a_ragged_batch_of_70(ctx, name):
     stats = gn.new_stats()

@@ -77,6 +77,14 @@ def test_oracle_al_sweep_about_riccati_plans(ctx, case, T):
     print(f"{case} T={T}: {_line(stats)}")
 
 
+def test_oracle_al_sweep_and_bits_at_reg_1e_2(ctx):
+    """gains_al.REG_CASE: the descriptor's reg away from its default, the oracle with the same reg (orc_set_constants)."""
+    stats = ga.new_stats()
+    ga.check_reg_case(ctx, stats)
+    print(f"reg case: {_line(stats)}")
+    assert stats["n"] >= 2 * ga.B
+
+
 @pytest.mark.parametrize("T", (9, 25))
 @pytest.mark.parametrize("case", CP_CASES)
 def test_oracle_al_sweep_about_batch_cp_plans(ctx, case, T):

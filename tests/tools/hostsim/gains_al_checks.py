@@ -51,6 +51,8 @@ def main():
             finally:
                 p.close()
             print(f"{case} T={T}: oracle, unmoved, bits, degenerate rows ok", flush=True)
+    ga.check_reg_case(ctx, stats)
+    print(f"{ga.REG_CASE}: oracle with the same reg, unmoved, bits ok", flush=True)
     ga.check_state_machine(ctx, batch_solvers=False)
     print(f"{stats['n']} instances against the oracle's AL sweep, {stats['ill']} by its sensitivity (worst ratio {stats['worst_ratio']:.2f}), "
           f"{stats['skipped']} skipped at a mask margin below {ga.MARGIN:g}; worst share of the tolerance: K {stats['worst_K']:.3f}, d {stats['worst_d']:.3f}; "

@@ -52,6 +52,8 @@ def main():
         print(f"{name} T={T}: early-stopped instances ok (iters {p.iters().tolist()})", flush=True)
     finally:
         p.close()
+    gn.check_reg_case(ctx, stats)
+    print(f"{gn.REG_CASE}: oracle with the same reg, unmoved, bits ok", flush=True)
     gn.check_state_machine(ctx, batch_solvers=False)
     print(f"{stats['n']} instances against the oracle's sweep, {stats['ill']} by its sensitivity (worst ratio {stats['worst_ratio']:.2f}); worst share "
           f"of the tolerance: K {stats['worst_K']:.3f}, d {stats['worst_d']:.3f}; replay: {rep['n']} samples, {rep['ill']} by their sensitivity; "
