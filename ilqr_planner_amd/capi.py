@@ -24,6 +24,7 @@ CL_CON_STATS, CL_OUTCOME_CON = 6, 5  # ILQR_CL_CON_STATS (mean/max con_max, mean
 KP_ERR_POS, KP_ERR_ORN, KP_ERR_VEL, KP_ERR_ANGVEL, KP_ERR_TIME = range(5)
 PROF_ROLLOUT, PROF_BACKWARD, PROF_FORWARD, PROF_OTHER, PROF_APPLY = 0, 1, 2, 3, 4
 ADOPT_STATE, ADOPT_TARGETS, ADOPT_CONTROLS0, ADOPT_CONTROLS, ADOPT_MULTIPLIERS = 1, 2, 4, 8, 16  # ILQR_ADOPT_* (bits of ilqr_problem_adopt's `what`)
+CLR_MAX_SPH, CLR_MAX_PLANES, CLR_STATS = 32, 8, 4  # ILQR_CLR_MAX_SPH, ILQR_CLR_MAX_PLANES, ILQR_CLR_STATS (mean, min, n_hit, n_bad)
 
 # every symbol include/ilqr_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
@@ -44,6 +45,7 @@ EXPORTS = [
     "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck", "ilqr_problem_gains", "ilqr_problem_gains_al",
     "ilqr_problem_adopt", "ilqr_problem_adopt_dev", "ilqr_problem_spread_controls", "ilqr_problem_spread_controls_dev",
     "ilqr_problem_select", "ilqr_problem_select_dev", "ilqr_problem_get_at", "ilqr_problem_get_at_dev",
+    "ilqr_problem_clearance", "ilqr_problem_clearance_dev", "ilqr_clearance_trajectories", "ilqr_clearance_trajectories_dev",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
     "ilqr_lqt_get_d",
@@ -143,6 +145,63 @@ class CovCon(C.Structure):
     _fields_ = [("con_var", C.c_void_p), ("con_z", C.c_void_p)]
 
 
+class ClrRobot(C.Structure):
+    """Mirror of ilqr_clr_robot."""
+
+    _fields_ = [("n_sph", C.c_int), ("sph_link", C.c_int * CLR_MAX_SPH), ("sph_c", (C.c_double * 3) * CLR_MAX_SPH), ("sph_r", C.c_double * CLR_MAX_SPH),
+                ("n_planes", C.c_int), ("plane_n", (C.c_double * 3) * CLR_MAX_PLANES), ("plane_d", C.c_double * CLR_MAX_PLANES)]
+
+
+class ClrWorld(C.Structure):
+    """Mirror of ilqr_clr_world: obs is a host or device pointer."""
+
+    _fields_ = [("obs", C.c_void_p), ("n_sets", C.c_int), ("n_obs", C.c_int), ("traj_per_set", C.c_int), ("margin", C.c_double), ("stats_group", C.c_int)]
+
+
+class ClrOut(C.Structure):
+    """Mirror of ilqr_clr_out: six pointers (host or device), 0 / None where the output is not asked for."""
+
+    _fields_ = [("clr", C.c_void_p), ("clr_min", C.c_void_p), ("clr_at", C.c_void_p), ("n_below", C.c_void_p), ("eligible", C.c_void_p), ("stats", C.c_void_p)]
+
+
+def clr_robot(spheres, planes=None):
+    """ClrRobot from spheres = [(link, (cx, cy, cz), r), ...] in chain order and planes = [((nx, ny, nz), d), ...] (n . p >= d)."""
+    rb = ClrRobot()
+    spheres, planes = list(spheres), list(planes or [])
+    if len(spheres) > CLR_MAX_SPH or len(planes) > CLR_MAX_PLANES:
+        raise ValueError(f"at most {CLR_MAX_SPH} spheres and {CLR_MAX_PLANES} planes")
+    rb.n_sph, rb.n_planes = len(spheres), len(planes)
+    for i, (link, c, r) in enumerate(spheres):
+        rb.sph_link[i], rb.sph_r[i] = int(link), float(r)
+        for a in range(3):
+            rb.sph_c[i][a] = float(c[a])
+    for l, (nn, d) in enumerate(planes):
+        rb.plane_d[l] = float(d)
+        for a in range(3):
+            rb.plane_n[l][a] = float(nn[a])
+    return rb
+
+
+def _clr_host_call(fn, n, T, robot, obstacles, traj_per_set, margin, stats_group, want):
+    """The host form of a clearance call: fn(robot*, world*, out*) -> rc.  obstacles [n_sets][n_obs][4] or None; returns a Clearance."""
+    tps = int(traj_per_set)
+    obs = _f64(obstacles) if obstacles is not None else np.zeros((n // tps if tps >= 1 else 0, 0, 4))   # planes only: empty sets
+    if obs.ndim != 3 or obs.shape[2] != 4:
+        raise ValueError(f"obstacles: expected [n_sets][n_obs][4], got {obs.shape}")
+    w = ClrWorld(obs.ctypes.data if obs.size else None, obs.shape[0], obs.shape[1], tps, float(margin), int(stats_group or 0))
+    ng = n // int(stats_group) if stats_group and int(stats_group) >= 1 else 0
+    clr, cmin = _out("clr" in want, n, T), _out("clr_min" in want, n)
+    at = np.empty((n, 3), dtype=np.int32) if "clr_at" in want else None
+    nb = np.empty(n, dtype=np.int32) if "n_below" in want else None
+    el = np.empty(n, dtype=np.int32) if "eligible" in want else None
+    st = _out("stats" in want, ng, CLR_STATS)
+    o = ClrOut(*(a.ctypes.data if a is not None else None for a in (clr, cmin, at, nb, el, st)))
+    fn(C.byref(robot), C.byref(w), C.byref(o))
+    return Clearance(clr, cmin, at, nb, el, st)
+
+
+CLR_OUTPUTS = ("clr", "clr_min", "clr_at", "n_below", "eligible")
+Clearance = collections.namedtuple("Clearance", "clr clr_min clr_at n_below eligible stats")
 ClosedLoopCov = collections.namedtuple("ClosedLoopCov", "Sigma kp_Sigma kp_var u_var lim_z")
 ClosedLoopReportCon = collections.namedtuple("ClosedLoopReportCon", "cost stats kp_err kp_stats lim_cost outcome con_max con_steps con_stats outcome_con")
 ClosedLoopCovCon = collections.namedtuple("ClosedLoopCovCon", "Sigma kp_Sigma kp_var u_var lim_z con_var con_z")
@@ -199,6 +258,10 @@ def load():
         getattr(L, n).argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     for n in ("ilqr_problem_get_at", "ilqr_problem_get_at_dev"):
         getattr(L, n).argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    for n in ("ilqr_problem_clearance", "ilqr_problem_clearance_dev"):
+        getattr(L, n).argtypes = [vp, C.POINTER(ClrRobot), C.POINTER(ClrWorld), C.POINTER(ClrOut)]
+    for n in ("ilqr_clearance_trajectories", "ilqr_clearance_trajectories_dev"):
+        getattr(L, n).argtypes = [vp, C.POINTER(ProblemDesc), C.c_int, C.c_int, vp, C.POINTER(ClrRobot), C.POINTER(ClrWorld), C.POINTER(ClrOut)]
     L.ilqr_problem_track.argtypes = [vp, C.c_int, dp, C.c_int, dp]
     L.ilqr_problem_track_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.ilqr_problem_closed_loop.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp]
@@ -398,6 +461,21 @@ class Context:
         pos, quat, jac = np.zeros((n, 3)), np.zeros((n, 4)), np.zeros((n, 6, dof))
         self.check(self.L.ilqr_fk_batch(self.h, C.byref(desc), n, _dp(q), _dp(pos), _dp(quat), _dp(jac)))
         return pos, quat, jac
+
+    def clearance_trajectories(self, desc: ProblemDesc, X, robot: ClrRobot, obstacles=None, traj_per_set=None, margin: float = 0.0, stats_group=None,
+                               want=CLR_OUTPUTS):
+        """Clearance of the trajectories X [n][T][n_x] (natural layout of desc) from the obstacles [n_sets][n_obs][4] and the robot's planes
+        (ilqr_clearance_trajectories).  traj_per_set: None = one world for all; stats_group: asks for `stats`.  Returns a Clearance; what is not
+        named in `want` is None."""
+        X = _f64(X)
+        n, T = X.shape[0], X.shape[1]
+        want = tuple(want) + (("stats",) if stats_group is not None else ())
+        return _clr_host_call(lambda r, w, o: self.check(self.L.ilqr_clearance_trajectories(self.h, C.byref(desc), n, T, X.ctypes.data, r, w, o)),
+                              n, T, robot, obstacles, n if traj_per_set is None else traj_per_set, margin, stats_group, want)
+
+    def clearance_trajectories_dev(self, desc: ProblemDesc, n: int, T: int, X_ptr, robot: ClrRobot, world: ClrWorld, out: ClrOut):
+        """Device pointers in X_ptr, world.obs and out; asynchronous on the context's stream."""
+        self.check(self.L.ilqr_clearance_trajectories_dev(self.h, C.byref(desc), int(n), int(T), X_ptr, C.byref(robot), C.byref(world), C.byref(out)))
 
     def close(self):
         if self.h:
@@ -826,6 +904,18 @@ class BatchProblem:
         """Device pointers (0 / None where the output is not asked for; indices clamped by the kernel); asynchronous on the context's stream."""
         self.ctx.check(self.L.ilqr_problem_get_at_dev(self.h, int(n), index_ptr, X_ptr or None, U_ptr or None, cost_ptr or None, iters_ptr or None,
                                                       status_ptr or None))
+
+    # ---- clearance of the plan from sphere obstacles and planes (include/ilqr_hip.h "clearance")
+    def clearance(self, robot: ClrRobot, obstacles=None, traj_per_set=None, margin: float = 0.0, stats_group=None, want=CLR_OUTPUTS):
+        """Clearance of the plan this problem holds (ilqr_problem_clearance), read where it lies; arguments and result as
+        Context.clearance_trajectories with n = B."""
+        want = tuple(want) + (("stats",) if stats_group is not None else ())
+        return _clr_host_call(lambda r, w, o: self.ctx.check(self.L.ilqr_problem_clearance(self.h, r, w, o)), self.B, self.T, robot, obstacles,
+                              self.B if traj_per_set is None else traj_per_set, margin, stats_group, want)
+
+    def clearance_dev(self, robot: ClrRobot, world: ClrWorld, out: ClrOut):
+        """Device pointers in world.obs and out; asynchronous on the context's stream."""
+        self.ctx.check(self.L.ilqr_problem_clearance_dev(self.h, C.byref(robot), C.byref(world), C.byref(out)))
 
     def close(self):
         if self.h:

@@ -1509,7 +1509,50 @@ BatchResult ILQRRecursive::solveBatch(const BatchInputs& in, int nb_iter, bool l
 struct MultiStartOut {
     std::vector<int> winner, n_candidates, coarse_iters;   // [G]; coarse_iters: the iterations the winner's coarse solve ran
     std::vector<double> coarse_best, coarse_first;         // [G]
+    std::vector<double> coarse_clearance, clearance;       // [G], with obstacles only
+    std::vector<int> clearance_at, n_below;                // [G][3], [G]
 };
+
+// ---- clearance (include/ilqr_hip.h "clearance")
+static void clearance_structs(const ClearanceInputs& c, int n, int traj_per_set, int stats_group, ilqr_clr_robot& rb, ilqr_clr_world& w) {
+    const size_t ns = c.sph_link.size(), np = c.plane_d.size();
+    if (ns < 1 || ns > ILQR_CLR_MAX_SPH) throw std::runtime_error("[clearance] 1 to 32 spheres are supported");
+    if (c.sph_c.size() != 3 * ns || c.sph_r.size() != ns) throw std::runtime_error("[clearance] spheres: one centre of 3 entries and one radius per link");
+    if (np > ILQR_CLR_MAX_PLANES || c.plane_n.size() != 3 * np) throw std::runtime_error("[clearance] planes: at most 8, one normal of 3 entries per offset");
+    if (c.n_sets < 0 || c.n_obs < 0 || c.obstacles.size() != (size_t)c.n_sets * c.n_obs * 4) throw std::runtime_error("[clearance] obstacles must be n_sets x n_obs x 4");
+    std::memset(&rb, 0, sizeof(rb));
+    rb.n_sph = (int)ns; rb.n_planes = (int)np;
+    std::copy(c.sph_link.begin(), c.sph_link.end(), rb.sph_link);
+    std::copy(c.sph_c.begin(), c.sph_c.end(), &rb.sph_c[0][0]);
+    std::copy(c.sph_r.begin(), c.sph_r.end(), rb.sph_r);
+    std::copy(c.plane_n.begin(), c.plane_n.end(), &rb.plane_n[0][0]);
+    std::copy(c.plane_d.begin(), c.plane_d.end(), rb.plane_d);
+    std::memset(&w, 0, sizeof(w));
+    w.obs = c.n_obs > 0 ? c.obstacles.data() : nullptr;
+    w.n_obs = c.n_obs;
+    w.traj_per_set = traj_per_set > 0 ? traj_per_set : n;
+    w.n_sets = c.n_obs > 0 ? c.n_sets : n / w.traj_per_set;   // without obstacles the sets are empty: any number of them
+    w.margin = c.margin;
+    w.stats_group = stats_group;
+}
+
+ClearanceResult clearance(sys::System& s, const std::vector<double>& X, int n, int T, const ClearanceInputs& c, int traj_per_set, int stats_group) {
+    ilqr_problem_desc d;
+    s.lower(&d);
+    ilqr_dims dm;
+    if (ilqr_dims_of(&d, &dm)) throw std::runtime_error("[clearance] unsupported system");
+    if (n < 1 || T < 1 || X.size() != (size_t)n * T * dm.n_x) throw std::runtime_error("[clearance] X must be n x T x nb_state_var");
+    ilqr_clr_robot rb;
+    ilqr_clr_world w;
+    clearance_structs(c, n, traj_per_set, stats_group, rb, w);
+    ClearanceResult r;
+    r.n = n; r.T = T; r.n_groups = stats_group > 0 ? n / stats_group : 0;
+    r.clr.resize((size_t)n * T); r.clr_min.resize(n); r.clr_at.resize((size_t)3 * n); r.n_below.resize(n); r.eligible.resize(n);
+    r.stats.resize((size_t)r.n_groups * ILQR_CLR_STATS);
+    ilqr_clr_out o{r.clr.data(), r.clr_min.data(), r.clr_at.data(), r.n_below.data(), r.eligible.data(), r.n_groups ? r.stats.data() : nullptr};
+    check(ilqr_clearance_trajectories(device_context(), &d, n, T, X.data(), &rb, &w, &o));
+    return r;
+}
 
 // Steps 2 to 7 of solveMultiStart on the task problem pg, which run_batch has loaded from the caller's inputs: a problem of G * S starts adopts
 // the tasks (index b / S), its controls are spread, every start runs the coarse solve, the best of each group is selected by cost, pg adopts the
@@ -1541,7 +1584,23 @@ static void multi_start(sys::System& s, ilqr_problem* pg, int G, const MultiStar
     check(ilqr_problem_spread_controls(starts.p, S, &sd));
     solve(starts.p, 0);
     o.winner.resize(G); o.n_candidates.resize(G); o.coarse_iters.resize(G); o.coarse_best.resize(G); o.coarse_first.resize(G);
-    check(ilqr_problem_select(starts.p, S, nullptr, nullptr, o.winner.data(), o.coarse_best.data(), o.n_candidates.data()));
+    const bool clr = ms.clearance.given();
+    ilqr_clr_robot rb;
+    ilqr_clr_world cw;
+    std::vector<int> eligible;
+    if (clr) {   // the filter between the coarse solves and the adoption: the starts that keep the margin are the candidates
+        if (ms.clearance.n_obs > 0 && ms.clearance.n_sets != G) throw std::runtime_error("[solveMultiStart] obstacles must hold one set per task (G x n_obs x 4)");
+        clearance_structs(ms.clearance, B, S, 0, rb, cw);
+        std::vector<double> cmin(B);
+        eligible.resize(B);
+        ilqr_clr_out co{nullptr, cmin.data(), nullptr, nullptr, eligible.data(), nullptr};
+        check(ilqr_problem_clearance(starts.p, &rb, &cw, &co));
+        check(ilqr_problem_select(starts.p, S, nullptr, eligible.data(), o.winner.data(), o.coarse_best.data(), o.n_candidates.data()));
+        o.coarse_clearance.resize(G);
+        for (int g = 0; g < G; g++) o.coarse_clearance[g] = cmin[o.winner[g]];
+    } else {
+        check(ilqr_problem_select(starts.p, S, nullptr, nullptr, o.winner.data(), o.coarse_best.data(), o.n_candidates.data()));
+    }
     {   // member 0's coarse cost and the iterations the winner's coarse solve ran, in one call: rows first[0 .. G-1], winner[0 .. G-1]
         std::vector<int> at(first), it(2 * (size_t)G);
         at.insert(at.end(), o.winner.begin(), o.winner.end());
@@ -1552,6 +1611,12 @@ static void multi_start(sys::System& s, ilqr_problem* pg, int G, const MultiStar
     }
     check(ilqr_problem_adopt(pg, starts.p, o.winner.data(), ILQR_ADOPT_CONTROLS | (al ? ILQR_ADOPT_MULTIPLIERS : 0)));
     solve(pg, 1);
+    if (clr) {   // the polished plans against their task's obstacles
+        clearance_structs(ms.clearance, G, 1, 0, rb, cw);
+        o.clearance.resize(G); o.clearance_at.resize((size_t)3 * G); o.n_below.resize(G);
+        ilqr_clr_out co{nullptr, o.clearance.data(), o.clearance_at.data(), o.n_below.data(), nullptr, nullptr};
+        check(ilqr_problem_clearance(pg, &rb, &cw, &co));
+    }
 }
 
 static MultiStartResult multi_start_result(BatchResult&& r, const MultiStartInputs& ms, MultiStartOut&& o) {
@@ -1560,6 +1625,8 @@ static MultiStartResult multi_start_result(BatchResult&& r, const MultiStartInpu
     m.S = ms.S;
     m.winner = std::move(o.winner); m.n_candidates = std::move(o.n_candidates);
     m.coarse_best = std::move(o.coarse_best); m.coarse_first = std::move(o.coarse_first);
+    m.coarse_clearance = std::move(o.coarse_clearance); m.clearance = std::move(o.clearance);
+    m.clearance_at = std::move(o.clearance_at); m.n_below = std::move(o.n_below);
     return m;
 }
 

@@ -482,17 +482,44 @@ struct BatchInputs {
 // Multi-start (include/ilqr_hip.h "multi-start"): every task of a BatchInputs (in.B = G tasks) is solved from S starts on G * S instances --
 // member 0 from the task's own U0, the others from U0 + sigma_u z (ilqr_problem_spread_controls) -- for coarse_iter iterations; the start with
 // the lowest cost wins its group (ilqr_problem_select), and its plan is polished by the caller's nb_iter iterations on the G problem.
+// Clearance (include/ilqr_hip.h "clearance"): the robot as spheres on the links of the system's chain, the cell as half-spaces, the obstacles
+// as spheres in sets.  Judged at the states of a trajectory; no solver gets an obstacle term.
+struct ClearanceInputs {
+    std::vector<int> sph_link;        // [n_sph], non-decreasing: -1 the base, s the frame behind segment s of the chain
+    std::vector<double> sph_c, sph_r; // [n_sph][3] in the link's frame, [n_sph]
+    std::vector<double> plane_n, plane_d;   // [n_planes][3] unit normals, [n_planes]: n . p >= d
+    std::vector<double> obstacles;    // [n_sets][n_obs][4] = (cx, cy, cz, R), R < 0: unused slot
+    int n_sets = 0, n_obs = 0;
+    double margin = 0;
+    bool given() const { return !sph_link.empty(); }
+};
+struct ClearanceResult {
+    int n = 0, T = 0, n_groups = 0;
+    std::vector<double> clr, clr_min, stats;        // [n][T], [n], [n_groups][ILQR_CLR_STATS] (empty without stats_group)
+    std::vector<int> clr_at, n_below, eligible;     // [n][3], [n], [n]
+};
+// ilqr_clearance_trajectories on X[n][T][n_x] in the layout of the system: traj_per_set trajectories share a set of obstacles (0: all of them),
+// stats_group > 0 asks for the per-group stats
+ClearanceResult clearance(sys::System& s, const std::vector<double>& X, int n, int T, const ClearanceInputs& c, int traj_per_set = 0, int stats_group = 0);
+
 struct MultiStartInputs {
     int S = 1;                      // starts per task
     unsigned long long seed = 0;
     std::vector<double> sigma_u;    // one value (every control entry) or n_u values in the user's layout; empty: 0
     int coarse_iter = 1;            // iterations every start runs before the selection
+    // given: obstacles[G][n_obs][4], one set per task.  The starts are scored after the coarse solves (ilqr_problem_clearance, traj_per_set = S)
+    // and only those with clearance >= margin are candidates of the selection; the polished plans are scored again.  A filter, not avoidance.
+    ClearanceInputs clearance;
 };
 // The usual result of the G tasks (the polished plans; cost_trace / alpha_trace are the polishing solve's) and what the selection saw
 struct MultiStartResult : BatchResult {
     int S = 0;
     std::vector<int> winner, n_candidates;           // [G]: the winning instance g * S + s, the number of candidates of the group
     std::vector<double> coarse_best, coarse_first;   // [G]: the winner's cost after the coarse iterations, member 0's
+    // with MultiStartInputs::clearance (else empty): the winner's clearance after the coarse iterations -- negative or below the margin where its
+    // group had no eligible start (winner = member 0, n_candidates = 0) -- and clr_min, clr_at, n_below of the polished plans
+    std::vector<double> coarse_clearance, clearance;   // [G]
+    std::vector<int> clearance_at, n_below;            // [G][3], [G]
 };
 struct MultiStartOut;   // ilqr_host.cpp
 

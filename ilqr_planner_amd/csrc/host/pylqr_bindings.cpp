@@ -106,9 +106,47 @@ static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& 
     return in;
 }
 
+// spheres: [(link, (cx, cy, cz), r), ...] in chain order; planes: [((nx, ny, nz), d), ...] or None; obstacles: [n_sets][n_obs][4] or None
+static solver::ClearanceInputs clearance_inputs(const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin) {
+    solver::ClearanceInputs c;
+    c.margin = margin;
+    if (spheres.is_none()) {
+        if (!planes.is_none() || !obstacles.is_none()) throw std::runtime_error("[clearance] planes and obstacles need the robot's spheres");
+        return c;
+    }
+    for (auto h : spheres.cast<py::list>()) {
+        py::tuple t = py::reinterpret_borrow<py::object>(h).cast<py::tuple>();
+        if (t.size() != 3) throw std::runtime_error("[clearance] a sphere is (link, (cx, cy, cz), r)");
+        c.sph_link.push_back(t[0].cast<int>());
+        arr_t ctr = arr_t::ensure(t[1]);
+        if (!ctr || ctr.size() != 3) throw std::runtime_error("[clearance] a sphere's centre has 3 entries");
+        c.sph_c.insert(c.sph_c.end(), ctr.data(), ctr.data() + 3);
+        c.sph_r.push_back(t[2].cast<double>());
+    }
+    if (!planes.is_none())
+        for (auto h : planes.cast<py::list>()) {
+            py::tuple t = py::reinterpret_borrow<py::object>(h).cast<py::tuple>();
+            if (t.size() != 2) throw std::runtime_error("[clearance] a plane is ((nx, ny, nz), d)");
+            arr_t nn = arr_t::ensure(t[0]);
+            if (!nn || nn.size() != 3) throw std::runtime_error("[clearance] a plane's normal has 3 entries");
+            c.plane_n.insert(c.plane_n.end(), nn.data(), nn.data() + 3);
+            c.plane_d.push_back(t[1].cast<double>());
+        }
+    if (!obstacles.is_none()) {
+        arr_t a = arr_t::ensure(obstacles);
+        if (!a || a.ndim() != 3 || a.shape(2) != 4) throw std::runtime_error("[clearance] obstacles must be n_sets x n_obs x 4");
+        c.n_sets = (int)a.shape(0);
+        c.n_obs = (int)a.shape(1);
+        c.obstacles.assign(a.data(), a.data() + a.size());
+    }
+    return c;
+}
+
 // solve_multistart(..., S, seed, sigma_u, coarse_iter): sigma_u None (0), a scalar or nb_ctrl_var values
-static solver::MultiStartInputs multistart_inputs(int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter) {
+static solver::MultiStartInputs multistart_inputs(int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter, const py::object& spheres = py::none(),
+                                                  const py::object& planes = py::none(), const py::object& obstacles = py::none(), double margin = 0.0) {
     solver::MultiStartInputs ms;
+    ms.clearance = clearance_inputs(spheres, planes, obstacles, margin);
     ms.S = S;
     ms.seed = seed;
     ms.coarse_iter = coarse_iter;
@@ -365,7 +403,42 @@ PYBIND11_MODULE(PyLQR, m) {
         .def_property_readonly("winner", [](const solver::MultiStartResult& r) { return py::array_t<int>(r.winner.size(), r.winner.data()); })
         .def_property_readonly("n_candidates", [](const solver::MultiStartResult& r) { return py::array_t<int>(r.n_candidates.size(), r.n_candidates.data()); })
         .def_property_readonly("coarse_best", [](const solver::MultiStartResult& r) { return shaped(r.coarse_best, {r.B}); })
-        .def_property_readonly("coarse_first", [](const solver::MultiStartResult& r) { return shaped(r.coarse_first, {r.B}); });
+        .def_property_readonly("coarse_first", [](const solver::MultiStartResult& r) { return shaped(r.coarse_first, {r.B}); })
+        // filled when solve_multistart is given spheres, else None
+        .def_property_readonly("coarse_clearance", [](const solver::MultiStartResult& r) -> py::object {
+            return r.clearance.empty() ? py::object(py::none()) : py::object(shaped(r.coarse_clearance, {r.B})); })
+        .def_property_readonly("clearance", [](const solver::MultiStartResult& r) -> py::object {
+            return r.clearance.empty() ? py::object(py::none()) : py::object(shaped(r.clearance, {r.B})); })
+        .def_property_readonly("clearance_at", [](const solver::MultiStartResult& r) -> py::object {
+            if (r.clearance.empty()) return py::none();
+            py::array_t<int> a({(py::ssize_t)r.B, (py::ssize_t)3});
+            std::copy(r.clearance_at.begin(), r.clearance_at.end(), a.mutable_data());
+            return a; })
+        .def_property_readonly("n_below", [](const solver::MultiStartResult& r) -> py::object {
+            return r.clearance.empty() ? py::object(py::none()) : py::object(py::array_t<int>(r.n_below.size(), r.n_below.data())); });
+    py::class_<solver::ClearanceResult>(m_sol, "ClearanceResult")
+        .def_property_readonly("clr", [](const solver::ClearanceResult& r) { return shaped(r.clr, {r.n, r.T}); })
+        .def_property_readonly("clr_min", [](const solver::ClearanceResult& r) { return shaped(r.clr_min, {r.n}); })
+        .def_property_readonly("clr_at", [](const solver::ClearanceResult& r) {
+            py::array_t<int> a({(py::ssize_t)r.n, (py::ssize_t)3});
+            std::copy(r.clr_at.begin(), r.clr_at.end(), a.mutable_data());
+            return a; })
+        .def_property_readonly("n_below", [](const solver::ClearanceResult& r) { return py::array_t<int>(r.n_below.size(), r.n_below.data()); })
+        .def_property_readonly("eligible", [](const solver::ClearanceResult& r) { return py::array_t<int>(r.eligible.size(), r.eligible.data()); })
+        .def_property_readonly("stats", [](const solver::ClearanceResult& r) -> py::object {
+            return r.n_groups ? py::object(shaped(r.stats, {r.n_groups, ILQR_CLR_STATS})) : py::object(py::none()); });
+    // clearance(system, X[n][T][n_x], spheres, ...): any trajectories in the system's state layout against sphere obstacles and planes
+    m.def("clearance",
+          [](const std::shared_ptr<sys::System>& s, const py::object& X, const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin,
+             int traj_per_set, int stats_group) {
+              arr_t x = arr_t::ensure(X);
+              if (!x || x.ndim() != 3) throw std::runtime_error("[clearance] X must be n x T x nb_state_var");
+              if (spheres.is_none()) throw std::runtime_error("[clearance] spheres are required");
+              return solver::clearance(*s, std::vector<double>(x.data(), x.data() + x.size()), (int)x.shape(0), (int)x.shape(1),
+                                       clearance_inputs(spheres, planes, obstacles, margin), traj_per_set, stats_group);
+          },
+          py::arg("system"), py::arg("X"), py::arg("spheres"), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0,
+          py::arg("traj_per_set") = 0, py::arg("stats_group") = 0);
     py::class_<solver::ClosedLoopResult>(m_sol, "ClosedLoopResult")
         .def_property_readonly("cost", [](const solver::ClosedLoopResult& r) { return shaped(r.cost, {r.B, r.S}); })
         .def_property_readonly("X", [](const solver::ClosedLoopResult& r) { return shaped(r.X, {r.B, r.S, r.T, r.n_x}); })
@@ -414,11 +487,14 @@ PYBIND11_MODULE(PyLQR, m) {
         // every task (the batch of U0 / q0 / kp_targets) from S starts: solve_batch's arguments, then the starts
         .def("solve_multistart",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter,
-                const py::object& q0, const py::object& dq0, const py::object& kp, bool pg) {
-                 return self.solveMultiStart(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), multistart_inputs(S, seed, sigma_u, coarse_iter), nb_iter, ls, es);
+                const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& spheres, const py::object& planes,
+                const py::object& obstacles, double margin) {
+                 return self.solveMultiStart(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin),
+                                             nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(),
-             py::arg("coarse_iter") = 1, py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
+             py::arg("coarse_iter") = 1, py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
+             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0)
         .def("closed_loop_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
                 const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
@@ -451,13 +527,15 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("al_gains_penalty") = py::none())
         .def("solve_multistart",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, int S, unsigned long long seed,
-                const py::object& sigma_u, int coarse_iter, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& agp) {
-                 return self.solveMultiStart(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), multistart_inputs(S, seed, sigma_u, coarse_iter), nb_iter, lag,
-                                             pen, sc, ls, es);
+                const py::object& sigma_u, int coarse_iter, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& agp,
+                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin) {
+                 return self.solveMultiStart(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp),
+                                             multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(), py::arg("coarse_iter") = 1, py::arg("q0") = py::none(),
-             py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("al_gains_penalty") = py::none())
+             py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("al_gains_penalty") = py::none(),
+             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0)
         .def_static("final_penalty", &solver::AL_ILQR::finalPenalty, py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"))
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,

@@ -6,7 +6,7 @@
 // which mirrors ILQRRecursive::solve / AL_ILQR::solve (reference src/solver/ILQRRecursive.cpp:21-181,
 // src/solver/AL-ILQR.cpp:50-232).  No CPU fallback exists: every entry point fails loudly if HIP does.
 // The one exception to "host-side only": the small kernels that join instances (ilqr_multistart_kernels.hpp, included at the end) are compiled
-// with this file, for the reason given there.
+// with this file, for the reason given there; the clearance kernels (ilqr_clearance_kernels.hpp) likewise.
 #include "../../include/ilqr_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ilqr_batchcp.hpp"
+#include "ilqr_clearance.hpp"
 #include "ilqr_closed_loop.hpp"
 #include "ilqr_closed_loop_cov.hpp"
 #include "ilqr_ctx.hpp"
@@ -128,12 +129,15 @@ extern "C" int ilqr_ctx_create(int device_id, ilqr_ctx** out) {
     return 0;
 }
 
+static void clr_release(ilqr_ctx* c);  // the clearance calls' buffers (below)
+
 extern "C" void ilqr_ctx_destroy(ilqr_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     while (!c->problems.empty()) ilqr_problem_destroy(c->problems.back());  // handles held by the caller become invalid
     while (!c->cleanups.empty()) { const auto cl = c->cleanups.back(); cl.destroy(cl.handle); }  // each destroy removes its own entry
     (void)hipStreamSynchronize(c->stream);
+    clr_release(c);
     for (auto& p : c->pending) (void)hipEventDestroy(p.a);
     for (auto e : c->pool) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1675,6 +1679,202 @@ extern "C" int ilqr_problem_get_at_dev(ilqr_problem* p, int n, const int* index,
     return get_at(p, n, index, X, U, cost, iters, status, true);
 }
 
+// ------------------------------------------------------------------------------------------------ clearance
+// include/ilqr_hip.h "clearance": every refusal first, then the three launches of ilqr_clearance.hpp on the context's stream, charged to
+// ILQR_PROF_OTHER.  The geometry buffer, the workspace (12 bytes per (trajectory, step)) and the staging of the host forms belong to the context
+// and only grow; the geometry is uploaded when it differs from the one the buffer holds.
+
+struct ClrBytes {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    int reserve(ilqr_ctx* c, size_t n) {
+        if (bytes >= n) return 0;
+        if (ptr) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(ptr)); ptr = nullptr; bytes = 0; }
+        HIPCHK(c, hipMalloc(&ptr, n));
+        bytes = n;
+        return 0;
+    }
+    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
+};
+struct ClrState {
+    ClrGeom host;        // what `geom` holds
+    bool have = false;
+    ClrBytes geom, ws, io;
+};
+
+static void clr_release(ilqr_ctx* c) {
+    if (!c->clr) return;
+    c->clr->geom.release(); c->clr->ws.release(); c->clr->io.release();
+    delete c->clr;
+    c->clr = nullptr;
+}
+
+static int clr_check(ilqr_ctx* c, const std::string& fn, const ilqr_problem_desc& d, int n, int T, const ilqr_clr_robot* rb, const ilqr_clr_world* w,
+                     const ilqr_clr_out* out, bool dev) {
+    auto no = [&](const std::string& m) { return fail(c, fn + ": " + m); };
+    auto S = [](long long v) { return std::to_string(v); };
+    if (!rb) return no("robot is a null pointer");
+    if (!w) return no("world is a null pointer");
+    if (!out) return no("out is a null pointer");
+    if (n < 1 || T < 1) return no("n and T must be >= 1 (got " + S(n) + ", " + S(T) + ")");
+    if (d.n_seg < 1) return no("the descriptor has no chain (n_seg = " + S(d.n_seg) + "): clearance needs the robot's kinematics");
+    {
+        DevChain ch;
+        if (lower_chain(c, d, ch)) return no("the descriptor's chain is refused: " + c->err);
+    }
+    if (rb->n_sph < 1 || rb->n_sph > ILQR_CLR_MAX_SPH) return no("n_sph must be 1 .. " + S(ILQR_CLR_MAX_SPH) + " (got " + S(rb->n_sph) + ")");
+    for (int i = 0; i < rb->n_sph; i++) {
+        if (rb->sph_link[i] < -1 || rb->sph_link[i] >= d.n_seg)
+            return no("sph_link[" + S(i) + "] = " + S(rb->sph_link[i]) + " is outside -1 .. " + S(d.n_seg - 1));
+        if (i > 0 && rb->sph_link[i] < rb->sph_link[i - 1])
+            return no("sph_link must be non-decreasing (sph_link[" + S(i) + "] = " + S(rb->sph_link[i]) + " follows " + S(rb->sph_link[i - 1]) + ")");
+        if (!(std::isfinite(rb->sph_r[i]) && rb->sph_r[i] >= 0.0)) return no("sph_r[" + S(i) + "] must be finite and >= 0 (got " + std::to_string(rb->sph_r[i]) + ")");
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(rb->sph_c[i][a])) return no("sph_c[" + S(i) + "][" + S(a) + "] is not finite");
+    }
+    if (rb->n_planes < 0 || rb->n_planes > ILQR_CLR_MAX_PLANES) return no("n_planes must be 0 .. " + S(ILQR_CLR_MAX_PLANES) + " (got " + S(rb->n_planes) + ")");
+    for (int l = 0; l < rb->n_planes; l++) {
+        const double* nn = rb->plane_n[l];
+        if (!(std::isfinite(nn[0]) && std::isfinite(nn[1]) && std::isfinite(nn[2]))) return no("plane_n[" + S(l) + "] is not finite");
+        if (!(std::fabs(std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]) - 1.0) <= 1e-9)) return no("plane_n[" + S(l) + "] is not a unit vector (| |n| - 1 | > 1e-9)");
+        if (!std::isfinite(rb->plane_d[l])) return no("plane_d[" + S(l) + "] is not finite");
+    }
+    if (w->n_obs < 0) return no("n_obs must be >= 0 (got " + S(w->n_obs) + ")");
+    if (w->n_obs > CLR_MAX_OBS) return no("n_obs must be at most " + S(CLR_MAX_OBS) + " (got " + S(w->n_obs) + ")");
+    if (w->n_obs == 0 && rb->n_planes == 0) return no("nothing to keep clear of: n_obs = 0 and n_planes = 0");
+    if (w->n_obs > 0 && !w->obs) return no("obs is a null pointer with n_obs = " + S(w->n_obs));
+    if (w->traj_per_set < 1 || n % w->traj_per_set != 0)
+        return no("the number of trajectories (" + S(n) + ") is not a multiple of traj_per_set (" + S(w->traj_per_set) + ")");
+    if (w->n_sets != n / w->traj_per_set)
+        return no("n_sets must be n / traj_per_set = " + S(n / w->traj_per_set) + " (got " + S(w->n_sets) + ")");
+    if (w->margin != w->margin) return no("margin is NaN");
+    if (!out->clr && !out->clr_min && !out->clr_at && !out->n_below && !out->eligible && !out->stats) return no("every output is a null pointer");
+    if (out->stats) {
+        if (w->stats_group < 1) return no("stats needs stats_group >= 1 (got " + S(w->stats_group) + ")");
+        if (n % w->stats_group != 0) return no("the number of trajectories (" + S(n) + ") is not a multiple of stats_group (" + S(w->stats_group) + ")");
+    }
+    if (!dev)
+        for (size_t e = 0; e < (size_t)w->n_sets * (size_t)w->n_obs * 4; e++)
+            if (!std::isfinite(w->obs[e]))
+                return no("obs[" + S((long long)(e / ((size_t)w->n_obs * 4))) + "][" + S((long long)(e / 4 % (size_t)w->n_obs)) + "][" + S((long long)(e % 4)) + "] is not finite");
+    return 0;
+}
+
+// p: the problem form (the plan where it lies); else X[n][T][n_x] in the natural layout of d
+static int clr_run(ilqr_ctx* c, const char* fn_, ilqr_problem* p, const ilqr_problem_desc& d, int n, int T, const double* X, const ilqr_clr_robot* rb,
+                   const ilqr_clr_world* w, const ilqr_clr_out* out_, bool dev) {
+    const std::string fn = std::string(fn_) + (dev ? "_dev" : "");
+    ilqr_dims ud;
+    if (ilqr_dims_of(&d, &ud)) return fail(c, fn + ": unsupported system kind / nb_deriv");
+    if (clr_check(c, fn, d, n, T, rb, w, out_, dev)) return 1;
+    if (!p && !X) return fail(c, fn + ": X is a null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->clr) c->clr = new ClrState();
+    ClrState& cs = *c->clr;
+    ClrGeom g;
+    std::memset(&g, 0, sizeof(g));
+    g.n_seg = d.n_seg; g.n_sph = rb->n_sph; g.n_planes = rb->n_planes;
+    g.n_walk = rb->sph_link[rb->n_sph - 1] + 1;   // non-decreasing: the last sphere's link is the farthest
+    std::memcpy(g.seg_joint, d.seg_joint, sizeof(int) * d.n_seg);
+    std::memcpy(g.seg_xyz, d.seg_xyz, sizeof(double) * 3 * d.n_seg);
+    std::memcpy(g.seg_R, d.seg_R, sizeof(double) * 9 * d.n_seg);
+    std::memcpy(g.seg_axis, d.seg_axis, sizeof(double) * 3 * d.n_seg);
+    std::memcpy(g.sph_link, rb->sph_link, sizeof(int) * rb->n_sph);
+    std::memcpy(g.sph_c, rb->sph_c, sizeof(double) * 3 * rb->n_sph);
+    std::memcpy(g.sph_r, rb->sph_r, sizeof(double) * rb->n_sph);
+    std::memcpy(g.plane_n, rb->plane_n, sizeof(double) * 3 * rb->n_planes);
+    std::memcpy(g.plane_d, rb->plane_d, sizeof(double) * rb->n_planes);
+    if (!cs.have || std::memcmp(&g, &cs.host, sizeof(g)) != 0) {   // kernels in flight may read the old one; the copy's source must outlive it
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (cs.geom.reserve(c, sizeof(ClrGeom))) return 1;
+        cs.host = g;
+        cs.have = false;
+        HIPCHK(c, hipMemcpyAsync(cs.geom.ptr, &cs.host, sizeof(ClrGeom), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        cs.have = true;
+    }
+    const size_t nT = (size_t)n * (size_t)T;
+    if (cs.ws.reserve(c, nT * 12)) return 1;
+    ClrArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.geom = (const ClrGeom*)cs.geom.ptr;
+    a.n = n; a.T = T; a.n_obs = w->n_obs; a.traj_per_set = w->traj_per_set;
+    a.ws_clr = (double*)cs.ws.ptr;
+    a.ws_code = (int*)(a.ws_clr + nT);
+    for (int j = 0; j < DOF; j++) a.qrow[j] = j < d.dof ? (p ? p->map.x.dev[j] : j) : 0;
+    a.obs = w->obs;
+    ilqr_clr_out o = *out_;
+    const int n_groups = out_->stats ? n / w->stats_group : 0;
+    const size_t n_obs_all = (size_t)w->n_sets * (size_t)w->n_obs * 4, nX = p ? 0 : nT * (size_t)ud.n_x;
+    if (!dev) {   // doubles: X | obs | clr | clr_min | stats; ints: clr_at | n_below | eligible
+        const size_t nd = nX + n_obs_all + (out_->clr ? nT : 0) + (size_t)n + (size_t)n_groups * ILQR_CLR_STATS, ni = (size_t)5 * n;
+        if (cs.io.reserve(c, nd * 8 + ni * 4)) return 1;
+        double* q = (double*)cs.io.ptr;
+        if (!p) { HIPCHK(c, hipMemcpyAsync(q, X, nX * 8, hipMemcpyHostToDevice, c->stream)); X = q; q += nX; }
+        if (n_obs_all) { HIPCHK(c, hipMemcpyAsync(q, w->obs, n_obs_all * 8, hipMemcpyHostToDevice, c->stream)); a.obs = q; q += n_obs_all; }
+        if (out_->clr) { o.clr = q; q += nT; }
+        if (out_->clr_min) o.clr_min = q;
+        q += n;
+        if (out_->stats) o.stats = q;
+        q += (size_t)n_groups * ILQR_CLR_STATS;
+        int* qi = (int*)q;
+        if (out_->clr_at) o.clr_at = qi;
+        if (out_->n_below) o.n_below = qi + (size_t)3 * n;
+        if (out_->eligible) o.eligible = qi + (size_t)4 * n;
+    }
+    {
+        ProfScope ps(c, ILQR_PROF_OTHER);
+        if (p) launch_clr_plan(p->bufs.X[0], p->bufs.X[1], p->bufs.cur, p->dims.n_x, p->Bp, a, c->stream);
+        else launch_clr_traj(X, ud.n_x, a, c->stream);
+    }
+    const size_t stride_i = p ? 1 : (size_t)T, stride_k = p ? (size_t)n : 1;
+    {
+        ProfScope ps(c, ILQR_PROF_OTHER);
+        launch_clr_fold(a, stride_i, stride_k, w->margin, o, c->stream);
+    }
+    if (out_->stats) {
+        ProfScope ps(c, ILQR_PROF_OTHER);
+        launch_clr_stats(o.clr_min ? o.clr_min : a.ws_clr, o.clr_min ? 1 : stride_i, n_groups, w->stats_group, w->margin, o.stats, c->stream);
+    }
+    HIPCHK(c, hipGetLastError());
+    prof_mark(c, -1);
+    if (!dev) {
+        if (out_->clr) HIPCHK(c, hipMemcpyAsync(out_->clr, o.clr, nT * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out_->clr_min) HIPCHK(c, hipMemcpyAsync(out_->clr_min, o.clr_min, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out_->stats) HIPCHK(c, hipMemcpyAsync(out_->stats, o.stats, (size_t)n_groups * ILQR_CLR_STATS * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out_->clr_at) HIPCHK(c, hipMemcpyAsync(out_->clr_at, o.clr_at, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+        if (out_->n_below) HIPCHK(c, hipMemcpyAsync(out_->n_below, o.n_below, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out_->eligible) HIPCHK(c, hipMemcpyAsync(out_->eligible, o.eligible, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+static int problem_clearance(ilqr_problem* p, const ilqr_clr_robot* rb, const ilqr_clr_world* w, const ilqr_clr_out* out, bool dev) {
+    if (!p) return 1;
+    if (!p->has_plan)
+        return fail(p->ctx, std::string("ilqr_problem_clearance") + (dev ? "_dev" : "") + " needs a plan: run a solver since the problem's inputs last changed (ilqr_solve_recursive with nb_iter = 0 rolls out the controls as they are)");
+    return clr_run(p->ctx, "ilqr_problem_clearance", p, p->desc, p->B, p->T, nullptr, rb, w, out, dev);
+}
+extern "C" int ilqr_problem_clearance(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, const ilqr_clr_out* out) {
+    return problem_clearance(p, robot, world, out, false);
+}
+extern "C" int ilqr_problem_clearance_dev(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, const ilqr_clr_out* out) {
+    return problem_clearance(p, robot, world, out, true);
+}
+extern "C" int ilqr_clearance_trajectories(ilqr_ctx* c, const ilqr_problem_desc* desc, int n, int T, const double* X, const ilqr_clr_robot* robot,
+                                           const ilqr_clr_world* world, const ilqr_clr_out* out) {
+    if (!c) return 1;
+    if (!desc) return fail(c, "ilqr_clearance_trajectories: desc is a null pointer");
+    return clr_run(c, "ilqr_clearance_trajectories", nullptr, *desc, n, T, X, robot, world, out, false);
+}
+extern "C" int ilqr_clearance_trajectories_dev(ilqr_ctx* c, const ilqr_problem_desc* desc, int n, int T, const double* X, const ilqr_clr_robot* robot,
+                                               const ilqr_clr_world* world, const ilqr_clr_out* out) {
+    if (!c) return 1;
+    if (!desc) return fail(c, "ilqr_clearance_trajectories_dev: desc is a null pointer");
+    return clr_run(c, "ilqr_clearance_trajectories", nullptr, *desc, n, T, X, robot, world, out, true);
+}
+
 // ------------------------------------------------------------------------------------------------ stand-alone FK
 
 extern "C" int ilqr_fk_batch(ilqr_ctx* c, const ilqr_problem_desc* d, int n, const double* q, double* pos, double* quat, double* jac) {
@@ -1722,3 +1922,7 @@ extern "C" int ilqr_fk_batch(ilqr_ctx* c, const ilqr_problem_desc* d, int n, con
 // the kernels that join instances (adopt, spread, select, get_at) and their launchers: this is the one translation unit that defines them
 #define ILQR_MULTISTART_KERNELS_TU
 #include "ilqr_multistart_kernels.hpp"
+
+// the clearance kernels (per state, fold, stats) and their launchers: likewise
+#define ILQR_CLEARANCE_KERNELS_TU
+#include "ilqr_clearance_kernels.hpp"

@@ -1,0 +1,53 @@
+// ilqr_clearance.hpp -- launchers of the clearance kernels (ilqr_problem_clearance, ilqr_clearance_trajectories; include/ilqr_hip.h "clearance");
+// their definitions are ilqr_clearance_kernels.hpp, which ilqr_capi.cpp includes.
+//
+// Three launches per call: the per-state kernel writes one key (clearance, sphere, obstacle) per (trajectory, step) into a workspace, k_clr_fold
+// folds the keys of a trajectory in ascending step order, k_clr_stats reduces clr_min per group.  Offsets are size_t (n T n_x may pass 2^31); a
+// trajectory index is an int.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/ilqr_hip.h"
+
+namespace ilqr {
+
+// The geometry of a call as the kernels read it: the descriptor's segments as they are (the kernel walks them; nothing is folded) and the robot's
+// spheres and planes.  It lies in device memory -- with 32 spheres it is far beyond what kernel arguments hold -- and every lane reads it at
+// wave-uniform addresses.
+struct ClrGeom {
+    int n_seg, n_walk;   // segments of the chain; segments the walk visits (up to the last sphere's link)
+    int n_sph, n_planes;
+    int seg_joint[ILQR_MAX_SEG];
+    double seg_xyz[ILQR_MAX_SEG][3];
+    double seg_R[ILQR_MAX_SEG][9];
+    double seg_axis[ILQR_MAX_SEG][3];
+    int sph_link[ILQR_CLR_MAX_SPH];
+    double sph_c[ILQR_CLR_MAX_SPH][3];
+    double sph_r[ILQR_CLR_MAX_SPH];
+    double plane_n[ILQR_CLR_MAX_PLANES][3];
+    double plane_d[ILQR_CLR_MAX_PLANES];
+};
+
+// Where the trajectories, the obstacles and the workspace of a call lie
+struct ClrArgs {
+    const ClrGeom* geom;
+    const double* obs;    // [n_sets][n_obs][4]
+    int n, T, n_obs, traj_per_set;
+    double* ws_clr;       // [n T] the clearance of every (trajectory, step), NaN on a bad step
+    int* ws_code;         // [n T] sphere | obstacle << 5 of the step's minimum, -1 without one
+    int qrow[7];          // the row of joint j's position within a state (private layout: through the index map of a narrow chain)
+};
+
+constexpr int CLR_MAX_OBS = (1 << 26) - ILQR_CLR_MAX_PLANES;   // the obstacle index shares an int with the sphere's
+
+// k_clr_plan: the plan of a problem where it lies, X0 / X1 [T][NX][Bp] chosen per instance by cur; key of (b, k) at ws[k n + b]
+void launch_clr_plan(const double* X0, const double* X1, const int* cur, int NX, int Bp, const ClrArgs& a, hipStream_t st);
+// k_clr_traj: X[n][T][n_x] in the natural layout; key of (i, k) at ws[i T + k]
+void launch_clr_traj(const double* X, int n_x, const ClrArgs& a, hipStream_t st);
+// k_clr_fold: the keys of every trajectory in ascending step order -> clr_min, clr_at, n_below, eligible, clr (each may be null); the key of
+// (i, k) lies at ws[i stride_i + k stride_k].  Afterwards ws_clr[i stride_i] holds clr_min of trajectory i (what k_clr_stats reads).
+void launch_clr_fold(const ClrArgs& a, size_t stride_i, size_t stride_k, double margin, const ilqr_clr_out& out, hipStream_t st);
+// k_clr_stats: stats[g] = { mean, min, n_hit, n_bad } over src[(g group + s) stride], s = 0 .. group-1
+void launch_clr_stats(const double* src, size_t stride, int n_groups, int group, double margin, double* stats, hipStream_t st);
+
+}  // namespace ilqr

@@ -575,6 +575,86 @@ int ilqr_problem_select_dev(ilqr_problem* p, int group_size, const double* score
 int ilqr_problem_get_at(ilqr_problem* p, int n, const int* index, double* X, double* U, double* cost, int* iters, int* status);
 int ilqr_problem_get_at_dev(ilqr_problem* p, int n, const int* index, double* X, double* U, double* cost, int* iters, int* status);
 
+/* ---- clearance: the distance of plans and executions from sphere obstacles and the planes of the cell (no reference function) ---------------
+ * The geometric judgement of trajectories on the device: nothing is brought to the host, and no solver gets an obstacle term -- the calls score
+ * trajectories that exist; choosing among starts with their `eligible` is a filter, not avoidance.  Clearance is judged at the T states of a
+ * trajectory only: nothing is said about the motion between two steps (no swept volumes), about the robot against itself, or about any shape but
+ * spheres and half-spaces.  Under ilqr_profile_enable all of it is charged to ILQR_PROF_OTHER.
+ *
+ * Robot (ilqr_clr_robot): n_sph spheres, 1 .. ILQR_CLR_MAX_SPH.  Sphere i is carried by link sph_link[i], has the centre sph_c[i] in that link's
+ *   frame and the radius sph_r[i] >= 0.  Link s in 0 .. n_seg-1 is the frame behind segment s of the descriptor's chain,
+ *       F_s = F_{s-1} Trans(seg_xyz[s]) seg_R[s] Rot(seg_axis[s], q[seg_joint[s]])      (no rotation for a fixed segment), F_{-1} = I:
+ *   link -1 is the base, link n_seg-1 the tool frame.  sph_link must be non-decreasing (the kernel advances a cursor along the chain).
+ * Cell: n_planes half-spaces plane_n[l] . p >= plane_d[l], 0 .. ILQR_CLR_MAX_PLANES, shared by all trajectories; | |plane_n[l]| - 1 | <= 1e-9.
+ * Obstacles (ilqr_clr_world): obs[n_sets][n_obs][4] = (cx, cy, cz, R) in the base frame; a slot with R < 0 is unused, so sets may hold different
+ *   numbers.  Trajectory i belongs to set i / traj_per_set; n % traj_per_set == 0 and n_sets == n / traj_per_set (one world for all:
+ *   traj_per_set = n).
+ * The clearance of a state is the minimum over the pairs (i, j) of
+ *       (|p_i - o_j| - r_i) - R_j   for the active obstacle j < n_obs,          (n_l . p_i - d_l) - r_i   for plane l, j = n_obs + l,
+ *   p_i being the centre of sphere i in the base frame at the state's joint positions: the first dof entries of x in the user's layout, for every
+ *   system kind and nb_deriv 1 and 2 (velocities and the time state play no part).  Ties go to the lowest i, then the lowest j.  Without an
+ *   active obstacle and without a plane the clearance is +inf.  A step whose clearance is neither finite nor +inf is a bad step: one with a NaN
+ *   or infinite position of a joint that moves a sphere (a joint at or before the last sphere's link; joints behind it are not read).
+ * The clearance of a trajectory is the minimum over its steps k = 0 .. T-1 in the total order "bad steps first (the lowest k), then
+ *   (clearance, k, i, j) lexicographic".  The order is total, so no result depends on how the kernels map steps to lanes.
+ * Outputs (ilqr_clr_out; each may be NULL, not all):
+ *   clr[n][T]       the clearance of every step, NaN on a bad step
+ *   clr_min[n]      of the trajectory; NaN if it has a bad step
+ *   clr_at[n][3]    (step, sphere, obstacle index j) of the minimum; (k, -1, -1) for a bad step; (0, -1, -1) if +inf throughout (ints)
+ *   n_below[n]      the good steps with clearance < margin (strict; ints)
+ *   eligible[n]     1 iff there is no bad step and clr_min >= margin: the array ilqr_problem_select takes (ints)
+ *   stats[n / stats_group][ILQR_CLR_STATS] = { mean, min, n_hit, n_bad } over clr_min of the group's trajectories in index order: mean is the sum
+ *                   over the good trajectories, added in ascending order with one rounding each, divided by their number; mean and min are NaN
+ *                   if none is good; n_hit counts the good ones with clr_min < margin, n_bad those with a bad step.  Needs stats_group >= 1 and
+ *                   n % stats_group == 0.
+ * The structs are read before the call returns (host memory, both forms).  The _dev forms take device pointers for every array, obs included, and
+ * are asynchronous on the context's stream; only a call whose robot or chain differs from the previous call's waits for the stream once, while it
+ * replaces the geometry the kernels read.  Offsets into arrays are size_t (n T n_x may pass 2^31); a trajectory index is an int.
+ *
+ * ilqr_problem_clearance(p, robot, world, out): the plan the problem holds (the X ilqr_problem_get_X returns), n = B, read where it lies (the
+ *   problem's own layout and buffer choice; nothing is copied out).  Needs a plan, as ilqr_problem_gains does, and changes nothing in the problem:
+ *   plan, gains, multipliers and flags stay as they are.
+ * ilqr_clearance_trajectories(ctx, desc, n, T, X, robot, world, out): any trajectories X[n][T][n_x] in the natural layout of desc
+ *   (ilqr_dims_of), e.g. the X[B][S][T][n_x] of a closed-loop call with n = B S, traj_per_set = stats_group = S.  Of desc only kind, nb_deriv, dof
+ *   and the chain are read.  Given the same states the two calls return the same bytes.
+ * Refused, each with a text of its own: a null struct; n_sph outside 1 .. 32; a sph_link outside -1 .. n_seg-1 or a decreasing one; a negative or
+ * non-finite radius, a non-finite centre; n_planes outside 0 .. 8, a non-unit or non-finite normal, a non-finite d; n_obs < 0 (or beyond 2^26 - 8),
+ * n_obs == 0 with no plane, obs NULL with n_obs > 0; the set and stats divisibility rules; a NaN margin; all outputs NULL; stats with
+ * stats_group < 1; a descriptor without a chain (n_seg < 1) or with a chain the lowering refuses; n < 1 or T < 1; no plan (problem form).  The host
+ * forms also refuse a non-finite obstacle entry and name it. */
+#define ILQR_CLR_MAX_SPH 32
+#define ILQR_CLR_MAX_PLANES 8
+#define ILQR_CLR_STATS 4
+typedef struct {
+    int n_sph;
+    int sph_link[ILQR_CLR_MAX_SPH];
+    double sph_c[ILQR_CLR_MAX_SPH][3];
+    double sph_r[ILQR_CLR_MAX_SPH];
+    int n_planes;
+    double plane_n[ILQR_CLR_MAX_PLANES][3];
+    double plane_d[ILQR_CLR_MAX_PLANES];
+} ilqr_clr_robot;
+typedef struct {
+    const double* obs;   /* [n_sets][n_obs][4] */
+    int n_sets, n_obs, traj_per_set;
+    double margin;
+    int stats_group;     /* read only where stats is asked for */
+} ilqr_clr_world;
+typedef struct {
+    double* clr;
+    double* clr_min;
+    int* clr_at;
+    int* n_below;
+    int* eligible;
+    double* stats;
+} ilqr_clr_out;
+int ilqr_problem_clearance(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, const ilqr_clr_out* out);
+int ilqr_problem_clearance_dev(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, const ilqr_clr_out* out);
+int ilqr_clearance_trajectories(ilqr_ctx* ctx, const ilqr_problem_desc* desc, int n, int T, const double* X, const ilqr_clr_robot* robot,
+                                const ilqr_clr_world* world, const ilqr_clr_out* out);
+int ilqr_clearance_trajectories_dev(ilqr_ctx* ctx, const ilqr_problem_desc* desc, int n, int T, const double* X, const ilqr_clr_robot* robot,
+                                    const ilqr_clr_world* world, const ilqr_clr_out* out);
+
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];
  * any output may be NULL.  Host pointers. */
