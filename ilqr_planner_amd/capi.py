@@ -46,6 +46,7 @@ EXPORTS = [
     "ilqr_problem_adopt", "ilqr_problem_adopt_dev", "ilqr_problem_spread_controls", "ilqr_problem_spread_controls_dev",
     "ilqr_problem_select", "ilqr_problem_select_dev", "ilqr_problem_get_at", "ilqr_problem_get_at_dev",
     "ilqr_problem_clearance", "ilqr_problem_clearance_dev", "ilqr_clearance_trajectories", "ilqr_clearance_trajectories_dev",
+    "ilqr_problem_set_obstacles", "ilqr_problem_set_obstacles_dev", "ilqr_problem_obstacle_terms", "ilqr_problem_obstacle_terms_dev",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
     "ilqr_lqt_get_d",
@@ -208,6 +209,7 @@ ClosedLoopCovCon = collections.namedtuple("ClosedLoopCovCon", "Sigma kp_Sigma kp
 ClosedLoopNoise = collections.namedtuple("ClosedLoopNoise", "cost stats X U w")
 ClosedLoopReport = collections.namedtuple("ClosedLoopReport", "cost stats kp_err kp_stats lim_cost outcome X U w")
 Selection = collections.namedtuple("Selection", "winner best n_candidates")
+ObstacleTerms = collections.namedtuple("ObstacleTerms", "cost lx lxx")
 Rows = collections.namedtuple("Rows", "X U cost iters status")
 
 _lib = None
@@ -262,6 +264,10 @@ def load():
         getattr(L, n).argtypes = [vp, C.POINTER(ClrRobot), C.POINTER(ClrWorld), C.POINTER(ClrOut)]
     for n in ("ilqr_clearance_trajectories", "ilqr_clearance_trajectories_dev"):
         getattr(L, n).argtypes = [vp, C.POINTER(ProblemDesc), C.c_int, C.c_int, vp, C.POINTER(ClrRobot), C.POINTER(ClrWorld), C.POINTER(ClrOut)]
+    for n in ("ilqr_problem_set_obstacles", "ilqr_problem_set_obstacles_dev"):
+        getattr(L, n).argtypes = [vp, C.POINTER(ClrRobot), C.POINTER(ClrWorld), C.c_double]
+    for n in ("ilqr_problem_obstacle_terms", "ilqr_problem_obstacle_terms_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp]
     L.ilqr_problem_track.argtypes = [vp, C.c_int, dp, C.c_int, dp]
     L.ilqr_problem_track_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.ilqr_problem_closed_loop.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp]
@@ -916,6 +922,39 @@ class BatchProblem:
     def clearance_dev(self, robot: ClrRobot, world: ClrWorld, out: ClrOut):
         """Device pointers in world.obs and out; asynchronous on the context's stream."""
         self.ctx.check(self.L.ilqr_problem_clearance_dev(self.h, C.byref(robot), C.byref(world), C.byref(out)))
+
+    # ---- obstacle terms in the stage cost of the Riccati solvers (include/ilqr_hip.h "obstacle terms")
+    def set_obstacles(self, spheres, planes, obstacles, margin: float, weight: float, traj_per_set=None):
+        """Hinge penalty weight * max(0, margin - clearance)^2 on every (sphere, obstacle or plane) pair at every step (ilqr_problem_set_obstacles).
+        spheres, planes as clr_robot takes them (or a ClrRobot in `spheres` with planes None); obstacles [n_sets][n_obs][4] or None (planes only);
+        traj_per_set: None = one world for all.  The problem copies everything; it holds no plan afterwards."""
+        rb = spheres if isinstance(spheres, ClrRobot) else clr_robot(spheres, planes)
+        tps = self.B if traj_per_set is None else int(traj_per_set)
+        obs = _f64(obstacles) if obstacles is not None else np.zeros((self.B // tps if tps >= 1 else 0, 0, 4))
+        if obs.ndim != 3 or obs.shape[2] != 4:
+            raise ValueError(f"obstacles: expected [n_sets][n_obs][4], got {obs.shape}")
+        w = ClrWorld(obs.ctypes.data if obs.size else None, obs.shape[0], obs.shape[1], tps, float(margin), 0)
+        self.ctx.check(self.L.ilqr_problem_set_obstacles(self.h, C.byref(rb), C.byref(w), float(weight)))
+
+    def set_obstacles_dev(self, robot: ClrRobot, world: ClrWorld, weight: float):
+        """world.obs is a device pointer; the problem copies the sets device to device."""
+        self.ctx.check(self.L.ilqr_problem_set_obstacles_dev(self.h, C.byref(robot), C.byref(world), float(weight)))
+
+    def clear_obstacles(self):
+        """Remove the obstacle terms: the problem is planned as before they were set (it holds no plan afterwards)."""
+        self.ctx.check(self.L.ilqr_problem_set_obstacles(self.h, None, None, 0.0))
+
+    def obstacle_terms(self, want=("cost", "lx", "lxx")):
+        """c_obs[B][T], its l_x[B][T][dof] and l_xx[B][T][dof][dof] at the plan this problem holds (ilqr_problem_obstacle_terms); what is not
+        wanted is None."""
+        dof = int(self.desc.dof)
+        cost, lx, lxx = _out("cost" in want, self.B, self.T), _out("lx" in want, self.B, self.T, dof), _out("lxx" in want, self.B, self.T, dof, dof)
+        self.ctx.check(self.L.ilqr_problem_obstacle_terms(self.h, *(a.ctypes.data if a is not None else None for a in (cost, lx, lxx))))
+        return ObstacleTerms(cost, lx, lxx)
+
+    def obstacle_terms_dev(self, cost_ptr=None, lx_ptr=None, lxx_ptr=None):
+        """Device pointers (or None); asynchronous on the context's stream."""
+        self.ctx.check(self.L.ilqr_problem_obstacle_terms_dev(self.h, cost_ptr or None, lx_ptr or None, lxx_ptr or None))
 
     def close(self):
         if self.h:

@@ -1395,12 +1395,25 @@ static std::string fmt(double v) {
     return o.str();
 }
 
+static void clearance_structs(const ClearanceInputs& c, int n, int traj_per_set, int stats_group, ilqr_clr_robot& rb, ilqr_clr_world& w);
+// ilqr_problem_set_obstacles from a ClearanceInputs: n instances, traj_per_set of them per obstacle set
+static void set_obstacle_terms(ilqr_problem* p, const ClearanceInputs& c, int n, int traj_per_set, double weight) {
+    if (!c.given()) throw std::runtime_error("[obstacle terms] obstacle_weight needs the robot's spheres");
+    ilqr_clr_robot rb;
+    ilqr_clr_world w;
+    clearance_structs(c, n, traj_per_set, 0, rb, w);
+    check(ilqr_problem_set_obstacles(p, &rb, &w, weight));
+}
+
 // Lower `s`, upload the per-instance inputs, run `solve`, read everything back.
 static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter, bool gains, const ilqr_problem_desc* override_desc,
                              const std::function<void(ilqr_problem*)>& pre_solve, const std::function<void(ilqr_problem*)>& solve,
                              const std::function<void(ilqr_problem*)>& post_solve) {
+    if (!s.builtin() && in.obstacle_weight != 0)
+        throw std::runtime_error("[ilqr_hip] obstacle terms need a built-in System: the host loop that runs a user-defined System / Keypoint subclass has no obstacle term");
     if (!s.builtin())
         throw std::runtime_error("[ilqr_hip] a user-defined System / Keypoint subclass has no device lowering: only ILQRRecursive::solve runs it (over its virtuals)");
+    if (!(std::isfinite(in.obstacle_weight) && in.obstacle_weight >= 0)) throw std::runtime_error("[ilqr_hip] obstacle_weight must be finite and >= 0");
     ilqr_problem_desc d;
     if (override_desc) d = *override_desc;
     else s.lower(&d);
@@ -1433,6 +1446,11 @@ static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter,
     else if (in.U0.size() == nU) U0 = tile(in.U0, nU);
     else throw std::runtime_error("[ilqr_hip] U0 must be (T-1) x nb_ctrl_var per instance");
     check(ilqr_problem_set_controls(g.p, U0.data()));
+    if (in.obstacle_weight > 0) {
+        const int n_sets = in.obstacles.n_obs > 0 ? in.obstacles.n_sets : 1;
+        if (n_sets < 1 || B % n_sets != 0) throw std::runtime_error("[ilqr_hip] obstacles: the batch must be a multiple of the number of obstacle sets");
+        set_obstacle_terms(g.p, in.obstacles, B, B / n_sets, in.obstacle_weight);
+    }
     if (pre_solve) pre_solve(g.p);
     const auto t0 = std::chrono::steady_clock::now();
     solve(g.p);
@@ -1582,6 +1600,12 @@ static void multi_start(sys::System& s, ilqr_problem* pg, int G, const MultiStar
     sd.seed = ms.seed;
     for (int i = 0; i < nu && !ms.sigma_u.empty(); i++) sd.sigma_u[i] = ms.sigma_u.size() == 1 ? ms.sigma_u[0] : ms.sigma_u[i];
     check(ilqr_problem_spread_controls(starts.p, S, &sd));
+    if (!(std::isfinite(ms.obstacle_weight) && ms.obstacle_weight >= 0)) throw std::runtime_error("[solveMultiStart] obstacle_weight must be finite and >= 0");
+    if (ms.obstacle_weight > 0) {   // avoidance on top of the filter: both solves get the terms, each start its task's set
+        if (ms.clearance.n_obs > 0 && ms.clearance.n_sets != G) throw std::runtime_error("[solveMultiStart] obstacles must hold one set per task (G x n_obs x 4)");
+        set_obstacle_terms(starts.p, ms.clearance, B, S, ms.obstacle_weight);
+        set_obstacle_terms(pg, ms.clearance, G, 1, ms.obstacle_weight);
+    }
     solve(starts.p, 0);
     o.winner.resize(G); o.n_candidates.resize(G); o.coarse_iters.resize(G); o.coarse_best.resize(G); o.coarse_first.resize(G);
     const bool clr = ms.clearance.given();

@@ -462,6 +462,18 @@ struct BatchResult {
     double seconds = 0;
 };
 
+// Clearance (include/ilqr_hip.h "clearance"): the robot as spheres on the links of the system's chain, the cell as half-spaces, the obstacles
+// as spheres in sets.  Judged at the states of a trajectory by the clearance calls; with a weight (BatchInputs::obstacle_weight, MultiStartInputs::obstacle_weight)
+// the same description is the obstacle term of the Riccati solvers' stage cost (include/ilqr_hip.h "obstacle terms").
+struct ClearanceInputs {
+    std::vector<int> sph_link;        // [n_sph], non-decreasing: -1 the base, s the frame behind segment s of the chain
+    std::vector<double> sph_c, sph_r; // [n_sph][3] in the link's frame, [n_sph]
+    std::vector<double> plane_n, plane_d;   // [n_planes][3] unit normals, [n_planes]: n . p >= d
+    std::vector<double> obstacles;    // [n_sets][n_obs][4] = (cx, cy, cz, R), R < 0: unused slot
+    int n_sets = 0, n_obs = 0;
+    double margin = 0;
+    bool given() const { return !sph_link.empty(); }
+};
 // Per-instance inputs of a batched solve; anything left empty takes the System's own value for every instance.
 struct BatchInputs {
     int B = 1;
@@ -477,22 +489,16 @@ struct BatchInputs {
     // leaves); it implies plan_gains, and closedLoopBatch / closedLoopCovBatch run on them.  0 = off.  AL_ILQR::finalPenalty gives the
     // penalty a solve ends with.
     double al_gains_penalty = 0;
+    // ILQRRecursive and AL_ILQR: obstacle_weight > 0 with spheres given adds the obstacle terms to the stage cost (ilqr_problem_set_obstacles with
+    // obstacles.margin as the activation distance): obstacles [n_sets][n_obs][4] with B % n_sets == 0, instance b reads set b / (B / n_sets).
+    // Such a solve runs on the generic kernels.  0 = off: the solve is exactly what it is without these fields.
+    ClearanceInputs obstacles;
+    double obstacle_weight = 0;
 };
 
 // Multi-start (include/ilqr_hip.h "multi-start"): every task of a BatchInputs (in.B = G tasks) is solved from S starts on G * S instances --
 // member 0 from the task's own U0, the others from U0 + sigma_u z (ilqr_problem_spread_controls) -- for coarse_iter iterations; the start with
 // the lowest cost wins its group (ilqr_problem_select), and its plan is polished by the caller's nb_iter iterations on the G problem.
-// Clearance (include/ilqr_hip.h "clearance"): the robot as spheres on the links of the system's chain, the cell as half-spaces, the obstacles
-// as spheres in sets.  Judged at the states of a trajectory; no solver gets an obstacle term.
-struct ClearanceInputs {
-    std::vector<int> sph_link;        // [n_sph], non-decreasing: -1 the base, s the frame behind segment s of the chain
-    std::vector<double> sph_c, sph_r; // [n_sph][3] in the link's frame, [n_sph]
-    std::vector<double> plane_n, plane_d;   // [n_planes][3] unit normals, [n_planes]: n . p >= d
-    std::vector<double> obstacles;    // [n_sets][n_obs][4] = (cx, cy, cz, R), R < 0: unused slot
-    int n_sets = 0, n_obs = 0;
-    double margin = 0;
-    bool given() const { return !sph_link.empty(); }
-};
 struct ClearanceResult {
     int n = 0, T = 0, n_groups = 0;
     std::vector<double> clr, clr_min, stats;        // [n][T], [n], [n_groups][ILQR_CLR_STATS] (empty without stats_group)
@@ -510,6 +516,10 @@ struct MultiStartInputs {
     // given: obstacles[G][n_obs][4], one set per task.  The starts are scored after the coarse solves (ilqr_problem_clearance, traj_per_set = S)
     // and only those with clearance >= margin are candidates of the selection; the polished plans are scored again.  A filter, not avoidance.
     ClearanceInputs clearance;
+    // > 0 (needs `clearance`): the same spheres, planes and obstacles are also obstacle terms of both solves' stage cost, with clearance.margin as
+    // the activation distance -- on the starts (traj_per_set = S) and on the tasks (1).  The filter and the reported clearances stay as they are.
+    // 0 = off: exactly the call without it.
+    double obstacle_weight = 0;
 };
 // The usual result of the G tasks (the polished plans; cost_trace / alpha_trace are the polishing solve's) and what the selection saw
 struct MultiStartResult : BatchResult {

@@ -142,11 +142,23 @@ static solver::ClearanceInputs clearance_inputs(const py::object& spheres, const
     return c;
 }
 
+// solve_batch(..., spheres, planes, obstacles, margin, obstacle_weight): the obstacle terms of the stage cost (weight 0: none)
+static solver::BatchInputs obstacle_terms(solver::BatchInputs in, const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin,
+                                          double weight) {
+    in.obstacles = clearance_inputs(spheres, planes, obstacles, margin);
+    in.obstacle_weight = weight;
+    if (weight != 0 && !in.obstacles.given()) throw std::runtime_error("[solve_batch] obstacle_weight needs the robot's spheres");
+    return in;
+}
+
 // solve_multistart(..., S, seed, sigma_u, coarse_iter): sigma_u None (0), a scalar or nb_ctrl_var values
 static solver::MultiStartInputs multistart_inputs(int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter, const py::object& spheres = py::none(),
-                                                  const py::object& planes = py::none(), const py::object& obstacles = py::none(), double margin = 0.0) {
+                                                  const py::object& planes = py::none(), const py::object& obstacles = py::none(), double margin = 0.0,
+                                                  double obstacle_weight = 0.0) {
     solver::MultiStartInputs ms;
     ms.clearance = clearance_inputs(spheres, planes, obstacles, margin);
+    ms.obstacle_weight = obstacle_weight;
+    if (obstacle_weight != 0 && !ms.clearance.given()) throw std::runtime_error("[solve_multistart] obstacle_weight needs the robot's spheres");
     ms.S = S;
     ms.seed = seed;
     ms.coarse_iter = coarse_iter;
@@ -479,22 +491,24 @@ PYBIND11_MODULE(PyLQR, m) {
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
         .def("solve", &solver::ILQRRecursive::solve, py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
-             [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg) {
-                 return self.solveBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), nb_iter, ls, es);
+             [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg,
+                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow) {
+                 return self.solveBatch(obstacle_terms(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), spheres, planes, obstacles, margin, ow), nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
-             py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false)
+             py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("spheres") = py::none(), py::arg("planes") = py::none(),
+             py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0)
         // every task (the batch of U0 / q0 / kp_targets) from S starts: solve_batch's arguments, then the starts
         .def("solve_multistart",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter,
                 const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& spheres, const py::object& planes,
-                const py::object& obstacles, double margin) {
-                 return self.solveMultiStart(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin),
+                const py::object& obstacles, double margin, double ow) {
+                 return self.solveMultiStart(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow),
                                              nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(),
              py::arg("coarse_iter") = 1, py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
-             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0)
+             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0)
         .def("closed_loop_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
                 const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
@@ -519,23 +533,26 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("line_search"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
-                const py::object& kp, bool pg, const py::object& agp) {
-                 return self.solveBatch(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), nb_iter, lag, pen, sc, ls, es);
+                const py::object& kp, bool pg, const py::object& agp, const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin,
+                double ow) {
+                 return self.solveBatch(obstacle_terms(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), spheres, planes, obstacles, margin, ow), nb_iter, lag, pen,
+                                        sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
-             py::arg("al_gains_penalty") = py::none())
+             py::arg("al_gains_penalty") = py::none(), py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(),
+             py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0)
         .def("solve_multistart",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, int S, unsigned long long seed,
                 const py::object& sigma_u, int coarse_iter, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& agp,
-                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin) {
+                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow) {
                  return self.solveMultiStart(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp),
-                                             multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin), nb_iter, lag, pen, sc, ls, es);
+                                             multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(), py::arg("coarse_iter") = 1, py::arg("q0") = py::none(),
              py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("al_gains_penalty") = py::none(),
-             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0)
+             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0)
         .def_static("final_penalty", &solver::AL_ILQR::finalPenalty, py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"))
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,

@@ -25,6 +25,7 @@
 #include "ilqr_ctx.hpp"
 #include "ilqr_kernels.hpp"
 #include "ilqr_multistart.hpp"
+#include "ilqr_obstacle.hpp"
 #include "ilqr_plan.hpp"
 
 using namespace ilqr;
@@ -75,6 +76,11 @@ struct ilqr_problem {
     DevScratch cl_cov_kps;  // closed_loop_cov through device pointers: kp_Sigma where the caller asks only for kp_var
     DevScratch ms_idx;   // adopt / get_at / select through host pointers: the index (or the eligibility flags) as ints
     DevScratch ms_out;   // select / get_at through host pointers: best | winner, n_candidates and iters | status as ints
+    // obstacle terms of the stage cost (ilqr_problem_set_obstacles): the geometry, the obstacle sets and the slots of k_obs_derivs are device
+    // memory of this problem; `obs` is what the kernels are given.  Problems with these terms run on the generic kernels (plan_input).
+    bool has_obs = false;
+    ObsArgs obs = {};
+    size_t obs_sets_bytes = 0;
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
     BatchCPState cp;
     BatchWideState cpw;
@@ -473,6 +479,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
     for (void* q : p->allocs) (void)hipFree(q);
+    for (const void* q : {(const void*)p->obs.geom, (const void*)p->obs.obs, (const void*)p->obs.obd}) (void)hipFree((void*)q);
     for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_con_ws, &p->cl_cost, &p->cl_cov_ws, &p->cl_cov_kps, &p->ms_idx, &p->ms_out}) b->release();
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
@@ -654,6 +661,7 @@ static PlanIn plan_input(const ilqr_problem* p, bool al, int nb_iter, int line_s
     in.kind = p->desc.kind; in.nd = p->desc.nb_deriv; in.al = al; in.m = p->bufs.m; in.per_step = p->bufs.per_step; in.con_state_only = p->con_state_only;
     in.limits2_set = p->desc.limits2_set != 0;
     in.shared_steps = has_shared_step(p->hdesc.steps);
+    in.obstacles = p->has_obs;
     in.uniform_R = true;
     for (int i = 1; i < p->dims.n_u; i++) in.uniform_R = in.uniform_R && (p->hdesc.R_diag[i] == p->hdesc.R_diag[0]);
     // the register-resident sweep addresses x, u and the multipliers with 32-bit byte offsets (ilqr_kernels_dpp.hip): batches whose arrays pass
@@ -722,8 +730,13 @@ static void launch_sweep(const ilqr_problem* p, const RiccatiPlan& pl, int h, bo
         case Sweep::SiDpp: sw.si_wg = pl.si_wg[h] ? 1 : 0; sw.si_io = pl.si_io[h] ? 1 : 0; sw.si_prep = pl.si_prep[h] ? 1 : 0; launch_backward_si_dpp(al, pl.fused, pl.kd_sym == 1, pl.si_lanes[h], bf, B, st, sw); break;
         case Sweep::Rows: launch_backward_rows(kind, nd, al, bf, B, st); break;
         case Sweep::Mfma: launch_backward_mfma(kind, nd, al, bf, B, st); break;
-        case Sweep::Generic: launch_backward_generic(kind, nd, al, bf, B, st); break;
+        case Sweep::Generic: launch_backward_generic(kind, nd, al, bf, B, st, p->has_obs ? &p->obs : nullptr); break;
     }
+}
+// l_x, l_xx of the obstacle terms at every step of the current trajectory, where k_kp_derivs runs: before every sweep.  (A problem with these
+// terms is never split: plan_riccati keeps it on the generic kernels.)
+static void launch_obs_terms(const ilqr_problem* p, const Bufs& bf, int B, hipStream_t st) {
+    if (p->has_obs) launch_obs_derivs(bf, p->obs, B, p->T, p->dims.n_x, 0, st);
 }
 
 static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double penalty0, double scaling, int line_search, int early_stop) {
@@ -752,7 +765,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
         const Bufs& bf = hv[h].bufs;
         ProfScope ps(c, ILQR_PROF_ROLLOUT);
         if (pl.init == Init::Lti) launch_init_lti(kind, nd, bf, hv[h].B, hv[h].st);
-        else launch_init(kind, nd, al, bf, hv[h].B, hv[h].st, penalty0);
+        else launch_init(kind, nd, al, bf, hv[h].B, hv[h].st, penalty0, p->has_obs ? &p->obs : nullptr);
         if (pl.init_al_update) {  // active-set weights of the initial trajectory: I_k = penalty * (g<0 && lambda==0 ? 0 : 1)
             f.it = -1; f.do_update = 0;
             launch_al_update(kind, nd, bf, hv[h].B, T, hv[h].st, f);
@@ -777,6 +790,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
             {   // l_x, l_xx at the keypoint steps (FK, log map, J'QJ) for every sweep: none of them holds keypoint code
                 ProfScope ps(c, ILQR_PROF_OTHER);
                 launch_kp_derivs(kind, nd, bf, B, st, fi);
+                launch_obs_terms(p, bf, B, st);
             }
             {
                 ProfScope ps(c, ILQR_PROF_BACKWARD);
@@ -790,7 +804,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
                     case Forward::WaveDpp: launch_forward_wave(kind, true, bf, B, st, fi); break;
                     case Forward::Lin: launch_forward_lin(bf, B, st, fi); break;
                     case Forward::Mfma: launch_forward_tm(kind, nd, bf, B, st, fi); break;
-                    case Forward::Generic: launch_forward_generic(kind, nd, al, bf, B, st, fi); break;
+                    case Forward::Generic: launch_forward_generic(kind, nd, al, bf, B, st, fi, p->has_obs ? &p->obs : nullptr); break;
                 }
             }
             if (pl.apply != Apply::None && (pl.apply != Apply::WaveLast || it == nb_iter - 1)) {
@@ -828,11 +842,15 @@ extern "C" int ilqr_solve_al(ilqr_problem* p, int nb_iter, int lag, double penal
 // reference's SequentialSystem stacks every sub-system's target into each of them (getMuVector(true) / getQMatrix(true)): not reproduced.
 static const char* const BATCH_SHARED_STEP_TEXT =
     "keypoints that share a timestep are not supported by the batch solvers (ilqr_solve_batch_cp, ilqr_solve_batch)";
+// The batch solvers' normal equations hold the keypoint and limit terms only.
+static const char* const BATCH_OBSTACLES_TEXT =
+    "obstacle terms are not supported by the batch solvers (ilqr_solve_batch_cp, ilqr_solve_batch): remove them (ilqr_problem_set_obstacles with robot = NULL) or use ilqr_solve_recursive / ilqr_solve_al";
 
 extern "C" int ilqr_solve_batch_cp(ilqr_problem* p, const double* psi, int Kw, int nb_iter, int early_stop) {
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
     if (has_shared_step(p->hdesc.steps)) return fail(c, BATCH_SHARED_STEP_TEXT);
+    if (p->has_obs) return fail(c, BATCH_OBSTACLES_TEXT);
     if (!p->has_state || !p->has_controls) return fail(c, "set_init_state and set_controls must be called before a solve");
     p->has_gains = p->has_plan = false;  // the batch solvers leave no gains (ilqr_problem_gains computes them about the plan)
     HIPCHK(c, hipSetDevice(c->device));
@@ -867,6 +885,7 @@ extern "C" int ilqr_solve_batch(ilqr_problem* p, int nb_iter, int early_stop) {
     if (!p) return 1;
     ilqr_ctx* c = p->ctx;
     if (has_shared_step(p->hdesc.steps)) return fail(c, BATCH_SHARED_STEP_TEXT);
+    if (p->has_obs) return fail(c, BATCH_OBSTACLES_TEXT);
     if (!p->has_state || !p->has_controls) return fail(c, "set_init_state and set_controls must be called before a solve");
     p->has_gains = p->has_plan = false;  // the batch solvers leave no gains (ilqr_problem_gains computes them about the plan)
     HIPCHK(c, hipSetDevice(c->device));
@@ -920,6 +939,7 @@ static int gains_about_plan(ilqr_problem* p, bool al, double penalty) {
         {
             ProfScope ps(c, ILQR_PROF_OTHER);
             launch_kp_derivs(kind, nd, bf, B, st, f);
+            launch_obs_terms(p, bf, B, st);
         }
         {
             ProfScope ps(c, ILQR_PROF_BACKWARD);
@@ -1709,13 +1729,14 @@ static void clr_release(ilqr_ctx* c) {
     c->clr = nullptr;
 }
 
+// need_out = false: the checks of robot, planes, obstacles and sets alone (ilqr_problem_set_obstacles, which has no outputs and reads no stats_group)
 static int clr_check(ilqr_ctx* c, const std::string& fn, const ilqr_problem_desc& d, int n, int T, const ilqr_clr_robot* rb, const ilqr_clr_world* w,
-                     const ilqr_clr_out* out, bool dev) {
+                     const ilqr_clr_out* out, bool dev, bool need_out = true) {
     auto no = [&](const std::string& m) { return fail(c, fn + ": " + m); };
     auto S = [](long long v) { return std::to_string(v); };
     if (!rb) return no("robot is a null pointer");
     if (!w) return no("world is a null pointer");
-    if (!out) return no("out is a null pointer");
+    if (need_out && !out) return no("out is a null pointer");
     if (n < 1 || T < 1) return no("n and T must be >= 1 (got " + S(n) + ", " + S(T) + ")");
     if (d.n_seg < 1) return no("the descriptor has no chain (n_seg = " + S(d.n_seg) + "): clearance needs the robot's kinematics");
     {
@@ -1748,8 +1769,8 @@ static int clr_check(ilqr_ctx* c, const std::string& fn, const ilqr_problem_desc
     if (w->n_sets != n / w->traj_per_set)
         return no("n_sets must be n / traj_per_set = " + S(n / w->traj_per_set) + " (got " + S(w->n_sets) + ")");
     if (w->margin != w->margin) return no("margin is NaN");
-    if (!out->clr && !out->clr_min && !out->clr_at && !out->n_below && !out->eligible && !out->stats) return no("every output is a null pointer");
-    if (out->stats) {
+    if (need_out && !out->clr && !out->clr_min && !out->clr_at && !out->n_below && !out->eligible && !out->stats) return no("every output is a null pointer");
+    if (need_out && out->stats) {
         if (w->stats_group < 1) return no("stats needs stats_group >= 1 (got " + S(w->stats_group) + ")");
         if (n % w->stats_group != 0) return no("the number of trajectories (" + S(n) + ") is not a multiple of stats_group (" + S(w->stats_group) + ")");
     }
@@ -1758,6 +1779,22 @@ static int clr_check(ilqr_ctx* c, const std::string& fn, const ilqr_problem_desc
             if (!std::isfinite(w->obs[e]))
                 return no("obs[" + S((long long)(e / ((size_t)w->n_obs * 4))) + "][" + S((long long)(e / 4 % (size_t)w->n_obs)) + "][" + S((long long)(e % 4)) + "] is not finite");
     return 0;
+}
+
+// The geometry as the kernels read it (checked by clr_check)
+static void clr_fill_geom(const ilqr_problem_desc& d, const ilqr_clr_robot& rb, ClrGeom& g) {
+    std::memset(&g, 0, sizeof(g));
+    g.n_seg = d.n_seg; g.n_sph = rb.n_sph; g.n_planes = rb.n_planes;
+    g.n_walk = rb.sph_link[rb.n_sph - 1] + 1;   // non-decreasing: the last sphere's link is the farthest
+    std::memcpy(g.seg_joint, d.seg_joint, sizeof(int) * d.n_seg);
+    std::memcpy(g.seg_xyz, d.seg_xyz, sizeof(double) * 3 * d.n_seg);
+    std::memcpy(g.seg_R, d.seg_R, sizeof(double) * 9 * d.n_seg);
+    std::memcpy(g.seg_axis, d.seg_axis, sizeof(double) * 3 * d.n_seg);
+    std::memcpy(g.sph_link, rb.sph_link, sizeof(int) * rb.n_sph);
+    std::memcpy(g.sph_c, rb.sph_c, sizeof(double) * 3 * rb.n_sph);
+    std::memcpy(g.sph_r, rb.sph_r, sizeof(double) * rb.n_sph);
+    std::memcpy(g.plane_n, rb.plane_n, sizeof(double) * 3 * rb.n_planes);
+    std::memcpy(g.plane_d, rb.plane_d, sizeof(double) * rb.n_planes);
 }
 
 // p: the problem form (the plan where it lies); else X[n][T][n_x] in the natural layout of d
@@ -1772,18 +1809,7 @@ static int clr_run(ilqr_ctx* c, const char* fn_, ilqr_problem* p, const ilqr_pro
     if (!c->clr) c->clr = new ClrState();
     ClrState& cs = *c->clr;
     ClrGeom g;
-    std::memset(&g, 0, sizeof(g));
-    g.n_seg = d.n_seg; g.n_sph = rb->n_sph; g.n_planes = rb->n_planes;
-    g.n_walk = rb->sph_link[rb->n_sph - 1] + 1;   // non-decreasing: the last sphere's link is the farthest
-    std::memcpy(g.seg_joint, d.seg_joint, sizeof(int) * d.n_seg);
-    std::memcpy(g.seg_xyz, d.seg_xyz, sizeof(double) * 3 * d.n_seg);
-    std::memcpy(g.seg_R, d.seg_R, sizeof(double) * 9 * d.n_seg);
-    std::memcpy(g.seg_axis, d.seg_axis, sizeof(double) * 3 * d.n_seg);
-    std::memcpy(g.sph_link, rb->sph_link, sizeof(int) * rb->n_sph);
-    std::memcpy(g.sph_c, rb->sph_c, sizeof(double) * 3 * rb->n_sph);
-    std::memcpy(g.sph_r, rb->sph_r, sizeof(double) * rb->n_sph);
-    std::memcpy(g.plane_n, rb->plane_n, sizeof(double) * 3 * rb->n_planes);
-    std::memcpy(g.plane_d, rb->plane_d, sizeof(double) * rb->n_planes);
+    clr_fill_geom(d, *rb, g);
     if (!cs.have || std::memcmp(&g, &cs.host, sizeof(g)) != 0) {   // kernels in flight may read the old one; the copy's source must outlive it
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (cs.geom.reserve(c, sizeof(ClrGeom))) return 1;
@@ -1874,6 +1900,92 @@ extern "C" int ilqr_clearance_trajectories_dev(ilqr_ctx* c, const ilqr_problem_d
     if (!desc) return fail(c, "ilqr_clearance_trajectories_dev: desc is a null pointer");
     return clr_run(c, "ilqr_clearance_trajectories", nullptr, *desc, n, T, X, robot, world, out, true);
 }
+
+// ------------------------------------------------------------------------------------------------ obstacle terms
+// include/ilqr_hip.h "obstacle terms".  The setter copies everything it is given into device memory of the problem (the geometry block of the
+// clearance kernels, the obstacle sets, and the slots k_obs_derivs fills before every sweep); from then on plan_input routes the problem to the
+// generic kernels, whose OBS forms read the terms.
+
+static int set_obstacles(ilqr_problem* p, const ilqr_clr_robot* rb, const ilqr_clr_world* w, double weight, bool dev) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    const std::string fn = std::string("ilqr_problem_set_obstacles") + (dev ? "_dev" : "");
+    if (!rb) {   // remove the terms: the problem is planned as before
+        p->has_obs = false;
+        p->has_gains = p->has_plan = false;
+        return 0;
+    }
+    if (clr_check(c, fn, p->desc, p->B, p->T, rb, w, nullptr, dev, false)) return 1;
+    if (std::isinf(w->margin)) return fail(c, fn + ": margin is infinite");
+    if (!(std::isfinite(weight) && weight >= 0.0)) return fail(c, fn + ": the weight must be finite and >= 0 (got " + std::to_string(weight) + ")");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // kernels in flight may read the previous terms
+    p->has_obs = false;
+    p->has_gains = p->has_plan = false;
+    ClrGeom g;
+    clr_fill_geom(p->desc, *rb, g);
+    if (!p->obs.geom) HIPCHK(c, hipMalloc((void**)&p->obs.geom, sizeof(ClrGeom)));
+    if (!p->obs.obd) HIPCHK(c, hipMalloc((void**)&p->obs.obd, sizeof(double) * (size_t)p->T * OBS_W * (size_t)p->Bp));
+    const size_t bytes = sizeof(double) * (size_t)w->n_sets * (size_t)w->n_obs * 4;
+    if (bytes > p->obs_sets_bytes) {
+        if (p->obs.obs) HIPCHK(c, hipFree((void*)p->obs.obs));
+        p->obs.obs = nullptr;
+        p->obs_sets_bytes = 0;
+        HIPCHK(c, hipMalloc((void**)&p->obs.obs, bytes));
+        p->obs_sets_bytes = bytes;
+    }
+    HIPCHK(c, hipMemcpyAsync((void*)p->obs.geom, &g, sizeof(ClrGeom), hipMemcpyHostToDevice, c->stream));
+    if (bytes) HIPCHK(c, hipMemcpyAsync((void*)p->obs.obs, w->obs, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // g is on this stack; the caller's arrays may go away
+    p->obs.n_obs = w->n_obs; p->obs.traj_per_set = w->traj_per_set; p->obs.margin = w->margin; p->obs.weight = weight;
+    p->has_obs = true;
+    return 0;
+}
+extern "C" int ilqr_problem_set_obstacles(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, double weight) {
+    return set_obstacles(p, robot, world, weight, false);
+}
+extern "C" int ilqr_problem_set_obstacles_dev(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, double weight) {
+    return set_obstacles(p, robot, world, weight, true);
+}
+
+static int obstacle_terms(ilqr_problem* p, double* cost, double* lx, double* lxx, bool dev) {
+    if (!p) return 1;
+    ilqr_ctx* c = p->ctx;
+    const std::string fn = std::string("ilqr_problem_obstacle_terms") + (dev ? "_dev" : "");
+    if (!p->has_obs) return fail(c, fn + ": the problem has no obstacle terms (ilqr_problem_set_obstacles)");
+    if (!p->has_plan)
+        return fail(c, fn + " needs a plan: run a solver since the problem's inputs last changed (ilqr_solve_recursive with nb_iter = 0 rolls out the controls as they are)");
+    if (!cost && !lx && !lxx) return fail(c, fn + ": every output is a null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int dof = p->desc.dof;
+    const size_t nT = (size_t)p->B * (size_t)p->T, n_lx = nT * dof, n_lxx = n_lx * dof;
+    double *dc = cost, *dl = lx, *dm = lxx;
+    if (!dev) {
+        if (p->staging.reserve(c, nT + n_lx + n_lxx)) return 1;
+        dc = cost ? p->staging.ptr : nullptr;
+        dl = lx ? p->staging.ptr + nT : nullptr;
+        dm = lxx ? p->staging.ptr + nT + n_lx : nullptr;
+    }
+    {
+        ProfScope ps(c, ILQR_PROF_OTHER);
+        launch_obs_derivs(p->bufs, p->obs, p->B, p->T, p->dims.n_x, 1, c->stream);
+    }
+    {
+        ProfScope ps(c, ILQR_PROF_OTHER);
+        launch_obs_query(p->obs, p->B, p->Bp, p->T, dof, dc, dl, dm, c->stream);
+    }
+    HIPCHK(c, hipGetLastError());
+    prof_mark(c, -1);
+    if (!dev) {
+        if (cost) HIPCHK(c, hipMemcpyAsync(cost, dc, nT * 8, hipMemcpyDeviceToHost, c->stream));
+        if (lx) HIPCHK(c, hipMemcpyAsync(lx, dl, n_lx * 8, hipMemcpyDeviceToHost, c->stream));
+        if (lxx) HIPCHK(c, hipMemcpyAsync(lxx, dm, n_lxx * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+extern "C" int ilqr_problem_obstacle_terms(ilqr_problem* p, double* cost, double* lx, double* lxx) { return obstacle_terms(p, cost, lx, lxx, false); }
+extern "C" int ilqr_problem_obstacle_terms_dev(ilqr_problem* p, double* cost, double* lx, double* lxx) { return obstacle_terms(p, cost, lx, lxx, true); }
 
 // ------------------------------------------------------------------------------------------------ stand-alone FK
 

@@ -38,6 +38,17 @@ struct ClrArgs {
     int qrow[7];          // the row of joint j's position within a state (private layout: through the index map of a narrow chain)
 };
 
+// C = A B on row-major 3 x 3 matrices, one rounding per operation: the walks of clr_state and obs_state (ilqr_obstacle.hpp) share it
+__device__ __forceinline__ void clr_mul(const double* A, const double* B, double* C) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+
 constexpr int CLR_MAX_OBS = (1 << 26) - ILQR_CLR_MAX_PLANES;   // the obstacle index shares an int with the sphere's
 
 // k_clr_plan: the plan of a problem where it lies, X0 / X1 [T][NX][Bp] chosen per instance by cur; key of (b, k) at ws[k n + b]

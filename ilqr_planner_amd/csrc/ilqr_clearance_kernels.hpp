@@ -22,16 +22,6 @@ namespace ilqr {
 
 struct ClrKey { double clr; int code; };   // a bad step: (NaN, -1); a step without an active obstacle or plane: (+inf, -1)
 
-__device__ __forceinline__ void clr_mul(const double* A, const double* B, double* C) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-
 // q(j): the position of joint j of this lane's state.  obs: this trajectory's set, [n_obs][4].
 template <class Q>
 __device__ __forceinline__ ClrKey clr_state(const ClrGeom& g, const double* __restrict__ obs, int n_obs, Q q) {

@@ -13,6 +13,7 @@
 #include "ilqr_closed_loop.hpp"
 #include "ilqr_closed_loop_cov.hpp"
 #include "ilqr_kernels.hpp"
+#include "ilqr_obstacle.hpp"
 #include "ilqr_step.hpp"
 
 namespace ilqr {
@@ -21,10 +22,27 @@ namespace ilqr {
 
 #define NOUNR _Pragma("unroll 1")
 
+// The obstacle term of a state inside the sequential kernels (the OBS forms of k_init_rollout / k_forward): obs_state<false> out of line, as
+// kp_cost_call keeps the keypoint code out of their loops.  The joint positions travel by value and are picked by a compare chain on the
+// (uniform) joint index: no private array is indexed.
+__device__ __noinline__ double obs_cost_call(const ClrGeom* g, const double* obs, int n_obs, double margin, double weight, double q0, double q1, double q2,
+                                             double q3, double q4, double q5, double q6) {
+    return obs_state<false>(*g, obs, n_obs, margin, weight,
+                            [&](int j) { return j == 0 ? q0 : j == 1 ? q1 : j == 2 ? q2 : j == 3 ? q3 : j == 4 ? q4 : j == 5 ? q5 : q6; }, nullptr, nullptr);
+}
+ILQR_DEV double obs_stage_cost(ObsArgs o, int b, const double* x) {
+    return obs_cost_call(o.geom, o.obs + (size_t)(b / o.traj_per_set) * (size_t)o.n_obs * 4, o.n_obs, o.margin, o.weight, x[0], x[1], x[2], x[3], x[4], x[5], x[6]);
+}
+
+ILQR_DEV const double* obs_slot(ObsArgs o, int k, int Bp) { return o.obd + (size_t)k * OBS_W * (size_t)Bp; }
+
 // Initial rollout from U0 (ILQRRecursive.cpp:27-56): X, cost0; resets the per-instance solve state.
-template <class S, bool AL>
-__global__ __launch_bounds__(64) void k_init_rollout(Bufs a, double penalty) {
+// O is empty, or ObsArgs: the OBS form, in which the obstacle term of every state joins its stage cost.  (A trailing pack and not a flag with an
+// argument, here and in k_backward / k_forward: the forms without the terms keep their text, their arguments and their code.)
+template <class S, bool AL, class... O>
+__global__ __launch_bounds__(64) void k_init_rollout(Bufs a, double penalty, O... o) {
     constexpr int NX = S::NX, NU = S::NU;
+    constexpr bool OBS = sizeof...(O) != 0;
     const DevDesc& d = *a.desc;
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= d.B) return;
@@ -46,7 +64,8 @@ __global__ __launch_bounds__(64) void k_init_rollout(Bufs a, double penalty) {
             }
         }
         const bool iskp = (st < d.steps.n && d.steps.t[st] == k);
-        cost += stage_cost<S>(d, a, b, iskp ? st : -1, x, u);
+        if constexpr (OBS) cost += stage_cost<S>(d, a, b, iskp ? st : -1, x, u) + obs_stage_cost(o..., b, x);
+        else cost += stage_cost<S>(d, a, b, iskp ? st : -1, x, u);
         if (iskp) st++;
         dyn_step<S>(d, x, u, xn);
         UNR for (int i = 0; i < NX; i++) x[i] = xn[i];
@@ -56,7 +75,8 @@ __global__ __launch_bounds__(64) void k_init_rollout(Bufs a, double penalty) {
         const bool iskp = (st < d.steps.n && d.steps.t[st] == T - 1);
         double zu[NU];
         UNR for (int i = 0; i < NU; i++) zu[i] = 0;
-        cost += stage_cost<S>(d, a, b, iskp ? st : -1, x, zu);
+        if constexpr (OBS) cost += stage_cost<S>(d, a, b, iskp ? st : -1, x, zu) + obs_stage_cost(o..., b, x);
+        else cost += stage_cost<S>(d, a, b, iskp ? st : -1, x, zu);
     }
     a.cost[b] = cost;
     a.alpha[b] = 1.0;
@@ -217,9 +237,11 @@ int backward_ws_entries(int kind, int nd) {
     return n;
 }
 
-template <class S, bool AL>
-__global__ __launch_bounds__(64) void k_backward(Bufs a) {
+// O = ObsArgs, the OBS form: the slot obd[k] of k_obs_derivs is added to the position block of l_x, l_xx behind the keypoint or limit terms.
+template <class S, bool AL, class... O>
+__global__ __launch_bounds__(64) void k_backward(Bufs a, O... o) {
     constexpr int NX = S::NX, NU = S::NU, ND = S::ND, TM = S::TM;
+    constexpr bool OBS = sizeof...(O) != 0;
     const DevDesc& d = *a.desc;
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= d.B) return;
@@ -237,7 +259,7 @@ __global__ __launch_bounds__(64) void k_backward(Bufs a) {
 #define WS(o, i, j, C) w[(size_t)((o) + (i) * (C) + (j)) * Bp]
 #define WV(o, i) w[(size_t)((o) + (i)) * Bp]
     // l_xx -> matrix at oM, l_x -> vector at oV for the state at ox (statement for statement stage_derivs / lim2_derivs of ilqr_step.hpp)
-    auto stage_to_ws = [&](int kpi_, int oM, int oV) {
+    auto stage_to_ws = [&](int kpi_, int k_, int oM, int oV) {
         if (kpi_ >= 0) {
             const double* src = a.kpd + (size_t)kpi_ * (NX + NX * NX) * Bp;
             NOUNR for (int i = 0; i < NX; i++) {
@@ -260,6 +282,13 @@ __global__ __launch_bounds__(64) void k_backward(Bufs a) {
                 WS(oM, i, i, NX) = lxxi;
             }
         }
+        if constexpr (OBS) {
+            const double* src = obs_slot(o..., k_, Bp);
+            NOUNR for (int i = 0; i < DOF; i++) {
+                WV(oV, i) += AT(src, OBS_LX + i, b);
+                NOUNR for (int j = 0; j < DOF; j++) WS(oM, i, j, NX) += AT(src, OBS_LXX + (i <= j ? obs_tri(i, j) : obs_tri(j, i)), b);
+            }
+        }
         if (d.lim2) {
             NOUNR for (int i = 0; i < NX; i++) {
                 if (d.lw2[i] != 0) {
@@ -279,7 +308,7 @@ __global__ __launch_bounds__(64) void k_backward(Bufs a) {
     NOUNR for (int i = 0; i < NX; i++) WV(ox, i) = AT(X, (T - 1) * NX + i, b);
     {
         const bool iskp = (kpi >= 0 && d.steps.t[kpi] == T - 1);
-        stage_to_ws(iskp ? kpi : -1, oP, op);
+        stage_to_ws(iskp ? kpi : -1, T - 1, oP, op);
         if (iskp) kpi--;
     }
     for (int k = T - 2; k >= 0; k--) {
@@ -304,7 +333,7 @@ __global__ __launch_bounds__(64) void k_backward(Bufs a) {
         }
         {   // l_xx, l_x of the stage go straight into the Qxx / Qx slots (Qxx = l_xx + A'PA below)
             const bool iskp = (kpi >= 0 && d.steps.t[kpi] == k);
-            stage_to_ws(iskp ? kpi : -1, oQxx, oQx);
+            stage_to_ws(iskp ? kpi : -1, k, oQxx, oQx);
             if (iskp) kpi--;
         }
         // BtP = B^T P (NU x NX), AtP = A^T P (NX x NX)
@@ -473,10 +502,12 @@ __global__ __launch_bounds__(64) void k_backward(Bufs a) {
 
 // Forward pass with step-halving line search (ILQRRecursive.cpp:101-176).  Each trial re-rolls the whole horizon
 // and overwrites the instance's inactive trajectory buffer; the last trial executed is the accepted one.
-template <class S, bool AL>
+// O = ObsArgs, the OBS form: the obstacle term of every state joins its stage cost, as in k_init_rollout.
+template <class S, bool AL, class... O>
 __global__ __launch_bounds__(64) void k_forward(Bufs a, int it, int line_search, int early_stop, double penalty_roll,
-                                                double penalty_update, int do_update, int nb_iter) {
+                                                double penalty_update, int do_update, int nb_iter, O... o) {
     constexpr int NX = S::NX, NU = S::NU;
+    constexpr bool OBS = sizeof...(O) != 0;
     const DevDesc& d = *a.desc;
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= d.B) return;
@@ -518,7 +549,8 @@ __global__ __launch_bounds__(64) void k_forward(Bufs a, int it, int line_search,
                 }
             }
             const bool iskp = (st < d.steps.n && d.steps.t[st] == k);
-            newCost += stage_cost<S>(d, a, b, iskp ? st : -1, x, u);
+            if constexpr (OBS) newCost += stage_cost<S>(d, a, b, iskp ? st : -1, x, u) + obs_stage_cost(o..., b, x);
+            else newCost += stage_cost<S>(d, a, b, iskp ? st : -1, x, u);
             if (iskp) st++;
             dyn_step<S>(d, x, u, xn);
             UNR for (int i = 0; i < NX; i++) x[i] = xn[i];
@@ -528,7 +560,8 @@ __global__ __launch_bounds__(64) void k_forward(Bufs a, int it, int line_search,
             const bool iskp = (st < d.steps.n && d.steps.t[st] == T - 1);
             double zu[NU];
             UNR for (int i = 0; i < NU; i++) zu[i] = 0;
-            newCost += stage_cost<S>(d, a, b, iskp ? st : -1, x, zu);
+            if constexpr (OBS) newCost += stage_cost<S>(d, a, b, iskp ? st : -1, x, zu) + obs_stage_cost(o..., b, x);
+            else newCost += stage_cost<S>(d, a, b, iskp ? st : -1, x, zu);
         }
     } while (((newCost >= cost0) || isnan(newCost)) && alpha > d.alpha_floor && line_search);
 
@@ -557,6 +590,44 @@ __global__ __launch_bounds__(64) void k_forward(Bufs a, int it, int line_search,
     bool stop = early_stop && (alpha * sqrt(dun) < d.stop_tol);
     if (!AL) stop = stop && (newCost < 1e-3);  // ILQRRecursive.cpp:174 vs AL-ILQR.cpp:225
     if (stop) a.active[b] = 0;
+}
+
+// ---- obstacle terms (ilqr_obstacle.hpp)
+
+// obd[k] = c_obs | l_x | upper triangle of l_xx of step k of every instance's current trajectory, one lane per (instance, step): lanes along the
+// batch, so every load is a whole run of a [row][Bp] row of X[cur] and every store a whole run of a row of the slot; the geometry is read at
+// wave-uniform addresses.  Runs where k_kp_derivs runs, before every sweep (all = 0: the instances the sweep visits), and for the query call
+// (all = 1).  The generic path applies a line search's winner inside its forward pass, so X[cur] is the accepted trajectory.
+__global__ __launch_bounds__(64) void k_obs_derivs(Bufs a, ObsArgs o, int nx, int k0, int all) {
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    const int k = k0 + (int)blockIdx.y;
+    if (b >= d.B) return;
+    if (!all && !a.active[b]) return;
+    const size_t Bps = (size_t)d.Bp;
+    const double* x = a.X[a.cur[b]] + (size_t)k * (size_t)nx * Bps + (size_t)b;
+    double lx[7], lxx[28];
+    const double c = obs_state<true>(*o.geom, o.obs + (size_t)(b / o.traj_per_set) * (size_t)o.n_obs * 4, o.n_obs, o.margin, o.weight,
+                                     [&](int j) { return x[(size_t)j * Bps]; }, lx, lxx);
+    double* out = o.obd + (size_t)k * OBS_W * Bps + (size_t)b;
+    out[0] = c;
+    UNR for (int i = 0; i < 7; i++) out[(size_t)(OBS_LX + i) * Bps] = lx[i];
+    UNR for (int e = 0; e < 28; e++) out[(size_t)(OBS_LXX + e) * Bps] = lxx[e];
+}
+
+// ilqr_problem_obstacle_terms: the slots in the natural layout on the user's joints; l_xx mirrored from its upper triangle
+__global__ __launch_bounds__(256) void k_obs_query(const double* __restrict__ obd, int B, int Bp, int T, int dof, double* __restrict__ cost,
+                                                   double* __restrict__ lx, double* __restrict__ lxx) {
+    const int b = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (b >= B) return;
+    const double* s = obd + (size_t)k * OBS_W * (size_t)Bp + (size_t)b;
+    const size_t e = (size_t)b * (size_t)T + (size_t)k;
+    if (cost) cost[e] = s[0];
+    for (int i = 0; i < dof; i++) {
+        if (lx) lx[e * dof + i] = s[(size_t)(OBS_LX + i) * Bp];
+        if (lxx)
+            for (int j = 0; j < dof; j++) lxx[(e * dof + i) * dof + j] = s[(size_t)(OBS_LXX + (i <= j ? obs_tri(i, j) : obs_tri(j, i))) * Bp];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ gather / scatter
@@ -1214,32 +1285,52 @@ void launch_gains_al_weights(int kind, int nd, const Bufs& a, int B, int T, doub
     });
 }
 
-void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty) {
+void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty, const ObsArgs* o) {
     SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
-        if (al) hipLaunchKernelGGL((k_init_rollout<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty);
+        if (o && al) hipLaunchKernelGGL((k_init_rollout<S, true, ObsArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty, *o);
+        else if (o) hipLaunchKernelGGL((k_init_rollout<S, false, ObsArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty, *o);
+        else if (al) hipLaunchKernelGGL((k_init_rollout<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty);
         else hipLaunchKernelGGL((k_init_rollout<S, false>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty);
     });
 }
 
-void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st) {
+void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const ObsArgs* o) {
     SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
-        if (al) hipLaunchKernelGGL((k_backward<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a);
+        if (o && al) hipLaunchKernelGGL((k_backward<S, true, ObsArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, *o);
+        else if (o) hipLaunchKernelGGL((k_backward<S, false, ObsArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, *o);
+        else if (al) hipLaunchKernelGGL((k_backward<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a);
         else hipLaunchKernelGGL((k_backward<S, false>), dim3((B + 63) / 64), dim3(64), 0, st, a);
     });
 }
 
-void launch_forward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f) {
+void launch_forward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f, const ObsArgs* o) {
     SysAll::dispatch(kind, nd, [&](auto s) {
         using S = decltype(s);
-        if (al)
+        if (o && al)
+            hipLaunchKernelGGL((k_forward<S, true, ObsArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
+                               f.penalty_update, f.do_update, f.nb_iter, *o);
+        else if (o)
+            hipLaunchKernelGGL((k_forward<S, false, ObsArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
+                               f.penalty_update, f.do_update, f.nb_iter, *o);
+        else if (al)
             hipLaunchKernelGGL((k_forward<S, true>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
                                f.penalty_update, f.do_update, f.nb_iter);
         else
             hipLaunchKernelGGL((k_forward<S, false>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
                                f.penalty_update, f.do_update, f.nb_iter);
     });
+}
+
+void launch_obs_derivs(const Bufs& a, const ObsArgs& o, int B, int T, int nx, int all, hipStream_t st) {
+    for (int k0 = 0; k0 < T; k0 += 65535) {   // the y extent of a grid
+        const int rows = T - k0 < 65535 ? T - k0 : 65535;
+        hipLaunchKernelGGL(k_obs_derivs, dim3((B + 63) / 64, rows), dim3(64), 0, st, a, o, nx, k0, all);
+    }
+}
+void launch_obs_query(const ObsArgs& o, int B, int Bp, int T, int dof, double* cost, double* lx, double* lxx, hipStream_t st) {
+    hipLaunchKernelGGL(k_obs_query, dim3((B + 255) / 256, T), dim3(256), 0, st, (const double*)o.obd, B, Bp, T, dof, cost, lx, lxx);
 }
 
 void launch_fx_all(int kind, int nd, const Bufs& a, int B, int T, double* out, hipStream_t st) {

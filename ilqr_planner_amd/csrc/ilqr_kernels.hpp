@@ -7,6 +7,8 @@
 
 namespace ilqr {
 
+struct ObsArgs;  // ilqr_obstacle.hpp: a problem's obstacle terms; a null pointer below = the problem has none
+
 // All trajectory-like buffers are [row][Bp] with the (padded) batch innermost; row = t * DIM + component.
 struct Bufs {
     const DevDesc* desc;
@@ -85,13 +87,13 @@ struct SweepArgs {
 
 // Launchers of one Riccati iteration; which of them run is decided by plan_riccati (ilqr_plan.hpp).
 // generic lane-per-instance kernels (ilqr_kernels.hip)
-void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty);  // k_init_rollout
+void launch_init(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty, const ObsArgs* o = nullptr);  // k_init_rollout (o: its OBS form)
 void launch_gains_prepare(const Bufs& a, int B, hipStream_t st);  // k_gains_prepare: every instance active, alpha = 1 (ilqr_problem_gains)
 void launch_gains_al_weights(int kind, int nd, const Bufs& a, int B, int T, double penalty, hipStream_t st);  // k_gains_al_weights: Is of the held plan (ilqr_problem_gains_al, the sweeps that read Is)
 void launch_kp_derivs(int kind, int nd, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // l_x, l_xx at the keypoint steps (FK + Jacobian), feeding every sweep
-void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st);  // k_backward, needs Bufs::ws
+void launch_backward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const ObsArgs* o = nullptr);  // k_backward (o: its OBS form, needs launch_obs_derivs first), needs Bufs::ws
 int backward_ws_entries(int kind, int nd);  // doubles per instance of k_backward's workspace
-void launch_forward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f);  // k_forward
+void launch_forward_generic(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f, const ObsArgs* o = nullptr);  // k_forward (o: its OBS form)
 // cooperative kernels
 void launch_init_lti(int kind, int nd, const Bufs& a, int B, hipStream_t st);  // followed by launch_al_update (it = -1) for AL solves
 void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw);  // rows in registers, DPP broadcasts (ilqr_kernels_dpp.hip)

@@ -80,6 +80,7 @@ struct PlanIn {
     bool con_state_only = false;   // no constraint row touches the controls
     bool limits2_set = false;      // a second limit set (generic kernels only)
     bool shared_steps = false;     // keypoints that share a timestep (generic kernels only: the cooperative kernels hold one keypoint per step)
+    bool obstacles = false;        // obstacle terms in the stage cost (generic kernels only: ilqr_obstacle.hpp)
     bool uniform_R = false;        // all control weights equal
     bool off32 = true;             // x, u and the multipliers are addressable with 32-bit byte offsets (k_backward_si_dpp)
     bool line_search = true;
@@ -131,8 +132,8 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     RiccatiPlan p;
     const int kind = in.kind, nd = in.nd;
     p.n_alpha = n_alpha_of(in.line_search, in.alpha_floor);
-    // a second limit set and keypoints that share a timestep exist in the generic kernels only, whatever the pins say
-    const bool cooperative = !in.generic && !in.limits2_set && !in.shared_steps;
+    // a second limit set, keypoints that share a timestep and obstacle terms exist in the generic kernels only, whatever the pins say
+    const bool cooperative = !in.generic && !in.limits2_set && !in.shared_steps && !in.obstacles;
     const bool coop_fwd = cooperative && p.n_alpha <= 16;       // all step sizes at once (16 lanes / rows per instance)
 
     // sweep.  The row-per-lane sweep (16 lanes per instance, rows in registers): a lone wave's chain is longer than the matrix-core sweep's (553

@@ -655,6 +655,47 @@ int ilqr_clearance_trajectories(ilqr_ctx* ctx, const ilqr_problem_desc* desc, in
 int ilqr_clearance_trajectories_dev(ilqr_ctx* ctx, const ilqr_problem_desc* desc, int n, int T, const double* X, const ilqr_clr_robot* robot,
                                     const ilqr_clr_world* world, const ilqr_clr_out* out);
 
+/* ---- obstacle terms: a hinge penalty on clearance in the stage cost of the Riccati solvers (no reference function) ---------------------------
+ * Avoidance, where the clearance calls above only judge: with these terms set, ilqr_solve_recursive, ilqr_solve_al, ilqr_problem_gains and
+ * ilqr_problem_gains_al plan with a cost that grows as a sphere of the robot comes nearer than `margin` to an obstacle or a plane.  Every system
+ * kind, nb_deriv 1 and 2, chains of 1 to 7 joints.  Robot, planes, obstacle sets and the pair clearances
+ *       clr_ij(q) = (|p_i - o_j| - r_i) - R_j   (active obstacle j),          (n_l . p_i - d_l) - r_i   (plane l, j = n_obs + l)
+ * are exactly those of "clearance"; q is the first dof entries of x in the user's layout.  With the activation distance margin = world->margin
+ * and the weight w >= 0, at every step k = 0 .. T-1 (the terminal state included, as for the limit terms):
+ *       h_ij   = max(0, margin - clr_ij(q_k))                  every pair (i, j): the active obstacles of the instance's set, then the planes
+ *       c_obs  = w * sum_ij h_ij^2                             joins the stage cost: cost, trace, line search, ilqr_problem_get_cost
+ *       l_x   += -w * sum_ij h_ij grad_ij                      joint-position entries only
+ *       l_xx  +=  w * sum_{ij : h_ij > 0} grad_ij grad_ij'     Gauss-Newton; the joint-position block only
+ *       grad_ij = n_ij' Jp_i(q),   n_ij = (p_i - o_j) / |p_i - o_j| for an obstacle, plane_n[l] for a plane;
+ *   Jp_i is the position Jacobian of sphere centre i: column m is a_m x (p_i - r_m), a_m and r_m the axis and origin of joint m in the base
+ *   frame, for the joints m that move link sph_link[i], and 0 for the others.  This is the reference's keypoint convention (cost = e'Qe,
+ *   l_x = -J'Qe, l_xx = J'QJ; System.cpp:248-308) for a one-sided scalar keypoint on clearance with target `margin` and precision w: l_x is
+ *   half the gradient of the cost, as for every other term.  The exact Hessian's term h_ij grad^2 clr_ij is left out.
+ *   A pair with p_i == o_j exactly adds its cost and a zero gradient.  Velocity, time and control entries get nothing, nor do the padded joints of
+ *   a chain of fewer than 7 joints.  The sum runs over ALL pairs, not only the nearest, so the cost is C1 in q.  Summation order: spheres
+ *   ascending; per sphere the obstacles ascending, then the planes; one rounding per operation (no contraction), and the weight multiplies the
+ *   finished sums.  A stage's terms are added as the limit terms are: behind the keypoint or first limit set's terms, before the second limit
+ *   set's; the stage's cost (system part + c_obs) is formed first and then joins the running sum.  One per-state function serves the solvers'
+ *   rollouts, their derivative pass and the query below: the same state gives the same cost bits everywhere.  A state with a NaN or infinite
+ *   position of a joint that moves a sphere gives a NaN cost (status ILQR_STATUS_NONFINITE by the usual rule).
+ *
+ * ilqr_problem_set_obstacles(p, robot, world, weight): instance b reads set b / traj_per_set (n = B in the rules of "clearance"); stats_group is
+ *   not read.  Everything is copied into memory the problem owns before the call returns: no pointer is kept (_dev: world->obs is a device
+ *   pointer and the copy is device to device; the structs are host memory in both forms).  robot == NULL removes the terms, and the problem is
+ *   then planned exactly as before.  A setter: afterwards the problem holds no plan and no gains.  Problems with obstacle terms run on the generic
+ *   lane-per-instance kernel set, whatever the pins say (as a second limit set and shared keypoint steps do): they pay that set's price.
+ *   Refused, each with its own text: what the clearance calls refuse about robot, planes, obstacles, sets and the chain; a negative or non-finite
+ *   weight; a NaN or infinite margin.  ilqr_solve_batch_cp and ilqr_solve_batch refuse a problem that has obstacle terms.
+ * ilqr_problem_obstacle_terms(p, cost, lx, lxx): the terms at the plan the problem holds (needs one, as ilqr_problem_gains does): cost[B][T],
+ *   lx[B][T][dof], lxx[B][T][dof][dof] (the full symmetric matrix, mirrored from one triangle); each may be NULL, not all.  Changes nothing in
+ *   the problem.  _dev: device pointers, asynchronous on the context's stream.
+ * The closed-loop calls (ilqr_problem_closed_loop*) do NOT add the obstacle term: their costs stay the system's stage cost.  Executions are
+ *   scored with ilqr_clearance_trajectories. */
+int ilqr_problem_set_obstacles(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, double weight);
+int ilqr_problem_set_obstacles_dev(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, double weight);
+int ilqr_problem_obstacle_terms(ilqr_problem* p, double* cost, double* lx, double* lxx);
+int ilqr_problem_obstacle_terms_dev(ilqr_problem* p, double* cost, double* lx, double* lxx);
+
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];
  * any output may be NULL.  Host pointers. */
