@@ -47,6 +47,7 @@ EXPORTS = [
     "ilqr_problem_select", "ilqr_problem_select_dev", "ilqr_problem_get_at", "ilqr_problem_get_at_dev",
     "ilqr_problem_clearance", "ilqr_problem_clearance_dev", "ilqr_clearance_trajectories", "ilqr_clearance_trajectories_dev",
     "ilqr_problem_set_obstacles", "ilqr_problem_set_obstacles_dev", "ilqr_problem_obstacle_terms", "ilqr_problem_obstacle_terms_dev",
+    "ilqr_ctx_set_obstacle_path",
     "ilqr_lqt_create", "ilqr_lqt_destroy", "ilqr_lqt_set_targets", "ilqr_lqt_set_targets_dev", "ilqr_lqt_solve_dp", "ilqr_lqt_solve_lin_al",
     "ilqr_lqt_command", "ilqr_lqt_command_dev", "ilqr_lqt_get_U", "ilqr_lqt_get_U_dev", "ilqr_lqt_get_X", "ilqr_lqt_get_X_dev", "ilqr_lqt_get_P",
     "ilqr_lqt_get_d",
@@ -237,6 +238,7 @@ def load():
     L.ilqr_ctx_set_stream.argtypes = [vp, vp]
     L.ilqr_ctx_synchronize.argtypes = [vp]
     L.ilqr_ctx_set_split.argtypes = [vp, C.c_int]
+    L.ilqr_ctx_set_obstacle_path.argtypes = [vp, C.c_int]
     L.ilqr_ctx_set_crosscheck.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.ilqr_problem_create.argtypes = [vp, C.POINTER(ProblemDesc), C.c_int, C.POINTER(vp)]
     L.ilqr_problem_destroy.argtypes = [vp]
@@ -412,6 +414,7 @@ class Context:
         self.L = load()
         self.h = C.c_void_p()
         self._problems = weakref.WeakSet()
+        self.obstacle_path = 0  # what set_obstacle_path last set (the C side has no getter)
         rc = self.L.ilqr_ctx_create(device_id, C.byref(self.h))
         if rc:
             raise RuntimeError(f"ilqr_ctx_create failed (code {rc}): no usable HIP device {device_id}; there is no CPU fallback")
@@ -444,6 +447,19 @@ class Context:
         env = os.environ
         self.set_crosscheck(env.get("ILQR_HIP_PATH") == "v1", env.get("ILQR_CP_SOLVE") == "lane", env.get("ILQR_CP") == "general",
                             sweep=env.get("ILQR_SWEEP") or None, forward=env.get("ILQR_FWD") or None, reroll=env.get("ILQR_APPLY") or None)
+
+    OBSTACLE_PATHS = {"generic": 0, "cooperative": 1}  # ILQR_OBSTACLE_PATH_*
+
+    def set_obstacle_path(self, path):
+        """Kernel path of problems with obstacle terms (ilqr_ctx_set_obstacle_path): "generic" (the default) or "cooperative" (the cooperative
+        kernels of the single-integrator systems, where the plan supports them), or the constant's integer; context state of its own, in force
+        until changed -- set_crosscheck / crosscheck_from_env do not touch it.  Anything else is refused."""
+        if isinstance(path, str):
+            if path not in self.OBSTACLE_PATHS:
+                raise ValueError(f"set_obstacle_path: path must be one of {list(self.OBSTACLE_PATHS)} (got {path!r})")
+            path = self.OBSTACLE_PATHS[path]
+        self.check(self.L.ilqr_ctx_set_obstacle_path(self.h, int(path)))
+        self.obstacle_path = int(path)
 
     def set_split(self, mode: int):
         """Two-stream solve of large batches (ilqr_ctx_set_split): 0 off (one kernel at a time, for profiler runs), 1 where it was measured to pay

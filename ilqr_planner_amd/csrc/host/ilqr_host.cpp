@@ -1405,6 +1405,21 @@ static void set_obstacle_terms(ilqr_problem* p, const ClearanceInputs& c, int n,
     check(ilqr_problem_set_obstacles(p, &rb, &w, weight));
 }
 
+// BatchInputs::obstacle_path for the length of a call: the host classes' context is theirs alone, so the mode they last set is the mode it has
+// (the C side has no getter); the previous one is put back on every exit path.
+static int g_obstacle_path = ILQR_OBSTACLE_PATH_GENERIC;
+struct ObstaclePathScope {
+    ilqr_ctx* ctx;
+    int prev;
+    ObstaclePathScope(ilqr_ctx* c, int path) : ctx(c), prev(g_obstacle_path) {
+        check(ilqr_ctx_set_obstacle_path(ctx, path));
+        g_obstacle_path = path;
+    }
+    ~ObstaclePathScope() {
+        if (ilqr_ctx_set_obstacle_path(ctx, prev) == 0) g_obstacle_path = prev;
+    }
+};
+
 // Lower `s`, upload the per-instance inputs, run `solve`, read everything back.
 static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter, bool gains, const ilqr_problem_desc* override_desc,
                              const std::function<void(ilqr_problem*)>& pre_solve, const std::function<void(ilqr_problem*)>& solve,
@@ -1422,6 +1437,7 @@ static BatchResult run_batch(sys::System& s, const BatchInputs& in, int nb_iter,
     ilqr_ctx* ctx = device_context();
     const int B = in.B, T = d.horizon, dof = d.dof;
     if (B <= 0) throw std::runtime_error("[ilqr_hip] batch must be positive");
+    const ObstaclePathScope path_scope(ctx, in.obstacle_path);
     ProblemGuard g;
     check(ilqr_problem_create(ctx, &d, B, &g.p));
     auto tile = [&](const Vec& v, size_t per) {

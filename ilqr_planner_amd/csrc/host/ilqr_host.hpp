@@ -491,9 +491,10 @@ struct BatchInputs {
     double al_gains_penalty = 0;
     // ILQRRecursive and AL_ILQR: obstacle_weight > 0 with spheres given adds the obstacle terms to the stage cost (ilqr_problem_set_obstacles with
     // obstacles.margin as the activation distance): obstacles [n_sets][n_obs][4] with B % n_sets == 0, instance b reads set b / (B / n_sets).
-    // Such a solve runs on the generic kernels.  0 = off: the solve is exactly what it is without these fields.
+    // Such a solve runs on the generic kernels unless obstacle_path asks for the cooperative ones.  0 = off: the solve is exactly what it is without these fields.
     ClearanceInputs obstacles;
     double obstacle_weight = 0;
+    int obstacle_path = 0;   // ILQR_OBSTACLE_PATH_* for this call (solveBatch / solveMultiStart): set on the context before the solves, the previous mode restored after
 };
 
 // Multi-start (include/ilqr_hip.h "multi-start"): every task of a BatchInputs (in.B = G tasks) is solved from S starts on G * S instances --

@@ -151,6 +151,14 @@ static solver::BatchInputs obstacle_terms(solver::BatchInputs in, const py::obje
     return in;
 }
 
+// obstacle_path = "generic" | "cooperative" on solve_batch / solve_multistart: the kernel path of the call's obstacle terms (ILQR_OBSTACLE_PATH_*)
+static solver::BatchInputs obstacle_path(solver::BatchInputs in, const std::string& path, const char* fn) {
+    if (path == "generic") in.obstacle_path = 0;
+    else if (path == "cooperative") in.obstacle_path = 1;
+    else throw std::runtime_error(std::string("[") + fn + "] obstacle_path must be \"generic\" or \"cooperative\" (got \"" + path + "\")");
+    return in;
+}
+
 // solve_multistart(..., S, seed, sigma_u, coarse_iter): sigma_u None (0), a scalar or nb_ctrl_var values
 static solver::MultiStartInputs multistart_inputs(int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter, const py::object& spheres = py::none(),
                                                   const py::object& planes = py::none(), const py::object& obstacles = py::none(), double margin = 0.0,
@@ -492,23 +500,24 @@ PYBIND11_MODULE(PyLQR, m) {
         .def("solve", &solver::ILQRRecursive::solve, py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg,
-                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow) {
-                 return self.solveBatch(obstacle_terms(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), spheres, planes, obstacles, margin, ow), nb_iter, ls, es);
+                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow, const std::string& op) {
+                 return self.solveBatch(obstacle_path(obstacle_terms(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), spheres, planes, obstacles, margin, ow), op, "solve_batch"), nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
              py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("spheres") = py::none(), py::arg("planes") = py::none(),
-             py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0)
+             py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0, py::arg("obstacle_path") = "generic")
         // every task (the batch of U0 / q0 / kp_targets) from S starts: solve_batch's arguments, then the starts
         .def("solve_multistart",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter,
                 const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& spheres, const py::object& planes,
-                const py::object& obstacles, double margin, double ow) {
-                 return self.solveMultiStart(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow),
+                const py::object& obstacles, double margin, double ow, const std::string& op) {
+                 return self.solveMultiStart(obstacle_path(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), op, "solve_multistart"), multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow),
                                              nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(),
              py::arg("coarse_iter") = 1, py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
-             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0)
+             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0,
+             py::arg("obstacle_path") = "generic")
         .def("closed_loop_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
                 const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
@@ -534,25 +543,26 @@ PYBIND11_MODULE(PyLQR, m) {
         .def("solve_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
                 const py::object& kp, bool pg, const py::object& agp, const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin,
-                double ow) {
-                 return self.solveBatch(obstacle_terms(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), spheres, planes, obstacles, margin, ow), nb_iter, lag, pen,
+                double ow, const std::string& op) {
+                 return self.solveBatch(obstacle_path(obstacle_terms(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), spheres, planes, obstacles, margin, ow), op, "solve_batch"), nb_iter, lag, pen,
                                         sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
              py::arg("al_gains_penalty") = py::none(), py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(),
-             py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0)
+             py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0, py::arg("obstacle_path") = "generic")
         .def("solve_multistart",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, int S, unsigned long long seed,
                 const py::object& sigma_u, int coarse_iter, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& agp,
-                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow) {
-                 return self.solveMultiStart(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp),
+                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow, const std::string& op) {
+                 return self.solveMultiStart(obstacle_path(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), op, "solve_multistart"),
                                              multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(), py::arg("coarse_iter") = 1, py::arg("q0") = py::none(),
              py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("al_gains_penalty") = py::none(),
-             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0)
+             py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0,
+             py::arg("obstacle_path") = "generic")
         .def_static("final_penalty", &solver::AL_ILQR::finalPenalty, py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"))
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,

@@ -6,7 +6,8 @@
 // which mirrors ILQRRecursive::solve / AL_ILQR::solve (reference src/solver/ILQRRecursive.cpp:21-181,
 // src/solver/AL-ILQR.cpp:50-232).  No CPU fallback exists: every entry point fails loudly if HIP does.
 // The one exception to "host-side only": the small kernels that join instances (ilqr_multistart_kernels.hpp, included at the end) are compiled
-// with this file, for the reason given there; the clearance kernels (ilqr_clearance_kernels.hpp) likewise.
+// with this file, for the reason given there; the clearance kernels (ilqr_clearance_kernels.hpp) and those of the obstacle terms' cooperative path
+// (ilqr_obstacle_coop_kernels.hpp) likewise.
 #include "../../include/ilqr_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -77,10 +78,14 @@ struct ilqr_problem {
     DevScratch ms_idx;   // adopt / get_at / select through host pointers: the index (or the eligibility flags) as ints
     DevScratch ms_out;   // select / get_at through host pointers: best | winner, n_candidates and iters | status as ints
     // obstacle terms of the stage cost (ilqr_problem_set_obstacles): the geometry, the obstacle sets and the slots of k_obs_derivs are device
-    // memory of this problem; `obs` is what the kernels are given.  Problems with these terms run on the generic kernels (plan_input).
+    // memory of this problem; `obs` is what the kernels are given.  Problems with these terms run on the generic kernels unless the context's
+    // obstacle path sends them to the cooperative ones (plan_input).
     bool has_obs = false;
     ObsArgs obs = {};
     size_t obs_sets_bytes = 0;
+    // the cooperative path of these terms (RiccatiPlan::obs_dense), allocated at its first solve: l_x | l_xx of every stage (one kpd entry per
+    // step) and the obstacle cost of every (step, step size) of a line search
+    ObsDense obs_dense = {};
     bool u0_zero = false;  // the initial controls given from the host are all zero (lets the wide-basis batch solver skip their projection)
     BatchCPState cp;
     BatchWideState cpw;
@@ -188,6 +193,14 @@ extern "C" int ilqr_ctx_set_crosscheck(ilqr_ctx* c, int generic_kernels, int cp_
     c->xc_generic = generic_kernels != 0;
     c->xc_cp_lane = cp_lane_solve != 0;
     c->xc_cp_general = cp_general != 0;
+    return 0;
+}
+
+extern "C" int ilqr_ctx_set_obstacle_path(ilqr_ctx* c, int path) {
+    if (!c) return 1;
+    if (path != ILQR_OBSTACLE_PATH_GENERIC && path != ILQR_OBSTACLE_PATH_COOPERATIVE)
+        return fail(c, "ilqr_ctx_set_obstacle_path: path must be ILQR_OBSTACLE_PATH_GENERIC (0) or ILQR_OBSTACLE_PATH_COOPERATIVE (1) (got " + std::to_string(path) + ")");
+    c->obs_coop = path == ILQR_OBSTACLE_PATH_COOPERATIVE;
     return 0;
 }
 
@@ -479,7 +492,7 @@ extern "C" void ilqr_problem_destroy(ilqr_problem* p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
     for (void* q : p->allocs) (void)hipFree(q);
-    for (const void* q : {(const void*)p->obs.geom, (const void*)p->obs.obs, (const void*)p->obs.obd}) (void)hipFree((void*)q);
+    for (const void* q : {(const void*)p->obs.geom, (const void*)p->obs.obs, (const void*)p->obs.obd, (const void*)p->obs_dense.sd, (const void*)p->obs_dense.part}) (void)hipFree((void*)q);
     for (DevScratch* b : {&p->staging, &p->cl_kpx, &p->cl_rep, &p->cl_con_ws, &p->cl_cost, &p->cl_cov_ws, &p->cl_cov_kps, &p->ms_idx, &p->ms_out}) b->release();
     batchcp_free(p->cp);
     batchwide_free(p->cpw);
@@ -662,6 +675,7 @@ static PlanIn plan_input(const ilqr_problem* p, bool al, int nb_iter, int line_s
     in.limits2_set = p->desc.limits2_set != 0;
     in.shared_steps = has_shared_step(p->hdesc.steps);
     in.obstacles = p->has_obs;
+    in.obstacles_coop = c->obs_coop;
     in.uniform_R = true;
     for (int i = 1; i < p->dims.n_u; i++) in.uniform_R = in.uniform_R && (p->hdesc.R_diag[i] == p->hdesc.R_diag[0]);
     // the register-resident sweep addresses x, u and the multipliers with 32-bit byte offsets (ilqr_kernels_dpp.hip): batches whose arrays pass
@@ -734,9 +748,20 @@ static void launch_sweep(const ilqr_problem* p, const RiccatiPlan& pl, int h, bo
     }
 }
 // l_x, l_xx of the obstacle terms at every step of the current trajectory, where k_kp_derivs runs: before every sweep.  (A problem with these
-// terms is never split: plan_riccati keeps it on the generic kernels.)
-static void launch_obs_terms(const ilqr_problem* p, const Bufs& bf, int B, hipStream_t st) {
-    if (p->has_obs) launch_obs_derivs(bf, p->obs, B, p->T, p->dims.n_x, 0, st);
+// terms is never split: plan_riccati keeps it on the generic kernels or on its unsplit cooperative path.)  On the cooperative path
+// (RiccatiPlan::obs_dense) k_stage_dense then forms l_x | l_xx of every stage for k_backward_si_dpp<.., SW_DENSE>, behind k_kp_derivs.
+static void launch_obs_terms(const ilqr_problem* p, const RiccatiPlan& pl, const Bufs& bf, int B, hipStream_t st) {
+    if (!p->has_obs) return;
+    launch_obs_derivs(bf, p->obs, B, p->T, p->dims.n_x, 0, st);
+    if (pl.obs_dense) launch_stage_dense(bf, p->obs, p->obs_dense.sd, B, p->T, 0, st);
+}
+// The buffers of the cooperative path, at its first use; freed with the problem
+static int ensure_obs_dense(ilqr_problem* p) {
+    ilqr_ctx* c = p->ctx;
+    const int N = p->dims.n_x;
+    if (!p->obs_dense.sd) HIPCHK(c, hipMalloc((void**)&p->obs_dense.sd, sizeof(double) * (size_t)p->T * (size_t)(N + N * N) * (size_t)p->Bp));
+    if (!p->obs_dense.part) HIPCHK(c, hipMalloc((void**)&p->obs_dense.part, sizeof(double) * (size_t)p->T * OBS_LS_ROWS * (size_t)p->Bp));
+    return 0;
 }
 
 static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double penalty0, double scaling, int line_search, int early_stop) {
@@ -754,6 +779,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     if (pl.kd_sym != KD_SYM_KEEP) p->bufs.kd_sym = pl.kd_sym;  // before half_bufs: it sizes the half's offset into KD
     if (pl.needs_ws && !p->bufs.ws)
         if (dalloc(p, &p->bufs.ws, (size_t)backward_ws_entries(kind, nd) * p->Bp, false)) return 1;
+    if (pl.obs_dense && ensure_obs_dense(p)) return 1;
 
     Half hv[2];
     int nh = 1;
@@ -761,11 +787,13 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     SplitJoin split_join{c, pl.split};  // on every exit path
     FwdArgs f = plan_fwd_args(p, pl);
     f.line_search = line_search; f.early_stop = early_stop; f.nb_iter = nb_iter; f.penalty_roll = penalty0; f.al = al ? 1 : 0;
+    if (pl.obs_dense) { f.obs = &p->obs; f.obs_part = p->obs_dense.part; f.obs_T = T; }  // launch_forward_wave: the obstacle cost of every step size
     for (int h = 0; h < nh; h++) {
         const Bufs& bf = hv[h].bufs;
         ProfScope ps(c, ILQR_PROF_ROLLOUT);
         if (pl.init == Init::Lti) launch_init_lti(kind, nd, bf, hv[h].B, hv[h].st);
         else launch_init(kind, nd, al, bf, hv[h].B, hv[h].st, penalty0, p->has_obs ? &p->obs : nullptr);
+        if (pl.obs_dense) launch_obs_ls(bf, p->obs, p->obs_dense.part, hv[h].B, T, p->dims.n_x, 1, 1, hv[h].st);  // the initial trajectory's obstacle cost joins cost, behind k_init_finish
         if (pl.init_al_update) {  // active-set weights of the initial trajectory: I_k = penalty * (g<0 && lambda==0 ? 0 : 1)
             f.it = -1; f.do_update = 0;
             launch_al_update(kind, nd, bf, hv[h].B, T, hv[h].st, f);
@@ -775,6 +803,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
     double penalty = penalty0;
     SweepArgs sw;
     sw.pen_in = penalty; sw.pen_update_prev = penalty; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0; sw.si_prep = 0;
+    sw.sd = pl.obs_dense ? p->obs_dense.sd : nullptr;
     for (int it = 0; it < nb_iter; it++) {
         FwdArgs fi = f;
         fi.it = it;
@@ -790,7 +819,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
             {   // l_x, l_xx at the keypoint steps (FK, log map, J'QJ) for every sweep: none of them holds keypoint code
                 ProfScope ps(c, ILQR_PROF_OTHER);
                 launch_kp_derivs(kind, nd, bf, B, st, fi);
-                launch_obs_terms(p, bf, B, st);
+                launch_obs_terms(p, pl, bf, B, st);
             }
             {
                 ProfScope ps(c, ILQR_PROF_BACKWARD);
@@ -917,6 +946,7 @@ static int gains_about_plan(ilqr_problem* p, bool al, double penalty) {
     p->bufs.kd_sym = pl.kd_sym;  // before half_bufs: it sizes the half's offset into KD
     if (pl.needs_ws && !p->bufs.ws)
         if (dalloc(p, &p->bufs.ws, (size_t)backward_ws_entries(kind, nd) * p->Bp, false)) return 1;
+    if (pl.obs_dense && ensure_obs_dense(p)) return 1;
     Half hv[2];
     int nh = 1;
     if (split_begin(p, pl.split, hv, nh)) return 1;
@@ -924,6 +954,7 @@ static int gains_about_plan(ilqr_problem* p, bool al, double penalty) {
     const FwdArgs f = plan_fwd_args(p, pl);
     SweepArgs sw;
     sw.pen_in = penalty; sw.pen_update_prev = penalty; sw.do_update_prev = 0; sw.si_wg = 0; sw.si_io = 0; sw.si_prep = 0;
+    sw.sd = pl.obs_dense ? p->obs_dense.sd : nullptr;
     for (int h = 0; h < nh; h++) {
         const Bufs& bf = hv[h].bufs;
         const int B = hv[h].B;
@@ -939,7 +970,7 @@ static int gains_about_plan(ilqr_problem* p, bool al, double penalty) {
         {
             ProfScope ps(c, ILQR_PROF_OTHER);
             launch_kp_derivs(kind, nd, bf, B, st, f);
-            launch_obs_terms(p, bf, B, st);
+            launch_obs_terms(p, pl, bf, B, st);
         }
         {
             ProfScope ps(c, ILQR_PROF_BACKWARD);
@@ -2038,3 +2069,6 @@ extern "C" int ilqr_fk_batch(ilqr_ctx* c, const ilqr_problem_desc* d, int n, con
 // the clearance kernels (per state, fold, stats) and their launchers: likewise
 #define ILQR_CLEARANCE_KERNELS_TU
 #include "ilqr_clearance_kernels.hpp"
+
+// the lane-per-item kernels of the obstacle terms' cooperative path (k_stage_dense, k_obs_ls, k_obs_ls_sum) and their launchers: likewise
+#include "ilqr_obstacle_coop_kernels.hpp"

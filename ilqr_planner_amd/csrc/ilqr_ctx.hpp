@@ -30,6 +30,7 @@ struct ilqr_ctx {
     // split solves (solve_riccati): the two halves of a batch run on their own streams, joined to `stream` by events
     int n_simd = 1024;  // SIMDs of the device (4 per CU)
     bool xc_generic = false, xc_cp_lane = false, xc_cp_general = false;  // cross-check kernel variants (ilqr_ctx_set_crosscheck)
+    bool obs_coop = false;  // ilqr_ctx_set_obstacle_path: problems with obstacle terms may take the cooperative kernels (state of its own: no pin touches it)
     ilqr::SweepPin xc_sweep = ilqr::SweepPin::Auto;      // variant pins (ILQR_XC_*): sweep of the 2nd-order / time systems,
     ilqr::FwdPin xc_forward = ilqr::FwdPin::Auto;        // forward pass of the single-integrator systems,
     ilqr::RerollPin xc_reroll = ilqr::RerollPin::Auto;   // re-roll of the line-search winner on the time systems

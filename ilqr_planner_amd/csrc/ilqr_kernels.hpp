@@ -73,6 +73,12 @@ struct FwdArgs {
     int fused;    // the acceptance of the line search is applied by the next sweep (k_backward_si_dpp<.., true>): until then the accepted
                   // trajectory of an instance with pend > 0 is xbar + alpha (x(1) - xbar) over its two buffers
     int fwd_lds;  // Forward::WaveWg runs its predecessor k_forward_wg (the pin ILQR_XC_FWD_WG_LDS) instead of k_forward_reg: same bits
+    // RiccatiPlan::obs_dense (null otherwise).  Read by launch_forward_wave alone, on the host, never by a kernel: between the rollout and k_select it
+    // runs launch_obs_ls, which adds the obstacle cost of every step size to Bufs::lsc.  obs: the problem's terms; obs_part: [T][16][Bp] scratch;
+    // obs_T: the horizon (the descriptor is device memory).
+    const ObsArgs* obs;
+    double* obs_part;
+    int obs_T;
 };
 
 // Fused acceptance in the cooperative sweep: what k_apply would have used at the end of the PREVIOUS iteration
@@ -83,6 +89,7 @@ struct SweepArgs {
     int si_wg;               // k_backward_si_dpp in its workgroup form (RiccatiPlan::si_wg of the launched half): same bits
     int si_io;               // ... with the I/O wave (RiccatiPlan::si_io of the launched half): same bits
     int si_prep;             // ... and the two preparing waves (RiccatiPlan::si_prep of the launched half): same bits
+    const double* sd;        // RiccatiPlan::obs_dense: l_x | l_xx of EVERY step, [T][N + N N][Bp] (k_stage_dense) -> k_backward_si_dpp<.., SW_DENSE>; null otherwise
 };
 
 // Launchers of one Riccati iteration; which of them run is decided by plan_riccati (ilqr_plan.hpp).

@@ -228,16 +228,25 @@ __device__ __forceinline__ int wait_consumed(int seen, unsigned addr, int need) 
     return __builtin_amdgcn_readfirstlane(cons < need ? 1 : 0);  // (uniform by construction; the compiler takes asm results for divergent)
 }
 }  // namespace
+// DENSE (IO = SW_DENSE; lone waves, not fused: a problem with obstacle terms on the cooperative path, RiccatiPlan::obs_dense): EVERY step is a precomputed step.  l_x | l_xx
+// of step k come from sw.sd[k] (k_stage_dense: the keypoint entry or the limit terms, plus the obstacle terms), in the element layout of a kpd entry;
+// the keypoint and limit branches are never taken, the AL terms follow as they do otherwise.  The lane's eight doubles of a step (its row of l_xx and
+// its component of l_x) ride in the same PF-steps-ahead ring as x, u and the multipliers: taken out at the top of the step, the slot's next loads
+// issued right behind, so the chain never waits for a load issued in the same step.  64-bit addresses (sd is four times the size of X | U).
+// The flag is bit 3 of IO (SW_DENSE), so that every other instantiation keeps its name: IOW below is what IO was.
 template <int LPI, int MR, bool FUSED, bool UNIF, bool WG = false, int IO = 0>
-__global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP : 0)) * 64 : 64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
+__global__ __launch_bounds__(WG ? (SW_WAVES + ((IO & 7) ? 1 : 0) + ((IO & 4) ? SW_PREP : 0)) * 64 : 64) void k_backward_si_dpp(Bufs a, SweepArgs sw) {
+    constexpr int IOW = IO & 7;              // the I/O wave's stages
+    constexpr bool DENSE = (IO & 8) != 0;    // SW_DENSE
     constexpr int N = 7, IPW = 64 / LPI;
+    static_assert(!DENSE || (!FUSED && !WG && IOW == 0), "the dense form: lone waves, the accepted trajectory in memory");
     constexpr int NWV = WG ? SW_WAVES : 1;
-    constexpr bool IOK = (IO & 1) != 0, IOX = (IO & 2) != 0;  // the I/O wave sends the gain records / stores the accepted x, u
-    constexpr bool PRP = (IO & 4) != 0;                       // two preparing waves hand the chain waves what a step needs of x, u and the multipliers
+    constexpr bool IOK = (IOW & 1) != 0, IOX = (IOW & 2) != 0;  // the I/O wave sends the gain records / stores the accepted x, u
+    constexpr bool PRP = (IOW & 4) != 0;                       // two preparing waves hand the chain waves what a step needs of x, u and the multipliers
     constexpr int NIMG = IOK ? SW_RING : 2, XRING = SW_RING, XROW = 18;
     static_assert(!PRP || (IOK && IOX && FUSED && SW_PRING == XRING && SW_WAVES * (64 / LPI) == 8 * SW_PREP), "the preparing waves: on top of the full I/O wave, one x | u slot per prepared slot");
     static_assert(!WG || (LPI == 16 && FUSED), "the workgroup form: 4 instances per wave, 16 per workgroup = one 128-byte line per row segment");
-    static_assert(!IO || (WG && MR <= 1), "the I/O wave: workgroup form, at most one constraint row (256 VGPRs at two waves on a SIMD)");
+    static_assert(!IOW || (WG && MR <= 1), "the I/O wave: workgroup form, at most one constraint row (256 VGPRs at two waves on a SIMD)");
     constexpr int MRR = MR > 0 ? MR : 1;
     constexpr int ROWP = kd_rowp(N), RS = UNIF ? KD_SYM_RS : N * ROWP;  // uniform R: K is symmetric, the record holds its upper triangle (ilqr_kernels.hpp)
     static_assert(ROWP == 8, "a gain row is the lane's eight doubles {K_r0..K_r6, d_r}");
@@ -249,7 +258,7 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
     __shared__ double sXU[IOX ? XRING : 1][IOX ? 2 * N + 1 : 1][IOX ? XROW : 1];
     // PRP: what the chain waves consume of a step, [slot][instance of the workgroup x 8 + row][u, lim, lx of the limits, I_k, lam + I_k g, beyond]
     __shared__ __attribute__((aligned(16))) double sPr[PRP ? SW_PRING : 1][PRP ? 8 * SW_WAVES * (64 / LPI) : 1][PRP ? SW_PENT : 2];
-    __shared__ int sFl[IO ? NWV + 1 + (PRP ? SW_PREP : 0) : 1];  // produced (per chain wave), consumed, prepared (per preparing wave)
+    __shared__ int sFl[IOW ? NWV + 1 + (PRP ? SW_PREP : 0) : 1];  // produced (per chain wave), consumed, prepared (per preparing wave)
     const DevDesc& d = *a.desc;
     const int wv = WG ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0;
     double (*const sK)[IMG + 64] = sKw[wv < NWV ? wv : 0];
@@ -263,7 +272,7 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
     const int bb = (b < d.B) ? b : 0;    // clamp so that every address stays valid; stores are guarded
     const int pendw = (FUSED && b < d.B) ? a.pend[bb] : 0;
     const bool acc = pendw > 0;
-    if (IO) {
+    if (IOW) {
         constexpr int RS_ = UNIF ? KD_SYM_RS : N * kd_rowp(N), PCS_ = RS_ / 2, NPQ2 = (IPW * PCS_ + 63) / 64;
         if (wv == NWV) {  // ---- the I/O wave: lane j looks at instance j mod 16 of the workgroup
             const int bi = xcd_tile() * (NWV * IPW) + (lane & 15);
@@ -518,7 +527,13 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
             xv = fma(aacc, x1 - xv, xv);
             if (wr) stg(Xb, oB + Vstep, xv);
         }
-        if (kp_next == T - 1) {
+        if (DENSE) {
+            const double* src = sw.sd + (size_t)(T - 1) * kpd_stride;
+            if (isV) {
+                UNR for (int j = 0; j < N; j++) P[j] = AT(src, N + v * N + j, bb);
+                p = AT(src, v, bb);
+            }
+        } else if (kp_next == T - 1) {
             const double* src = a.kpd + (size_t)kpi * kpd_stride;
             if (isV) {
                 UNR for (int j = 0; j < N; j++) P[j] = AT(src, N + v * N + j, bb);
@@ -539,6 +554,11 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
     // PF-steps-ahead prefetch ring (vmcnt retires in issue order: a load issued one step ahead would wait for the previous step's stores)
     constexpr int PF = 4;
     double xr[PF], ur[PF], x1r[PF], u1r[PF], lr[PF][MRR], ir[PF][MRR];
+    constexpr int ND = DENSE ? N + 1 : 1;
+    double dr[PF][ND];  // DENSE: the lane's row of l_xx and its component of l_x
+    const size_t sd_row = (size_t)Bp;
+    const double* sdm = DENSE ? sw.sd + (size_t)(T - 2) * kpd_stride + (size_t)(N + v * N) * Bp + bb : nullptr;  // row v of l_xx of the step being loaded
+    const double* sdx = DENSE ? sw.sd + (size_t)(T - 2) * kpd_stride + (size_t)v * Bp + bb : nullptr;            // component v of l_x
     unsigned rofs[MRR];
     UNR for (int rr = 0; rr < MRR; rr++) rofs[rr] = (unsigned)((MR > 0 && rr < m) ? rr : 0) * Bp * 8u;
     auto fetch = [&](int slot, int kk) {  // loads of timestep max(kk, 0) into ring slot; every load unconditional (a CFG path that skips
@@ -550,6 +570,11 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
             lr[slot][rr] = ir[slot][rr] = 0;
             if (MR > 0) { lr[slot][rr] = ldg(a.lambda, oL + rofs[rr]); if (!FUSED) ir[slot][rr] = ldg(a.Is, oL + rofs[rr]); }
         }
+        if (DENSE) {
+            UNR for (int j = 0; j < N; j++) dr[slot][j] = sdm[(size_t)j * sd_row];
+            dr[slot][ND - 1] = sdx[0];
+            if (kk > 0) { sdm -= kpd_stride; sdx -= kpd_stride; }
+        }
         if (kk > 0) { oA -= Vstep; oB -= Vstep; oL -= Lstep; }  // uniform; no load inside the branch
     };
     if (!PRP) { UNR for (int q = 0; q < PF; q++) { fetch(q, T - 2 - q); __builtin_amdgcn_sched_barrier(0); } }
@@ -558,7 +583,7 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
     unsigned oLw = ((unsigned)(T - 2) * m * Bp + bb) * 8u;
 
     static_assert(SW_RING % PF == 0, "a step's slot is the group's first slot + its place in the group");
-    const unsigned fl_cons = lds_addr(&sFl[IO ? NWV : 0]);
+    const unsigned fl_cons = lds_addr(&sFl[IOW ? NWV : 0]);
     const int fl_pi = PRP ? NWV + 1 + wv / (SW_WAVES / SW_PREP) : 0;  // PRP: the wave's preparing wave
     const unsigned fl_prep = lds_addr(&sFl[fl_pi]);
     const int pent = (wv * IPW + g) * 8 + r;                             // PRP: the lane's entry of a prepared slot (both halves of an instance read the same)
@@ -580,12 +605,15 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
             lam[rr] = (MR > 0 && !PRP) ? ring_take(lr[jj][rr]) : 0.0;
             Isk[rr] = PRP ? 0.0 : (MR > 0 && !FUSED) ? ring_take(ir[jj][rr]) : ir[jj][rr];
         }
+        double dlxx[N], dlx = 0;
+        UNR for (int j = 0; j < N; j++) dlxx[j] = DENSE ? ring_take(dr[jj][j]) : 0.0;
+        if (DENSE) dlx = ring_take(dr[jj][ND - 1]);
         if (!PRP) {
             __builtin_amdgcn_sched_barrier(0);  // the slots are free: only now their next loads
             fetch(jj, k - PF);
         }
         const int prepared = (PRP && jj == 0) ? flag_read(&sFl[fl_pi]) : 0;       // read here, needed behind the pivots
-        const int consumed = (IO && jj == 0) ? flag_read(&sFl[IO ? NWV : 0]) : 0;  // read here, needed at the step's end
+        const int consumed = (IOW && jj == 0) ? flag_read(&sFl[IOW ? NWV : 0]) : 0;  // read here, needed at the step's end
         // the image of the step before this one (in time) leaves now: LDS -> registers here, registers -> memory after the pivots
         const bool kprev = k < T - 2;
         double kqa[NPQ], kqb[NPQ];  // (two arrays of doubles: an array of double2 -- or anything a lambda captures by reference -- goes to scratch)
@@ -661,7 +689,7 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
         // doubled the launch (measured: 381 -> 194 us at B = 8192 with these stores removed).  The rows go into a wave-local LDS image of
         // the wave's records as they lie in memory; the image leaves during the NEXT step as 16-byte pieces of whole lines (1 KiB
         // contiguous per instruction), so neither the LDS round trip nor the stores sit on this step's chain.
-        if (IO && jj == 0) {  // once per group of PF steps n .. n + PF - 1 (n = T - 1 - k), behind the x | u write of step n and ahead of every other
+        if (IOW && jj == 0) {  // once per group of PF steps n .. n + PF - 1 (n = T - 1 - k), behind the x | u write of step n and ahead of every other
             // write of the group and of the x | u write of step n + PF, which opens the next group ahead of that group's check: the last of these
             // slots, step n + PF's, is free once step n + PF - SW_RING is consumed (the x | u slot of step n itself was covered by the check of
             // the group before, or is the ring's first use).
@@ -681,12 +709,14 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
             w[2] = make_double2(Kr[4], Kr[5]);
             w[3] = make_double2(Kr[6], dv);
         }
-        if (IO) flag_write(&sFl[wv], T - 1 - k);  // produced: after the data it announces
+        if (IOW) flag_write(&sFl[wv], T - 1 - k);  // produced: after the data it announces
         Kout -= Kstep;
         // ---- stage derivatives l_xx (row r), l_x (component r), accumulated onto -D N / dt^2
         double Pn[N], lx = 0;
         UNR for (int j = 0; j < N; j++) Pn[j] = -cDN * Nn[j];
-        if (k == kp_next) {  // uniform: keypoint step, precomputed by k_kp_derivs (incl. limits)
+        if (DENSE) {  // every step precomputed (k_stage_dense); the loads were consumed at the top of the step
+            if (isV) { UNR for (int j = 0; j < N; j++) Pn[j] += dlxx[j]; lx = dlx; }
+        } else if (k == kp_next) {  // uniform: keypoint step, precomputed by k_kp_derivs (incl. limits)
             const double* src = a.kpd + (size_t)kpi * kpd_stride;
             double lxx[N];
             UNR for (int j = 0; j < N; j++) lxx[j] = AT(src, N + v * N + j, bb);
@@ -739,9 +769,9 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
         p = lx + p - (Qu + Dv * dv) * idt - reg * (Dv * Md - dv) * idt;
         if (FUSED && MR > 0) oLw -= Lstep;
       }
-      if (IO) k0 = gave_up ? 0 : k0;  // (a select on the loop counter, no branch: the loop ends here)
+      if (IOW) k0 = gave_up ? 0 : k0;  // (a select on the loop counter, no branch: the loop ends here)
     }
-    if (IO && gave_up) {  // the I/O wave is gone: the wave's instances are out of the solve, whatever was stored for them
+    if (IOW && gave_up) {  // the I/O wave is gone: the wave's instances are out of the solve, whatever was stored for them
         if (l == 0 && b < d.B) { a.active[bb] = 0; atomicOr(&a.status[bb], ILQR_STATUS_SWEEP_IO); }
         return;
     }
@@ -756,16 +786,23 @@ __global__ __launch_bounds__(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP
 
 constexpr int SW_IO = 3;  // what the I/O wave carries: the gain records and the accepted x, u (the stages that were measured: profiles/sweep_io_variations.txt)
 constexpr int SW_IO_PREP = SW_IO | 4;  // ... with the two preparing waves
+constexpr int SW_DENSE = 8;            // the dense form (no I/O wave): every step's l_x | l_xx from SweepArgs::sd
 template <int LPI, bool FUSED, bool UNIF, bool WG = false, int IO = 0>
 static void launch_dpp2(bool al, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
     constexpr int IWG = (WG ? SW_WAVES : 1) * (64 / LPI);  // instances per workgroup
-    const dim3 grid(grid_x8((B + IWG - 1) / IWG)), block(WG ? (SW_WAVES + (IO ? 1 : 0) + ((IO & 4) ? SW_PREP : 0)) * 64 : 64);
+    const dim3 grid(grid_x8((B + IWG - 1) / IWG)), block(WG ? (SW_WAVES + ((IO & 7) ? 1 : 0) + ((IO & 4) ? SW_PREP : 0)) * 64 : 64);
     if (!al || a.m == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 0, FUSED, UNIF, WG, IO>), grid, block, 0, st, a, sw);
     else if (a.m <= 1) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 1, FUSED, UNIF, WG, IO>), grid, block, 0, st, a, sw);
-    else if constexpr (IO == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 4, FUSED, UNIF, WG>), grid, block, 0, st, a, sw);
+    else if constexpr ((IO & 7) == 0) hipLaunchKernelGGL((k_backward_si_dpp<LPI, 4, FUSED, UNIF, WG, IO>), grid, block, 0, st, a, sw);
 }
 
+// The dense instantiations live in a translation unit of their own (ilqr_kernels_dpp_dense.hip, which includes this file with
+// ILQR_DPP_DENSE_TU defined): with them in this unit's code object every existing kernel moved by 0x4900 bytes, and the C3 bench line follows
+// the placement of its kernels (ilqr_multistart_kernels.hpp).  This unit's kernels are the parent's, where the parent had them.
+void launch_dpp_dense(bool al, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw);
+#ifndef ILQR_DPP_DENSE_TU
 void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
+    if (sw.sd && !fused) return launch_dpp_dense(al, uniform_R, lpi, a, B, st, sw);
     if (lpi == 16 && fused && sw.si_wg && sw.si_io && sw.si_prep && (!al || a.m <= 1)) {  // ... with the I/O wave and the preparing waves (RiccatiPlan::si_prep)
         if (uniform_R) launch_dpp2<16, true, true, true, SW_IO_PREP>(al, a, B, st, sw); else launch_dpp2<16, true, false, true, SW_IO_PREP>(al, a, B, st, sw);
     } else if (lpi == 16 && fused && sw.si_wg && sw.si_io && (!al || a.m <= 1)) {  // ... with the I/O wave (RiccatiPlan::si_io): at most one constraint row
@@ -780,5 +817,13 @@ void launch_backward_si_dpp(bool al, bool fused, bool uniform_R, int lpi, const 
         else { if (uniform_R) launch_dpp2<8, false, true>(al, a, B, st, sw); else launch_dpp2<8, false, false>(al, a, B, st, sw); }
     }
 }
+
+#else
+// the dense form (RiccatiPlan::obs_dense): lone waves, either grouping
+void launch_dpp_dense(bool al, bool uniform_R, int lpi, const Bufs& a, int B, hipStream_t st, const SweepArgs& sw) {
+    if (lpi == 16) { if (uniform_R) launch_dpp2<16, false, true, false, SW_DENSE>(al, a, B, st, sw); else launch_dpp2<16, false, false, false, SW_DENSE>(al, a, B, st, sw); }
+    else { if (uniform_R) launch_dpp2<8, false, true, false, SW_DENSE>(al, a, B, st, sw); else launch_dpp2<8, false, false, false, SW_DENSE>(al, a, B, st, sw); }
+}
+#endif
 
 }  // namespace ilqr

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "ilqr_lanes.hpp"
+#include "ilqr_obstacle.hpp"
 #include "ilqr_plan.hpp"
 #include "ilqr_step.hpp"
 
@@ -975,20 +976,25 @@ static void launch_forward_wave_sys(bool small, const Bufs& a, int B, hipStream_
     const dim3 grid(grid_x8((B + FW_IW - 1) / FW_IW)), block(FW_IW * 32);  // k_forward_wg: 16 instances per workgroup
     const dim3 rgrid(grid_x8((B + 4 * FR_WAVES - 1) / (4 * FR_WAVES)));    // large batches: k_forward_reg, or k_forward_wg under its pin (f.fwd_lds)
     const dim3 sgrid(grid_x8((B + 3) / 4));  // small batches: 16 lanes per instance, one wave per workgroup (k_forward_dpp)
+    // RiccatiPlan::obs_dense: the obstacle cost of every step size joins lsc between the rollout and the decision (ilqr_obstacle.hpp)
+    const auto obs_ls = [&]() { if (f.obs) launch_obs_ls(a, *f.obs, f.obs_part, B, f.obs_T, S::NX, f.n_alpha, 0, st); };
     if (f.n_alpha <= 1) {
         if (small) launch_forward_dpp<1>(a, sgrid, st, f);
         else if (f.fwd_lds) hipLaunchKernelGGL((k_forward_wg<1>), grid, block, 0, st, a, f);
         else launch_forward_reg(a, rgrid, st, f);
+        obs_ls();
         launch_select<S, 1>(a, B, st, f);
     } else if (f.n_alpha <= 11) {
         if (small) launch_forward_dpp<11>(a, sgrid, st, f);
         else if (f.fwd_lds) hipLaunchKernelGGL((k_forward_wg<11>), grid, block, 0, st, a, f);
         else launch_forward_reg(a, rgrid, st, f);
+        obs_ls();
         launch_select<S, 11>(a, B, st, f);
     } else {
         if (small) launch_forward_dpp<16>(a, sgrid, st, f);
         else if (f.fwd_lds) hipLaunchKernelGGL((k_forward_wg<16>), grid, block, 0, st, a, f);
         else launch_forward_reg(a, rgrid, st, f);
+        obs_ls();
         launch_select<S, 16>(a, B, st, f);
     }
 }

@@ -1,6 +1,8 @@
 // ilqr_obstacle.hpp -- the sphere-obstacle terms of the stage cost (include/ilqr_hip.h "obstacle terms"): the per-state function, the argument
 // block of the kernels that call it and their launchers.  The kernels themselves are in ilqr_kernels.hip (k_obs_derivs, k_obs_query, and the OBS
-// forms of the generic k_init_rollout / k_backward / k_forward); no cooperative kernel knows these terms (ilqr_plan.hpp: PlanIn::obstacles).
+// forms of the generic k_init_rollout / k_backward / k_forward, and, compiled with ilqr_capi.cpp, k_stage_dense, k_obs_ls, k_obs_ls_sum of the
+// cooperative path: ilqr_obstacle_coop_kernels.hpp); of the cooperative kernels only k_backward_si_dpp<.., SW_DENSE> takes them, as precomputed stage derivatives (ilqr_plan.hpp:
+// PlanIn::obstacles_coop).
 //
 //   obs_state<WITH_DERIVS>   THE per-state function: clr_state's walk (ilqr_clearance_kernels.hpp: the segments as they are, the spheres by a
 //                            cursor, a joint position loaded through a functor when the walk reaches its joint), with the hinge on every pair in
@@ -147,5 +149,22 @@ __device__ __forceinline__ double obs_state(const ClrGeom& g, const double* __re
 void launch_obs_derivs(const Bufs& a, const ObsArgs& o, int B, int T, int nx, int all, hipStream_t st);
 // k_obs_query: obd -> cost[B][T], lx[B][T][dof], lxx[B][T][dof][dof] (each may be null)
 void launch_obs_query(const ObsArgs& o, int B, int Bp, int T, int dof, double* cost, double* lx, double* lxx, hipStream_t st);
+
+// ---- the cooperative path of the single-integrator systems (RiccatiPlan::obs_dense; a device state is the 7 joint positions)
+// Device memory the problem owns, allocated at the first solve on this path.
+constexpr int OBS_LS_ROWS = 16;   // step sizes a line search of this path can hold (forward_wave_supported)
+struct ObsDense {
+    double* sd;     // [T][7 + 49][Bp]: l_x | l_xx (by rows) of every stage of the current trajectory, the element layout of one entry of Bufs::kpd
+    double* part;   // [T][OBS_LS_ROWS][Bp]: c_obs of step k at step size index i of the line search in flight (k_obs_ls -> k_obs_ls_sum)
+};
+// k_stage_dense: sd[k] of every step of every instance the sweep visits (all = 0: the active ones), behind launch_kp_derivs and launch_obs_derivs.
+// One fixed order per entry: base + obstacle term, where base is the entry of kpd at a keypoint step (limits already in it) and the limit terms
+// (inspectJointLimit, the expressions of k_backward_si_dpp) at any other step, and the obstacle term is obd[k] with l_xx mirrored from its triangle.
+void launch_stage_dense(const Bufs& a, const ObsArgs& o, double* sd, int B, int T, int all, hipStream_t st);
+// k_obs_ls + k_obs_ls_sum.  init = 0, between the rollout of a line search and k_select: c_obs at x(alpha)_k for every step k and every step size
+// index i < n_alpha of the active instances, x(alpha) = x(1) at i = 0 and fma(2^-i, x(1) - xbar, xbar) beyond (k_apply's expression; xbar = X[cur],
+// x(1) = X[1 - cur]); then Bufs::lsc[i][b] += sum over k ascending, one lane per (instance, i): the order depends on T alone.
+// init = 1, behind k_init_finish: one step size at xbar; cost[b] += that sum and status[b] is formed again from the cost.
+void launch_obs_ls(const Bufs& a, const ObsArgs& o, double* part, int B, int T, int nx, int n_alpha, int init, hipStream_t st);
 
 }  // namespace ilqr

@@ -31,6 +31,12 @@ constexpr bool init_lti_supported(int kind, int nd) {
     return ((kind == 0 || kind == 1) && (nd == 1 || nd == 2)) || ((kind == 2 || kind == 3) && nd == 1);
 }
 
+// The dense cooperative path of a problem with obstacle terms (RiccatiPlan::obs_dense): the single-integrator systems, every stage's l_x, l_xx
+// precomputed (k_stage_dense), k_backward_si_dpp<.., SW_DENSE> on lone waves, the wave rollouts with the per-step-size obstacle cost (k_obs_ls).
+constexpr bool obs_coop_supported(int kind, int nd, bool al, int m, int per_step, bool con_state_only, int n_alpha) {
+    return backward_si_supported(kind, nd, al, m, per_step, con_state_only) && forward_wave_supported(kind, nd, n_alpha);
+}
+
 // number of step sizes the do/while of ILQRRecursive.cpp:101-155 can reach: 1, 1/2, ... until alpha <= alpha_floor
 inline int n_alpha_of(bool line_search, double alpha_floor) {
     int n = 1;
@@ -80,7 +86,8 @@ struct PlanIn {
     bool con_state_only = false;   // no constraint row touches the controls
     bool limits2_set = false;      // a second limit set (generic kernels only)
     bool shared_steps = false;     // keypoints that share a timestep (generic kernels only: the cooperative kernels hold one keypoint per step)
-    bool obstacles = false;        // obstacle terms in the stage cost (generic kernels only: ilqr_obstacle.hpp)
+    bool obstacles = false;        // obstacle terms in the stage cost (generic kernels unless obstacles_coop: ilqr_obstacle.hpp)
+    bool obstacles_coop = false;   // ilqr_ctx_set_obstacle_path(COOPERATIVE): such a problem may take the dense cooperative path (obs_coop_supported)
     bool uniform_R = false;        // all control weights equal
     bool off32 = true;             // x, u and the multipliers are addressable with 32-bit byte offsets (k_backward_si_dpp)
     bool line_search = true;
@@ -126,12 +133,31 @@ struct RiccatiPlan {
     int kd_sym = 0;               // layout the sweep writes: 1 packed symmetric (KD_SYM_RS), 0 plain, or KD_SYM_KEEP
     bool split = false;           // two halves on two streams
     bool needs_ws = false;        // the generic sweep keeps the matrices of a step in an explicit workspace
+    bool obs_dense = false;       // obstacle terms on the cooperative kernels: dense stage derivatives (k_stage_dense) into k_backward_si_dpp<.., SW_DENSE>,
+                                  // the obstacle cost of every step size (k_obs_ls) between the rollout and k_select, the accepted trajectory in memory
 };
 
 inline RiccatiPlan plan_riccati(const PlanIn& in) {
     RiccatiPlan p;
     const int kind = in.kind, nd = in.nd;
     p.n_alpha = n_alpha_of(in.line_search, in.alpha_floor);
+    // Obstacle terms on the cooperative kernels (opt-in; the generic pin wins): not fused -- the accepted trajectory is in memory before the
+    // derivative kernels read it (Apply::Wave) -- and on lone waves, since the workgroup, I/O-wave and preparing-wave forms are all fused.
+    if (in.obstacles && in.obstacles_coop && !in.generic && !in.limits2_set && !in.shared_steps && in.off32 &&
+        obs_coop_supported(kind, nd, in.al, in.m, in.per_step, in.con_state_only, p.n_alpha)) {
+        p.obs_dense = true;
+        p.init = Init::Lti;
+        p.init_al_update = in.al;
+        p.sweep = Sweep::SiDpp;
+        p.si_lanes[0] = si_lanes(in.B, in.n_simd);
+        p.si_lanes[1] = si_lanes(0, in.n_simd);
+        const bool dpp = in.forward == FwdPin::Dpp || (in.forward == FwdPin::Auto && (in.B + 3) / 4 <= 3 * in.n_simd / 4);
+        p.forward = dpp ? Forward::WaveDpp : Forward::WaveWg;
+        p.fwd_lds = in.forward == FwdPin::WgLds;
+        p.apply = Apply::Wave;
+        p.kd_sym = in.nb_iter == 0 ? KD_SYM_KEEP : 0;
+        return p;  // fused, al_update, split, needs_ws, si_wg, si_io, si_prep: false
+    }
     // a second limit set, keypoints that share a timestep and obstacle terms exist in the generic kernels only, whatever the pins say
     const bool cooperative = !in.generic && !in.limits2_set && !in.shared_steps && !in.obstacles;
     const bool coop_fwd = cooperative && p.n_alpha <= 16;       // all step sizes at once (16 lanes / rows per instance)

@@ -683,7 +683,8 @@ int ilqr_clearance_trajectories_dev(ilqr_ctx* ctx, const ilqr_problem_desc* desc
  *   not read.  Everything is copied into memory the problem owns before the call returns: no pointer is kept (_dev: world->obs is a device
  *   pointer and the copy is device to device; the structs are host memory in both forms).  robot == NULL removes the terms, and the problem is
  *   then planned exactly as before.  A setter: afterwards the problem holds no plan and no gains.  Problems with obstacle terms run on the generic
- *   lane-per-instance kernel set, whatever the pins say (as a second limit set and shared keypoint steps do): they pay that set's price.
+ *   lane-per-instance kernel set, whatever the pins say (as a second limit set and shared keypoint steps do): they pay that set's price --
+ *   unless ilqr_ctx_set_obstacle_path (below) sends them to the cooperative kernels.
  *   Refused, each with its own text: what the clearance calls refuse about robot, planes, obstacles, sets and the chain; a negative or non-finite
  *   weight; a NaN or infinite margin.  ilqr_solve_batch_cp and ilqr_solve_batch refuse a problem that has obstacle terms.
  * ilqr_problem_obstacle_terms(p, cost, lx, lxx): the terms at the plan the problem holds (needs one, as ilqr_problem_gains does): cost[B][T],
@@ -695,6 +696,21 @@ int ilqr_problem_set_obstacles(ilqr_problem* p, const ilqr_clr_robot* robot, con
 int ilqr_problem_set_obstacles_dev(ilqr_problem* p, const ilqr_clr_robot* robot, const ilqr_clr_world* world, double weight);
 int ilqr_problem_obstacle_terms(ilqr_problem* p, double* cost, double* lx, double* lxx);
 int ilqr_problem_obstacle_terms_dev(ilqr_problem* p, double* cost, double* lx, double* lxx);
+/* The kernel path of a problem with obstacle terms: context state of its own (ilqr_ctx_set_crosscheck does not touch it; no environment variable),
+ * in force for every later solve and gains call on the context.  ILQR_OBSTACLE_PATH_GENERIC (the default): the generic lane-per-instance set, as
+ * described above.  ILQR_OBSTACLE_PATH_COOPERATIVE: the cooperative kernels of the single-integrator systems, where all of this holds: PosOrn or
+ * JointSpace with nb_deriv 1, at most 16 step sizes, no AL rows or at most 4 shared rows on the state alone, no second limit set, no keypoints
+ * that share a timestep, arrays addressable with 32-bit offsets, and generic_kernels not pinned (that pin wins).  Every other problem, and every
+ * problem without obstacle terms, is planned and solved exactly as under GENERIC.  The term's definition does not depend on the path; the two
+ * paths agree to rounding, not bit for bit.  On the cooperative path a stage's l_x, l_xx are formed in one fixed order before the sweep reads
+ * them -- the keypoint's entry (limits in it) at a keypoint step, the limit terms at any other, and the obstacle terms added to that --; the
+ * line search's cost of step size alpha is (task cost at the keypoints + limit cost) + sum_k c_obs(x(alpha)_k), the inner sum over the steps in
+ * ascending k, whatever the batch size, traj_per_set or the forward pin, with x(alpha) = fma(alpha, x(1) - xbar, xbar) (x(1) itself at alpha = 1),
+ * the expression that forms the accepted plan; the initial trajectory's cost is (system cost) + that sum at xbar.  A NaN position gives a NaN sum.
+ * Any other value of `path` is refused with a text. */
+#define ILQR_OBSTACLE_PATH_GENERIC 0
+#define ILQR_OBSTACLE_PATH_COOPERATIVE 1
+int ilqr_ctx_set_obstacle_path(ilqr_ctx* ctx, int path);
 
 /* ---- stand-alone batched kinematics: KDLRobot::updateKinematics for n configurations ---------------------- */
 /* (src/sim/KDLRobot.cpp:83-115): q[n][dof] (dq[n][dof] or NULL) -> pos[n][3], quat[n][4] (w,x,y,z), jac[n][6][dof];
