@@ -429,10 +429,10 @@ class Context:
     def synchronize(self):
         self.check(self.L.ilqr_ctx_synchronize(self.h))
 
-    _PINS = {"sweep": {None: 0, "mfma": 1, "rows": 2, "siwave": 4, "siwg": 5, "siwgio": 6, "siwgprep": 7}, "forward": {None: 0, "wg": 1, "dpp": 2, "wglds": 3}, "reroll": {None: 0, "rows": 1, "dpp": 2}}  # ILQR_XC_*
+    _PINS = {"sweep": {None: 0, "mfma": 1, "rows": 2, "siwave": 4, "siwg": 5, "siwgio": 6, "siwgprep": 7}, "forward": {None: 0, "wg": 1, "dpp": 2, "wglds": 3, "wgio": 4}, "reroll": {None: 0, "rows": 1, "dpp": 2}}  # ILQR_XC_*
 
     def set_crosscheck(self, generic_kernels=False, cp_lane_solve=False, cp_general=False, sweep=None, forward=None, reroll=None):
-        """Cross-check kernel variants (ilqr_ctx_set_crosscheck); context state, in force until changed.  sweep "mfma"|"rows"|"siwave"|"siwg"|"siwgio"|"siwgprep", forward "wg"|"dpp"|"wglds",
+        """Cross-check kernel variants (ilqr_ctx_set_crosscheck); context state, in force until changed.  sweep "mfma"|"rows"|"siwave"|"siwg"|"siwgio"|"siwgprep", forward "wg"|"dpp"|"wglds"|"wgio",
         reroll "rows"|"dpp"; None = by batch size."""
         pins = []
         for name, v in (("sweep", sweep), ("forward", forward), ("reroll", reroll)):
@@ -443,7 +443,7 @@ class Context:
 
     def crosscheck_from_env(self):
         """TEST PLUMBING of this Python wrapper (the library itself reads no environment variable): the parity tests select the cross-check
-        variants per test case through ILQR_HIP_PATH=v1, ILQR_CP_SOLVE=lane, ILQR_CP=general, ILQR_SWEEP=mfma|rows|siwave|siwg|siwgio|siwgprep, ILQR_FWD=wg|dpp|wglds, ILQR_APPLY=rows|dpp; every solve of BatchProblem passes them on."""
+        variants per test case through ILQR_HIP_PATH=v1, ILQR_CP_SOLVE=lane, ILQR_CP=general, ILQR_SWEEP=mfma|rows|siwave|siwg|siwgio|siwgprep, ILQR_FWD=wg|dpp|wglds|wgio, ILQR_APPLY=rows|dpp; every solve of BatchProblem passes them on."""
         env = os.environ
         self.set_crosscheck(env.get("ILQR_HIP_PATH") == "v1", env.get("ILQR_CP_SOLVE") == "lane", env.get("ILQR_CP") == "general",
                             sweep=env.get("ILQR_SWEEP") or None, forward=env.get("ILQR_FWD") or None, reroll=env.get("ILQR_APPLY") or None)

@@ -179,13 +179,13 @@ extern "C" int ilqr_ctx_set_split(ilqr_ctx* c, int on) {
 
 static_assert((int)SweepPin::Mfma == ILQR_XC_SWEEP_MFMA && (int)SweepPin::Rows == ILQR_XC_SWEEP_ROWS && (int)SweepPin::SiWave == ILQR_XC_SWEEP_SI_WAVE &&
               (int)SweepPin::SiWg == ILQR_XC_SWEEP_SI_WG && (int)SweepPin::SiWgIo == ILQR_XC_SWEEP_SI_WG_IO && (int)SweepPin::SiWgPrep == ILQR_XC_SWEEP_SI_WG_PREP && (int)FwdPin::Wg == ILQR_XC_FWD_WG &&
-              (int)FwdPin::Dpp == ILQR_XC_FWD_DPP && (int)FwdPin::WgLds == ILQR_XC_FWD_WG_LDS && (int)RerollPin::Rows == ILQR_XC_REROLL_ROWS && (int)RerollPin::Dpp == ILQR_XC_REROLL_DPP,
+              (int)FwdPin::Dpp == ILQR_XC_FWD_DPP && (int)FwdPin::WgLds == ILQR_XC_FWD_WG_LDS && (int)FwdPin::WgIo == ILQR_XC_FWD_WG_IO && (int)RerollPin::Rows == ILQR_XC_REROLL_ROWS && (int)RerollPin::Dpp == ILQR_XC_REROLL_DPP,
               "variant pins of ilqr_plan.hpp and include/ilqr_hip.h");
 
 extern "C" int ilqr_ctx_set_crosscheck(ilqr_ctx* c, int generic_kernels, int cp_lane_solve, int cp_general, int sweep, int forward, int reroll) {
     if (!c) return 1;
     if (sweep < 0 || sweep > 7 || sweep == 3) return fail(c, "ilqr_ctx_set_crosscheck: sweep must be ILQR_XC_AUTO, ILQR_XC_SWEEP_MFMA, ILQR_XC_SWEEP_ROWS, ILQR_XC_SWEEP_SI_WAVE, ILQR_XC_SWEEP_SI_WG, ILQR_XC_SWEEP_SI_WG_IO or ILQR_XC_SWEEP_SI_WG_PREP");
-    if (forward < 0 || forward > 3) return fail(c, "ilqr_ctx_set_crosscheck: forward must be ILQR_XC_AUTO, ILQR_XC_FWD_WG, ILQR_XC_FWD_DPP or ILQR_XC_FWD_WG_LDS");
+    if (forward < 0 || forward > 4) return fail(c, "ilqr_ctx_set_crosscheck: forward must be ILQR_XC_AUTO, ILQR_XC_FWD_WG, ILQR_XC_FWD_DPP, ILQR_XC_FWD_WG_LDS or ILQR_XC_FWD_WG_IO");
     if (reroll < 0 || reroll > 2) return fail(c, "ilqr_ctx_set_crosscheck: reroll must be ILQR_XC_AUTO, ILQR_XC_REROLL_ROWS or ILQR_XC_REROLL_DPP");
     c->xc_sweep = (SweepPin)sweep;
     c->xc_forward = (FwdPin)forward;
@@ -733,6 +733,7 @@ static FwdArgs plan_fwd_args(const ilqr_problem* p, const RiccatiPlan& pl) {
     f.n_kp_all = p->desc.n_kp;
     f.fused = pl.fused ? 1 : 0;
     f.fwd_lds = pl.fwd_lds ? 1 : 0;
+    f.fwd_io = pl.fwd_io ? 1 : 0;
     f.limits = p->desc.limits_set ? 1 : 0;
     for (int k = 0; k < p->desc.n_kp; k++) f.kp_ext |= p->desc.kp_dist[k] | p->desc.kp_has_frame[k] | p->desc.kp_has_Ru[k] | p->desc.kp_joint[k];
     return f;

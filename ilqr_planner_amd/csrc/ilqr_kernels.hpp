@@ -73,6 +73,7 @@ struct FwdArgs {
     int fused;    // the acceptance of the line search is applied by the next sweep (k_backward_si_dpp<.., true>): until then the accepted
                   // trajectory of an instance with pend > 0 is xbar + alpha (x(1) - xbar) over its two buffers
     int fwd_lds;  // Forward::WaveWg runs its predecessor k_forward_wg (the pin ILQR_XC_FWD_WG_LDS) instead of k_forward_reg: same bits
+    int fwd_io;   // Forward::WaveWg runs k_forward_reg with its helper waves (RiccatiPlan::fwd_io): same bits
     // RiccatiPlan::obs_dense (null otherwise).  Read by launch_forward_wave alone, on the host, never by a kernel: between the rollout and k_select it
     // runs launch_obs_ls, which adds the obstacle cost of every step size to Bufs::lsc.  obs: the problem's terms; obs_part: [T][16][Bp] scratch;
     // obs_T: the horizon (the descriptor is device memory).

@@ -144,15 +144,9 @@ __device__ __forceinline__ double oct_row_g(double a_l, double x_l, double b) {
     return oct_sum_rounded(p) - b;
 }
 
-// LDS byte address of a __shared__ object (for inline assembly)
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)p; }
-// Flag words in LDS: plain ds_read / ds_write kept in place by compiler barriers.  (Not `volatile`: through a generic pointer that is a flat
-// access, which counts in vmcnt too and made every step of the chain wait for its prefetched loads -- vmcnt(0).)
-typedef __attribute__((address_space(3))) int lds_int;
-__device__ __forceinline__ int flag_read(const int* p) { LDS_ORDER(); const int v = *(const lds_int*)p; LDS_ORDER(); return v; }
-__device__ __forceinline__ void flag_write(int* p, int v) { LDS_ORDER(); *(lds_int*)p = v; LDS_ORDER(); }
-// Bounded wait of a chain wave for the I/O wave's "consumed" word (LDS byte address `addr`, last read as `seen`) to reach `need`: polls at
-// most SW_POLL_CHAIN times with s_sleep 1 between the polls and returns 1 if it gave up.  One asm statement: no control flow for the compiler.
+// (lds_addr, flag_read, flag_write and the bounded poll flag_wait_ge: ilqr_lanes.hpp)
+// Bounded wait of a chain wave for the I/O wave's "consumed" word (LDS byte address `addr`, last read as `seen`) to reach `need`: at most
+// SW_POLL_CHAIN polls; returns 1 if it gave up.
 __device__ __forceinline__ int wait_consumed(int seen, unsigned addr, int need);
 __device__ __forceinline__ double ldg(const double* base, unsigned byte_off) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + byte_off); }
 __device__ __forceinline__ void stg(double* base, unsigned byte_off, double v) { *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + byte_off) = v; }
@@ -206,27 +200,7 @@ constexpr int SW_PREP = 2;             // preparing waves: 8 instances each
 constexpr int SW_PRING = 8;            // slots of the prepared ring = how far a preparing wave runs ahead of the I/O wave
 constexpr int SW_PENT = 6;             // doubles per (instance, row) and slot: three 16-byte reads for the chain wave
 namespace {
-__device__ __forceinline__ int wait_consumed(int seen, unsigned addr, int need) {
-    int v = seen, cons, cnt;
-    asm volatile(
-        "s_mov_b32 %[cnt], 0\n"
-        "1:\n\t"
-        "v_readfirstlane_b32 %[cons], %[v]\n\t"
-        "s_cmp_ge_i32 %[cons], %[need]\n\t"
-        "s_cbranch_scc1 2f\n\t"
-        "s_cmp_ge_u32 %[cnt], %[lim]\n\t"
-        "s_cbranch_scc1 2f\n\t"
-        "s_sleep 1\n\t"
-        "ds_read_b32 %[v], %[addr]\n\t"
-        "s_add_u32 %[cnt], %[cnt], 1\n\t"
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "s_branch 1b\n"
-        "2:"
-        : [v] "+v"(v), [cons] "=&s"(cons), [cnt] "=&s"(cnt)
-        : [addr] "v"(addr), [need] "s"(need), [lim] "s"(SW_POLL_CHAIN)
-        : "memory", "scc");
-    return __builtin_amdgcn_readfirstlane(cons < need ? 1 : 0);  // (uniform by construction; the compiler takes asm results for divergent)
-}
+__device__ __forceinline__ int wait_consumed(int seen, unsigned addr, int need) { return flag_wait_ge(seen, addr, need, SW_POLL_CHAIN); }
 }  // namespace
 // DENSE (IO = SW_DENSE; lone waves, not fused: a problem with obstacle terms on the cooperative path, RiccatiPlan::obs_dense): EVERY step is a precomputed step.  l_x | l_xx
 // of step k come from sw.sd[k] (k_stage_dense: the keypoint entry or the limit terms, plus the obstacle terms), in the element layout of a kpd entry;

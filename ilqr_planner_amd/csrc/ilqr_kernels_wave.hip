@@ -1,5 +1,6 @@
 // ilqr_kernels_wave.hip -- the single-integrator fast path around the backward sweep (PosOrn / JointSpace, nb_deriv = 1):
 //   k_forward_reg     forward pass of the linear line search for large batches: 16 lanes per instance on registers, a 4-wave workgroup per 16 instances
+//                     (IO: + 3 helper waves that carry the loop's loads and line stores; hand-off through rings and flag words in LDS, ilqr_fwd_io_plan.hpp)
 //   k_forward_wg      its predecessor (one 8-wave workgroup per 16 instances, 32 lanes per instance), kept under a pin as its bitwise reference
 //   k_forward_dpp     the same pass for small batches: a bare chain, one wave per workgroup (agrees with the two above to rounding)
 //   k_select          line-search decision: task cost of every step size from the exported keypoint deviations (one lane per alpha)
@@ -23,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "ilqr_fwd_io_plan.hpp"
 #include "ilqr_lanes.hpp"
 #include "ilqr_obstacle.hpp"
 #include "ilqr_plan.hpp"
@@ -423,8 +425,30 @@ __global__ __launch_bounds__(64) void k_forward_dpp(Bufs a, FwdArgs f) { (void)f
 constexpr int FR_WAVES = 4;   // waves per workgroup: 16 instances, one 128-byte line per row segment
 constexpr int FR_PF = 8;      // steps per group = depth of the gain ring = steps per store block
 // The number of step sizes is a run-time value here (f.n_alpha): it only gates the store of the limit costs, the limit branch evaluates all sixteen lanes anyway.
-template <bool LIM, bool ES, bool SYM>
-__global__ __launch_bounds__(FR_WAVES * 64) void k_forward_reg(Bufs a, FwdArgs f) {
+//
+// IO: the form with helper waves (the pin ILQR_XC_FWD_WG_IO; RiccatiPlan::fwd_io).  The workgroup gains FR_HELPERS = 3 waves that execute no rollout
+// arithmetic and own the loop's memory traffic; the four chain waves keep pick (one step ahead), the arithmetic as spelled out above, their one
+// ds_write of x(1) | u(1) per lane and step, the limit test, ||du|| and the rare keypoint export -- no global access besides that export, no gain
+// ring in registers, no stage, no block_store, no barrier in the loop.
+//   gain loader   wave 4: per step the workgroup's 16 records, one contiguous run (16 x 288 bytes packed, 16 x 448 plain) in 16-byte pieces
+//                 (nontemporal), 8 steps ahead in registers (6 with plain records: at most 63 vector-memory instructions in flight), then dropped as they lie in memory into slot n mod FIO_RING of the gain ring
+//   x | u loader  wave 5: per step the 14 rows of xbar | ubar of the 16 instances as whole 128-byte lines (lane j: instance j mod 16, rows j / 16 + 4 q),
+//                 each instance out of its own `cur` buffer, FIO_DEPTH_V steps ahead in registers, into the in ring
+//   storer        wave 6: reads x(1) | u(1) of a step out of the out ring and stores them as row segments, each instance into its own other buffer
+//                 under its own `active` (and only steps k < T - 1): exactly the addresses block_store writes
+// Hand-off by plain LDS flag words written after the data they announce (a wave's LDS operations execute in order): loaded_g, loaded_v, one
+// "produced" per chain wave, stored.  Which value each access needs is in ilqr_fwd_io_plan.hpp, which the host model of
+// tests/cpp/fwd_io_protocol_main.cpp runs too; no cycle of waits can form (there and DESIGN.md 5.3).  A chain wave looks at the flags once per group
+// of FIO_GROUP steps.  The helpers wait for LIVE chain waves only: a chain wave whose four instances are all inactive or beyond B ends behind the
+// one barrier ahead of the loop (every wave has read `active` and `cur` by then; the flags are zero).  Every wait is bounded (FIO_POLL_CHAIN /
+// FIO_POLL_HELPER polls with s_sleep between them, more than 20 ms): a wave that gives up clears `active` of its instances, sets
+// ILQR_STATUS_SWEEP_IO on them and ends; its partners then run into their own bounds.  Same bits (tests/test_gpu_forward_io.py).
+constexpr int FR_HELPERS = 3;
+constexpr int FIO_DEPTH_V = 8;            // steps the x | u loader holds in registers (4 loads each)
+constexpr int FIO_POLL_CHAIN = 1 << 20;   // polls of s_sleep 1 (64 clocks) + an LDS round trip: 28 ms at 2.4 GHz from the sleeps alone
+constexpr int FIO_POLL_HELPER = 1 << 18;  // polls of s_sleep 4 (256 clocks) + an LDS round trip: 28 ms at 2.4 GHz from the sleeps alone
+template <bool LIM, bool ES, bool SYM, bool IO = false>
+__global__ __launch_bounds__((FR_WAVES + (IO ? FR_HELPERS : 0)) * 64) void k_forward_reg(Bufs a, FwdArgs f) {
 #pragma clang fp contract(off)  // every fused operation below is written as one
     constexpr int NX = 7, NU = 7, ROWP = kd_rowp(NX), PF = FR_PF, IPW = 4;
     static_assert(ROWP == 8, "record row = 7 gains + feed-forward");
@@ -432,10 +456,16 @@ __global__ __launch_bounds__(FR_WAVES * 64) void k_forward_reg(Bufs a, FwdArgs f
     constexpr int RSD = SYM ? KD_SYM_RS : NU * ROWP;  // doubles per record
     constexpr int NPC = IPW * RSD / 2;                // 16-byte pieces of the wave's four records: 72 or 112
     static_assert(NPC > 64 && NPC <= 128, "two pieces per lane");
-    __shared__ __attribute__((aligned(16))) double sK[FR_WAVES][2][IPW * RSD];
+    __shared__ __attribute__((aligned(16))) double sK[IO ? 1 : FR_WAVES][2][IO ? 2 : IPW * RSD];
     // x(1) | u(1) of a group of PF steps, [step][row][instance] with the row padded by two (bank spread), double-buffered: see block_store
     constexpr int NR = NX + NU, IWG = FR_WAVES * IPW, OSTR = IWG + 2, NT = FR_WAVES * 64, NOUT = PF * NR * IWG, NRND = (NOUT + NT - 1) / NT;
-    __shared__ double sOut[2][PF * NR * OSTR];
+    __shared__ double sOut[IO ? 1 : 2][IO ? 1 : PF * NR * OSTR];
+    // IO: the three rings ([row][instance] with the same padded row, and a dump row for the lanes without a row) and the flag words
+    // (produced per chain wave, loaded_g, loaded_v, stored).  71 KB packed, 92 KB plain: one workgroup per CU from 80 KB on
+    __shared__ __attribute__((aligned(16))) double sG[IO ? FIO_RING : 1][IO ? IWG * RSD : 2];
+    __shared__ double sIn[IO ? FIO_RING : 1][IO ? (NR + 1) * OSTR : 1];
+    __shared__ double sOu[IO ? FIO_RING : 1][IO ? (NR + 1) * OSTR : 1];
+    __shared__ int sFl[IO ? FR_WAVES + 3 : 1];
     const DevDesc& d = *a.desc;
     const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, g = lane >> 4, l = lane & 15, h = l >> 3, r8 = l & 7;
@@ -447,6 +477,126 @@ __global__ __launch_bounds__(FR_WAVES * 64) void k_forward_reg(Bufs a, FwdArgs f
         const int bi = b0 - wv * IPW + (lane & (IWG - 1));
         const bool any = (bi < B) && (a.active[bi < B ? bi : 0] != 0);
         if (__ballot(any ? 1 : 0) == 0ull) return;
+    }
+    if constexpr (IO) {
+        if (wv == 0 && lane < FR_WAVES + 3) sFl[lane] = 0;
+        if (wv >= FR_WAVES) {   // ---- the helper waves: lane j looks at instance j mod 16 of the workgroup
+            const int wgb0 = xcd_tile() * IWG, li = lane & (IWG - 1), rq = lane >> 4;
+            const int bi = wgb0 + li;
+            const bool in = bi < B;
+            const int bbi = in ? bi : 0;
+            const bool oki = in && (a.active[bbi] != 0);
+            const int curi = a.cur[bbi];
+            __syncthreads();  // every wave has read active and cur of the 16 instances; the flags are zero
+            const unsigned livem = (unsigned)__ballot((oki && lane < IWG) ? 1 : 0);  // bit i: instance i runs; chain wave w is live if any of its four does
+            const int T1 = T - 1;
+            const size_t Vstep = (size_t)NX * Bp;
+            int have = 0;  // the least "produced" of the live chain waves, as last seen (uniform)
+            // waits until every live chain wave has produced `need` steps; false: gave up
+            auto wait_produced = [&](int need) -> bool {
+                if (have >= need) return true;
+                const bool want = lane < FR_WAVES && ((livem >> (lane * IPW)) & 15u) != 0u;  // lane w polls chain wave w's word
+                for (int spins = 0;; spins++) {
+                    const int pv = flag_read(&sFl[lane < FR_WAVES ? lane : 0]);
+                    if (__ballot((want && pv < need) ? 1 : 0) == 0ull) {
+                        int mn = 0x7fffffff;
+                        UNR for (int w = 0; w < FR_WAVES; w++) {
+                            const int pw = __builtin_amdgcn_readlane(pv, w);
+                            if (((livem >> (w * IPW)) & 15u) != 0u && pw < mn) mn = pw;
+                        }
+                        have = mn;
+                        return true;
+                    }
+                    if (spins >= FIO_POLL_HELPER) return false;
+                    __builtin_amdgcn_s_sleep(4);
+                }
+            };
+            auto give_up = [&]() {   // a chain wave never got there: give up on the workgroup's instances
+                if (lane < IWG && in) { a.active[bbi] = 0; atomicOr(&a.status[bbi], ILQR_STATUS_SWEEP_IO); }
+            };
+            // the lane's rows of x | u: rq + 4 q; a lane without a fourth row re-reads row 13 and keeps to the dump row of the rings
+            int lrow[4];
+            UNR for (int q = 0; q < 4; q++) lrow[q] = (rq + 4 * q < NR ? rq + 4 * q : NR) * OSTR + li;
+            if (wv == FR_WAVES) {   // ---- gain loader
+                constexpr int NP16 = IWG * RSD / 2, NPQ = (NP16 + 63) / 64, DG = SYM ? 8 : 6;  // 16-byte pieces of the 16 records: 288 in 5 loads, 448 in 7
+                static_assert(DG * NPQ <= 63, "the loader stays within the vector-memory counter");
+                typedef double d2v __attribute__((ext_vector_type(2)));
+                const char* kb = reinterpret_cast<const char*>(a.KD + (size_t)wgb0 * RSD);
+                const size_t Kstep = (size_t)Bp * RSD * sizeof(double);
+                unsigned pc16[NPQ];   // the lane's pieces (a lane without a last piece takes the run's last one again)
+                UNR for (int q = 0; q < NPQ; q++) pc16[q] = (unsigned)(lane + 64 * q < NP16 ? lane + 64 * q : NP16 - 1);
+                double ga[DG][NPQ], gb[DG][NPQ];
+                auto fetch = [&](int slot, int kk) {  // unconditional; the base stops at the last control step.  Nontemporal: see fetch_g
+                    UNR for (int q = 0; q < NPQ; q++) {
+                        const d2v v = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(kb + pc16[q] * 16u));
+                        ga[slot][q] = v.x; gb[slot][q] = v.y;
+                    }
+                    kb += (kk < T - 2) ? Kstep : 0;
+                };
+                UNR for (int q = 0; q < DG; q++) { fetch(q, q); __builtin_amdgcn_sched_barrier(0); }
+                for (int n0 = 0; n0 < T1; n0 += DG) {
+                    UNR for (int jj = 0; jj < DG; jj++) {
+                        const int n = n0 + jj;
+                        if (n < T1) {   // uniform
+                            if (!wait_produced(fio_need_produced_load(n))) { give_up(); return; }
+                            double* im = &sG[fio_slot(n)][0];
+                            UNR for (int q = 0; q < NPQ; q++) {
+                                const double ta = ring_take(ga[jj][q]), tb = ring_take(gb[jj][q]);
+                                *reinterpret_cast<double2*>(im + 2 * pc16[q]) = make_double2(ta, tb);
+                            }
+                            flag_write(&sFl[FR_WAVES], n + 1);  // loaded_g: after the data it announces
+                        }
+                        __builtin_amdgcn_sched_barrier(0);   // the slot is free: only now its next load
+                        fetch(jj, n + DG);
+                    }
+                }
+            } else if (wv == FR_WAVES + 1) {   // ---- x | u loader
+                constexpr int DV = FIO_DEPTH_V;
+                const double* pv[4];
+                UNR for (int q = 0; q < 4; q++) {
+                    const int rw = rq + 4 * q < NR ? rq + 4 * q : NR - 1;
+                    pv[q] = (rw < NX ? a.X[curi] + (size_t)rw * Bp : a.U[curi] + (size_t)(rw - NX) * Bp) + bbi;
+                }
+                double xv[DV][4];
+                auto fetch = [&](int slot, int kk) {
+                    UNR for (int q = 0; q < 4; q++) { xv[slot][q] = *pv[q]; pv[q] += (kk < T - 2) ? Vstep : 0; }
+                };
+                UNR for (int q = 0; q < DV; q++) { fetch(q, q); __builtin_amdgcn_sched_barrier(0); }
+                for (int n0 = 0; n0 < T1; n0 += DV) {
+                    UNR for (int jj = 0; jj < DV; jj++) {
+                        const int n = n0 + jj;
+                        if (n < T1) {   // uniform
+                            if (!wait_produced(fio_need_produced_load(n))) { give_up(); return; }
+                            double* im = &sIn[fio_slot(n)][0];
+                            UNR for (int q = 0; q < 4; q++) im[lrow[q]] = ring_take(xv[jj][q]);
+                            flag_write(&sFl[FR_WAVES + 1], n + 1);  // loaded_v
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        fetch(jj, n + DV);
+                    }
+                }
+            } else {   // ---- storer
+                double* pd[4];
+                bool sto[4];
+                UNR for (int q = 0; q < 4; q++) {
+                    const int rw = rq + 4 * q < NR ? rq + 4 * q : NR - 1;
+                    sto[q] = oki && rq + 4 * q < NR;
+                    pd[q] = (rw < NX ? a.X[1 - curi] + (size_t)rw * Bp : a.U[1 - curi] + (size_t)(rw - NX) * Bp) + bbi;
+                }
+                for (int n = 0; n < T1; n++) {
+                    if (!wait_produced(fio_need_produced_store(n))) { give_up(); return; }
+                    LDS_ORDER();
+                    const double* im = &sOu[fio_slot(n)][0];
+                    double v[4];
+                    UNR for (int q = 0; q < 4; q++) v[q] = im[lrow[q]];
+                    flag_write(&sFl[FR_WAVES + 2], n + 1);  // stored: the slot is free once the values are in registers
+                    UNR for (int q = 0; q < 4; q++) { if (sto[q]) *pd[q] = v[q]; pd[q] += Vstep; }
+                }
+            }
+            return;
+        }
+        __syncthreads();
+        if (__ballot(inst_ok ? 1 : 0) == 0ull) return;  // a chain wave without a running instance produces nothing: the helpers do not wait for it
     }
     const int bb = (b < B) ? b : 0;
     const bool row = r8 < NX;              // lanes (h, 7) shadow row 6: never the source of a broadcast
@@ -527,16 +677,18 @@ __global__ __launch_bounds__(FR_WAVES * 64) void k_forward_reg(Bufs a, FwdArgs f
             K[0] = v0.x; K[1] = v0.y; K[2] = v1.x; K[3] = v1.y;
         }
     };
-    UNR for (int q = 0; q < PF; q++) { fetch_g(q, q); fetch_v(q, q); __builtin_amdgcn_sched_barrier(0); }
     double Kc[4];                           // the entries of the step being computed
-    stage(0, 0);
-    LDS_ORDER();
-    pick(0, Kc);
-    stage(1, 1);
-    LDS_ORDER();
-    __builtin_amdgcn_sched_barrier(0);
-    fetch_g(0, PF);
-    fetch_g(1, PF + 1);
+    if constexpr (!IO) {                    // (IO: the helper waves load, and the chain waves hold no ring and no image)
+        UNR for (int q = 0; q < PF; q++) { fetch_g(q, q); fetch_v(q, q); __builtin_amdgcn_sched_barrier(0); }
+        stage(0, 0);
+        LDS_ORDER();
+        pick(0, Kc);
+        stage(1, 1);
+        LDS_ORDER();
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_g(0, PF);
+        fetch_g(1, PF + 1);
+    }
 
     double dx = 0, dun = 0, pc[4] = {0, 0, 0, 0};
     // k_forward_wg's limit cost of a column pair (c0, c1) for one step size (inspectJointLimit, System.cpp:163-179): cost(c0) + cost(c1) with
@@ -581,12 +733,21 @@ __global__ __launch_bounds__(FR_WAVES * 64) void k_forward_reg(Bufs a, FwdArgs f
         __builtin_amdgcn_sched_barrier(0);               /* the slot is free: only now its next load */            \
         fetch_g((JJ + 2) % PF, k + 2 + PF);                                                                        \
         if (!CHK || k < T - 1) {                                                                                   \
-            const double vb = ring_take(vr[JJ]);         /* xbar_r | ubar_r */                                     \
+            FR_BODY_(CHK, ring_take(vr[JJ]), sOut[ob][JJ * NR * OSTR + ow])                                        \
+        }                                                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                         \
+        fetch_v(JJ, k + PF);                                                                                       \
+        UNR for (int j = 0; j < 4; j++) Kc[j] = Kn[j];                                                             \
+    }
+    // the arithmetic of step k, shared by both forms: VB = xbar_r | ubar_r of the step, OUT = where x(1)_r | u(1)_r goes in LDS
+#define FR_BODY_(CHK, VB, OUT)                                                                                     \
+        {                                                                                                          \
+            const double vb = VB;                        /* xbar_r | ubar_r */                                     \
             const double x0 = dpp_bcast_halves<0, 4>(dx), x1 = dpp_bcast_halves<1, 5>(dx);                         \
             const double x2 = dpp_bcast_halves<2, 6>(dx), x3 = dpp_bcast_halves<3, -1>(dx, 1.0);                   \
             const double part = fma(Kc[0], x0, Kc[1] * x1) + fma(Kc[2], x2, Kc[3] * x3);                           \
             const double du = part + dpp_f64<0x128>(part);   /* row_ror:8: the other half's part */                \
-            sOut[ob][JJ * NR * OSTR + ow] = vb + (h ? du : dx);   /* x(1)_r | u(1)_r */                            \
+            OUT = vb + (h ? du : dx);                    /* x(1)_r | u(1)_r */                                     \
             if (ES) {                                    /* ||du_k(1)||: s_j = fma(du_2j, du_2j, du_2j+1^2), s_3 = du_6^2 */ \
                 const double o = dpp_f64<0xB1>(du);      /* the pair's other row */                                \
                 const double pa = ev ? du : o, pb = ev ? o : du;                                                   \
@@ -603,20 +764,60 @@ __global__ __launch_bounds__(FR_WAVES * 64) void k_forward_reg(Bufs a, FwdArgs f
                 kp_next = (kpi < n_kp) ? __builtin_amdgcn_readfirstlane(d.kp_t[kpi]) : -1;                         \
             }                                                                                                      \
             dx = fma(dt, du, dx);   /* deviation dynamics (both halves) */                                         \
-        }                                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                                         \
-        fetch_v(JJ, k + PF);                                                                                       \
-        UNR for (int j = 0; j < 4; j++) Kc[j] = Kn[j];                                                             \
-    }
+        }
     // one copy of the group (k_forward_dpp runs a second one without the two tests where no keypoint step and no end of the horizon falls into the
     // group: here the values that leave either copy would each keep registers of their own across the other, and the copies that bring the ring
     // back together at the end of a group wait for nearly every load in flight)
-    for (int k0 = 0, ob = 0; k0 < T - 1; k0 += PF, ob ^= 1) {
-        UNR for (int jj = 0; jj < PF; jj++) FR_STEP_(jj, true)
-        lds_barrier();   // the group's x(1), u(1) of every wave are in sOut[ob]
-        block_store(ob, k0);
+    if constexpr (!IO) {
+        for (int k0 = 0, ob = 0; k0 < T - 1; k0 += PF, ob ^= 1) {
+            UNR for (int jj = 0; jj < PF; jj++) FR_STEP_(jj, true)
+            lds_barrier();   // the group's x(1), u(1) of every wave are in sOut[ob]
+            block_store(ob, k0);
+        }
+    } else {
+        // IO: everything of a step comes out of the rings and goes into one; the flags are looked at once per group of FIO_GROUP steps
+        // (ilqr_fwd_io_plan.hpp).  No global access in the loop but the keypoint export, no barrier.
+        constexpr int G = FIO_GROUP;
+        const int T1 = T - 1;
+        const unsigned fl_g = lds_addr(&sFl[FR_WAVES]), fl_v = lds_addr(&sFl[FR_WAVES + 1]), fl_s = lds_addr(&sFl[FR_WAVES + 2]);
+        const int go = (wv * IPW) * RSD;                     // the wave's records in a slot of the gain ring
+        auto pick_io = [&](int slot, double (&K)[4]) {
+            const double* im = &sG[slot][go];
+            if (SYM) {
+                UNR for (int j = 0; j < 4; j++) K[j] = im[ro[j]];
+            } else {
+                const double2 v0 = *reinterpret_cast<const double2*>(im + ro[0]), v1 = *reinterpret_cast<const double2*>(im + ro[2]);
+                K[0] = v0.x; K[1] = v0.y; K[2] = v1.x; K[3] = v1.y;
+            }
+        };
+        int gave = flag_wait_ge(flag_read(&sFl[FR_WAVES]), fl_g, fio_need_loaded_g(0, T1), FIO_POLL_CHAIN);  // (its data: the first pick)
+        LDS_ORDER();
+        pick_io(0, Kc);
+        for (int k0 = 0; k0 < T1; k0 += G) {
+            const int seen_g = flag_read(&sFl[FR_WAVES]), seen_v = flag_read(&sFl[FR_WAVES + 1]), seen_s = flag_read(&sFl[FR_WAVES + 2]);
+            gave |= flag_wait_ge(seen_g, fl_g, __builtin_amdgcn_readfirstlane(fio_need_loaded_g(k0, T1)), FIO_POLL_CHAIN);
+            gave |= flag_wait_ge(seen_v, fl_v, __builtin_amdgcn_readfirstlane(fio_need_loaded_v(k0, T1)), FIO_POLL_CHAIN);
+            gave |= flag_wait_ge(seen_s, fl_s, __builtin_amdgcn_readfirstlane(fio_need_stored(k0)), FIO_POLL_CHAIN);
+            if (gave) break;   // uniform; a helper is gone
+            const int s0 = fio_slot(k0);                     // uniform; the group's slots are s0 .. s0 + G - 1
+            UNR for (int jj = 0; jj < G; jj++) {
+                const int k = k0 + jj;
+                double Kn[4];
+                pick_io(jj + 1 < G ? s0 + jj + 1 : fio_slot(k0 + G), Kn);   /* the entries of step k + 1 */
+                if (k < T1) {
+                    FR_BODY_(true, sIn[s0 + jj][ow], sOu[s0 + jj][ow])   /* the lane's entry of a step: the same place in both rings */
+                    flag_write(&sFl[wv], k + 1);             // produced: after the data it announces
+                }
+                UNR for (int j = 0; j < 4; j++) Kc[j] = Kn[j];
+            }
+        }
+        if (gave) {   // the wave gives up on its instances (its partners run into their own bounds)
+            if (inst_ok && l == 0) { a.active[bb] = 0; atomicOr(&a.status[bb], ILQR_STATUS_SWEEP_IO); }
+            return;
+        }
     }
 #undef FR_STEP_
+#undef FR_BODY_
     {   // terminal state
         if (sx) a.X[1 - cur][((size_t)(T - 1) * NX + r) * Bp + bb] = xT + dx;   // one 32-byte piece per line, once
         if (LIM && __ballot((seg_bad(xT) & sx) ? 1 : 0) != 0ull) limits_all(xT);
@@ -955,11 +1156,14 @@ static void launch_forward_dpp(const Bufs& a, dim3 grid, hipStream_t st, const F
     }
 }
 static void launch_forward_reg(const Bufs& a, dim3 grid, hipStream_t st, const FwdArgs& f) {
-    const dim3 block(FR_WAVES * 64);
-#define FR_LAUNCH_(LIM, ES)                                                                             \
-    do {                                                                                                \
-        if (a.kd_sym) hipLaunchKernelGGL((k_forward_reg<LIM, ES, true>), grid, block, 0, st, a, f);  \
-        else hipLaunchKernelGGL((k_forward_reg<LIM, ES, false>), grid, block, 0, st, a, f);          \
+    const dim3 block(FR_WAVES * 64), ioblock((FR_WAVES + FR_HELPERS) * 64);
+#define FR_LAUNCH_(LIM, ES)                                                                                                     \
+    do {                                                                                                                        \
+        if (f.fwd_io) {                                                                                                         \
+            if (a.kd_sym) hipLaunchKernelGGL((k_forward_reg<LIM, ES, true, true>), grid, ioblock, 0, st, a, f);                 \
+            else hipLaunchKernelGGL((k_forward_reg<LIM, ES, false, true>), grid, ioblock, 0, st, a, f);                         \
+        } else if (a.kd_sym) hipLaunchKernelGGL((k_forward_reg<LIM, ES, true>), grid, block, 0, st, a, f);                      \
+        else hipLaunchKernelGGL((k_forward_reg<LIM, ES, false>), grid, block, 0, st, a, f);                                     \
     } while (0)
     if (f.limits) {
         if (f.early_stop) FR_LAUNCH_(true, true);

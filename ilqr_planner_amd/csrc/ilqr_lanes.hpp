@@ -1,5 +1,5 @@
 // ilqr_lanes.hpp -- lane-level building blocks of the cooperative kernels (gfx950, fp64, device code only): moves of a double between the
-// lanes of a wave, the sums built on them, the ring move and the LDS ordering helpers.  One definition each; the inline-assembly DPP
+// lanes of a wave, the sums built on them, the ring move, the LDS ordering helpers and the flag words (with their bounded poll) by which the waves of a workgroup hand work to each other.  One definition each; the inline-assembly DPP
 // blocks (v_fmac_f64_dpp strings and their bank masks) stay in the kernel files that schedule them by hand.
 // Not for ilqr_kernels.hip, ilqr_step.hpp or ilqr_device.hpp: tests/tools/hostsim compiles those with g++.
 #pragma once
@@ -12,6 +12,38 @@ namespace ilqr {
 // Workgroup barrier that only drains LDS traffic (__syncthreads() also emits s_waitcnt vmcnt(0): it would wait for loads
 // prefetched steps ahead).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// ------------------------------------------------------------------------------------------------ flag words in LDS (k_backward_si_dpp, k_forward_reg)
+// LDS byte address of a __shared__ object (for inline assembly)
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)p; }
+// Flag words in LDS: plain ds_read / ds_write kept in place by compiler barriers.  (Not `volatile`: through a generic pointer that is a flat
+// access, which counts in vmcnt too and made every step of the chain wait for its prefetched loads -- vmcnt(0).)
+typedef __attribute__((address_space(3))) int lds_int;
+__device__ __forceinline__ int flag_read(const int* p) { LDS_ORDER(); const int v = *(const lds_int*)p; LDS_ORDER(); return v; }
+__device__ __forceinline__ void flag_write(int* p, int v) { LDS_ORDER(); *(lds_int*)p = v; LDS_ORDER(); }
+// Bounded wait of a wave for a flag word (LDS byte address `addr`, last read as `seen`) to reach `need`: polls at most `polls` times with
+// s_sleep 1 between the polls and returns 1 if it gave up.  One asm statement: no control flow for the compiler.
+__device__ __forceinline__ int flag_wait_ge(int seen, unsigned addr, int need, int polls) {
+    int v = seen, cons, cnt;
+    asm volatile(
+        "s_mov_b32 %[cnt], 0\n"
+        "1:\n\t"
+        "v_readfirstlane_b32 %[cons], %[v]\n\t"
+        "s_cmp_ge_i32 %[cons], %[need]\n\t"
+        "s_cbranch_scc1 2f\n\t"
+        "s_cmp_ge_u32 %[cnt], %[lim]\n\t"
+        "s_cbranch_scc1 2f\n\t"
+        "s_sleep 1\n\t"
+        "ds_read_b32 %[v], %[addr]\n\t"
+        "s_add_u32 %[cnt], %[cnt], 1\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "s_branch 1b\n"
+        "2:"
+        : [v] "+v"(v), [cons] "=&s"(cons), [cnt] "=&s"(cnt)
+        : [addr] "v"(addr), [need] "s"(need), [lim] "s"(polls)
+        : "memory", "scc");
+    return __builtin_amdgcn_readfirstlane(cons < need ? 1 : 0);  // (uniform by construction; the compiler takes asm results for divergent)
+}
 
 // ------------------------------------------------------------------------------------------------ moves
 // DPP move of a double by its 32-bit halves, CTRL = the DPP control word.  For patterns in which every lane has a source: no "old"

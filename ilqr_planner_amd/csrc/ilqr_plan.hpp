@@ -74,9 +74,22 @@ constexpr bool si_io_supported(bool al, int m) { return !al || m <= 1; }
 // four-wave form under AUTO as there.  The pin forces it wherever the I/O wave is supported.
 constexpr int SI_PREP_MIN_BATCH = 256;
 
+// k_forward_reg with helper waves (a gain loader, an x | u loader and a storer per workgroup carry the loop's loads and line stores; the four
+// chain waves keep the arithmetic: ilqr_kernels_wave.hip, ilqr_fwd_io_plan.hpp), wherever AUTO takes Forward::WaveWg on an unsplit solve and the
+// LAUNCHED batch lies in [FWD_IO_MIN_BATCH, FWD_IO_MAX_BATCH].  Same bits (tests/test_gpu_forward_io.py), so the range is a pure speed choice.
+// Measured on C3 (profiles/fwd_io_batch_scan.txt, ms per solve, ILQR_FWD=wg against wgio): B = 1024 5.18 / 5.06, 2048 5.27 / 5.15, 3072 5.36 / 5.24,
+// 4096 5.54 / 5.45, 8192 9.83 / 9.87 -- faster from the smallest measured size up to 4096 instances, where 256 workgroups land on 256 CUs, and slower
+// at 8192, where a CU runs a second round (71 KB of LDS per workgroup with packed records, 92 KB with plain ones: one workgroup per CU from 80 KB on).
+// Nothing was measured between 4096 and 8192: the range ends at the largest size measured to win.  (AUTO takes Forward::WaveWg beyond 3072 instances
+// only, so of this range it uses 3073 .. 4096; the rest matters where a later change moves that crossover.)  The halves of a split solve were not
+// measured and keep the four-wave form.
+constexpr int FWD_IO_MIN_BATCH = 1024;
+constexpr int FWD_IO_MAX_BATCH = 4096;
+constexpr bool fwd_io_auto(int launched_B) { return launched_B >= FWD_IO_MIN_BATCH && launched_B <= FWD_IO_MAX_BATCH; }
+
 // Variant pins of ilqr_ctx_set_crosscheck: AUTO (0) = by batch size; the values are the ILQR_XC_* constants of include/ilqr_hip.h
 enum class SweepPin { Auto = 0, Mfma = 1, Rows = 2, SiWave = 4, SiWg = 5, SiWgIo = 6, SiWgPrep = 7 };  // SiWave / SiWg / SiWgIo / SiWgPrep: the form of k_backward_si_dpp (same bits); AUTO elsewhere.  (3 is no pin: ilqr_ctx_set_crosscheck refuses it)
-enum class FwdPin { Auto = 0, Wg = 1, Dpp = 2, WgLds = 3 };  // WgLds: Wg with k_forward_wg, the predecessor of k_forward_reg (same bits)
+enum class FwdPin { Auto = 0, Wg = 1, Dpp = 2, WgLds = 3, WgIo = 4 };  // WgLds: Wg with k_forward_wg, the predecessor of k_forward_reg; WgIo: Wg with k_forward_reg's helper waves (same bits, all three)
 enum class RerollPin { Auto = 0, Rows = 1, Dpp = 2 };
 
 struct PlanIn {
@@ -127,6 +140,7 @@ struct RiccatiPlan {
     bool si_io[2] = {false, false};  // ... with the I/O wave (SI_IO_MIN_BATCH on an unsplit solve, or the pin SiWgIo; never under SiWave / SiWg): only where si_wg, at most one AL row
     Forward forward = Forward::Generic;
     bool fwd_lds = false;         // Forward::WaveWg under the pin FwdPin::WgLds: k_forward_wg instead of k_forward_reg
+    bool fwd_io = false;          // Forward::WaveWg: k_forward_reg with its helper waves (fwd_io_auto on an unsplit solve, or the pin FwdPin::WgIo; never under Wg / WgLds)
     Apply apply = Apply::None;
     bool al_update = false;       // k_al_post after every line search (the wave path does it in k_apply or the fused sweep)
     bool fused = false;           // the sweep applies the previous line search's winner itself (ilqr_kernels_dpp.hip)
@@ -154,9 +168,10 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
         const bool dpp = in.forward == FwdPin::Dpp || (in.forward == FwdPin::Auto && (in.B + 3) / 4 <= 3 * in.n_simd / 4);
         p.forward = dpp ? Forward::WaveDpp : Forward::WaveWg;
         p.fwd_lds = in.forward == FwdPin::WgLds;
+        p.fwd_io = in.forward == FwdPin::WgIo;  // the pin only: the form was not measured on this path
         p.apply = Apply::Wave;
         p.kd_sym = in.nb_iter == 0 ? KD_SYM_KEEP : 0;
-        return p;  // fused, al_update, split, needs_ws, si_wg, si_io, si_prep: false
+        return p;  // fused, al_update, split, needs_ws, si_wg, si_io, si_prep: false (fwd_io: by its pin alone)
     }
     // a second limit set, keypoints that share a timestep and obstacle terms exist in the generic kernels only, whatever the pins say
     const bool cooperative = !in.generic && !in.limits2_set && !in.shared_steps && !in.obstacles;
@@ -211,6 +226,8 @@ inline RiccatiPlan plan_riccati(const PlanIn& in) {
     // 0.53 ms per iteration against 0.49 unsplit).
     p.split = coop_fwd && ((p.sweep == Sweep::Mfma && in.split) || in.split == 2) && !in.profile && in.halves && in.nb_iter > 0;
     p.needs_ws = p.sweep == Sweep::Generic && in.nb_iter > 0;
+    // the helper-wave form of k_forward_reg: its pin, or AUTO on an unsplit solve in the measured range of launched batch sizes
+    p.fwd_io = p.forward == Forward::WaveWg && !p.fwd_lds && (in.forward == FwdPin::WgIo || (in.forward == FwdPin::Auto && !p.split && fwd_io_auto(in.B)));
     const int b0 = p.split ? split_first_half(in.B) : in.B;
     p.si_lanes[0] = si_lanes(b0, in.n_simd);
     p.si_lanes[1] = si_lanes(in.B - b0, in.n_simd);

@@ -47,7 +47,7 @@ extern "C" {
 #define ILQR_STATUS_OK 0
 #define ILQR_STATUS_NONFINITE 1   /* accepted cost is NaN/Inf (the reference prints -nan and carries on) */
 #define ILQR_STATUS_ALPHA_FLOOR 2 /* last line search bottomed out at alpha <= alpha_floor (accept-anyway rule) */
-#define ILQR_STATUS_SWEEP_IO 4    /* a wave of the sweep's I/O-wave form gave up a bounded wait on its partner (a protocol error, never seen): the instance was \
+#define ILQR_STATUS_SWEEP_IO 4    /* a wave of the sweep's I/O-wave form, or of the forward pass's helper-wave form (ILQR_XC_FWD_WG_IO), gave up a bounded wait on its partner (a protocol error, never seen): the instance was \
                                      made inactive, no later kernel of the solve touches it and its outputs are not a solution.  Sticky until the next solve. */
 
 typedef struct ilqr_ctx ilqr_ctx;
@@ -186,6 +186,8 @@ int ilqr_ctx_set_split(ilqr_ctx* ctx, int on);
 #define ILQR_XC_FWD_WG 1       /* forward pass of the single-integrator systems: the large-batch k_forward_reg (AUTO: beyond 3 n_simd instances) */
 #define ILQR_XC_FWD_DPP 2      /*   ... the latency-built k_forward_dpp (AUTO: up to 3 n_simd); agrees with the others to rounding */
 #define ILQR_XC_FWD_WG_LDS 3   /*   ... k_forward_wg, the predecessor of k_forward_reg, at any batch size: the same bits as ILQR_XC_FWD_WG (never AUTO) */
+#define ILQR_XC_FWD_WG_IO 4    /*   ... k_forward_reg with three helper waves per workgroup that carry its loads and line stores, at any batch size: the same bits as ILQR_XC_FWD_WG, which pins the four-wave form \
+                                    (AUTO: where it takes k_forward_reg on an unsplit solve of 1024 to 4096 launched instances) */
 #define ILQR_XC_REROLL_ROWS 1  /* re-roll of the line-search winner on the time systems: k_apply_rows_tm (AUTO: beyond n_simd instances) */
 #define ILQR_XC_REROLL_DPP 2   /*   ... k_apply_dpp_tm (AUTO: up to n_simd) */
 /* Cross-check kernel variants for parity tests (no reference counterpart; the library reads no environment variable -- these are context state,
