@@ -25,6 +25,7 @@ KP_ERR_POS, KP_ERR_ORN, KP_ERR_VEL, KP_ERR_ANGVEL, KP_ERR_TIME = range(5)
 PROF_ROLLOUT, PROF_BACKWARD, PROF_FORWARD, PROF_OTHER, PROF_APPLY = 0, 1, 2, 3, 4
 ADOPT_STATE, ADOPT_TARGETS, ADOPT_CONTROLS0, ADOPT_CONTROLS, ADOPT_MULTIPLIERS = 1, 2, 4, 8, 16  # ILQR_ADOPT_* (bits of ilqr_problem_adopt's `what`)
 CLR_MAX_SPH, CLR_MAX_PLANES, CLR_STATS = 32, 8, 4  # ILQR_CLR_MAX_SPH, ILQR_CLR_MAX_PLANES, ILQR_CLR_STATS (mean, min, n_hit, n_bad)
+CLR_MAX_SELF, CLR_MAX_ANCHOR = 64, 8  # ILQR_CLR_MAX_SELF, ILQR_CLR_MAX_ANCHOR
 
 # every symbol include/ilqr_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
@@ -151,7 +152,8 @@ class ClrRobot(C.Structure):
     """Mirror of ilqr_clr_robot."""
 
     _fields_ = [("n_sph", C.c_int), ("sph_link", C.c_int * CLR_MAX_SPH), ("sph_c", (C.c_double * 3) * CLR_MAX_SPH), ("sph_r", C.c_double * CLR_MAX_SPH),
-                ("n_planes", C.c_int), ("plane_n", (C.c_double * 3) * CLR_MAX_PLANES), ("plane_d", C.c_double * CLR_MAX_PLANES)]
+                ("n_planes", C.c_int), ("plane_n", (C.c_double * 3) * CLR_MAX_PLANES), ("plane_d", C.c_double * CLR_MAX_PLANES),
+                ("n_self", C.c_int), ("self_pair", (C.c_int * 2) * CLR_MAX_SELF)]
 
 
 class ClrWorld(C.Structure):
@@ -166,12 +168,16 @@ class ClrOut(C.Structure):
     _fields_ = [("clr", C.c_void_p), ("clr_min", C.c_void_p), ("clr_at", C.c_void_p), ("n_below", C.c_void_p), ("eligible", C.c_void_p), ("stats", C.c_void_p)]
 
 
-def clr_robot(spheres, planes=None):
-    """ClrRobot from spheres = [(link, (cx, cy, cz), r), ...] in chain order and planes = [((nx, ny, nz), d), ...] (n . p >= d)."""
+def clr_robot(spheres, planes=None, self_pairs=None):
+    """ClrRobot from spheres = [(link, (cx, cy, cz), r), ...] in chain order, planes = [((nx, ny, nz), d), ...] (n . p >= d) and
+    self_pairs = [(a, b), ...]: sphere indices with a < b on different links (the robot against itself)."""
     rb = ClrRobot()
-    spheres, planes = list(spheres), list(planes or [])
-    if len(spheres) > CLR_MAX_SPH or len(planes) > CLR_MAX_PLANES:
-        raise ValueError(f"at most {CLR_MAX_SPH} spheres and {CLR_MAX_PLANES} planes")
+    spheres, planes, self_pairs = list(spheres), list(planes or []), list(self_pairs if self_pairs is not None else [])
+    if len(spheres) > CLR_MAX_SPH or len(planes) > CLR_MAX_PLANES or len(self_pairs) > CLR_MAX_SELF:
+        raise ValueError(f"at most {CLR_MAX_SPH} spheres, {CLR_MAX_PLANES} planes and {CLR_MAX_SELF} self pairs")
+    rb.n_self = len(self_pairs)
+    for e, (a, b) in enumerate(self_pairs):
+        rb.self_pair[e][0], rb.self_pair[e][1] = int(a), int(b)
     rb.n_sph, rb.n_planes = len(spheres), len(planes)
     for i, (link, c, r) in enumerate(spheres):
         rb.sph_link[i], rb.sph_r[i] = int(link), float(r)
@@ -940,11 +946,12 @@ class BatchProblem:
         self.ctx.check(self.L.ilqr_problem_clearance_dev(self.h, C.byref(robot), C.byref(world), C.byref(out)))
 
     # ---- obstacle terms in the stage cost of the Riccati solvers (include/ilqr_hip.h "obstacle terms")
-    def set_obstacles(self, spheres, planes, obstacles, margin: float, weight: float, traj_per_set=None):
-        """Hinge penalty weight * max(0, margin - clearance)^2 on every (sphere, obstacle or plane) pair at every step (ilqr_problem_set_obstacles).
-        spheres, planes as clr_robot takes them (or a ClrRobot in `spheres` with planes None); obstacles [n_sets][n_obs][4] or None (planes only);
-        traj_per_set: None = one world for all.  The problem copies everything; it holds no plan afterwards."""
-        rb = spheres if isinstance(spheres, ClrRobot) else clr_robot(spheres, planes)
+    def set_obstacles(self, spheres, planes, obstacles, margin: float, weight: float, traj_per_set=None, self_pairs=None):
+        """Hinge penalty weight * max(0, margin - clearance)^2 on every (sphere, obstacle or plane) pair and every self pair at every step
+        (ilqr_problem_set_obstacles).  spheres, planes, self_pairs as clr_robot takes them (or a ClrRobot in `spheres` with planes and self_pairs
+        None); obstacles [n_sets][n_obs][4] or None (planes or self pairs only); traj_per_set: None = one world for all.  The problem copies
+        everything; it holds no plan afterwards."""
+        rb = spheres if isinstance(spheres, ClrRobot) else clr_robot(spheres, planes, self_pairs)
         tps = self.B if traj_per_set is None else int(traj_per_set)
         obs = _f64(obstacles) if obstacles is not None else np.zeros((self.B // tps if tps >= 1 else 0, 0, 4))
         if obs.ndim != 3 or obs.shape[2] != 4:

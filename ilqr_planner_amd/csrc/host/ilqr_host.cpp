@@ -1553,6 +1553,7 @@ static void clearance_structs(const ClearanceInputs& c, int n, int traj_per_set,
     if (ns < 1 || ns > ILQR_CLR_MAX_SPH) throw std::runtime_error("[clearance] 1 to 32 spheres are supported");
     if (c.sph_c.size() != 3 * ns || c.sph_r.size() != ns) throw std::runtime_error("[clearance] spheres: one centre of 3 entries and one radius per link");
     if (np > ILQR_CLR_MAX_PLANES || c.plane_n.size() != 3 * np) throw std::runtime_error("[clearance] planes: at most 8, one normal of 3 entries per offset");
+    if (c.self_pairs.size() % 2 != 0 || c.self_pairs.size() > 2 * ILQR_CLR_MAX_SELF) throw std::runtime_error("[clearance] self pairs: at most 64, two sphere indices each");
     if (c.n_sets < 0 || c.n_obs < 0 || c.obstacles.size() != (size_t)c.n_sets * c.n_obs * 4) throw std::runtime_error("[clearance] obstacles must be n_sets x n_obs x 4");
     std::memset(&rb, 0, sizeof(rb));
     rb.n_sph = (int)ns; rb.n_planes = (int)np;
@@ -1561,6 +1562,8 @@ static void clearance_structs(const ClearanceInputs& c, int n, int traj_per_set,
     std::copy(c.sph_r.begin(), c.sph_r.end(), rb.sph_r);
     std::copy(c.plane_n.begin(), c.plane_n.end(), &rb.plane_n[0][0]);
     std::copy(c.plane_d.begin(), c.plane_d.end(), rb.plane_d);
+    rb.n_self = (int)(c.self_pairs.size() / 2);
+    std::copy(c.self_pairs.begin(), c.self_pairs.end(), &rb.self_pair[0][0]);
     std::memset(&w, 0, sizeof(w));
     w.obs = c.n_obs > 0 ? c.obstacles.data() : nullptr;
     w.n_obs = c.n_obs;

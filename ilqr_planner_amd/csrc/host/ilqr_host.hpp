@@ -470,6 +470,7 @@ struct ClearanceInputs {
     std::vector<double> sph_c, sph_r; // [n_sph][3] in the link's frame, [n_sph]
     std::vector<double> plane_n, plane_d;   // [n_planes][3] unit normals, [n_planes]: n . p >= d
     std::vector<double> obstacles;    // [n_sets][n_obs][4] = (cx, cy, cz, R), R < 0: unused slot
+    std::vector<int> self_pairs;      // [n_self][2] = (a, b): two of the robot's own spheres, a < b on different links (ilqr_clr_robot::self_pair)
     int n_sets = 0, n_obs = 0;
     double margin = 0;
     bool given() const { return !sph_link.empty(); }

@@ -106,14 +106,23 @@ static solver::BatchInputs batch_inputs(const py::object& U0, const py::object& 
     return in;
 }
 
-// spheres: [(link, (cx, cy, cz), r), ...] in chain order; planes: [((nx, ny, nz), d), ...] or None; obstacles: [n_sets][n_obs][4] or None
-static solver::ClearanceInputs clearance_inputs(const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin) {
+// spheres: [(link, (cx, cy, cz), r), ...] in chain order; planes: [((nx, ny, nz), d), ...] or None; obstacles: [n_sets][n_obs][4] or None;
+// self_pairs: [(a, b), ...] sphere indices or None
+static solver::ClearanceInputs clearance_inputs(const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin,
+                                                const py::object& self_pairs = py::none()) {
     solver::ClearanceInputs c;
     c.margin = margin;
     if (spheres.is_none()) {
-        if (!planes.is_none() || !obstacles.is_none()) throw std::runtime_error("[clearance] planes and obstacles need the robot's spheres");
+        if (!planes.is_none() || !obstacles.is_none() || !self_pairs.is_none()) throw std::runtime_error("[clearance] planes, obstacles and self pairs need the robot's spheres");
         return c;
     }
+    if (!self_pairs.is_none())
+        for (auto h : self_pairs.cast<py::list>()) {
+            py::tuple t = py::reinterpret_borrow<py::object>(h).cast<py::tuple>();
+            if (t.size() != 2) throw std::runtime_error("[clearance] a self pair is (a, b)");
+            c.self_pairs.push_back(t[0].cast<int>());
+            c.self_pairs.push_back(t[1].cast<int>());
+        }
     for (auto h : spheres.cast<py::list>()) {
         py::tuple t = py::reinterpret_borrow<py::object>(h).cast<py::tuple>();
         if (t.size() != 3) throw std::runtime_error("[clearance] a sphere is (link, (cx, cy, cz), r)");
@@ -144,8 +153,8 @@ static solver::ClearanceInputs clearance_inputs(const py::object& spheres, const
 
 // solve_batch(..., spheres, planes, obstacles, margin, obstacle_weight): the obstacle terms of the stage cost (weight 0: none)
 static solver::BatchInputs obstacle_terms(solver::BatchInputs in, const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin,
-                                          double weight) {
-    in.obstacles = clearance_inputs(spheres, planes, obstacles, margin);
+                                          double weight, const py::object& self_pairs) {
+    in.obstacles = clearance_inputs(spheres, planes, obstacles, margin, self_pairs);
     in.obstacle_weight = weight;
     if (weight != 0 && !in.obstacles.given()) throw std::runtime_error("[solve_batch] obstacle_weight needs the robot's spheres");
     return in;
@@ -162,9 +171,9 @@ static solver::BatchInputs obstacle_path(solver::BatchInputs in, const std::stri
 // solve_multistart(..., S, seed, sigma_u, coarse_iter): sigma_u None (0), a scalar or nb_ctrl_var values
 static solver::MultiStartInputs multistart_inputs(int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter, const py::object& spheres = py::none(),
                                                   const py::object& planes = py::none(), const py::object& obstacles = py::none(), double margin = 0.0,
-                                                  double obstacle_weight = 0.0) {
+                                                  double obstacle_weight = 0.0, const py::object& self_pairs = py::none()) {
     solver::MultiStartInputs ms;
-    ms.clearance = clearance_inputs(spheres, planes, obstacles, margin);
+    ms.clearance = clearance_inputs(spheres, planes, obstacles, margin, self_pairs);
     ms.obstacle_weight = obstacle_weight;
     if (obstacle_weight != 0 && !ms.clearance.given()) throw std::runtime_error("[solve_multistart] obstacle_weight needs the robot's spheres");
     ms.S = S;
@@ -450,15 +459,15 @@ PYBIND11_MODULE(PyLQR, m) {
     // clearance(system, X[n][T][n_x], spheres, ...): any trajectories in the system's state layout against sphere obstacles and planes
     m.def("clearance",
           [](const std::shared_ptr<sys::System>& s, const py::object& X, const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin,
-             int traj_per_set, int stats_group) {
+             int traj_per_set, int stats_group, const py::object& sp) {
               arr_t x = arr_t::ensure(X);
               if (!x || x.ndim() != 3) throw std::runtime_error("[clearance] X must be n x T x nb_state_var");
               if (spheres.is_none()) throw std::runtime_error("[clearance] spheres are required");
               return solver::clearance(*s, std::vector<double>(x.data(), x.data() + x.size()), (int)x.shape(0), (int)x.shape(1),
-                                       clearance_inputs(spheres, planes, obstacles, margin), traj_per_set, stats_group);
+                                       clearance_inputs(spheres, planes, obstacles, margin, sp), traj_per_set, stats_group);
           },
           py::arg("system"), py::arg("X"), py::arg("spheres"), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0,
-          py::arg("traj_per_set") = 0, py::arg("stats_group") = 0);
+          py::arg("traj_per_set") = 0, py::arg("stats_group") = 0, py::arg("self_pairs") = py::none());
     py::class_<solver::ClosedLoopResult>(m_sol, "ClosedLoopResult")
         .def_property_readonly("cost", [](const solver::ClosedLoopResult& r) { return shaped(r.cost, {r.B, r.S}); })
         .def_property_readonly("X", [](const solver::ClosedLoopResult& r) { return shaped(r.X, {r.B, r.S, r.T, r.n_x}); })
@@ -500,24 +509,24 @@ PYBIND11_MODULE(PyLQR, m) {
         .def("solve", &solver::ILQRRecursive::solve, py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("cb"))
         .def("solve_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg,
-                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow, const std::string& op) {
-                 return self.solveBatch(obstacle_path(obstacle_terms(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), spheres, planes, obstacles, margin, ow), op, "solve_batch"), nb_iter, ls, es);
+                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow, const std::string& op, const py::object& sp) {
+                 return self.solveBatch(obstacle_path(obstacle_terms(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), spheres, planes, obstacles, margin, ow, sp), op, "solve_batch"), nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
              py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("spheres") = py::none(), py::arg("planes") = py::none(),
-             py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0, py::arg("obstacle_path") = "generic")
+             py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0, py::arg("obstacle_path") = "generic", py::arg("self_pairs") = py::none())
         // every task (the batch of U0 / q0 / kp_targets) from S starts: solve_batch's arguments, then the starts
         .def("solve_multistart",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, int S, unsigned long long seed, const py::object& sigma_u, int coarse_iter,
                 const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& spheres, const py::object& planes,
-                const py::object& obstacles, double margin, double ow, const std::string& op) {
-                 return self.solveMultiStart(obstacle_path(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), op, "solve_multistart"), multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow),
+                const py::object& obstacles, double margin, double ow, const std::string& op, const py::object& sp) {
+                 return self.solveMultiStart(obstacle_path(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), op, "solve_multistart"), multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow, sp),
                                              nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(),
              py::arg("coarse_iter") = 1, py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
              py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0,
-             py::arg("obstacle_path") = "generic")
+             py::arg("obstacle_path") = "generic", py::arg("self_pairs") = py::none())
         .def("closed_loop_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
                 const py::object& x0, const py::object& w, bool ff, const py::object& samples, const py::object& seed, const py::object& sigma_w,
@@ -543,26 +552,26 @@ PYBIND11_MODULE(PyLQR, m) {
         .def("solve_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
                 const py::object& kp, bool pg, const py::object& agp, const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin,
-                double ow, const std::string& op) {
-                 return self.solveBatch(obstacle_path(obstacle_terms(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), spheres, planes, obstacles, margin, ow), op, "solve_batch"), nb_iter, lag, pen,
+                double ow, const std::string& op, const py::object& sp) {
+                 return self.solveBatch(obstacle_path(obstacle_terms(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), spheres, planes, obstacles, margin, ow, sp), op, "solve_batch"), nb_iter, lag, pen,
                                         sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false,
              py::arg("al_gains_penalty") = py::none(), py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(),
-             py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0, py::arg("obstacle_path") = "generic")
+             py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0, py::arg("obstacle_path") = "generic", py::arg("self_pairs") = py::none())
         .def("solve_multistart",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, int S, unsigned long long seed,
                 const py::object& sigma_u, int coarse_iter, const py::object& q0, const py::object& dq0, const py::object& kp, bool pg, const py::object& agp,
-                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow, const std::string& op) {
+                const py::object& spheres, const py::object& planes, const py::object& obstacles, double margin, double ow, const std::string& op, const py::object& sp) {
                  return self.solveMultiStart(obstacle_path(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), op, "solve_multistart"),
-                                             multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow), nb_iter, lag, pen, sc, ls, es);
+                                             multistart_inputs(S, seed, sigma_u, coarse_iter, spheres, planes, obstacles, margin, ow, sp), nb_iter, lag, pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("S"), py::arg("seed") = 0, py::arg("sigma_u") = py::none(), py::arg("coarse_iter") = 1, py::arg("q0") = py::none(),
              py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(), py::arg("plan_gains") = false, py::arg("al_gains_penalty") = py::none(),
              py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("margin") = 0.0, py::arg("obstacle_weight") = 0.0,
-             py::arg("obstacle_path") = "generic")
+             py::arg("obstacle_path") = "generic", py::arg("self_pairs") = py::none())
         .def_static("final_penalty", &solver::AL_ILQR::finalPenalty, py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"))
         .def("closed_loop_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,

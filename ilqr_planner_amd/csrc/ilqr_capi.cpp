@@ -81,7 +81,7 @@ struct ilqr_problem {
     // memory of this problem; `obs` is what the kernels are given.  Problems with these terms run on the generic kernels unless the context's
     // obstacle path sends them to the cooperative ones (plan_input).
     bool has_obs = false;
-    ObsArgs obs = {};
+    ObsProblem obs = {};
     size_t obs_sets_bytes = 0;
     // the cooperative path of these terms (RiccatiPlan::obs_dense), allocated at its first solve: l_x | l_xx of every stage (one kpd entry per
     // step) and the obstacle cost of every (step, step size) of a line search
@@ -753,7 +753,8 @@ static void launch_sweep(const ilqr_problem* p, const RiccatiPlan& pl, int h, bo
 // (RiccatiPlan::obs_dense) k_stage_dense then forms l_x | l_xx of every stage for k_backward_si_dpp<.., SW_DENSE>, behind k_kp_derivs.
 static void launch_obs_terms(const ilqr_problem* p, const RiccatiPlan& pl, const Bufs& bf, int B, hipStream_t st) {
     if (!p->has_obs) return;
-    launch_obs_derivs(bf, p->obs, B, p->T, p->dims.n_x, 0, st);
+    if (p->obs.n_anchor) launch_obs_derivs_self(bf, p->obs, B, p->T, p->dims.n_x, 0, st);   // a geometry with self pairs
+    else launch_obs_derivs(bf, p->obs, B, p->T, p->dims.n_x, 0, st);
     if (pl.obs_dense) launch_stage_dense(bf, p->obs, p->obs_dense.sd, B, p->T, 0, st);
 }
 // The buffers of the cooperative path, at its first use; freed with the problem
@@ -793,6 +794,7 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
         const Bufs& bf = hv[h].bufs;
         ProfScope ps(c, ILQR_PROF_ROLLOUT);
         if (pl.init == Init::Lti) launch_init_lti(kind, nd, bf, hv[h].B, hv[h].st);
+        else if (p->has_obs && p->obs.n_anchor) launch_init_self(kind, nd, al, bf, hv[h].B, hv[h].st, penalty0, p->obs);   // a geometry with self pairs
         else launch_init(kind, nd, al, bf, hv[h].B, hv[h].st, penalty0, p->has_obs ? &p->obs : nullptr);
         if (pl.obs_dense) launch_obs_ls(bf, p->obs, p->obs_dense.part, hv[h].B, T, p->dims.n_x, 1, 1, hv[h].st);  // the initial trajectory's obstacle cost joins cost, behind k_init_finish
         if (pl.init_al_update) {  // active-set weights of the initial trajectory: I_k = penalty * (g<0 && lambda==0 ? 0 : 1)
@@ -834,7 +836,10 @@ static int solve_riccati(ilqr_problem* p, bool al, int nb_iter, int lag, double 
                     case Forward::WaveDpp: launch_forward_wave(kind, true, bf, B, st, fi); break;
                     case Forward::Lin: launch_forward_lin(bf, B, st, fi); break;
                     case Forward::Mfma: launch_forward_tm(kind, nd, bf, B, st, fi); break;
-                    case Forward::Generic: launch_forward_generic(kind, nd, al, bf, B, st, fi, p->has_obs ? &p->obs : nullptr); break;
+                    case Forward::Generic:
+                        if (p->has_obs && p->obs.n_anchor) launch_forward_generic_self(kind, nd, al, bf, B, st, fi, p->obs);   // a geometry with self pairs
+                        else launch_forward_generic(kind, nd, al, bf, B, st, fi, p->has_obs ? &p->obs : nullptr);
+                        break;
                 }
             }
             if (pl.apply != Apply::None && (pl.apply != Apply::WaveLast || it == nb_iter - 1)) {
@@ -1792,9 +1797,31 @@ static int clr_check(ilqr_ctx* c, const std::string& fn, const ilqr_problem_desc
         if (!(std::fabs(std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]) - 1.0) <= 1e-9)) return no("plane_n[" + S(l) + "] is not a unit vector (| |n| - 1 | > 1e-9)");
         if (!std::isfinite(rb->plane_d[l])) return no("plane_d[" + S(l) + "] is not finite");
     }
+    if (rb->n_self < 0 || rb->n_self > ILQR_CLR_MAX_SELF) return no("n_self must be 0 .. " + S(ILQR_CLR_MAX_SELF) + " (got " + S(rb->n_self) + ")");
+    {
+        bool anchor[ILQR_CLR_MAX_SPH] = {};
+        int n_anchor = 0;
+        for (int e = 0; e < rb->n_self; e++) {
+            const int a = rb->self_pair[e][0], b = rb->self_pair[e][1];
+            const std::string pe = "self_pair[" + S(e) + "] = (" + S(a) + ", " + S(b) + ")";
+            if (a < 0 || a >= rb->n_sph || b < 0 || b >= rb->n_sph) return no(pe + " names a sphere outside 0 .. " + S(rb->n_sph - 1));
+            if (a >= b) return no(pe + " must have a < b");
+            if (rb->sph_link[a] == rb->sph_link[b]) return no(pe + ": both spheres are on link " + S(rb->sph_link[a]) + ", their distance is constant");
+            bool moves = false;
+            for (int s = rb->sph_link[a] + 1; s <= rb->sph_link[b]; s++) moves = moves || d.seg_joint[s] >= 0;
+            if (!moves) return no(pe + ": no moving joint lies between link " + S(rb->sph_link[a]) + " and link " + S(rb->sph_link[b]) + ", their distance is constant");
+            for (int f = 0; f < e; f++)
+                if (rb->self_pair[f][0] == a && rb->self_pair[f][1] == b) return no(pe + " repeats self_pair[" + S(f) + "]");
+            if (!anchor[a]) { anchor[a] = true; n_anchor++; }
+        }
+        if (n_anchor > ILQR_CLR_MAX_ANCHOR)
+            return no("the self pairs have " + S(n_anchor) + " distinct first members (anchors); at most " + S(ILQR_CLR_MAX_ANCHOR) + " are supported");
+    }
     if (w->n_obs < 0) return no("n_obs must be >= 0 (got " + S(w->n_obs) + ")");
     if (w->n_obs > CLR_MAX_OBS) return no("n_obs must be at most " + S(CLR_MAX_OBS) + " (got " + S(w->n_obs) + ")");
-    if (w->n_obs == 0 && rb->n_planes == 0) return no("nothing to keep clear of: n_obs = 0 and n_planes = 0");
+    if (rb->n_self > 0 && w->n_obs > CLR_MAX_OBS - ILQR_CLR_MAX_SPH)
+        return no("n_obs must be at most " + S(CLR_MAX_OBS - ILQR_CLR_MAX_SPH) + " with self pairs (got " + S(w->n_obs) + ")");
+    if (w->n_obs == 0 && rb->n_planes == 0 && rb->n_self == 0) return no("nothing to keep clear of: n_obs = 0 and n_planes = 0");
     if (w->n_obs > 0 && !w->obs) return no("obs is a null pointer with n_obs = " + S(w->n_obs));
     if (w->traj_per_set < 1 || n % w->traj_per_set != 0)
         return no("the number of trajectories (" + S(n) + ") is not a multiple of traj_per_set (" + S(w->traj_per_set) + ")");
@@ -1827,6 +1854,20 @@ static void clr_fill_geom(const ilqr_problem_desc& d, const ilqr_clr_robot& rb, 
     std::memcpy(g.sph_r, rb.sph_r, sizeof(double) * rb.n_sph);
     std::memcpy(g.plane_n, rb.plane_n, sizeof(double) * 3 * rb.n_planes);
     std::memcpy(g.plane_d, rb.plane_d, sizeof(double) * rb.n_planes);
+    // the self pairs: anchors in ascending sphere order, so that "slots ascending" is "anchors ascending"
+    g.n_self = rb.n_self;
+    for (int i = 0; i < ILQR_CLR_MAX_SPH; i++) g.self_slot[i] = -1;
+    for (int i = 0; i < rb.n_sph; i++) {
+        bool is_anchor = false;
+        for (int e = 0; e < rb.n_self; e++) is_anchor = is_anchor || rb.self_pair[e][0] == i;
+        if (!is_anchor) continue;
+        const int t = g.n_anchor++;
+        g.self_slot[i] = t;
+        g.anc_sph[t] = i;
+        g.anc_r[t] = rb.sph_r[i];
+        for (int s = 0; s <= rb.sph_link[i]; s++) g.anc_first[t] += d.seg_joint[s] >= 0;   // joints are numbered in chain order (lower_chain)
+    }
+    for (int e = 0; e < rb.n_self; e++) g.self_mask[rb.self_pair[e][1]] |= 1 << g.self_slot[rb.self_pair[e][0]];
 }
 
 // p: the problem form (the plan where it lies); else X[n][T][n_x] in the natural layout of d
@@ -1856,6 +1897,7 @@ static int clr_run(ilqr_ctx* c, const char* fn_, ilqr_problem* p, const ilqr_pro
     ClrArgs a;
     std::memset(&a, 0, sizeof(a));
     a.geom = (const ClrGeom*)cs.geom.ptr;
+    a.n_anchor = g.n_anchor;
     a.n = n; a.T = T; a.n_obs = w->n_obs; a.traj_per_set = w->traj_per_set;
     a.ws_clr = (double*)cs.ws.ptr;
     a.ws_code = (int*)(a.ws_clr + nT);
@@ -1970,6 +2012,7 @@ static int set_obstacles(ilqr_problem* p, const ilqr_clr_robot* rb, const ilqr_c
     if (bytes) HIPCHK(c, hipMemcpyAsync((void*)p->obs.obs, w->obs, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // g is on this stack; the caller's arrays may go away
     p->obs.n_obs = w->n_obs; p->obs.traj_per_set = w->traj_per_set; p->obs.margin = w->margin; p->obs.weight = weight;
+    p->obs.n_anchor = g.n_anchor;
     p->has_obs = true;
     return 0;
 }
@@ -2000,7 +2043,8 @@ static int obstacle_terms(ilqr_problem* p, double* cost, double* lx, double* lxx
     }
     {
         ProfScope ps(c, ILQR_PROF_OTHER);
-        launch_obs_derivs(p->bufs, p->obs, p->B, p->T, p->dims.n_x, 1, c->stream);
+        if (p->obs.n_anchor) launch_obs_derivs_self(p->bufs, p->obs, p->B, p->T, p->dims.n_x, 1, c->stream);
+        else launch_obs_derivs(p->bufs, p->obs, p->B, p->T, p->dims.n_x, 1, c->stream);
     }
     {
         ProfScope ps(c, ILQR_PROF_OTHER);

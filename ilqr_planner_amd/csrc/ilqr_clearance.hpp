@@ -26,7 +26,29 @@ struct ClrGeom {
     double sph_r[ILQR_CLR_MAX_SPH];
     double plane_n[ILQR_CLR_MAX_PLANES][3];
     double plane_d[ILQR_CLR_MAX_PLANES];
+    // The self pairs as the walk uses them (clr_fill_geom).  The distinct first members are the anchors, slots 0 .. n_anchor-1 in ascending sphere
+    // order; the walk keeps their world centres until it reaches the second members.
+    int n_self, n_anchor;
+    int self_slot[ILQR_CLR_MAX_SPH];    // the anchor slot of a sphere, or -1
+    int self_mask[ILQR_CLR_MAX_SPH];    // bit t: the sphere is the second member of a pair with anchor slot t
+    int anc_sph[ILQR_CLR_MAX_ANCHOR];   // the anchor's sphere index a
+    int anc_first[ILQR_CLR_MAX_ANCHOR]; // the first joint behind the anchor's link: the joints m >= anc_first move b and not a
+    double anc_r[ILQR_CLR_MAX_ANCHOR];  // r_a
 };
+
+// W[t] = w where t == slot; t[3] = W[slot]: an anchor's centre written and read by unrolled compares against the wave-uniform slot, so that W
+// stays in registers (the idiom of obs_state's A[m] / O[m]).
+__device__ __forceinline__ void clr_anchor_put(double (*W)[3], int slot, double wx, double wy, double wz) {
+#pragma unroll
+    for (int t = 0; t < ILQR_CLR_MAX_ANCHOR; t++)
+        if (t == slot) { W[t][0] = wx; W[t][1] = wy; W[t][2] = wz; }
+}
+__device__ __forceinline__ void clr_anchor_get(const double (*W)[3], int slot, double* c) {
+    c[0] = c[1] = c[2] = 0;
+#pragma unroll
+    for (int t = 0; t < ILQR_CLR_MAX_ANCHOR; t++)
+        if (t == slot) { c[0] = W[t][0]; c[1] = W[t][1]; c[2] = W[t][2]; }
+}
 
 // Where the trajectories, the obstacles and the workspace of a call lie
 struct ClrArgs {
@@ -36,6 +58,7 @@ struct ClrArgs {
     double* ws_clr;       // [n T] the clearance of every (trajectory, step), NaN on a bad step
     int* ws_code;         // [n T] sphere | obstacle << 5 of the step's minimum, -1 without one
     int qrow[7];          // the row of joint j's position within a state (private layout: through the index map of a narrow chain)
+    int n_anchor;         // host: the geometry's anchors; > 0 launches the self forms of the per-state kernels
 };
 
 // C = A B on row-major 3 x 3 matrices, one rounding per operation: the walks of clr_state and obs_state (ilqr_obstacle.hpp) share it

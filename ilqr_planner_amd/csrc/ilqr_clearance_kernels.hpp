@@ -5,8 +5,9 @@
 //
 //   clr_state    THE per-state function, shared by both entry points: the walk over the descriptor's segments (one rolled copy of the joint step,
 //                pose only, as the rolled form of fk<false>), the spheres by a cursor along the chain, the obstacle and plane loops and the key
-//                update.  Contraction is off, so the two callers -- which differ only in how a joint position is loaded -- return the same bytes
+//                update; the self pairs of a sphere behind its planes, against the anchors' centres kept in registers.  Contraction is off, so the two callers -- which differ only in how a joint position is loaded -- return the same bytes
 //                for the same states.  A joint position is loaded when the walk reaches its joint: no register array, nothing indexed.
+//   (k_clr_plan_self, k_clr_traj_self: the same two with clr_state<true>, launched for a geometry with self pairs)
 //   k_clr_plan   the plan where it lies: lanes along the batch (every load of a wave is one whole 512-byte run of a [row][Bp] row), steps on blockIdx.y
 //   k_clr_traj   natural layout: lanes along the flat (trajectory, step) index
 //   k_clr_fold   one lane per trajectory: its keys in ascending step order under the total order of include/ilqr_hip.h
@@ -23,12 +24,20 @@ namespace ilqr {
 struct ClrKey { double clr; int code; };   // a bad step: (NaN, -1); a step without an active obstacle or plane: (+inf, -1)
 
 // q(j): the position of joint j of this lane's state.  obs: this trajectory's set, [n_obs][4].
-template <class Q>
+// SELF: the form with the self-pair block; the launchers take it only for a geometry that has pairs (ClrArgs::n_anchor), so a geometry without
+// them runs the code it ran before there were any.
+template <bool SELF, class Q>
 __device__ __forceinline__ ClrKey clr_state(const ClrGeom& g, const double* __restrict__ obs, int n_obs, Q q) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
+    double W[SELF ? ILQR_CLR_MAX_ANCHOR : 1][3];   // the anchors' centres (self pairs); a slot is written before any pair reads it
+    if (SELF) {
+#pragma unroll
+        for (int t = 0; t < ILQR_CLR_MAX_ANCHOR; t++) W[t][0] = W[t][1] = W[t][2] = 0;
+    }
+    const int n_anchor = SELF ? g.n_anchor : 0, self_base = n_obs + g.n_planes;
     ClrKey key{INFINITY, -1};
     bool bad = false;
     int cur = 0;
@@ -77,35 +86,60 @@ __device__ __forceinline__ ClrKey clr_state(const ClrGeom& g, const double* __re
                 const double d = ((((g.plane_n[l][0] * wx + g.plane_n[l][1] * wy) + g.plane_n[l][2] * wz)) - g.plane_d[l]) - r;
                 if (d < key.clr) { key.clr = d; key.code = cur | ((n_obs + l) << 5); }
             }
+            if constexpr (SELF) if (n_anchor) {   // wave-uniform, as mask and slot are
+                const int mask = g.self_mask[cur];
+#pragma unroll 1
+                for (int t = 0; t < n_anchor; t++) {   // the anchors ascending
+                    if (!(mask >> t & 1)) continue;
+                    double c[3];
+                    clr_anchor_get(W, t, c);
+                    const double dx = wx - c[0], dy = wy - c[1], dz = wz - c[2];
+                    const double d = (sqrt((dx * dx + dy * dy) + dz * dz) - r) - g.anc_r[t];
+                    if (d < key.clr) { key.clr = d; key.code = cur | ((self_base + g.anc_sph[t]) << 5); }
+                }
+                clr_anchor_put(W, g.self_slot[cur], wx, wy, wz);
+            }
         }
     }
     if (bad) { key.clr = (double)NAN; key.code = -1; }
     return key;
 }
 
-__global__ __launch_bounds__(256) void k_clr_plan(const double* __restrict__ X0, const double* __restrict__ X1, const int* __restrict__ cur, int NX, int Bp,
-                                                  int k0, ClrArgs a) {
+template <bool SELF>
+__device__ __forceinline__ void clr_plan_body(const double* __restrict__ X0, const double* __restrict__ X1, const int* __restrict__ cur, int NX, int Bp, int k0,
+                                              const ClrArgs& a) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     const int k = k0 + (int)blockIdx.y;
     if (b >= a.n) return;
     const double* x = (cur[b] ? X1 : X0) + (size_t)k * (size_t)NX * (size_t)Bp + (size_t)b;
     const size_t Bps = (size_t)Bp;
-    const ClrKey key = clr_state(*a.geom, a.obs + (size_t)(b / a.traj_per_set) * (size_t)a.n_obs * 4, a.n_obs,
-                                 [&](int j) { return x[(size_t)a.qrow[j] * Bps]; });
+    const ClrKey key = clr_state<SELF>(*a.geom, a.obs + (size_t)(b / a.traj_per_set) * (size_t)a.n_obs * 4, a.n_obs,
+                                       [&](int j) { return x[(size_t)a.qrow[j] * Bps]; });
     const size_t w = (size_t)k * (size_t)a.n + (size_t)b;
     a.ws_clr[w] = key.clr;
     a.ws_code[w] = key.code;
 }
+__global__ __launch_bounds__(256) void k_clr_plan(const double* __restrict__ X0, const double* __restrict__ X1, const int* __restrict__ cur, int NX, int Bp,
+                                                  int k0, ClrArgs a) {
+    clr_plan_body<false>(X0, X1, cur, NX, Bp, k0, a);
+}
+__global__ __launch_bounds__(256) void k_clr_plan_self(const double* __restrict__ X0, const double* __restrict__ X1, const int* __restrict__ cur, int NX,
+                                                       int Bp, int k0, ClrArgs a) {
+    clr_plan_body<true>(X0, X1, cur, NX, Bp, k0, a);
+}
 
-__global__ __launch_bounds__(256) void k_clr_traj(const double* __restrict__ X, int n_x, ClrArgs a) {
+template <bool SELF>
+__device__ __forceinline__ void clr_traj_body(const double* __restrict__ X, int n_x, const ClrArgs& a) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;   // n T may pass 2^31
     if (t >= (size_t)a.n * (size_t)a.T) return;
     const int i = (int)(t / (size_t)a.T);
     const double* x = X + t * (size_t)n_x;
-    const ClrKey key = clr_state(*a.geom, a.obs + (size_t)(i / a.traj_per_set) * (size_t)a.n_obs * 4, a.n_obs, [&](int j) { return x[a.qrow[j]]; });
+    const ClrKey key = clr_state<SELF>(*a.geom, a.obs + (size_t)(i / a.traj_per_set) * (size_t)a.n_obs * 4, a.n_obs, [&](int j) { return x[a.qrow[j]]; });
     a.ws_clr[t] = key.clr;
     a.ws_code[t] = key.code;
 }
+__global__ __launch_bounds__(256) void k_clr_traj(const double* __restrict__ X, int n_x, ClrArgs a) { clr_traj_body<false>(X, n_x, a); }
+__global__ __launch_bounds__(256) void k_clr_traj_self(const double* __restrict__ X, int n_x, ClrArgs a) { clr_traj_body<true>(X, n_x, a); }
 
 // Steps ascend, so a strict `<` keeps the lowest step of equal clearances; sphere and obstacle were settled within the step.
 __global__ __launch_bounds__(256) void k_clr_fold(double* __restrict__ ws_clr, const int* __restrict__ ws_code, int n, int T, size_t stride_i, size_t stride_k,
@@ -164,13 +198,15 @@ __global__ __launch_bounds__(256) void k_clr_stats(const double* __restrict__ sr
 void launch_clr_plan(const double* X0, const double* X1, const int* cur, int NX, int Bp, const ClrArgs& a, hipStream_t st) {
     for (int k0 = 0; k0 < a.T; k0 += 65535) {   // the y extent of a grid
         const int rows = a.T - k0 < 65535 ? a.T - k0 : 65535;
-        hipLaunchKernelGGL(k_clr_plan, dim3((a.n + 255) / 256, rows), dim3(256), 0, st, X0, X1, cur, NX, Bp, k0, a);
+        if (a.n_anchor) hipLaunchKernelGGL(k_clr_plan_self, dim3((a.n + 255) / 256, rows), dim3(256), 0, st, X0, X1, cur, NX, Bp, k0, a);
+        else hipLaunchKernelGGL(k_clr_plan, dim3((a.n + 255) / 256, rows), dim3(256), 0, st, X0, X1, cur, NX, Bp, k0, a);
     }
 }
 
 void launch_clr_traj(const double* X, int n_x, const ClrArgs& a, hipStream_t st) {
     const size_t total = (size_t)a.n * (size_t)a.T;
-    hipLaunchKernelGGL(k_clr_traj, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, X, n_x, a);
+    if (a.n_anchor) hipLaunchKernelGGL(k_clr_traj_self, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, X, n_x, a);
+    else hipLaunchKernelGGL(k_clr_traj, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, X, n_x, a);
 }
 
 void launch_clr_fold(const ClrArgs& a, size_t stride_i, size_t stride_k, double margin, const ilqr_clr_out& out, hipStream_t st) {

@@ -7,7 +7,8 @@
 
 namespace ilqr {
 
-struct ObsArgs;  // ilqr_obstacle.hpp: a problem's obstacle terms; a null pointer below = the problem has none
+struct ObsArgs;     // ilqr_obstacle.hpp: a problem's obstacle terms; a null pointer below = the problem has none
+struct ObsProblem;  // ilqr_obstacle.hpp: ObsArgs with what the host alone reads
 
 // All trajectory-like buffers are [row][Bp] with the (padded) batch innermost; row = t * DIM + component.
 struct Bufs {
@@ -77,7 +78,7 @@ struct FwdArgs {
     // RiccatiPlan::obs_dense (null otherwise).  Read by launch_forward_wave alone, on the host, never by a kernel: between the rollout and k_select it
     // runs launch_obs_ls, which adds the obstacle cost of every step size to Bufs::lsc.  obs: the problem's terms; obs_part: [T][16][Bp] scratch;
     // obs_T: the horizon (the descriptor is device memory).
-    const ObsArgs* obs;
+    const ObsProblem* obs;
     double* obs_part;
     int obs_T;
 };

@@ -6,6 +6,7 @@
 #pragma once
 #include "ilqr_kernels.hpp"
 #include "ilqr_obstacle.hpp"
+#include "ilqr_step.hpp"
 
 namespace ilqr {
 
@@ -56,7 +57,8 @@ __global__ __launch_bounds__(64) void k_stage_dense(Bufs a, const double* __rest
 
 // c_obs of step k at step size index i of every active instance, one lane per (instance, step, step size): grid (ceil(B / 64), T, n_alpha), lanes
 // along the batch.  The position is k_apply's: x(1) at i = 0, fma(2^-i, x(1) - xbar, xbar) beyond; init: xbar itself (the initial trajectory).
-__global__ __launch_bounds__(64) void k_obs_ls(Bufs a, ObsArgs o, double* __restrict__ part, int nx, int k0, int init) {
+template <bool SELF>
+__device__ __forceinline__ void obs_ls_body(const Bufs& a, const ObsArgs& o, double* __restrict__ part, int nx, int k0, int init) {
     const DevDesc& d = *a.desc;
     const int b = blockIdx.x * 64 + threadIdx.x;
     const int k = k0 + (int)blockIdx.y, i = blockIdx.z;   // uniform
@@ -69,7 +71,7 @@ __global__ __launch_bounds__(64) void k_obs_ls(Bufs a, ObsArgs o, double* __rest
     const double* x1 = a.X[1 - cur] + off;
     const double aa = ldexp(1.0, -i);
     const int mode = init ? 0 : (i == 0 ? 1 : 2);   // uniform
-    const double c = obs_state<false>(*o.geom, o.obs + (size_t)(b / o.traj_per_set) * (size_t)o.n_obs * 4, o.n_obs, o.margin, o.weight,
+    const double c = obs_state<false, SELF>(*o.geom, o.obs + (size_t)(b / o.traj_per_set) * (size_t)o.n_obs * 4, o.n_obs, o.margin, o.weight,
                                       [&](int j) {
                                           if (mode == 0) return xb[(size_t)j * Bps];
                                           const double v1 = x1[(size_t)j * Bps];
@@ -79,6 +81,26 @@ __global__ __launch_bounds__(64) void k_obs_ls(Bufs a, ObsArgs o, double* __rest
                                       },
                                       nullptr, nullptr);
     part[((size_t)k * OBS_LS_ROWS + (size_t)i) * Bps + (size_t)b] = c;
+}
+__global__ __launch_bounds__(64) void k_obs_ls(Bufs a, ObsArgs o, double* __restrict__ part, int nx, int k0, int init) { obs_ls_body<false>(a, o, part, nx, k0, init); }
+__global__ __launch_bounds__(64) void k_obs_ls_self(Bufs a, ObsArgs o, double* __restrict__ part, int nx, int k0, int init) { obs_ls_body<true>(a, o, part, nx, k0, init); }
+// k_obs_derivs (ilqr_kernels.hip) for a geometry with self pairs: the same text around obs_state<true, true>.  It lives here and not beside
+// k_obs_derivs for the reason at the top of this file: ilqr_kernels.hip's code object is byte for byte what it was before there were self pairs.
+__global__ __launch_bounds__(64) void k_obs_derivs_self(Bufs a, ObsArgs o, int nx, int k0, int all) {
+    const DevDesc& d = *a.desc;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    const int k = k0 + (int)blockIdx.y;
+    if (b >= d.B) return;
+    if (!all && !a.active[b]) return;
+    const size_t Bps = (size_t)d.Bp;
+    const double* x = a.X[a.cur[b]] + (size_t)k * (size_t)nx * Bps + (size_t)b;
+    double lx[7], lxx[28];
+    const double c = obs_state<true, true>(*o.geom, o.obs + (size_t)(b / o.traj_per_set) * (size_t)o.n_obs * 4, o.n_obs, o.margin, o.weight,
+                                           [&](int j) { return x[(size_t)j * Bps]; }, lx, lxx);
+    double* out = o.obd + (size_t)k * OBS_W * Bps + (size_t)b;
+    out[0] = c;
+    UNR for (int i = 0; i < 7; i++) out[(size_t)(OBS_LX + i) * Bps] = lx[i];
+    UNR for (int e = 0; e < 28; e++) out[(size_t)(OBS_LXX + e) * Bps] = lxx[e];
 }
 // The sum over the steps in ascending k, one lane per (instance, step size): the order depends on T alone.  Line search: joins the limit cost the
 // rollout left in lsc, which select_decide adds to the task cost.  init: joins the initial trajectory's cost behind k_init_finish.
@@ -105,11 +127,51 @@ void launch_stage_dense(const Bufs& a, const ObsArgs& o, double* sd, int B, int 
         hipLaunchKernelGGL(k_stage_dense, dim3((B + 63) / 64, rows), dim3(64), 0, st, a, (const double*)o.obd, sd, k0, all);
     }
 }
-void launch_obs_ls(const Bufs& a, const ObsArgs& o, double* part, int B, int T, int nx, int n_alpha, int init, hipStream_t st) {
+// ---- the sequential rollouts of the generic set for a geometry with self pairs: the templates of ilqr_rollout_kernels.hpp with ObsSelfArgs.
+// obs_state<false, true> is inlined (in ilqr_kernels.hip the pairless term is a call, obs_cost_call): a kernel has the geometry pointer in
+// scalar registers, and no function boundary makes it save registers on the stack.  The joint positions are picked by a compare chain on the
+// (uniform) joint index: no private array is indexed.
+ILQR_DEV double obs_stage_cost(ObsSelfArgs o, int b, const double* x) {
+    const double q0 = x[0], q1 = x[1], q2 = x[2], q3 = x[3], q4 = x[4], q5 = x[5], q6 = x[6];
+    return obs_state<false, true>(*o.geom, o.obs + (size_t)(b / o.traj_per_set) * (size_t)o.n_obs * 4, o.n_obs, o.margin, o.weight,
+                                  [&](int j) { return j == 0 ? q0 : j == 1 ? q1 : j == 2 ? q2 : j == 3 ? q3 : j == 4 ? q4 : j == 5 ? q5 : q6; }, nullptr, nullptr);
+}
+#include "ilqr_rollout_kernels.hpp"
+
+void launch_init_self(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, double penalty, const ObsArgs& o) {
+    ObsSelfArgs os;
+    static_cast<ObsArgs&>(os) = o;
+    SysAll::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if (al) hipLaunchKernelGGL((k_init_rollout<S, true, ObsSelfArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty, os);
+        else hipLaunchKernelGGL((k_init_rollout<S, false, ObsSelfArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, penalty, os);
+    });
+}
+void launch_forward_generic_self(int kind, int nd, bool al, const Bufs& a, int B, hipStream_t st, const FwdArgs& f, const ObsArgs& o) {
+    ObsSelfArgs os;
+    static_cast<ObsArgs&>(os) = o;
+    SysAll::dispatch(kind, nd, [&](auto s) {
+        using S = decltype(s);
+        if (al)
+            hipLaunchKernelGGL((k_forward<S, true, ObsSelfArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
+                               f.penalty_update, f.do_update, f.nb_iter, os);
+        else
+            hipLaunchKernelGGL((k_forward<S, false, ObsSelfArgs>), dim3((B + 63) / 64), dim3(64), 0, st, a, f.it, f.line_search, f.early_stop, f.penalty_roll,
+                               f.penalty_update, f.do_update, f.nb_iter, os);
+    });
+}
+void launch_obs_derivs_self(const Bufs& a, const ObsArgs& o, int B, int T, int nx, int all, hipStream_t st) {
+    for (int k0 = 0; k0 < T; k0 += 65535) {   // the y extent of a grid
+        const int rows = T - k0 < 65535 ? T - k0 : 65535;
+        hipLaunchKernelGGL(k_obs_derivs_self, dim3((B + 63) / 64, rows), dim3(64), 0, st, a, o, nx, k0, all);
+    }
+}
+void launch_obs_ls(const Bufs& a, const ObsProblem& o, double* part, int B, int T, int nx, int n_alpha, int init, hipStream_t st) {
     const int na = init ? 1 : (n_alpha < OBS_LS_ROWS ? n_alpha : OBS_LS_ROWS);
     for (int k0 = 0; k0 < T; k0 += 65535) {   // the y extent of a grid
         const int rows = T - k0 < 65535 ? T - k0 : 65535;
-        hipLaunchKernelGGL(k_obs_ls, dim3((B + 63) / 64, rows, na), dim3(64), 0, st, a, o, part, nx, k0, init);
+        if (o.n_anchor) hipLaunchKernelGGL(k_obs_ls_self, dim3((B + 63) / 64, rows, na), dim3(64), 0, st, a, o, part, nx, k0, init);
+        else hipLaunchKernelGGL(k_obs_ls, dim3((B + 63) / 64, rows, na), dim3(64), 0, st, a, o, part, nx, k0, init);
     }
     hipLaunchKernelGGL(k_obs_ls_sum, dim3((B + 63) / 64, na), dim3(64), 0, st, a, (const double*)part, T, init);
 }

@@ -580,8 +580,8 @@ int ilqr_problem_get_at_dev(ilqr_problem* p, int n, const int* index, double* X,
 /* ---- clearance: the distance of plans and executions from sphere obstacles and the planes of the cell (no reference function) ---------------
  * The geometric judgement of trajectories on the device: nothing is brought to the host, and no solver gets an obstacle term -- the calls score
  * trajectories that exist; choosing among starts with their `eligible` is a filter, not avoidance.  Clearance is judged at the T states of a
- * trajectory only: nothing is said about the motion between two steps (no swept volumes), about the robot against itself, or about any shape but
- * spheres and half-spaces.  Under ilqr_profile_enable all of it is charged to ILQR_PROF_OTHER.
+ * trajectory only: nothing is said about the motion between two steps (no swept volumes) or about any shape but spheres and half-spaces; the
+ * robot against itself is judged on the self pairs the caller names (below), not on every pair of its spheres.  Under ilqr_profile_enable all of it is charged to ILQR_PROF_OTHER.
  *
  * Robot (ilqr_clr_robot): n_sph spheres, 1 .. ILQR_CLR_MAX_SPH.  Sphere i is carried by link sph_link[i], has the centre sph_c[i] in that link's
  *   frame and the radius sph_r[i] >= 0.  Link s in 0 .. n_seg-1 is the frame behind segment s of the descriptor's chain,
@@ -591,18 +591,25 @@ int ilqr_problem_get_at_dev(ilqr_problem* p, int n, const int* index, double* X,
  * Obstacles (ilqr_clr_world): obs[n_sets][n_obs][4] = (cx, cy, cz, R) in the base frame; a slot with R < 0 is unused, so sets may hold different
  *   numbers.  Trajectory i belongs to set i / traj_per_set; n % traj_per_set == 0 and n_sets == n / traj_per_set (one world for all:
  *   traj_per_set = n).
+ * Self pairs (n_self, 0 .. ILQR_CLR_MAX_SELF; a zeroed tail of the struct means none): self_pair[e] = (a, b) names two of the robot's own spheres
+ *   with a < b and sph_link[a] < sph_link[b], and at least one moving segment s with sph_link[a] < s <= sph_link[b] (otherwise the pair's distance
+ *   is a constant of the geometry).  The spheres that appear as a first member a are the anchors; at most ILQR_CLR_MAX_ANCHOR of them may be
+ *   distinct (the walk keeps an anchor's centre until it reaches b, and the limit lets it do so in registers).  No pair may be given twice.
  * The clearance of a state is the minimum over the pairs (i, j) of
  *       (|p_i - o_j| - r_i) - R_j   for the active obstacle j < n_obs,          (n_l . p_i - d_l) - r_i   for plane l, j = n_obs + l,
+ *       (|p_b - p_a| - r_b) - r_a   for the self pair (a, b), as the pair (i, j) = (b, n_obs + n_planes + a): the numbering continues the
+ *                                   obstacles, then the planes, then the robot's own spheres; evaluated at sphere b behind b's obstacles and
+ *                                   planes, the anchors ascending,
  *   p_i being the centre of sphere i in the base frame at the state's joint positions: the first dof entries of x in the user's layout, for every
  *   system kind and nb_deriv 1 and 2 (velocities and the time state play no part).  Ties go to the lowest i, then the lowest j.  Without an
- *   active obstacle and without a plane the clearance is +inf.  A step whose clearance is neither finite nor +inf is a bad step: one with a NaN
+ *   active obstacle, a plane or a self pair the clearance is +inf.  A step whose clearance is neither finite nor +inf is a bad step: one with a NaN
  *   or infinite position of a joint that moves a sphere (a joint at or before the last sphere's link; joints behind it are not read).
  * The clearance of a trajectory is the minimum over its steps k = 0 .. T-1 in the total order "bad steps first (the lowest k), then
  *   (clearance, k, i, j) lexicographic".  The order is total, so no result depends on how the kernels map steps to lanes.
  * Outputs (ilqr_clr_out; each may be NULL, not all):
  *   clr[n][T]       the clearance of every step, NaN on a bad step
  *   clr_min[n]      of the trajectory; NaN if it has a bad step
- *   clr_at[n][3]    (step, sphere, obstacle index j) of the minimum; (k, -1, -1) for a bad step; (0, -1, -1) if +inf throughout (ints)
+ *   clr_at[n][3]    (step, sphere, pair index j: obstacle, plane or own sphere as numbered above) of the minimum; (k, -1, -1) for a bad step; (0, -1, -1) if +inf throughout (ints)
  *   n_below[n]      the good steps with clearance < margin (strict; ints)
  *   eligible[n]     1 iff there is no bad step and clr_min >= margin: the array ilqr_problem_select takes (ints)
  *   stats[n / stats_group][ILQR_CLR_STATS] = { mean, min, n_hit, n_bad } over clr_min of the group's trajectories in index order: mean is the sum
@@ -620,13 +627,17 @@ int ilqr_problem_get_at_dev(ilqr_problem* p, int n, const int* index, double* X,
  *   (ilqr_dims_of), e.g. the X[B][S][T][n_x] of a closed-loop call with n = B S, traj_per_set = stats_group = S.  Of desc only kind, nb_deriv, dof
  *   and the chain are read.  Given the same states the two calls return the same bytes.
  * Refused, each with a text of its own: a null struct; n_sph outside 1 .. 32; a sph_link outside -1 .. n_seg-1 or a decreasing one; a negative or
- * non-finite radius, a non-finite centre; n_planes outside 0 .. 8, a non-unit or non-finite normal, a non-finite d; n_obs < 0 (or beyond 2^26 - 8),
- * n_obs == 0 with no plane, obs NULL with n_obs > 0; the set and stats divisibility rules; a NaN margin; all outputs NULL; stats with
+ * non-finite radius, a non-finite centre; n_planes outside 0 .. 8, a non-unit or non-finite normal, a non-finite d; n_obs < 0 (or beyond 2^26 - 8, with self
+ * pairs 2^26 - 8 - 32: the pair index shares an int with the sphere's), n_obs == 0 with no plane and no self pair, obs NULL with n_obs > 0; n_self
+ * outside 0 .. 64, a self pair's index outside 0 .. n_sph-1, a >= b, the two spheres on one link or with no moving joint between, a repeated
+ * pair, more than 8 distinct anchors; the set and stats divisibility rules; a NaN margin; all outputs NULL; stats with
  * stats_group < 1; a descriptor without a chain (n_seg < 1) or with a chain the lowering refuses; n < 1 or T < 1; no plan (problem form).  The host
  * forms also refuse a non-finite obstacle entry and name it. */
 #define ILQR_CLR_MAX_SPH 32
 #define ILQR_CLR_MAX_PLANES 8
 #define ILQR_CLR_STATS 4
+#define ILQR_CLR_MAX_SELF 64
+#define ILQR_CLR_MAX_ANCHOR 8
 typedef struct {
     int n_sph;
     int sph_link[ILQR_CLR_MAX_SPH];
@@ -635,6 +646,8 @@ typedef struct {
     int n_planes;
     double plane_n[ILQR_CLR_MAX_PLANES][3];
     double plane_d[ILQR_CLR_MAX_PLANES];
+    int n_self;
+    int self_pair[ILQR_CLR_MAX_SELF][2];   /* (a, b): sphere indices */
 } ilqr_clr_robot;
 typedef struct {
     const double* obs;   /* [n_sets][n_obs][4] */
@@ -659,9 +672,11 @@ int ilqr_clearance_trajectories_dev(ilqr_ctx* ctx, const ilqr_problem_desc* desc
 
 /* ---- obstacle terms: a hinge penalty on clearance in the stage cost of the Riccati solvers (no reference function) ---------------------------
  * Avoidance, where the clearance calls above only judge: with these terms set, ilqr_solve_recursive, ilqr_solve_al, ilqr_problem_gains and
- * ilqr_problem_gains_al plan with a cost that grows as a sphere of the robot comes nearer than `margin` to an obstacle or a plane.  Every system
+ * ilqr_problem_gains_al plan with a cost that grows as a sphere of the robot comes nearer than `margin` to an obstacle, a plane or the other
+ * sphere of a self pair.  Every system
  * kind, nb_deriv 1 and 2, chains of 1 to 7 joints.  Robot, planes, obstacle sets and the pair clearances
  *       clr_ij(q) = (|p_i - o_j| - r_i) - R_j   (active obstacle j),          (n_l . p_i - d_l) - r_i   (plane l, j = n_obs + l)
+ * and, for every self pair (a, b) of the robot,   clr_ab(q) = (|p_b - p_a| - r_b) - r_a,
  * are exactly those of "clearance"; q is the first dof entries of x in the user's layout.  With the activation distance margin = world->margin
  * and the weight w >= 0, at every step k = 0 .. T-1 (the terminal state included, as for the limit terms):
  *       h_ij   = max(0, margin - clr_ij(q_k))                  every pair (i, j): the active obstacles of the instance's set, then the planes
@@ -673,9 +688,14 @@ int ilqr_clearance_trajectories_dev(ilqr_ctx* ctx, const ilqr_problem_desc* desc
  *   frame, for the joints m that move link sph_link[i], and 0 for the others.  This is the reference's keypoint convention (cost = e'Qe,
  *   l_x = -J'Qe, l_xx = J'QJ; System.cpp:248-308) for a one-sided scalar keypoint on clearance with target `margin` and precision w: l_x is
  *   half the gradient of the cost, as for every other term.  The exact Hessian's term h_ij grad^2 clr_ij is left out.
+ *   A self pair (a, b) is one more term of the sums, h_ab = max(0, margin - clr_ab) with the same margin and weight, added at sphere b behind b's
+ *   planes, the anchors ascending.  Its normal is n_ab = (p_b - p_a) / |p_b - p_a| and grad_ab[m] = n_ab . (a_m x (p_b - r_m)) for the joints m that
+ *   move b's link but not a's; it is exactly 0 for every other joint: a joint that moves both spheres moves them rigidly, its column
+ *   a_m x (p_b - p_a) is orthogonal to n_ab, and the library writes that 0 -- it does not compute and cancel.  Coincident centres add their cost
+ *   and a zero gradient, as for an obstacle.
  *   A pair with p_i == o_j exactly adds its cost and a zero gradient.  Velocity, time and control entries get nothing, nor do the padded joints of
  *   a chain of fewer than 7 joints.  The sum runs over ALL pairs, not only the nearest, so the cost is C1 in q.  Summation order: spheres
- *   ascending; per sphere the obstacles ascending, then the planes; one rounding per operation (no contraction), and the weight multiplies the
+ *   ascending; per sphere the obstacles ascending, then the planes, then the self pairs whose b it is; one rounding per operation (no contraction), and the weight multiplies the
  *   finished sums.  A stage's terms are added as the limit terms are: behind the keypoint or first limit set's terms, before the second limit
  *   set's; the stage's cost (system part + c_obs) is formed first and then joins the running sum.  One per-state function serves the solvers'
  *   rollouts, their derivative pass and the query below: the same state gives the same cost bits everywhere.  A state with a NaN or infinite
