@@ -1,5 +1,5 @@
 // ilqr_clearance.hpp -- launchers of the clearance kernels (ilqr_problem_clearance, ilqr_clearance_trajectories; include/ilqr_hip.h "clearance");
-// their definitions are ilqr_clearance_kernels.hpp, which ilqr_capi.cpp includes.
+// their definitions are ilqr_clearance_kernels.hpp, which ilqr_capi_kernels.cpp includes.
 //
 // Three launches per call: the per-state kernel writes one key (clearance, sphere, obstacle) per (trajectory, step) into a workspace, k_clr_fold
 // folds the keys of a trajectory in ascending step order, k_clr_stats reduces clr_min per group.  Offsets are size_t (n T n_x may pass 2^31); a

@@ -1,4 +1,4 @@
-// ilqr_clearance_kernels.hpp -- the clearance kernels: definitions and launchers, included by ilqr_capi.cpp alone (inside no namespace), for the
+// ilqr_clearance_kernels.hpp -- the clearance kernels: definitions and launchers, included by ilqr_capi_kernels.cpp alone (inside no namespace), for the
 // reasons at the top of ilqr_multistart_kernels.hpp: that file is compiled as HIP for the product library and as C++ for the host build of
 // tests/tools/hostsim, so both get the kernels from one text and no list of files changes, and no kernel of the .hip units moves.  Plain C++ without
 // lane communication: the host build runs the very same code.
@@ -15,7 +15,7 @@
 // The workspace holds 12 bytes per (trajectory, step): the clearance and sphere | obstacle << 5.
 #pragma once
 #ifndef ILQR_CLEARANCE_KERNELS_TU
-#error "ilqr_clearance_kernels.hpp holds definitions with external linkage: one translation unit (ilqr_capi.cpp) defines ILQR_CLEARANCE_KERNELS_TU and includes it; every other one includes ilqr_clearance.hpp"
+#error "ilqr_clearance_kernels.hpp holds definitions with external linkage: one translation unit (ilqr_capi_kernels.cpp) defines ILQR_CLEARANCE_KERNELS_TU and includes it; every other one includes ilqr_clearance.hpp"
 #endif
 #include "ilqr_clearance.hpp"
 

@@ -130,7 +130,7 @@ ILQR_DEV void cl_store_kpx(const ClArgs& c, const DevDesc& d, int st, int g, con
 // generic kernel (ilqr_kernels.hip); m: the maps of a chain of fewer than 7 joints, or null
 void launch_closed_loop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const DofMap* m, hipStream_t st);
 // cooperative kernels (ilqr_closed_loop.hip), 7-joint layouts only; kpx: [steps.n][n_x + n_u][B * S] workspace.  A weak declaration: the host
-// builds of the generic kernel set link without that file, and a launch that needs it there is an error (closed_loop, ilqr_capi.cpp).
+// builds of the generic kernel set link without that file, and a launch that needs it there is an error (closed_loop, ilqr_capi_closed_loop.cpp).
 __attribute__((weak)) void launch_closed_loop_coop(int kind, int nd, const Bufs& a, const ClArgs& c, int B, const ClosedLoopPlan& pl, double* kpx, hipStream_t st);
 
 

@@ -1,5 +1,5 @@
 // ilqr_closed_loop_plan.hpp -- which kernel runs a batched closed-loop rollout (ilqr_problem_closed_loop): one pure decision from the system,
-// the number of samples per instance and the context's pin, consumed by closed_loop (ilqr_capi.cpp).  No HIP here:
+// the number of samples per instance and the context's pin, consumed by closed_loop (ilqr_capi_closed_loop.cpp).  No HIP here:
 // tests/cpp/closed_loop_plan_main.cpp checks the table on the host.
 #pragma once
 

@@ -1,5 +1,5 @@
 // ilqr_ctx.hpp -- the context behind the opaque ilqr_ctx of include/ilqr_hip.h, shared by the translation units of the C ABI
-// (ilqr_capi.cpp, ilqr_lqt.cpp).  Internal: not installed, not part of the ABI.
+// (ilqr_capi_*.cpp, ilqr_lqt.cpp).  Internal: not installed, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,7 +26,7 @@ struct ilqr_ctx {
     // callbacks keeps this file free of references to their translation units.
     struct Cleanup { void (*destroy)(void*); void* handle; };
     std::vector<Cleanup> cleanups;
-    struct ClrState* clr = nullptr;  // the clearance calls' geometry buffer and workspace (ilqr_capi.cpp), made by the first call and reused
+    struct ClrState* clr = nullptr;  // the clearance calls' geometry buffer and workspace (ilqr_capi_clearance.cpp), made by the first call and reused
     // split solves (solve_riccati): the two halves of a batch run on their own streams, joined to `stream` by events
     int n_simd = 1024;  // SIMDs of the device (4 per CU)
     bool xc_generic = false, xc_cp_lane = false, xc_cp_general = false;  // cross-check kernel variants (ilqr_ctx_set_crosscheck)

@@ -23,7 +23,7 @@ constexpr int MAX_NQ = 13;
 constexpr int MAX_NX = 15;
 constexpr int MAX_NU = 8;
 
-// Chain with consecutive fixed segments folded into the following joint's pre-transform (host side, csrc/ilqr_capi.cpp).
+// Chain with consecutive fixed segments folded into the following joint's pre-transform (host side, csrc/ilqr_capi_problem.cpp).
 struct DevChain {
     double Rpre[DOF][9];   // fixed rotation applied before joint j's rotation (row-major)
     double ppre[DOF][3];   // translation (in the frame before Rpre) to joint j's origin

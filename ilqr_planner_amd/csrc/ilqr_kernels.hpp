@@ -1,4 +1,4 @@
-// ilqr_kernels.hpp -- device buffer table + kernel launchers shared by ilqr_kernels.hip and ilqr_capi.cpp
+// ilqr_kernels.hpp -- device buffer table + kernel launchers shared by ilqr_kernels.hip and the units of the C ABI (ilqr_capi_*.cpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // ilqr_lqt_capi.cpp -- the ilqr_lqt_* entry points of include/ilqr_hip.h: batched linear-quadratic tracking (solver::LQT, reference
 // src/solver/lqt.cpp).  Buffer ownership, argument checks and the launch order; the kernels are in ilqr_lqt.hip.  Kept apart from
-// ilqr_capi.cpp, which references none of these symbols: a handle is freed with its context through ilqr_ctx::cleanups.
+// the units of ilqr_capi_*.cpp, which reference none of these symbols: a handle is freed with its context through ilqr_ctx::cleanups.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1,5 +1,5 @@
 // ilqr_multistart.hpp -- launchers of the kernels that join instances (ilqr_problem_adopt, ilqr_problem_spread_controls, ilqr_problem_select,
-// ilqr_problem_get_at); their definitions are ilqr_multistart_kernels.hpp, which ilqr_capi.cpp includes.
+// ilqr_problem_get_at); their definitions are ilqr_multistart_kernels.hpp, which ilqr_capi_kernels.cpp includes.
 //
 // Every other kernel of the library stays inside one instance; these four read or write across the batch.  Offsets: an instance index is an int
 // (B < 2^31), every offset into a [row][Bp] buffer or a natural-layout array is formed as size_t (B T n may pass 2^31).

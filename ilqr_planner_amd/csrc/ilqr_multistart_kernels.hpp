@@ -1,9 +1,9 @@
-// ilqr_multistart_kernels.hpp -- the kernels that join instances: definitions and launchers, included by ilqr_capi.cpp alone (inside no namespace).
+// ilqr_multistart_kernels.hpp -- the kernels that join instances: definitions and launchers, included by ilqr_capi_kernels.cpp alone (inside no namespace).
 // That file is compiled as HIP for the product library and as C++ for the host build of tests/tools/hostsim, so both get the kernels from one
 // text and no list of files changes.  They are NOT in ilqr_kernels.hip: a kernel added there moves every kernel of that translation unit's code
 // object, and the C3 bench line followed it -- 5.550 .. 5.575 ms per step against the parent's 5.529 .. 5.546 in one session, six runs each in
 // rotating order, with these kernels at the end of that unit; 5.525 .. 5.554 with the unit left as it was (k_kp_derivs, which runs between the
-// streaming kernels of every iteration and is bound by fetching its code, is the one kernel of that unit on the C3 path).  ilqr_capi.cpp held
+// streaming kernels of every iteration and is bound by fetching its code, is the one kernel of that unit on the C3 path).  The C-ABI unit held
 // no kernel before: nothing moves.  Plain C++; the lane moves of k_select_group are the helpers of ilqr_lanes.hpp and exist in the device build
 // only (the host build runs its one-lane form).
 //
@@ -15,7 +15,7 @@
 // Offsets and flat thread indices are size_t throughout (B T n and G W may pass 2^31); an instance or group index is an int.
 #pragma once
 #ifndef ILQR_MULTISTART_KERNELS_TU
-#error "ilqr_multistart_kernels.hpp holds definitions with external linkage: one translation unit (ilqr_capi.cpp) defines ILQR_MULTISTART_KERNELS_TU and includes it; every other one includes ilqr_multistart.hpp"
+#error "ilqr_multistart_kernels.hpp holds definitions with external linkage: one translation unit (ilqr_capi_kernels.cpp) defines ILQR_MULTISTART_KERNELS_TU and includes it; every other one includes ilqr_multistart.hpp"
 #endif
 #include "ilqr_multistart.hpp"
 #include "ilqr_noise.hpp"

@@ -1,6 +1,6 @@
 // ilqr_obstacle.hpp -- the sphere-obstacle terms of the stage cost (include/ilqr_hip.h "obstacle terms"): the per-state function, the argument
 // block of the kernels that call it and their launchers.  The kernels themselves are in ilqr_kernels.hip (k_obs_derivs, k_obs_query, and the OBS
-// forms of the generic k_init_rollout / k_backward / k_forward, and, compiled with ilqr_capi.cpp, k_stage_dense, k_obs_ls, k_obs_ls_sum of the
+// forms of the generic k_init_rollout / k_backward / k_forward, and, compiled with ilqr_capi_kernels.cpp, k_stage_dense, k_obs_ls, k_obs_ls_sum of the
 // cooperative path: ilqr_obstacle_coop_kernels.hpp); of the cooperative kernels only k_backward_si_dpp<.., SW_DENSE> takes them, as precomputed stage derivatives (ilqr_plan.hpp:
 // PlanIn::obstacles_coop).
 //
@@ -179,7 +179,7 @@ __device__ __forceinline__ double obs_state(const ClrGeom& g, const double* __re
 // k_obs_derivs: the slot obd[k] of every step of every instance's current trajectory (all = 0: of the active instances only, as k_kp_derivs),
 // lanes along the batch, one grid row per step.  nx: rows of a device state.
 void launch_obs_derivs(const Bufs& a, const ObsArgs& o, int B, int T, int nx, int all, hipStream_t st);
-// The forms of a geometry with self pairs (ObsProblem::n_anchor > 0), which the caller picks; all of them are compiled with ilqr_capi.cpp, beside
+// The forms of a geometry with self pairs (ObsProblem::n_anchor > 0), which the caller picks; all of them are compiled with ilqr_capi_kernels.cpp, beside
 // the cooperative obstacle kernels (ilqr_obstacle_coop_kernels.hpp), and none in ilqr_kernels.hip.
 // k_obs_derivs_self: k_obs_derivs with obs_state<true, true>
 void launch_obs_derivs_self(const Bufs& a, const ObsArgs& o, int B, int T, int nx, int all, hipStream_t st);

@@ -1,5 +1,5 @@
 // ilqr_obstacle_coop_kernels.hpp -- the lane-per-item kernels of the obstacle terms' cooperative path (RiccatiPlan::obs_dense) and their launchers,
-// declared in ilqr_obstacle.hpp: definitions, included by ilqr_capi.cpp alone.  That file is compiled as HIP for the product library and as C++
+// declared in ilqr_obstacle.hpp: definitions, included by ilqr_capi_kernels.cpp alone.  That file is compiled as HIP for the product library and as C++
 // for the host build of tests/tools/hostsim, so both get them from one text and no list of files changes.  They are NOT in ilqr_kernels.hip beside
 // k_obs_derivs: a kernel added there moves every kernel of that unit's code object, and the C3 bench line follows it (ilqr_multistart_kernels.hpp
 // has the figures; with these three kernels in that unit the line read 5.5152 ms per step against the parent's 5.4878 in one session).

@@ -1,5 +1,5 @@
 // ilqr_plan.hpp -- which kernels run a Riccati solve (ILQRRecursive / AL_ILQR): one pure decision from the problem's shape, the batch size and
-// the context's pins, consumed by solve_riccati (ilqr_capi.cpp).  No HIP here: tests/cpp/plan_table_main.cpp checks the table on the host.
+// the context's pins, consumed by solve_riccati (ilqr_capi_solve.cpp).  No HIP here: tests/cpp/plan_table_main.cpp checks the table on the host.
 #pragma once
 
 namespace ilqr {

@@ -1,6 +1,6 @@
 // ilqr_rollout_kernels.hpp -- the two sequential rollout kernels of the generic (lane-per-instance) set, k_init_rollout and k_forward, as
 // templates in a header: ilqr_kernels.hip instantiates the forms without obstacle terms and the ObsArgs forms, and the unit built with
-// ilqr_capi.cpp (ilqr_obstacle_coop_kernels.hpp) the ObsSelfArgs forms of a geometry with self pairs -- so that ilqr_kernels.hip's code object
+// ilqr_capi_kernels.cpp (ilqr_obstacle_coop_kernels.hpp) the ObsSelfArgs forms of a geometry with self pairs -- so that ilqr_kernels.hip's code object
 // holds what it held before there were self pairs.  Included inside namespace ilqr, behind ilqr_step.hpp and an overload
 // obs_stage_cost(O, b, x) for every O the unit instantiates.
 #pragma once

@@ -1,6 +1,7 @@
 """Shared test helpers: load golden fixtures, build oracle Systems, synthetic batches."""
 from __future__ import annotations
 
+import glob
 import json
 import os
 import subprocess
@@ -17,14 +18,22 @@ from oracle import oracle as orc  # noqa: E402  (tests are allowed to use the or
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
+def hostsim_sources():
+    """The host sources of the library, as tests/tools/hostsim/build.sh lists them: the lane-per-instance kernels, every unit of the C-ABI
+    orchestration (ilqr_capi*.cpp), the URDF reader and the stubs of everything else."""
+    hostsim = os.path.join(ROOT, "tests", "tools", "hostsim")
+    src = os.path.join(ROOT, "ilqr_planner_amd", "csrc")
+    return ([os.path.join(src, "ilqr_kernels.hip")] + sorted(glob.glob(os.path.join(src, "ilqr_capi*.cpp"))) +
+            [os.path.join(src, "urdf_chain.cpp"), os.path.join(hostsim, "stubs.cpp")])
+
+
 def build_hostsim(lib):
     """The lane-per-instance kernels and the C-ABI orchestration built with g++ into the shared library `lib`: the sources and include paths
     of tests/tools/hostsim/build.sh, without sanitizers.  Returns `lib`."""
     hostsim = os.path.join(ROOT, "tests", "tools", "hostsim")
     src = os.path.join(ROOT, "ilqr_planner_amd", "csrc")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-I" + hostsim, "-I" + src, "-Wno-unused-result", "-x", "c++",
-                           os.path.join(src, "ilqr_kernels.hip"), os.path.join(src, "ilqr_capi.cpp"), os.path.join(src, "urdf_chain.cpp"),
-                           os.path.join(hostsim, "stubs.cpp"), "-o", str(lib)])
+                           *hostsim_sources(), "-o", str(lib)])
     return str(lib)
 
 

@@ -106,7 +106,7 @@ def same(a, b, tag):
 
 
 def final_penalty(nb_iter, lag, penalty, scaling):
-    """The penalty an AL solve of nb_iter iterations ends with: one multiplication per update iteration (ilqr_capi.cpp: solve_riccati)."""
+    """The penalty an AL solve of nb_iter iterations ends with: one multiplication per update iteration (ilqr_capi_solve.cpp: solve_riccati)."""
     for it in range(nb_iter):
         if (it + 1) % lag == 0:
             penalty *= scaling

@@ -1,5 +1,5 @@
 """Every subset of the outputs of the six ilqr_problem_closed_loop* entry points gives the same bytes, through host and through device pointers
-(tests/cpp/closed_loop_outputs_main.cpp): the staging layout and the workspaces of closed_loop (ilqr_planner_amd/csrc/ilqr_capi.cpp) for every
+(tests/cpp/closed_loop_outputs_main.cpp): the staging layout and the workspaces of closed_loop (ilqr_planner_amd/csrc/ilqr_capi_closed_loop.cpp) for every
 combination of outputs, not only the few the other tests ask for.  The program is built from the host sources of tests/helpers.build_hostsim
 with the address and undefined-behaviour sanitizers into an executable of its own and run as a child process.
 
@@ -8,7 +8,8 @@ Calls made, S = 2: ilqr_problem_closed_loop 4 subsets of {X, U} x 4 of {x0, w} =
 import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import ROOT, hostsim_sources
+
 CASES = 2 * (4 * 4 + (2 ** 5 - 8) + 2 * (2 ** 6 - 4))
 
 
@@ -18,8 +19,7 @@ def test_every_output_subset_gives_the_same_bytes(tmp_path):
     exe = str(tmp_path / "closed_loop_outputs")
     subprocess.check_call(["g++", "-std=c++17", "-O0", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + hostsim,
                            "-I" + src, "-I" + os.path.join(ROOT, "include"), "-Wno-unused-result", "-x", "c++",
-                           os.path.join(src, "ilqr_kernels.hip"), os.path.join(src, "ilqr_capi.cpp"), os.path.join(src, "urdf_chain.cpp"),
-                           os.path.join(hostsim, "stubs.cpp"), os.path.join(ROOT, "tests", "cpp", "closed_loop_outputs_main.cpp"), "-o", exe])
+                           *hostsim_sources(), os.path.join(ROOT, "tests", "cpp", "closed_loop_outputs_main.cpp"), "-o", exe])
     r = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "panda_chain.urdf")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = r.stdout.strip().splitlines()

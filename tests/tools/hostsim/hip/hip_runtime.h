@@ -1,6 +1,6 @@
 // Host stand-in for <hip/hip_runtime.h> -- SANITIZER HARNESS ONLY (tests/tools/hostsim).
 //
-// Lets the lane-per-instance (v1) kernels of ilqr_kernels.hip and the C-ABI orchestration of ilqr_capi.cpp be compiled as plain host
+// Lets the lane-per-instance (v1) kernels of ilqr_kernels.hip and the C-ABI orchestration of ilqr_capi_*.cpp be compiled as plain host
 // C++ with -fsanitize=address,undefined, so that index overruns, use-after-free across problem/context teardown and undefined
 // behaviour in the device code show up on the CPU under a sanitizer instead of as a GPU fault.  A kernel launch becomes a serial loop
 // over (block, thread); that is valid only for kernels whose lanes never communicate (no LDS, no shuffles, no barriers) -- the v1 set.
