@@ -42,7 +42,7 @@ EXPORTS = [
     "ilqr_problem_closed_loop", "ilqr_problem_closed_loop_dev", "ilqr_problem_closed_loop_noise", "ilqr_problem_closed_loop_noise_dev",
     "ilqr_problem_closed_loop_report", "ilqr_problem_closed_loop_report_dev", "ilqr_problem_closed_loop_cov", "ilqr_problem_closed_loop_cov_dev",
     "ilqr_problem_closed_loop_report_con", "ilqr_problem_closed_loop_report_con_dev", "ilqr_problem_closed_loop_cov_con",
-    "ilqr_problem_closed_loop_cov_con_dev",
+    "ilqr_problem_closed_loop_cov_con_dev", "ilqr_problem_closed_loop_cov_clr", "ilqr_problem_closed_loop_cov_clr_dev",
     "ilqr_ctx_set_split", "ilqr_ctx_set_crosscheck", "ilqr_problem_gains", "ilqr_problem_gains_al",
     "ilqr_problem_adopt", "ilqr_problem_adopt_dev", "ilqr_problem_spread_controls", "ilqr_problem_spread_controls_dev",
     "ilqr_problem_select", "ilqr_problem_select_dev", "ilqr_problem_get_at", "ilqr_problem_get_at_dev",
@@ -148,6 +148,12 @@ class CovCon(C.Structure):
     _fields_ = [("con_var", C.c_void_p), ("con_z", C.c_void_p)]
 
 
+class ClCovClr(C.Structure):
+    """Mirror of ilqr_cl_cov_clr: five pointers (host or device), 0 / None where the output is not asked for."""
+
+    _fields_ = [("clr_var", C.c_void_p), ("clr_z", C.c_void_p), ("clr_z_min", C.c_void_p), ("clr_z_at", C.c_void_p), ("eligible", C.c_void_p)]
+
+
 class ClrRobot(C.Structure):
     """Mirror of ilqr_clr_robot."""
 
@@ -213,6 +219,8 @@ Clearance = collections.namedtuple("Clearance", "clr clr_min clr_at n_below elig
 ClosedLoopCov = collections.namedtuple("ClosedLoopCov", "Sigma kp_Sigma kp_var u_var lim_z")
 ClosedLoopReportCon = collections.namedtuple("ClosedLoopReportCon", "cost stats kp_err kp_stats lim_cost outcome con_max con_steps con_stats outcome_con")
 ClosedLoopCovCon = collections.namedtuple("ClosedLoopCovCon", "Sigma kp_Sigma kp_var u_var lim_z con_var con_z")
+COV_CLR_OUTPUTS = ("clr_var", "clr_z", "clr_z_min", "clr_z_at", "eligible")
+ClosedLoopCovClr = collections.namedtuple("ClosedLoopCovClr", "Sigma kp_Sigma kp_var u_var lim_z clr_var clr_z clr_z_min clr_z_at eligible")
 ClosedLoopNoise = collections.namedtuple("ClosedLoopNoise", "cost stats X U w")
 ClosedLoopReport = collections.namedtuple("ClosedLoopReport", "cost stats kp_err kp_stats lim_cost outcome X U w")
 Selection = collections.namedtuple("Selection", "winner best n_candidates")
@@ -292,6 +300,8 @@ def load():
                                                           C.c_double, C.POINTER(Con)]
     L.ilqr_problem_closed_loop_cov_con.argtypes = [vp, dp, dp, C.POINTER(Cov), C.POINTER(CovCon)]
     L.ilqr_problem_closed_loop_cov_con_dev.argtypes = [vp, dp, dp, C.POINTER(Cov), C.POINTER(CovCon)]
+    for n in ("ilqr_problem_closed_loop_cov_clr", "ilqr_problem_closed_loop_cov_clr_dev"):
+        getattr(L, n).argtypes = [vp, dp, dp, C.POINTER(Cov), C.POINTER(ClrRobot), C.POINTER(ClrWorld), C.c_double, C.POINTER(ClCovClr)]
     L.ilqr_solve_recursive.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.ilqr_solve_al.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]
     L.ilqr_solve_batch_cp.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
@@ -868,6 +878,40 @@ class BatchProblem:
         co = CovCon(con_var_ptr or None, con_z_ptr or None)
         self.ctx.crosscheck_from_env()
         self.ctx.check(self.L.ilqr_problem_closed_loop_cov_con_dev(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)), C.byref(cv), C.byref(co)))
+
+    def closed_loop_cov_clr(self, sigma_w, sigma_x0, robot: ClrRobot, world, z_tol: float = 0.0, want=COV_CLR_OUTPUTS):
+        """closed_loop_cov with the clearance pairs read off the same recursion (ilqr_problem_closed_loop_cov_clr; definitions in
+        include/ilqr_hip.h): clr_var, clr_z [B][T], clr_z_min [B], clr_z_at [B][3] (int32) and eligible [B] (int32).  robot: clr_robot(...);
+        world: a ClrWorld whose obs is a host pointer, or (obstacles [n_sets][n_obs][4] or None, traj_per_set or None for B, margin).  want:
+        names of COV_CLR_OUTPUTS and of the five covariance outputs ("Sigma", "kp_Sigma", "kp_var", "u_var", "lim_z").  Returns a
+        ClosedLoopCovClr; what was not asked for is None."""
+        nx = self.dims.n_x
+        if not isinstance(world, ClrWorld):
+            obstacles, tps, margin = world
+            tps = self.B if tps is None else int(tps)
+            obs = _f64(obstacles) if obstacles is not None else np.zeros((self.B // tps if tps >= 1 else 0, 0, 4))
+            if obs.ndim != 3 or obs.shape[2] != 4:
+                raise ValueError(f"obstacles: expected [n_sets][n_obs][4], got {obs.shape}")
+            world = ClrWorld(obs.ctypes.data if obs.size else None, obs.shape[0], obs.shape[1], tps, float(margin), 0)
+        Sigma, kp_Sigma = _out("Sigma" in want, self.B, self.T, nx, nx), _out("kp_Sigma" in want, self.B, self.n_kp, nx, nx)
+        kp_var, u_var = _out("kp_var" in want, self.B, self.n_kp, KP_ERR), _out("u_var" in want, self.B, self.T - 1, self.dims.n_u)
+        lim_z = _out("lim_z" in want, self.B)
+        var, z, zmin = _out("clr_var" in want, self.B, self.T), _out("clr_z" in want, self.B, self.T), _out("clr_z_min" in want, self.B)
+        at = np.empty((self.B, 3), dtype=np.int32) if "clr_z_at" in want else None
+        el = np.empty(self.B, dtype=np.int32) if "eligible" in want else None
+        cv = Cov(*(a.ctypes.data if a is not None else None for a in (Sigma, kp_Sigma, kp_var, u_var, lim_z)))
+        ck = ClCovClr(*(a.ctypes.data if a is not None else None for a in (var, z, zmin, at, el)))
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_cov_clr(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)), C.byref(cv), C.byref(robot),
+                                                               C.byref(world), float(z_tol), C.byref(ck)))
+        return ClosedLoopCovClr(Sigma, kp_Sigma, kp_var, u_var, lim_z, var, z, zmin, at, el)
+
+    def closed_loop_cov_clr_dev(self, sigma_w, sigma_x0, robot: ClrRobot, world: ClrWorld, z_tol: float, clr: ClCovClr, cov: Cov = None):
+        """Device pointers in world.obs, clr and cov (cov may be None); asynchronous on the context's stream; the sigmas are host values."""
+        self.ctx.crosscheck_from_env()
+        self.ctx.check(self.L.ilqr_problem_closed_loop_cov_clr_dev(self.h, _dp(self._sigma(sigma_w)), _dp(self._sigma(sigma_x0)),
+                                                                   C.byref(cov) if cov is not None else None, C.byref(robot), C.byref(world),
+                                                                   float(z_tol), C.byref(clr) if clr is not None else None))
 
     # ---- multi-start: the calls that join instances (include/ilqr_hip.h "multi-start")
     @staticmethod

@@ -1788,6 +1788,17 @@ static void closed_loop_cov_of(ilqr_problem* p, sys::System& s, int B, const Clo
         ilqr_cl_cov_con co{o.con_var.data(), o.con_z.data()};
         check(ilqr_problem_closed_loop_cov_con(p, sg[0].empty() ? nullptr : sg[0].data(), sg[1].empty() ? nullptr : sg[1].data(), nullptr, &co));
     }
+    if (cv.clearance.given()) {  // likewise a call of its own
+        const ClearanceInputs& c = cv.clearance;
+        if (c.n_obs > 0 && (c.n_sets < 1 || B % c.n_sets != 0)) throw std::runtime_error("[closed_loop_cov_batch] the batch must be a multiple of the number of obstacle sets");
+        ilqr_clr_robot rb;
+        ilqr_clr_world w;
+        clearance_structs(c, B, c.n_obs > 0 ? B / c.n_sets : B, 0, rb, w);
+        o.clr_var.resize((size_t)B * o.T); o.clr_z.resize((size_t)B * o.T); o.clr_z_min.resize((size_t)B);
+        o.clr_z_at.resize((size_t)3 * B); o.eligible.resize((size_t)B);
+        ilqr_cl_cov_clr ck{o.clr_var.data(), o.clr_z.data(), o.clr_z_min.data(), o.clr_z_at.data(), o.eligible.data()};
+        check(ilqr_problem_closed_loop_cov_clr(p, sg[0].empty() ? nullptr : sg[0].data(), sg[1].empty() ? nullptr : sg[1].data(), nullptr, &rb, &w, cv.z_tol, &ck));
+    }
 }
 
 std::pair<BatchResult, ClosedLoopCovResult> ILQRRecursive::closedLoopCovBatch(const BatchInputs& in, const ClosedLoopCovInputs& cv, int nb_iter, bool line_search,

@@ -571,6 +571,10 @@ struct ClosedLoopCovInputs {
     std::vector<double> sigma_w, sigma_x0;   // one value (every entry) or n_x values; empty: 0
     bool want_Sigma = false;                 // the covariance at every step (B T n_x^2 doubles)
     bool want_con = false;                   // AL_ILQR: the variance of the constraint rows the class lowers (ilqr_problem_closed_loop_cov_con)
+    // given: the clearance pairs of the plans under the covariance (ilqr_problem_closed_loop_cov_clr): obstacles [n_sets][n_obs][4] with
+    // B % n_sets == 0, instance b reads set b / (B / n_sets); clearance.margin is the margin of z, z_tol the bound of `eligible`
+    ClearanceInputs clearance;
+    double z_tol = 0;
 };
 // the one place of closed_loop_cov_batch's rule for a sigma (a scalar or nb_state_var entries) and of its error text, which is closed_loop_batch's
 [[noreturn]] void closed_loop_cov_sigma_error();
@@ -580,6 +584,8 @@ struct ClosedLoopCovResult {
     std::vector<double> kp_Sigma, kp_var, u_var, lim_z;  // [B][n_kp][n_x][n_x], [B][n_kp][5], [B][T-1][n_u], [B]
     int m = 0;                                           // the rows the class lowered
     std::vector<double> con_var, con_z;                  // [B][T-1][m], [B]; empty unless want_con
+    std::vector<double> clr_var, clr_z, clr_z_min;       // [B][T], [B][T], [B]; empty unless ClosedLoopCovInputs::clearance is given
+    std::vector<int> clr_z_at, eligible;                 // [B][3], [B]; likewise
 };
 
 struct Constraint {  // AL-ILQR.h:20-23

@@ -63,6 +63,11 @@ static py::array_t<double> shaped(const std::vector<double>& v, std::vector<py::
     std::copy(v.begin(), v.end(), a.mutable_data());
     return a;
 }
+static py::array_t<int> shaped_i(const std::vector<int>& v, std::vector<py::ssize_t> shape) {
+    py::array_t<int> a(shape);
+    std::copy(v.begin(), v.end(), a.mutable_data());
+    return a;
+}
 
 // solve_batch(..., plan_gains = True): K, d of the result are the gains about the plan the solve leaves (ilqr_problem_gains)
 static solver::BatchInputs plan_gains(solver::BatchInputs in, bool on) {
@@ -247,6 +252,15 @@ static solver::ClosedLoopCovInputs closed_loop_cov_inputs(const py::object& sigm
         if (!a || a.ndim() > 1) solver::closed_loop_cov_sigma_error();   // (the length is checked where nb_state_var is known)
         (which ? cv.sigma_x0 : cv.sigma_w).assign(a.data(), a.data() + a.size());
     }
+    return cv;
+}
+
+// closed_loop_cov_batch(..., spheres, planes, obstacles, self_pairs, margin, z_tol): the clearance pairs under the covariance
+// (ilqr_problem_closed_loop_cov_clr); without spheres the call is what it was
+static solver::ClosedLoopCovInputs cov_clearance(solver::ClosedLoopCovInputs cv, const py::object& spheres, const py::object& planes, const py::object& obstacles,
+                                                 const py::object& self_pairs, double margin, double z_tol) {
+    cv.clearance = clearance_inputs(spheres, planes, obstacles, margin, self_pairs);
+    cv.z_tol = z_tol;
     return cv;
 }
 
@@ -502,7 +516,18 @@ PYBIND11_MODULE(PyLQR, m) {
         .def_property_readonly("con_var", [](const solver::ClosedLoopCovResult& r) -> py::object {
             return r.con_z.empty() ? py::object(py::none()) : py::object(shaped(r.con_var, {r.B, r.T - 1, r.m})); })
         .def_property_readonly("con_z", [](const solver::ClosedLoopCovResult& r) -> py::object {
-            return r.con_z.empty() ? py::object(py::none()) : py::object(shaped(r.con_z, {r.B})); });
+            return r.con_z.empty() ? py::object(py::none()) : py::object(shaped(r.con_z, {r.B})); })
+        // filled when closed_loop_cov_batch is given spheres (ilqr_problem_closed_loop_cov_clr), else None
+        .def_property_readonly("clr_var", [](const solver::ClosedLoopCovResult& r) -> py::object {
+            return r.eligible.empty() ? py::object(py::none()) : py::object(shaped(r.clr_var, {r.B, r.T})); })
+        .def_property_readonly("clr_z", [](const solver::ClosedLoopCovResult& r) -> py::object {
+            return r.eligible.empty() ? py::object(py::none()) : py::object(shaped(r.clr_z, {r.B, r.T})); })
+        .def_property_readonly("clr_z_min", [](const solver::ClosedLoopCovResult& r) -> py::object {
+            return r.eligible.empty() ? py::object(py::none()) : py::object(shaped(r.clr_z_min, {r.B})); })
+        .def_property_readonly("clr_z_at", [](const solver::ClosedLoopCovResult& r) -> py::object {
+            return r.eligible.empty() ? py::object(py::none()) : py::object(shaped_i(r.clr_z_at, {r.B, 3})); })
+        .def_property_readonly("eligible", [](const solver::ClosedLoopCovResult& r) -> py::object {
+            return r.eligible.empty() ? py::object(py::none()) : py::object(shaped_i(r.eligible, {r.B})); });
     py::class_<solver::Constraint>(m_sol, "Constraint").def(py::init<>()).def_readwrite("A", &solver::Constraint::A).def_readwrite("b", &solver::Constraint::b);
     py::class_<solver::ILQRRecursive>(m_sol, "ILQRRecursive")
         .def(py::init<const std::shared_ptr<sys::System>&>(), py::arg("s"))
@@ -539,11 +564,13 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("samples") = py::none(), py::arg("seed") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("kp_tol") = py::none(), py::arg("lim_tol") = py::none(), py::arg("plan_gains") = false)
         .def("closed_loop_cov_batch",
              [](solver::ILQRRecursive& self, const py::object& U0, int nb_iter, bool ls, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
-                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg) {
-                 return self.closedLoopCovBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, ls, es);
+                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg, const py::object& spheres, const py::object& planes, const py::object& obstacles, const py::object& self_pairs, double margin, double z_tol) {
+                 return self.closedLoopCovBatch(plan_gains(batch_inputs(U0, q0, dq0, kp), pg),
+                                                cov_clearance(closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), spheres, planes, obstacles, self_pairs, margin, z_tol), nb_iter, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("line_search"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(),
-             py::arg("kp_targets") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("plan_gains") = false);
+             py::arg("kp_targets") = py::none(), py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("plan_gains") = false, py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("self_pairs") = py::none(), py::arg("margin") = 0.0,
+             py::arg("z_tol") = 0.0);
     py::class_<solver::AL_ILQR>(m_sol, "AL_ILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const std::vector<solver::Constraint>&, const std::vector<Vec>&>(), py::arg("s"), py::arg("inequality"),
              py::arg("initLambda"))
@@ -589,13 +616,16 @@ PYBIND11_MODULE(PyLQR, m) {
         .def("closed_loop_cov_batch",
              [](solver::AL_ILQR& self, const py::object& U0, int nb_iter, int lag, double pen, double sc, bool ls, bool es, const py::object& q0, const py::object& dq0,
                 const py::object& kp, const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, bool pg, bool want_con,
-                const py::object& agp) {
-                 return self.closedLoopCovBatch(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma, want_con), nb_iter, lag, pen, sc, ls, es);
+                const py::object& agp, const py::object& spheres, const py::object& planes, const py::object& obstacles, const py::object& self_pairs, double margin, double z_tol) {
+                 return self.closedLoopCovBatch(al_gains(plan_gains(batch_inputs(U0, q0, dq0, kp), pg), agp),
+                                                cov_clearance(closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma, want_con), spheres, planes, obstacles, self_pairs, margin, z_tol), nb_iter, lag,
+                                                pen, sc, ls, es);
              },
              py::arg("U0"), py::arg("nb_iter"), py::arg("lag_update_step"), py::arg("penalty"), py::arg("scaling_factor"), py::arg("line_search"),
              py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
              py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("plan_gains") = false,
-             py::arg("want_con") = false, py::arg("al_gains_penalty") = py::none());
+             py::arg("want_con") = false, py::arg("al_gains_penalty") = py::none(), py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("self_pairs") = py::none(), py::arg("margin") = 0.0,
+             py::arg("z_tol") = 0.0);
     // bindings.cpp:778-782
     py::class_<solver::BatchILQR>(m_sol, "BatchILQR")
         .def(py::init<const std::shared_ptr<sys::System>&, const Mat&>(), py::arg("s"), py::arg("Q"))
@@ -620,11 +650,13 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("lim_tol") = py::none())
         .def("closed_loop_cov_batch",
              [](solver::BatchILQR& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
-                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
-                 return self.closedLoopCovBatch(batch_inputs(u0, q0, dq0, kp, true), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, es);
+                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, const py::object& spheres, const py::object& planes, const py::object& obstacles, const py::object& self_pairs, double margin, double z_tol) {
+                 return self.closedLoopCovBatch(batch_inputs(u0, q0, dq0, kp, true),
+                                                cov_clearance(closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), spheres, planes, obstacles, self_pairs, margin, z_tol), nb_iter, es);
              },
              py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
-             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false);
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("self_pairs") = py::none(), py::arg("margin") = 0.0,
+             py::arg("z_tol") = 0.0);
     // bindings.cpp:862-869: positional arguments only, no defaults
     py::class_<solver::LQT>(m_sol, "LQT")
         .def(py::init<const Mat&, const Mat&, const std::vector<Mat>&, const Vec&, float, int>())
@@ -657,9 +689,11 @@ PYBIND11_MODULE(PyLQR, m) {
              py::arg("lim_tol") = py::none())
         .def("closed_loop_cov_batch",
              [](solver::BatchILQRCP& self, int nb_iter, const py::object& u0, bool es, const py::object& q0, const py::object& dq0, const py::object& kp,
-                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma) {
-                 return self.closedLoopCovBatch(batch_inputs(u0, q0, dq0, kp, true), closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), nb_iter, es);
+                const py::object& sigma_w, const py::object& sigma_x0, bool want_Sigma, const py::object& spheres, const py::object& planes, const py::object& obstacles, const py::object& self_pairs, double margin, double z_tol) {
+                 return self.closedLoopCovBatch(batch_inputs(u0, q0, dq0, kp, true),
+                                                cov_clearance(closed_loop_cov_inputs(sigma_w, sigma_x0, want_Sigma), spheres, planes, obstacles, self_pairs, margin, z_tol), nb_iter, es);
              },
              py::arg("nb_iter"), py::arg("u0"), py::arg("early_stop"), py::arg("q0") = py::none(), py::arg("dq0") = py::none(), py::arg("kp_targets") = py::none(),
-             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false);
+             py::arg("sigma_w") = py::none(), py::arg("sigma_x0") = py::none(), py::arg("want_Sigma") = false, py::arg("spheres") = py::none(), py::arg("planes") = py::none(), py::arg("obstacles") = py::none(), py::arg("self_pairs") = py::none(), py::arg("margin") = 0.0,
+             py::arg("z_tol") = 0.0);
 }

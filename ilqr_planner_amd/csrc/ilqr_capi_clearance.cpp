@@ -12,11 +12,12 @@ struct ClrState {
     ClrGeom host;        // what `geom` holds
     bool have = false;
     DevScratch geom, ws, io;  // the geometry block, the workspace, the staging of the host forms
+    DevScratch cov[2];        // ilqr_problem_closed_loop_cov_clr: Sigma where the caller does not ask for it, the keys of k_cov_clr
 };
 
 void ilqr_capi::clr_release(ilqr_ctx* c) {
     if (!c->clr) return;
-    c->clr->geom.release(); c->clr->ws.release(); c->clr->io.release();
+    c->clr->geom.release(); c->clr->ws.release(); c->clr->io.release(); c->clr->cov[0].release(); c->clr->cov[1].release();
     delete c->clr;
     c->clr = nullptr;
 }
@@ -125,19 +126,16 @@ static void clr_fill_geom(const ilqr_problem_desc& d, const ilqr_clr_robot& rb, 
     for (int e = 0; e < rb.n_self; e++) g.self_mask[rb.self_pair[e][1]] |= 1 << g.self_slot[rb.self_pair[e][0]];
 }
 
-// p: the problem form (the plan where it lies); else X[n][T][n_x] in the natural layout of d
-static int clr_run(ilqr_ctx* c, const char* fn_, ilqr_problem* p, const ilqr_problem_desc& d, int n, int T, const double* X, const ilqr_clr_robot* rb,
-                   const ilqr_clr_world* w, const ilqr_clr_out* out_, bool dev) {
-    const std::string fn = std::string(fn_) + (dev ? "_dev" : "");
-    ilqr_dims ud;
-    if (ilqr_dims_of(&d, &ud)) return fail(c, fn + ": unsupported system kind / nb_deriv");
-    if (clr_check(c, fn, d, n, T, rb, w, out_, dev)) return 1;
-    if (!p && !X) return fail(c, fn + ": X is a null pointer");
-    HIPCHK(c, hipSetDevice(c->device));
+int ilqr_capi::clr_check_world(ilqr_ctx* c, const std::string& fn, const ilqr_problem_desc& d, int n, int T, const ilqr_clr_robot* rb,
+                               const ilqr_clr_world* w, bool dev) {
+    return clr_check(c, fn, d, n, T, rb, w, nullptr, dev, false);
+}
+
+int ilqr_capi::clr_bind_geom(ilqr_ctx* c, const ilqr_problem_desc& d, const ilqr_clr_robot& rb, const ClrGeom** geom, int* n_anchor) {
     if (!c->clr) c->clr = new ClrState();
     ClrState& cs = *c->clr;
     ClrGeom g;
-    clr_fill_geom(d, *rb, g);
+    clr_fill_geom(d, rb, g);
     if (!cs.have || std::memcmp(&g, &cs.host, sizeof(g)) != 0) {   // kernels in flight may read the old one; the copy's source must outlive it
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (cs.geom.reserve(c, sizeof(ClrGeom))) return 1;
@@ -147,12 +145,31 @@ static int clr_run(ilqr_ctx* c, const char* fn_, ilqr_problem* p, const ilqr_pro
         HIPCHK(c, hipStreamSynchronize(c->stream));
         cs.have = true;
     }
-    const size_t nT = (size_t)n * (size_t)T;
-    if (cs.ws.reserve(c, nT * 12)) return 1;
+    *geom = (const ClrGeom*)cs.geom.ptr;
+    *n_anchor = g.n_anchor;
+    return 0;
+}
+
+DevScratch& ilqr_capi::clr_cov_scratch(ilqr_ctx* c, int which) {
+    if (!c->clr) c->clr = new ClrState();
+    return c->clr->cov[which];
+}
+
+// p: the problem form (the plan where it lies); else X[n][T][n_x] in the natural layout of d
+static int clr_run(ilqr_ctx* c, const char* fn_, ilqr_problem* p, const ilqr_problem_desc& d, int n, int T, const double* X, const ilqr_clr_robot* rb,
+                   const ilqr_clr_world* w, const ilqr_clr_out* out_, bool dev) {
+    const std::string fn = std::string(fn_) + (dev ? "_dev" : "");
+    ilqr_dims ud;
+    if (ilqr_dims_of(&d, &ud)) return fail(c, fn + ": unsupported system kind / nb_deriv");
+    if (clr_check(c, fn, d, n, T, rb, w, out_, dev)) return 1;
+    if (!p && !X) return fail(c, fn + ": X is a null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
     ClrArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.geom = (const ClrGeom*)cs.geom.ptr;
-    a.n_anchor = g.n_anchor;
+    if (clr_bind_geom(c, d, *rb, &a.geom, &a.n_anchor)) return 1;
+    ClrState& cs = *c->clr;
+    const size_t nT = (size_t)n * (size_t)T;
+    if (cs.ws.reserve(c, nT * 12)) return 1;
     a.n = n; a.T = T; a.n_obs = w->n_obs; a.traj_per_set = w->traj_per_set;
     a.ws_clr = (double*)cs.ws.ptr;
     a.ws_code = (int*)(a.ws_clr + nT);

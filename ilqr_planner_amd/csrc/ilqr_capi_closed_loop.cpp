@@ -1,4 +1,4 @@
-// ilqr_capi_closed_loop.cpp -- C ABI (include/ilqr_hip.h): the closed loop of the tracking law and its covariance, twelve entry points.
+// ilqr_capi_closed_loop.cpp -- C ABI (include/ilqr_hip.h): the closed loop of the tracking law and its covariance, fourteen entry points.
 #include "ilqr_capi_internal.hpp"
 
 using namespace ilqr_capi;
@@ -241,11 +241,22 @@ extern "C" int ilqr_problem_closed_loop_report_con_dev(ilqr_problem* p, int n_sa
 // kp_var is formed from kp_Sigma by a kernel of its own, so kp_Sigma always exists where kp_var is asked for: the caller's array, a slice of
 // staging, or the problem's workspace.
 // with_con: ilqr_problem_closed_loop_cov_con -- `out_` may be null, and the kernels also read the constraint rows off Sigma_k (con).
+// cr: ilqr_problem_closed_loop_cov_clr -- `out_` may be null; the covariance kernels run as they are, with Sigma in a buffer of the context where
+// the caller does not ask for it, and k_cov_clr / k_cov_clr_fold (ilqr_cov_clearance.hpp) read the clearance pairs off it.
+struct CovClrRequest {
+    const ilqr_clr_robot* robot;
+    const ilqr_clr_world* world;
+    double z_tol;
+    const ilqr_cl_cov_clr* clr;
+};
 static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out_, bool dev, bool with_con = false,
-                           const ilqr_cl_cov_con* con = nullptr) {
+                           const ilqr_cl_cov_con* con = nullptr, const CovClrRequest* cr = nullptr) {
     if (!p) return 1;
     const ilqr_cl_cov none = {};
-    const ilqr_cl_cov* out = (with_con && !out_) ? &none : out_;
+    const ilqr_cl_cov* out = ((with_con || cr) && !out_) ? &none : out_;
+    const ilqr_cl_cov_clr ok = (cr && cr->clr) ? *cr->clr : ilqr_cl_cov_clr{};
+    const bool want_clr = ok.clr_var || ok.clr_z || ok.clr_z_min || ok.clr_z_at || ok.eligible;
+    const std::string clr_fn = std::string("ilqr_problem_closed_loop_cov_clr") + (dev ? "_dev" : "");
     const ilqr_cl_cov_con oc = (with_con && con) ? *con : ilqr_cl_cov_con{};
     ilqr_ctx* c = p->ctx;
     const int T = p->T, nxu = p->udims.n_x, nuu = p->udims.n_u, B = p->B, n_kp = p->hdesc.steps.kp[p->hdesc.steps.n];
@@ -253,14 +264,19 @@ static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double*
         for (const double* sg : {sigma_w, sigma_x0})
             if (sg && (!(sg[i] >= 0) || !std::isfinite(sg[i]))) return fail(c, "closed loop: every sigma_w and sigma_x0 must be finite and >= 0");
     const bool no_out = !out || (!out->Sigma && !out->kp_Sigma && !out->kp_var && !out->u_var && !out->lim_z);
-    if (!with_con && no_out) return fail(c, "closed loop cov: every output is a null pointer");
+    if (!with_con && !cr && no_out) return fail(c, "closed loop cov: every output is a null pointer");
     const size_t nn = (size_t)nxu * nxu, n_S = (size_t)B * T * nn, n_kS = (size_t)B * n_kp * nn;
-    if (const char* why = cl_cov_size_refusal(B, T, n_kp, nxu, out->Sigma != nullptr, out->kp_Sigma != nullptr)) return fail(c, why);
+    if (const char* why = cl_cov_size_refusal(B, T, n_kp, nxu, out->Sigma != nullptr || want_clr, out->kp_Sigma != nullptr)) return fail(c, why);
     if (!p->has_gains)   // (behind the bounds on the call itself: those do not depend on the state of the problem)
         return fail(c, "closed loop needs the gains of a Riccati solve (ilqr_solve_recursive or ilqr_solve_al with nb_iter >= 1) or of ilqr_problem_gains since the problem's inputs last changed");
     if (with_con) {
         if (p->bufs.m <= 0) return fail(c, "closed loop cov con: no constraints set");
         if (no_out && !oc.con_var && !oc.con_z) return fail(c, "closed loop cov con: con and out both ask for nothing");
+    }
+    if (cr) {
+        if (clr_check_world(c, clr_fn, p->desc, B, T, cr->robot, cr->world, dev)) return 1;
+        if (std::isnan(cr->z_tol)) return fail(c, clr_fn + ": z_tol is NaN");
+        if (no_out && !want_clr) return fail(c, clr_fn + ": clr and out both ask for nothing");
     }
     const size_t n_cv = (size_t)B * (T - 1) * (with_con ? p->bufs.m : 0);
     HIPCHK(c, hipSetDevice(c->device));
@@ -279,8 +295,20 @@ static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double*
     double* kp_var = out->kp_var;
     a.Sigma = out->Sigma; a.kp_Sigma = out->kp_Sigma; a.u_var = out->u_var; a.lim_z = out->lim_z;
     a.con_var = oc.con_var; a.con_z = oc.con_z;
+    CovClrArgs ca;
+    std::memset(&ca, 0, sizeof(ca));
+    ilqr_cl_cov_clr dk = ok;   // the device side of the five outputs
+    const size_t nT = (size_t)B * (size_t)T;
+    const size_t n_obs_all = want_clr ? (size_t)cr->world->n_sets * (size_t)cr->world->n_obs * 4 : 0;
+    if (want_clr) ca.obs = cr->world->obs;
     auto bind = [&](Staging& stg) {  // the staging slices of a host-pointer call (Staging::lay: first the sizing walk, then the real one)
-        if (out->Sigma) a.Sigma = stg.take_out(out->Sigma, n_S);
+        if (out->Sigma || want_clr) a.Sigma = stg.take_out(out->Sigma, n_S);   // k_cov_clr reads it there, asked for or not
+        if (n_obs_all) ca.obs = stg.take_in(cr->world->obs, n_obs_all);
+        if (ok.clr_var) dk.clr_var = stg.take_out(ok.clr_var, nT);
+        if (ok.clr_z) dk.clr_z = stg.take_out(ok.clr_z, nT);
+        if (ok.clr_z_min) dk.clr_z_min = stg.take_out(ok.clr_z_min, (size_t)B);
+        if (ok.clr_z_at) dk.clr_z_at = stg.take_out(ok.clr_z_at, (size_t)3 * B);
+        if (ok.eligible) dk.eligible = stg.take_out(ok.eligible, (size_t)B);
         a.kp_Sigma = want_kS ? stg.take_out(out->kp_Sigma, n_kS) : nullptr;
         if (out->kp_var) kp_var = stg.take_out(out->kp_var, n_kv);
         if (out->u_var) a.u_var = stg.take_out(out->u_var, n_uv);
@@ -291,9 +319,28 @@ static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double*
     Staging stg{c};
     if (!dev) {
         if (stg.lay(p->staging, bind)) return 1;
-    } else if (want_kS && !out->kp_Sigma) {
-        if (p->cl_cov_kps.reserve_doubles(c, n_kS)) return 1;
-        a.kp_Sigma = p->cl_cov_kps.doubles();
+    } else {
+        if (want_kS && !out->kp_Sigma) {
+            if (p->cl_cov_kps.reserve_doubles(c, n_kS)) return 1;
+            a.kp_Sigma = p->cl_cov_kps.doubles();
+        }
+        if (want_clr && !out->Sigma) {
+            DevScratch& sg = clr_cov_scratch(c, 0);
+            if (sg.reserve_doubles(c, n_S)) return 1;
+            a.Sigma = sg.doubles();
+        }
+    }
+    if (want_clr) {
+        if (clr_bind_geom(c, p->desc, *cr->robot, &ca.geom, &ca.n_anchor)) return 1;
+        DevScratch& ws = clr_cov_scratch(c, 1);
+        if (ws.reserve(c, nT * 20)) return 1;
+        ca.Sigma = a.Sigma;
+        ca.n = B; ca.T = T; ca.n_obs = cr->world->n_obs; ca.traj_per_set = cr->world->traj_per_set; ca.n_x = nxu; ca.dof = p->desc.dof;
+        ca.margin = cr->world->margin;
+        ca.ws_z = ws.doubles();
+        ca.ws_var = ca.ws_z + nT;
+        ca.ws_code = (int*)(ca.ws_var + nT);
+        for (int j = 0; j < DOF; j++) ca.qrow[j] = j < p->desc.dof ? p->map.x.dev[j] : 0;
     }
     if (!want_kS) a.kp_Sigma = nullptr;
     if (!pl.rows) {
@@ -304,6 +351,17 @@ static int closed_loop_cov(ilqr_problem* p, const double* sigma_w, const double*
     if (pl.rows) launch_closed_loop_cov_rows(kind, nd, p->bufs, a, B, c->stream);
     else launch_closed_loop_cov(kind, nd, p->bufs, a, B, p->mapped ? &p->map : nullptr, c->stream);
     if (out->kp_var) launch_closed_loop_cov_kp(kind, nd, p->bufs, B, n_kp, p->mapped ? p->map.dof : DOF, a.kp_Sigma, kp_var, c->stream);
+    if (want_clr) {
+        {
+            ProfScope ps(c, ILQR_PROF_OTHER);
+            launch_cov_clr(p->bufs.X[0], p->bufs.X[1], p->bufs.cur, p->dims.n_x, p->Bp, ca, c->stream);
+        }
+        {
+            ProfScope ps(c, ILQR_PROF_OTHER);
+            launch_cov_clr_fold(ca, cr->z_tol, dk, c->stream);
+        }
+        prof_mark(c, -1);
+    }
     HIPCHK(c, hipGetLastError());
     return dev ? 0 : stg.fetch();
 }
@@ -321,4 +379,15 @@ extern "C" int ilqr_problem_closed_loop_cov_con(ilqr_problem* p, const double* s
 extern "C" int ilqr_problem_closed_loop_cov_con_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
                                                     const ilqr_cl_cov_con* con) {
     return closed_loop_cov(p, sigma_w, sigma_x0, out, true, true, con);
+}
+
+extern "C" int ilqr_problem_closed_loop_cov_clr(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
+                                                const ilqr_clr_robot* robot, const ilqr_clr_world* world, double z_tol, const ilqr_cl_cov_clr* clr) {
+    const CovClrRequest cr{robot, world, z_tol, clr};
+    return closed_loop_cov(p, sigma_w, sigma_x0, out, false, false, nullptr, &cr);
+}
+extern "C" int ilqr_problem_closed_loop_cov_clr_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
+                                                    const ilqr_clr_robot* robot, const ilqr_clr_world* world, double z_tol, const ilqr_cl_cov_clr* clr) {
+    const CovClrRequest cr{robot, world, z_tol, clr};
+    return closed_loop_cov(p, sigma_w, sigma_x0, out, true, false, nullptr, &cr);
 }

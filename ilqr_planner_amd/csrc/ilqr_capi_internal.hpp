@@ -20,6 +20,7 @@
 #include "ilqr_clearance.hpp"
 #include "ilqr_closed_loop.hpp"
 #include "ilqr_closed_loop_cov.hpp"
+#include "ilqr_cov_clearance.hpp"
 #include "ilqr_ctx.hpp"
 #include "ilqr_kernels.hpp"
 #include "ilqr_multistart.hpp"
@@ -167,6 +168,13 @@ ProfHook prof_hook(ilqr_ctx* c);
 
 int lower_chain(ilqr_ctx* c, const ilqr_problem_desc& d, DevChain& ch);  // ilqr_capi_problem.cpp
 void clr_release(ilqr_ctx* c);  // the clearance calls' buffers (ilqr_capi_clearance.cpp)
+// What ilqr_problem_closed_loop_cov_clr shares with the clearance calls (ilqr_capi_clearance.cpp).  clr_check_world: their refusals about robot,
+// planes, obstacles, sets and the chain, under the name fn.  clr_bind_geom: the context's geometry block holds this call's geometry (uploaded
+// where it differs from the previous call's); n_anchor is the geometry's.  clr_cov_scratch: the context's buffers of that call -- 0: Sigma where
+// the caller does not ask for it, 1: the keys of k_cov_clr.
+int clr_check_world(ilqr_ctx* c, const std::string& fn, const ilqr_problem_desc& d, int n, int T, const ilqr_clr_robot* rb, const ilqr_clr_world* w, bool dev);
+int clr_bind_geom(ilqr_ctx* c, const ilqr_problem_desc& d, const ilqr_clr_robot& rb, const ClrGeom** geom, int* n_anchor);
+DevScratch& clr_cov_scratch(ilqr_ctx* c, int which);
 
 // A geometry with self pairs (ObsProblem::n_anchor > 0) takes the ObsSelfArgs forms of the three kernels that read the obstacle terms
 // (ilqr_obstacle.hpp); o is null for a problem without the terms.

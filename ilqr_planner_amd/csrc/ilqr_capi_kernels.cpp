@@ -1,6 +1,7 @@
 // ilqr_capi_kernels.cpp -- the kernels compiled beside the C-ABI units, and nothing else: the kernels that join instances
-// (ilqr_multistart_kernels.hpp), the clearance kernels (ilqr_clearance_kernels.hpp) and those of the obstacle terms' cooperative path
-// (ilqr_obstacle_coop_kernels.hpp), each for the reason given there.  The includes in front of them, and their order, are those of the unit that
+// (ilqr_multistart_kernels.hpp), the clearance kernels (ilqr_clearance_kernels.hpp), those of the obstacle terms' cooperative path
+// (ilqr_obstacle_coop_kernels.hpp) and, behind them all, those of clearance under the closed-loop covariance (ilqr_cov_clearance_kernels.hpp),
+// each for the reason given there.  The includes in front of them, and their order, are those of the unit that
 // held these kernels before the C ABI was split by concern: the unit's code object stays what it was, and no edit of host orchestration
 // re-emits it.
 #include "../../include/ilqr_hip.h"
@@ -36,3 +37,8 @@ using namespace ilqr;
 
 // the lane-per-item kernels of the obstacle terms' cooperative path (k_stage_dense, k_obs_ls, k_obs_ls_sum) and their launchers: likewise
 #include "ilqr_obstacle_coop_kernels.hpp"
+
+// clearance under the closed-loop covariance (k_cov_clr, k_cov_clr_self, k_cov_clr_fold) and their launchers: likewise, and last, so that every
+// kernel in front of them is compiled from the text it was compiled from before
+#define ILQR_COV_CLEARANCE_KERNELS_TU
+#include "ilqr_cov_clearance_kernels.hpp"

@@ -505,6 +505,55 @@ int ilqr_problem_closed_loop_cov_con(ilqr_problem* p, const double* sigma_w, con
 int ilqr_problem_closed_loop_cov_con_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
                                          const ilqr_cl_cov_con* con);
 
+/* Analytic: ilqr_problem_closed_loop_cov_clr.  The same covariance, judged against the surroundings: the first-order variance of every clearance
+ * pair of "clearance" (below) and how many standard deviations the plan keeps from `margin`.  ilqr_clr_robot and ilqr_clr_world are declared
+ * below with the clearance calls; this paragraph uses their definitions.
+ * Pairs and gradient.  Robot, planes, obstacle sets (instance b reads set b / traj_per_set, n = B; stats_group is not read), self pairs,
+ *   margin = world->margin, the pair clearances clr_ij(q), clr_ab(q) and the pair numbering j (obstacles, then planes at n_obs + l, then the self
+ *   pair (a, b) as (i, j) = (b, n_obs + n_planes + a)) are exactly those of "clearance".  The gradient grad_ij = n_ij' Jp_i(q) is that of "obstacle
+ *   terms": n_ij = (p_i - o_j) / |p_i - o_j| for an obstacle, plane_n[l] for a plane, column m of Jp_i = a_m x (p_i - r_m) for the joints m that
+ *   move sphere i's link and 0 for the others; for a self pair grad_ab = n_ab' (Jp_b - Jp_a), n_ab = (p_b - p_a) / |p_b - p_a|: entry m is
+ *   n_ab . (a_m x (p_b - r_m)) for the joints that move b's link but not a's and exactly 0 for every other joint (a joint that moves both moves them
+ *   rigidly; the library writes that 0, it does not compute and cancel).  The gradient is zero where the two centres coincide.  q is the first dof
+ *   entries of xbar_k (the plan ilqr_problem_get_X returns) in the user's layout; velocities and the time state get gradient 0.  Every system kind,
+ *   nb_deriv 1 and 2, chains of 1 to 7 joints.
+ * Per pair, at step k = 0 .. T-1:
+ *   var_ij[k] = grad' Sigma_k[q,q] grad, Sigma_k[q,q] the leading dof x dof block of the Sigma_k ilqr_problem_closed_loop_cov returns for the same
+ *     sigmas.  Summation order: s = 0; rows i ascending, within a row the columns j ascending, s = s + (grad_i * Sigma_k[i][j]) * grad_j; one
+ *     rounding per operation, no contraction.  A sum that rounding leaves below 0 counts as 0.
+ *   z_ij[k] = (clr_ij - margin) / sqrt(var_ij) where var_ij > 0; where var_ij == 0, z_ij = +inf if clr_ij >= margin, else -inf.
+ * Per step:
+ *   clr_z[B][T]    the minimum of z_ij over the step's pairs (every sphere against the active obstacles of the set and the planes, and the self
+ *                  pairs); ties go to the lowest i, then the lowest j.  +inf without any pair.
+ *   clr_var[B][T]  var_ij of the pair that attains clr_z; 0 without any pair, and 0 where clr_z is +inf (only a pair with var_ij == 0 has it).
+ *   A bad step, as "clearance" defines it, gives NaN in both; so does a step with an entry of Sigma_k[q,q] that is not finite.
+ * Per plan:
+ *   clr_z_min[B], clr_z_at[B][3] = (k, i, j) (ints): the minimum over the steps in the total order "bad steps first (the lowest k), then
+ *                  (z, k, i, j) lexicographic"; clr_z_min is NaN with a bad step.  clr_z_at is (k, -1, -1) for a bad step and (0, -1, -1) if
+ *                  clr_z is +inf throughout.
+ *   eligible[B]    1 iff there is no bad step and clr_z_min >= z_tol (ints): the array ilqr_problem_select takes, so a multi-start can prefer the
+ *                  starts that keep z_tol standard deviations from the cell.
+ * `out` may be NULL; what it asks for is what ilqr_problem_closed_loop_cov returns, bit for bit per kernel, and the existing covariance entry
+ * points return what they returned before.  The call changes nothing in the problem: plan, gains, multipliers, flags and obstacle terms stay as
+ * they are; the obstacle terms a problem may hold play no part: the geometry is the call's.  The covariance kernels run as in
+ * ilqr_problem_closed_loop_cov, with Sigma in a buffer of the context where the caller does not ask for it; k_cov_clr then reads xbar_k where
+ * the plan lies and Sigma_k in its natural layout, lanes along the batch and one grid row per step, and k_cov_clr_fold folds a plan's steps in
+ * ascending order on one lane.  Under ilqr_profile_enable the two are charged to ILQR_PROF_OTHER.
+ * Refused, each with its own text: what ilqr_problem_closed_loop_cov refuses (a NULL `out` is not; B T n_x^2 >= 2^31 is refused whenever `clr`
+ * asks for something, since Sigma is then formed); what the clearance calls refuse about robot, planes, obstacles, sets and the chain; a NaN
+ * z_tol; clr and out both asking for nothing.
+ * _dev: the arrays inside `out` and `clr` and world->obs are device pointers (the sigmas and the structs are read on the host before the call
+ * returns); asynchronous on the context's stream, except that a call whose robot or chain differs from the previous call's waits for the stream
+ * once, as the clearance calls do. */
+typedef struct {
+    double* clr_var;   /* [B][T] or NULL */
+    double* clr_z;     /* [B][T] or NULL */
+    double* clr_z_min; /* [B] or NULL */
+    int*    clr_z_at;  /* [B][3] or NULL */
+    int*    eligible;  /* [B] or NULL */
+} ilqr_cl_cov_clr;
+/* (the two prototypes stand behind ilqr_clr_robot and ilqr_clr_world, with the clearance calls) */
+
 /* ---- multi-start: the calls that join instances (no reference function: the reference solves one problem from one U0) -------------------
  * iLQR is a local method; a caller with one task runs it from S starts on the idle lanes, keeps the best plan and polishes it.  Everything above
  * stays inside one instance; these four calls move data between instances, and between two problems, without leaving HBM.
@@ -669,6 +718,11 @@ int ilqr_clearance_trajectories(ilqr_ctx* ctx, const ilqr_problem_desc* desc, in
                                 const ilqr_clr_world* world, const ilqr_clr_out* out);
 int ilqr_clearance_trajectories_dev(ilqr_ctx* ctx, const ilqr_problem_desc* desc, int n, int T, const double* X, const ilqr_clr_robot* robot,
                                     const ilqr_clr_world* world, const ilqr_clr_out* out);
+/* "Analytic: ilqr_problem_closed_loop_cov_clr" above */
+int ilqr_problem_closed_loop_cov_clr(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
+                                     const ilqr_clr_robot* robot, const ilqr_clr_world* world, double z_tol, const ilqr_cl_cov_clr* clr);
+int ilqr_problem_closed_loop_cov_clr_dev(ilqr_problem* p, const double* sigma_w, const double* sigma_x0, const ilqr_cl_cov* out,
+                                         const ilqr_clr_robot* robot, const ilqr_clr_world* world, double z_tol, const ilqr_cl_cov_clr* clr);
 
 /* ---- obstacle terms: a hinge penalty on clearance in the stage cost of the Riccati solvers (no reference function) ---------------------------
  * Avoidance, where the clearance calls above only judge: with these terms set, ilqr_solve_recursive, ilqr_solve_al, ilqr_problem_gains and
